@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: (group x gene) tests/sec of the asymptotic Wilcoxon rank-sum hot path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5shard|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5shard|c5] [--dump-outputs DIR] [--full]
 
 Workloads (BASELINE.json configs, synthetic data generated on the device, SURVEY.md 8d recipe: Poisson(gene mean
 ~U(0.1, 15)) counts as float32 with a fraction of the entries zeroed, one reference group of N/30 cells, the other
@@ -20,10 +20,22 @@ default -- the SAME workload, its genes split into one contiguous range per rank
 is generated per 256-gene block from (seed, block), so every N computes the identical problem and no input is ever
 exchanged.  The path's one collective -- the gather of every rank's planes to rank 0 -- is INSIDE the timed steps:
 step k's gather runs on RCCL's stream under step k + 1's pass, and all K gathers have completed when the clock
-stops, so `value` = tests / (pass + gather).  `pass_only` (the same steps without the gather) is reported beside it.
+stops, so `value` = tests / (pass + gather).  `--full` reports `pass_only` (the same steps without the gather) beside it.
 `--scaling weak` gives every rank a full workload-sized gene shard instead.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line from rank 0: `metric`, `value` (tests per second
+of the timed steps), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall milliseconds of one timed step), `steps`,
+`warmup`, `config` and `steady_state` (and, at N > 1 with the gather in the step, `final_gather`).  Nothing else is
+measured, checked or profiled in it.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed -- the three float64 [G, M] planes
+a caller receives -- as DIR/p_value.npy, DIR/statistic.npy and DIR/fold_change.npy.  When the planes exceed 63 MB in all,
+a fixed sample of the genes is written (np.random.RandomState(0), sorted; the same genes for the same shape), every
+group kept.  The inputs depend on the arguments alone (seeded generators), so two builds run with the same arguments
+can be compared output for output.
+
+`--full` adds everything else the benchmark measures or checks, each in runs of its own after the timed steps (the
+`--no-*` options below switch single legs of it off).  Rank 0's line then carries these extra objects:
   roofline       achieved algorithmic GB/s of the dominant kernel (HIP events on the engine's stream, live, inside the
                  timed region) against the 8 TB/s HBM peak; `traffic` = PMC bytes per launch from profiles/traffic.json
   cpu_baseline   the CPU oracle (C restatement of illico's algorithm, oracle/, built -O3 -march=native on this box,
@@ -33,7 +45,7 @@ Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
   timing_scopes  SURVEY.md 8d: (i) engine = ms_per_step, (ii) engine + H2D / D2H transfers, (iii) the drop-in call
   c5_strong      BASELINE configs[4] (1M x 30k x 5k dense OVO) measured in the same launch, genes split over the N
                  ranks: ms per pass, ms per gather, ms per pass + gather (overlapped as above), bytes into rank 0,
-                 roofline fraction -- so a driver that only ever runs `bench.py --gpus N` records configs[4] at every N
+                 roofline fraction -- so a driver that runs `bench.py --gpus N --full` records configs[4] at every N
                  (`--no-c5` skips it; `--c5-cells/--c5-genes/--c5-groups` shrink it for tests)
 """
 from __future__ import annotations
@@ -112,7 +124,15 @@ def parse(argv=None):
     ap.add_argument("--backend", default="nccl", help=argparse.SUPPRESS)       # test hook: gloo
     ap.add_argument("--share-device", action="store_true", help=argparse.SUPPRESS)  # test hook: every rank on GPU 0
     ap.add_argument("--engine-option", action="append", default=[], help="key=value passed to illico_ctx_set_option")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the planes of the last timed step to DIR/{p_value,statistic,fold_change}.npy (float64, a fixed sample of "
+                         "the genes when they exceed 63 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: roofline, parity, CPU baseline, timing scopes, single call, "
+                         "the other BASELINE configs and c5_strong (the --no-* options switch single legs off)")
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.gpus > 1 and args.no_gather_in_step:
+        ap.error("--dump-outputs at --gpus > 1 needs the gather in the timed step (rank 0 writes the gathered planes)")
     w = WORKLOADS[args.workload]
     for k in ("cells", "genes", "groups", "sparsity", "test", "fmt"):
         if getattr(args, k) is None:
@@ -387,6 +407,30 @@ class Job:
                         got[k][:, i] = self.stages[b][k][:, c - lb].cpu().numpy()
         return got
 
+    def output_columns(self, cols):
+        """Global genes `cols` (sorted) of the three [G, M_total] planes of the last step, as rank 0 holds them: its own staging
+        planes at N = 1, the gathered ones at N > 1 (complete once `sync` has drained the last gather).  A (3, G, len(cols)) array."""
+        from illico_amd.distributed import rank_gene_range, shard_bounds
+        torch = self.torch
+        cols = np.asarray(cols, dtype=np.int64)
+        out = np.empty((3, self.G, cols.size), dtype=np.float64)
+        if self.world == 1:
+            pieces = [(self.g_lb + lb, self.g_lb + ub, st) for (lb, ub), st in zip(self.blocks, self.stages)]
+        else:
+            assert self.gather and self.rank == 0, "the gathered planes are on rank 0"
+            recv = self.recv_sets[(self.step_no - 1) & 1]
+            pieces = []
+            for r in range(self.world):
+                r_lb, r_ub = rank_gene_range(self.M_total, r, self.world)
+                for b, (lb, ub) in enumerate(shard_bounds(r_ub - r_lb, len(self.blocks))):
+                    pieces.append((r_lb + lb, r_lb + ub, recv[b][r]))
+        for lb, ub, planes in pieces:
+            sel = np.nonzero((cols >= lb) & (cols < ub))[0]
+            if sel.size:
+                idx = torch.as_tensor(cols[sel] - lb, device=planes.device)
+                out[:, :, sel] = planes.index_select(2, idx).cpu().numpy()
+        return out
+
     def parity(self, n_genes=16):
         import oracle
         cols = sorted(set(np.linspace(0, self.M - 1, min(n_genes, self.M)).astype(int).tolist()))
@@ -406,8 +450,27 @@ class Job:
                 "bar": "statistic exact; p_value and fold_change rtol 1e-12", "against": "oracle/ (CPU restatement pinned to the reference's outputs)"}
 
 
-def measure(job, steps, warmup, settle=5, events=True):
-    """First call, settle + warm-up, one profiled step, the timed steps (gather inside when job.gather); returns a dict."""
+DUMP_BUDGET = 63_000_000  # bytes of planes --dump-outputs writes at most (the 64 MB bound, less the .npy headers)
+
+
+def dump_outputs(job, out_dir):
+    """The last timed step's planes as DIR/<plane>.npy (float64): every gene when they fit DUMP_BUDGET, else a fixed, seeded
+    sample of the genes (the same for the same shape) with every group.  Rank 0 only."""
+    per_gene = 3 * job.G * 8
+    k = min(job.M_total, max(1, DUMP_BUDGET // per_gene))
+    cols = np.arange(job.M_total) if k == job.M_total else np.sort(np.random.RandomState(0).choice(job.M_total, k, replace=False))
+    planes = job.output_columns(cols)
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, plane in zip(("p_value", "statistic", "fold_change"), planes):
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(plane))
+    print(f"[bench] --dump-outputs: p_value / statistic / fold_change, {job.G} groups x {cols.size} of {job.M_total} genes"
+          f"{'' if k == job.M_total else ' (RandomState(0) sample)'} -> {out_dir}", file=sys.stderr)
+
+
+def measure(job, steps, warmup, settle=5, events=True, profile=True):
+    """First call, settle + warm-up, one profiled step, the timed steps (gather inside when job.gather); returns a dict.
+    profile=False (a plain run): no profiled step and no events in the timed region."""
     eng = job.eng
     job.sync()
     t0 = time.perf_counter()
@@ -420,6 +483,10 @@ def measure(job, steps, warmup, settle=5, events=True):
     for _ in range(settle + warmup):
         job.step()
     job.sync()
+    if not profile:
+        dt = job.timed(steps)
+        return {"dt": dt, "ms_per_step": dt / steps * 1e3, "first_call_ms": first_call_ms, "breakdown": {}, "dom": None, "prof": {},
+                "settle": settle}
     # One untimed step with HIP events around every kernel: the per-kernel breakdown, and which kernel dominates.
     # Inside the timed region only that kernel carries events (each event pair drains the stream around a launch).
     eng.profile(True)
@@ -695,14 +762,17 @@ def main():
     in_step = world > 1 and not args.no_gather_in_step
     job.setup(args.gather_batches, gather=in_step)
 
-    m = measure(job, args.steps, args.warmup, events=not args.no_events)
+    m = measure(job, args.steps, args.warmup, events=not args.no_events, profile=args.full)
     ms_per_step = m["ms_per_step"]
     tests_per_step = G * M_total
     value = tests_per_step / (m["dt"] / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job, args.dump_outputs)
 
+    # everything below but the result line is --full only
     # N > 1: the same steps without the gather (pass only), and -- when the gather is not in the step -- the gather alone
     pass_only_ms, gather_ms = ms_per_step, None
-    if world > 1:
+    if world > 1 and args.full:
         if in_step:
             job.sync()
             job.setup(args.gather_batches, gather=False)
@@ -722,13 +792,13 @@ def main():
             gather_ms = max(0.0, float(t.item()) * 1e3 - ms_per_step)
     m["pass_ms"] = pass_only_ms
     single = None
-    if not args.no_single_call:
+    if args.full and not args.no_single_call:
         single = single_call_of(torch, dist, eng, args, job, job_kw, max(args.gather_batches, 4), tests_per_step, ms_per_step)
 
     # what this box's HBM delivers to a plain streaming read (boxes of the pool differ by up to 15 %: 1.65 vs 1.90 ms for the
     # same C2 kernel): torch's sum over the resident input
     calib = None
-    if rank == 0 and M > 0:
+    if args.full and rank == 0 and M > 0:
         src = job.X if job.X is not None else job.csx[0]
         src.sum(); torch.cuda.synchronize()
         tc = time.perf_counter()
@@ -749,17 +819,17 @@ def main():
         roofline = roofline_of(job, m, args.steps, wl_key)
 
         # ---- parity of what was just timed: 16 genes of the final step's planes against the oracle ----
-        parity = None if args.no_parity or M == 0 else job.parity(16)
+        parity = None if not args.full or args.no_parity or M == 0 else job.parity(16)
 
         # ---- CPU baseline: the oracle on this box's host cores, bounded sample, threads pinned ----
         cpu = None
-        if not args.no_cpu_baseline and world == 1:  # contract: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
             cpu = cpu_baseline_of(job, args.cpu_seconds)
 
         # ---- timing scopes (ii) engine + transfers and (iii) the drop-in call, SURVEY.md 8d ----
         scopes = {"engine_ms": round(ms_per_step, 4), "first_call_ms": round(m["first_call_ms"], 3),
                   "claim": "the >= 100x-over-CPU target of BASELINE.json is an engine-scope (input resident in HBM) figure; (ii) and (iii) are PCIe-bound"}
-        if not args.no_scopes and world == 1:
+        if args.full and not args.no_scopes and world == 1:
             try:
                 import pandas as pd
                 from illico_amd import AnnDataLite, asymptotic_wilcoxon
@@ -805,27 +875,29 @@ def main():
         result = {
             "metric": "(group x gene) tests/sec", "value": round(value, 1), "unit": "tests/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "scaling": args.scaling, "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full,
             "config": {"workload": WORKLOADS[args.workload]["label"].format(N=N, M=M_total, G=G) + ("" if args.values == "counts" else f" [{args.values} values]"),
                        "workload_id": args.workload, "cells": N, "genes_per_gpu": M, "genes_total": M_total, "groups": G, "format": args.fmt,
                        "test": args.test, "sparsity": args.sparsity, "values": args.values, "gene_mean_max": args.mean_max, "nnz_per_gpu": nnz,
                        "settle_steps": m["settle"],
                        "parallelism": f"gene-shard x{world}, planes gathered to rank 0" if world > 1 else "single GPU"},
-            "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "timing_scopes": scopes, "box_calibration": calib,
-            "single_call": single,
             "steady_state": {"ms_per_step": round(ms_per_step, 4), "tests_per_s": round(value, 1),
                              "note": "`value`: the timed steps back to back" + (", step k's gather under step k + 1's pass" if in_step else "")},
         }
+        if args.full:
+            result.update({"roofline": roofline, "cpu_baseline": cpu, "parity": parity, "timing_scopes": scopes, "box_calibration": calib,
+                           "single_call": single})
         if world > 1:
             plane_bytes = 24 * G * M
-            result["pass_only"] = {"ms_per_step": round(pass_only_ms, 4), "tests_per_s": round(tests_per_step / (pass_only_ms * 1e-3), 1),
-                                   "note": "the same steps without the gather: every rank's planes stay in its own HBM"}
+            if args.full:
+                result["pass_only"] = {"ms_per_step": round(pass_only_ms, 4), "tests_per_s": round(tests_per_step / (pass_only_ms * 1e-3), 1),
+                                       "note": "the same steps without the gather: every rank's planes stay in its own HBM"}
             if in_step:
                 result["final_gather"] = {"in_timed_step": True, "blocks_per_step": len(job.blocks), "bytes_per_rank_per_step": plane_bytes,
                                           "bytes_into_rank0_per_step": 24 * G * (M_total - M),
                                           "note": "value = tests / (pass + gather): step k's gather (torch.distributed.gather over RCCL) runs under step "
                                                   "k + 1's pass, every gather has completed when the clock stops"}
-            else:
+            elif args.full:
                 result["final_gather"] = {"in_timed_step": False, "ms": round(gather_ms, 3), "bytes_per_rank": plane_bytes,
                                           "bytes_into_rank0": 24 * G * (M_total - M),
                                           "one_pass_plus_gather_ms": round(ms_per_step + gather_ms, 3),
@@ -835,7 +907,7 @@ def main():
     torch.cuda.empty_cache()
 
     # ---- the other single-GPU BASELINE configs (and one continuous line) in the same launch ----
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         for tag in EXTRAS:
             try:
                 result[tag] = extra_config(torch, dist, eng, args, device, tag)
@@ -843,7 +915,7 @@ def main():
                 result[tag] = {"skipped": f"{type(e).__name__}: {str(e)[:300]}"}
 
     # ---- BASELINE configs[4] in the same launch: 1M x 30k x 5k dense OVO, genes split over the ranks ----
-    if not args.no_c5:
+    if args.full and not args.no_c5:
         c5 = None
         try:
             t_gen = time.perf_counter()

@@ -4,6 +4,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -22,7 +23,18 @@ def test_workload_table_and_overrides():
     assert (a.cells, a.genes, a.groups) == (1_000_000, 3_750, 5_000)   # 8 ranks x 3750 = the 30k genes of configs[4]
     a = bench.parse(["--workload", "c5"])
     assert (a.cells, a.genes, a.groups, a.scaling) == (1_000_000, 30_000, 5_000, "strong")   # configs[4] whole, genes split over the ranks
-    assert (a.c5_cells, a.c5_genes, a.c5_groups) == (1_000_000, 30_000, 5_000) and not a.no_c5  # ... and in every default line (c5_strong)
+    assert (a.c5_cells, a.c5_genes, a.c5_groups) == (1_000_000, 30_000, 5_000) and not a.no_c5  # ... and in every --full line (c5_strong)
+
+
+def test_plain_run_is_the_default_and_dump_outputs_needs_a_gathered_step():
+    sys.path.insert(0, str(ROOT))
+    import bench
+    a = bench.parse(["--steps", "7"])
+    assert a.steps == 7 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):   # at N > 1 rank 0 writes the gathered planes: there must be a gather in the step
+        bench.parse(["--gpus", "2", "--no-gather-in-step", "--dump-outputs", "out"])
 
 
 def test_gpus_flag_refuses_to_measure_fewer_ranks_than_asked():
@@ -38,13 +50,13 @@ def test_gpus_flag_refuses_to_measure_fewer_ranks_than_asked():
 
 @pytest.mark.gpu
 def test_two_ranks_spawned_by_bench_itself_gloo_shared_device():
-    """`python bench.py --gpus 2` with no launcher: bench.py starts the ranks, they rendezvous, split ONE workload's genes
+    """`python bench.py --gpus 2 --full` with no launcher: bench.py starts the ranks, they rendezvous, split ONE workload's genes
     (strong scaling, the default), run the timed steps WITH the gather inside them and rank 0 prints one line with n_gpus = 2,
     value = tests / (pass + gather), the pass-only figure beside it and the c5_strong object (BASELINE configs[4], here at a
     reduced size).  (gloo + one shared GPU: the box has a single GPU; RCCL itself runs in the driver's 8-GPU tier.)"""
     import os
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    common = ["--steps", "2", "--warmup", "1", "--cells", "20000", "--genes", "256", "--groups", "50", "--no-cpu-baseline", "--no-scopes",
+    common = ["--full", "--steps", "2", "--warmup", "1", "--cells", "20000", "--genes", "256", "--groups", "50", "--no-cpu-baseline", "--no-scopes",
               "--c5-cells", "30000", "--c5-genes", "192", "--c5-groups", "40", "--c5-steps", "2"]
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device", *common],
                        capture_output=True, text=True, env=env, timeout=900)
@@ -95,7 +107,7 @@ def test_two_ranks_spawned_by_bench_itself_gloo_shared_device():
         assert x["parity"]["statistic_mismatches"] == 0 and x["parity"]["p_value_max_rel_err"] <= 1e-12 and x["parity"]["fold_change_max_rel_err"] <= 1e-12
         assert x["cpu_baseline"] is None   # (--no-cpu-baseline in `common`)
     # ... with their CPU baselines when the headline has one
-    r3 = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--cells", "20000", "--genes", "256", "--groups", "50",
+    r3 = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cells", "20000", "--genes", "256", "--groups", "50",
                          "--no-scopes", "--no-c5", "--no-single-call", "--cpu-seconds", "0.3", "--extras-cpu-seconds", "0.2", "--extras-steps", "2"],
                         capture_output=True, text=True, env=env, timeout=900)
     assert r3.returncode == 0, r3.stderr[-2000:]
@@ -126,3 +138,61 @@ def test_matrix_blocks_do_not_depend_on_the_sharding():
     nb = bench.make_matrix(torch, 20000, 512, 0.5, 1, dev, values="nb")
     mx = nb.max(dim=0).values
     assert 0.05 < float((mx > 63).float().mean()) < 0.45 and float((mx > 255).float().mean()) > 0.005
+
+
+FULL_ONLY = ("roofline", "cpu_baseline", "parity", "timing_scopes", "box_calibration", "single_call", "pass_only", "c5_strong",
+             "c3", "c3_csr", "c4", "c2_continuous_ovr")
+
+
+def _bench_line(args, env, cwd):
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), *args], capture_output=True, text=True, env=env, cwd=cwd, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def _planes(d):
+    return [np.load(Path(d) / f"{name}.npy") for name in ("p_value", "statistic", "fold_change")]
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_steps_planes(tmp_path):
+    """A plain run is the headline alone -- no profiled, checked or baseline leg -- and `--dump-outputs DIR` writes the planes of
+    its last timed step: every gene here, the oracle's values, the same for a second run and for two ranks splitting the genes."""
+    import os
+    import torch
+    import oracle
+    sys.path.insert(0, str(ROOT))
+    import bench
+    from conftest import assert_planes_match
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    shape = ["--cells", "20000", "--genes", "256", "--groups", "50"]
+    one = _bench_line(["--steps", "3", "--warmup", "1", *shape, "--dump-outputs", str(tmp_path / "a")], env, tmp_path)
+    assert one["steps"] == 3 and one["warmup"] == 1 and one["full"] is False and one["n_gpus"] == 1
+    assert (one["metric"], one["unit"], one["higher_is_better"], one["dtype"]) == ("(group x gene) tests/sec", "tests/s", True, "f32")
+    assert one["ms_per_step"] > 0 and one["value"] == pytest.approx(50 * 256 / (one["ms_per_step"] * 1e-3), rel=1e-3)
+    assert not [k for k in FULL_ONLY if k in one], one.keys()
+    got = _planes(tmp_path / "a")
+    assert all(g.dtype == np.float64 and g.shape == (50, 256) for g in got)
+    # the planes are the oracle's for the workload's own matrix (bench.py's generator, seed 0)
+    cols = [0, 1, 127, 128, 255]
+    X = bench.make_matrix(torch, 20000, 256, 0.5, 0, torch.device("cuda", 0))[:, cols].contiguous().cpu().numpy()
+    grpc = bench.group_container(bench.make_labels(20000, 50, 0), 50, False)
+    want = oracle.run(X, grpc, batch_size=1)
+    assert_planes_match([g[:, cols] for g in got], want, ref_row=0, what="bench --dump-outputs")
+    # the same arguments, the same outputs; two ranks (strong scaling) whose planes rank 0 gathers: the same problem's planes
+    _bench_line(["--steps", "2", "--warmup", "1", *shape, "--dump-outputs", str(tmp_path / "b")], env, tmp_path)
+    again = _planes(tmp_path / "b")
+    two = _bench_line(["--gpus", "2", "--backend", "gloo", "--share-device", "--steps", "2", "--warmup", "1", *shape, "--gather-batches", "2",
+                       "--dump-outputs", str(tmp_path / "c")], env, tmp_path)
+    assert two["n_gpus"] == 2 and two["final_gather"]["in_timed_step"] is True and not [k for k in FULL_ONLY if k in two]
+    for a, b in zip(got, again):
+        np.testing.assert_array_equal(a, b)
+    assert_planes_match(_planes(tmp_path / "c"), got, ref_row=0, what="two ranks against one")
+    # planes beyond 63 MB: a fixed sample of the genes, every group
+    _bench_line(["--steps", "1", "--warmup", "0", "--cells", "3000", "--genes", "1400", "--groups", "2000", "--dump-outputs", str(tmp_path / "d")],
+                env, tmp_path)
+    big = _planes(tmp_path / "d")
+    assert all(g.shape == (2000, 1312) for g in big)
+    assert sum((tmp_path / "d" / f).stat().st_size for f in ("p_value.npy", "statistic.npy", "fold_change.npy")) <= 64_000_000

@@ -6,11 +6,11 @@ set -u
 BASE=$1; OUT=$2; shift 3
 SO=illico_amd/csrc/libillico_hip.so
 cp $SO /tmp/new.so
-python3 bench.py "$@" > ${OUT}_new.json 2> ${OUT}_new.err || exit 1
+python3 bench.py --full "$@" > ${OUT}_new.json 2> ${OUT}_new.err || exit 1
 cp $BASE $SO
-python3 bench.py "$@" > ${OUT}_base.json 2> ${OUT}_base.err || exit 1
+python3 bench.py --full "$@" > ${OUT}_base.json 2> ${OUT}_base.err || exit 1
 cp /tmp/new.so $SO
-python3 bench.py "$@" > ${OUT}_new2.json 2> ${OUT}_new2.err || exit 1
+python3 bench.py --full "$@" > ${OUT}_new2.json 2> ${OUT}_new2.err || exit 1
 python3 - <<PY
 import json
 for t in ("new", "base", "new2"):

@@ -9,7 +9,7 @@ PART=${2:-all}
 want() { [ "$PART" = all ] || [ "$PART" = "$1" ]; }
 O=gpurun_out
 mkdir -p $O
-b() { name=$1; shift; python3 bench.py "$@" > $O/${T}_bench_$name.json 2> $O/${T}_bench_$name.err; echo "bench $name rc=$?"; }
+b() { name=$1; shift; python3 bench.py --full "$@" > $O/${T}_bench_$name.json 2> $O/${T}_bench_$name.err; echo "bench $name rc=$?"; }
 want b1 && b c2 
 want b1 && b c3 --workload c3 --no-c5 --no-extras
 want b1 && b c3_ovr --workload c3 --test ovr --no-c5 --no-extras

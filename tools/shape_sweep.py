@@ -185,7 +185,7 @@ SETS: dict[str, list[tuple[str, str]]] = {
         ("csr_cont_f32_ovo", "--workload c3 --format csr --values continuous"),
     ],
 }
-COMMON = "--no-c5 --no-extras --warmup 1 --no-cpu-baseline --no-scopes --no-single-call"
+COMMON = "--full --no-c5 --no-extras --warmup 1 --no-cpu-baseline --no-scopes --no-single-call"
 
 
 def run_one(tag: str, args: str, steps: int, timeout: int, extra: str) -> str:
