@@ -23,6 +23,11 @@ IDX_I32, IDX_I64 = 0, 1
 ALTERNATIVES = {"two-sided": 0, "less": 1, "greater": 2}
 FLAG_LOG1P, FLAG_CONTINUITY, FLAG_TIE_CORRECT, FLAG_INPUT_DEVICE, FLAG_OUTPUT_DEVICE, FLAG_DEFER = 1, 2, 4, 8, 16, 32
 
+ADJ_BH, ADJ_BY, ADJ_BONFERRONI = 0, 1, 2
+ADJUST_METHODS = {"bh": ADJ_BH, "by": ADJ_BY, "bonferroni": ADJ_BONFERRONI}
+#: longest row of p-values one workgroup sorts in LDS (ILLICO_ADJ_LDS_COLS); longer rows take the route through device scratch
+ADJUST_LDS_COLS = 8192
+
 _DTYPES = {np.dtype(np.float32): F32, np.dtype(np.float64): F64, np.dtype(np.int32): I32, np.dtype(np.int64): I64}
 
 # every symbol include/illico_hip.h declares
@@ -32,6 +37,7 @@ SYMBOLS = [
     "illico_run_csr", "illico_csr_indices_sorted", "illico_rank_statistics", "illico_profile_num_kernels", "illico_profile_kernel_name",
     "illico_profile_get", "illico_profile_reset", "illico_version", "illico_csr_bind", "illico_csc_bind", "illico_run_bound",
     "illico_matrix_release", "illico_matrix_touch", "illico_profile_input_bytes", "illico_planes_to_host",
+    "illico_adjust_pvalues",
 ]
 
 _lib = None
@@ -76,6 +82,7 @@ def load() -> ctypes.CDLL:
         lib.illico_matrix_touch.argtypes = [vp, vp]
         lib.illico_profile_input_bytes.argtypes = [vp, ctypes.POINTER(i64)]
         lib.illico_planes_to_host.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64]
+        lib.illico_adjust_pvalues.argtypes = [vp, vp, i64, i64, i64, ci, ci, vp, i64, i64, vp, i64]
         for name in SYMBOLS:  # fail at load time, not at first use, if the library and the header have drifted
             getattr(lib, name)
         _lib = lib
@@ -394,6 +401,35 @@ class Engine:
         del keep
         return two_u, tie, vsum
 
+    def adjust_pvalues(self, p, method="bh", *, n_top=0, out=None):
+        """Per-row multiple-testing correction of a p-value plane (include/illico_hip.h: illico_adjust_pvalues).
+
+        ``p``: float64 ``[G, M]``, a numpy array or a CUDA tensor with unit column stride (a view of a wider plane is fine).
+        ``method``: ``"bh"``, ``"by"`` or ``"bonferroni"``.  Outputs live where ``p`` lives; ``out`` (same side, float64 ``[G, M]``,
+        unit column stride; ``p`` itself adjusts in place) receives the adjusted values.  Returns ``adj``, or ``(adj, top)`` with
+        ``top`` int64 ``[G, n_top]`` -- each row's first ``n_top`` columns by ascending p, ties by column -- when ``n_top > 0``."""
+        code = _adjust_method(method)
+        p, G, M, ld, on_dev = _adjust_plane(p, "p", copy_ok=True)
+        n_top = _adjust_n_top(n_top, M)
+        if on_dev:
+            import torch
+            adj = torch.empty((G, M), dtype=torch.float64, device=p.device) if out is None else out
+            top = torch.empty((G, n_top), dtype=torch.int64, device=p.device) if n_top else None
+        else:
+            adj = np.empty((G, M), dtype=np.float64) if out is None else out
+            top = np.empty((G, n_top), dtype=np.int64) if n_top else None
+        adj, oG, oM, out_ld, o_dev = _adjust_plane(adj, "out", copy_ok=False)
+        if (oG, oM) != (G, M) or o_dev != on_dev:
+            raise ValueError(f"out must be a float64 [{G}, {M}] plane on the same side as p")
+        if not on_dev and not adj.flags.writeable:
+            raise ValueError("out must be writeable")
+        if G and M:
+            self._bind_torch_stream(p, adj, top)
+            ptr = (lambda x: x.data_ptr()) if on_dev else (lambda x: x.ctypes.data)
+            self._check(self.lib.illico_adjust_pvalues(self.h, ptr(p), G, M, ld, code, (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0,
+                                                       ptr(adj), out_ld, n_top, ptr(top) if n_top else None, max(n_top, 1)))
+        return (adj, top) if n_top else adj
+
     def csr_indices_sorted(self, indices, indptr, n_rows) -> bool:
         i, p = _Buf(indices), _Buf(indptr)
         if i.np_dtype != p.np_dtype:
@@ -466,6 +502,46 @@ class BoundMatrix:
             self.release()
         except Exception:
             pass
+
+
+def _adjust_method(method) -> int:
+    try:
+        return ADJUST_METHODS[method]
+    except (KeyError, TypeError):
+        raise ValueError(f"Unknown p-value adjustment method {method!r}: one of {sorted(ADJUST_METHODS)}") from None
+
+
+def _adjust_n_top(n_top, M) -> int:
+    if isinstance(n_top, bool) or not isinstance(n_top, (int, np.integer)):
+        raise ValueError(f"n_top must be an integer, got {n_top!r}")
+    if n_top < 0 or n_top > M:
+        raise ValueError(f"n_top = {n_top} outside [0, {M}] (the plane has {M} columns)")
+    return int(n_top)
+
+
+def _adjust_plane(x, what, copy_ok):
+    """(plane, rows, columns, row pitch in elements, on the device) of a float64 2-D plane whose rows the C side can walk: unit
+    column stride, rows evenly pitched and not overlapping.  copy_ok: a host plane that is not laid out so is copied."""
+    if _is_torch_tensor(x):
+        import torch
+        if not x.is_cuda:
+            raise ValueError(f"{what} must be a numpy array or a CUDA tensor (got a CPU tensor)")
+        if x.dtype != torch.float64 or x.dim() != 2:
+            raise ValueError(f"{what} must be a float64 2-D tensor, got {x.dtype} with {x.dim()} dimensions")
+        G, M = (int(v) for v in x.shape)
+        if (M > 1 and x.stride(1) != 1) or (G > 1 and x.stride(0) < M):
+            raise ValueError(f"{what} must have unit column stride and rows that do not overlap")
+        return x, G, M, int(x.stride(0)) if G > 1 else M, True
+    if not isinstance(x, np.ndarray):
+        raise ValueError(f"{what} must be a numpy array or a CUDA tensor, got {type(x).__name__}")
+    if x.dtype != np.float64 or x.ndim != 2:
+        raise ValueError(f"{what} must be a float64 2-D array, got {x.dtype} with {x.ndim} dimensions")
+    G, M = x.shape
+    if not ((M <= 1 or x.strides[1] == 8) and (G <= 1 or (x.strides[0] % 8 == 0 and x.strides[0] >= 8 * M))):
+        if not copy_ok:
+            raise ValueError(f"{what} must have unit column stride and rows that do not overlap")
+        x = np.ascontiguousarray(x)
+    return x, G, M, x.strides[0] // 8 if G > 1 else M, False
 
 
 def _current_device() -> int:

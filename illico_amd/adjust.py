@@ -1,0 +1,89 @@
+"""Multiple-testing correction and top-gene ranking of the engine's p-value planes, on the device.
+
+``adjust_pvalues`` corrects a ``[G, M]`` plane of p-values within each row (group) -- Benjamini-Hochberg as scipy's
+``stats.false_discovery_control(p, axis=1)`` computes it, Benjamini-Yekutieli, Bonferroni -- and optionally returns each row's
+``n_top`` columns by ascending p.  ``differential_expression`` is ``asymptotic_wilcoxon`` followed by that step: the same
+DataFrame plus a ``p_value_adj`` column, optionally cut to each group's top genes.
+"""
+from __future__ import annotations
+
+import numpy as np
+import pandas as pd
+
+from illico_amd import _lib
+from illico_amd.asymptotic_wilcoxon import _planes_frame, _wilcoxon_planes
+
+__all__ = ["adjust_pvalues", "differential_expression"]
+
+#: method names -> the engine's codes (include/illico_hip.h: ILLICO_ADJ_*)
+METHODS = {"bh": "bh", "benjamini-hochberg": "bh", "by": "by", "benjamini-yekutieli": "by", "bonferroni": "bonferroni"}
+
+
+def _method(name) -> str:
+    try:
+        return METHODS[name.lower()]
+    except (KeyError, AttributeError):
+        raise ValueError(f"Unknown p-value correction method {name!r}: one of {sorted(METHODS)}") from None
+
+
+def adjust_pvalues(p, method: str = "benjamini-hochberg", *, n_top: int = 0):
+    """Adjust each row of a p-value plane for multiple testing.
+
+    ``p``: float64 ``[G, M]`` numpy array or CUDA tensor with unit column stride (a view of a wider plane is fine), every value in
+    [0, 1].  ``method``: ``"bh"`` / ``"benjamini-hochberg"``, ``"by"`` / ``"benjamini-yekutieli"`` or ``"bonferroni"``.  The result
+    lives where ``p`` lives: ``adj`` float64 ``[G, M]``, or ``(adj, top)`` with ``top`` int64 ``[G, n_top]`` -- each row's first
+    ``n_top`` columns sorted by ascending p, ties by column (``np.argsort(p + 0.0, axis=1, kind="stable")[:, :n_top]``) -- when
+    ``n_top > 0``.  Raises ``ValueError`` for a NaN or a value outside [0, 1], naming its position, as scipy does.
+    """
+    code = _method(method)
+    _check_plane(p)
+    _lib._adjust_n_top(n_top, int(p.shape[1]))
+    device = p.device.index if _lib._is_torch_tensor(p) else None
+    return _lib.get_engine(device).adjust_pvalues(p, code, n_top=n_top)
+
+
+def _check_plane(p):
+    """The dtype / rank / residency checks of Engine.adjust_pvalues, before any engine exists."""
+    if _lib._is_torch_tensor(p):
+        import torch
+        if not p.is_cuda:
+            raise ValueError("p must be a numpy array or a CUDA tensor (got a CPU tensor)")
+        if p.dtype != torch.float64 or p.dim() != 2:
+            raise ValueError(f"p must be a float64 2-D tensor, got {p.dtype} with {p.dim()} dimensions")
+    elif not isinstance(p, np.ndarray):
+        raise ValueError(f"p must be a numpy array or a CUDA tensor, got {type(p).__name__}")
+    elif p.dtype != np.float64 or p.ndim != 2:
+        raise ValueError(f"p must be a float64 2-D array, got {p.dtype} with {p.ndim} dimensions")
+
+
+def differential_expression(adata, is_log1p: bool, group_keys: str, reference: str | None = None, *,
+                            corr_method: str = "benjamini-hochberg", n_genes: int | None = None, **kw) -> pd.DataFrame:
+    """``asymptotic_wilcoxon`` plus the multiple-testing correction that follows it in a DE workflow.
+
+    ``kw`` takes the other arguments of ``asymptotic_wilcoxon`` (``batch_size``, ``alternative``, ``layer``, ...).  Returns its
+    DataFrame -- the same ``p_value``, ``statistic`` and ``fold_change`` -- plus a float64 ``p_value_adj`` column: ``corr_method``
+    applied within each group across all genes of the call.  With ``n_genes``, each group keeps only its ``n_genes`` rows of smallest
+    p (ties by gene order), in that order; the groups keep their order.  The reference group's row of a one-versus-one call stays,
+    as ``asymptotic_wilcoxon`` keeps it (its p are 1.0, so are their adjusted values).
+    """
+    code = _method(corr_method)
+    if n_genes is not None and (isinstance(n_genes, bool) or not isinstance(n_genes, (int, np.integer)) or n_genes < 1):
+        raise ValueError(f"n_genes must be a positive integer or None, got {n_genes!r}")
+    unknown = set(kw) - {"n_threads", "batch_size", "alternative", "use_continuity", "tie_correct", "layer", "precompile"}
+    if unknown:
+        raise TypeError(f"differential_expression() got unexpected keyword arguments {sorted(unknown)}")
+    args = dict(n_threads=1, batch_size="auto", alternative="two-sided", use_continuity=True, tie_correct=True, layer=None)
+    args.update({k: v for k, v in kw.items() if k != "precompile"})
+    planes, index = _wilcoxon_planes(adata, is_log1p, group_keys, reference, **args)
+    G, M = planes.shape[1], planes.shape[2]
+    n_top = min(int(n_genes), M) if n_genes is not None else 0
+    if G and M:
+        res = _lib.get_engine().adjust_pvalues(planes[0], code, n_top=n_top)
+        adj, top = res if n_top else (res, None)
+    else:
+        adj, top = np.empty((G, M), dtype=np.float64), np.empty((G, 0), dtype=np.int64)
+    df = _planes_frame(planes, index, p_value_adj=adj)
+    if n_genes is None:
+        return df
+    rows = (np.arange(G, dtype=np.int64)[:, None] * M + top[:, :n_top]).reshape(-1)
+    return df.iloc[rows]

@@ -87,6 +87,22 @@ def asymptotic_wilcoxon(
     Raises ``ValueError`` (unsorted CSR indices, unknown reference label, bad ``batch_size`` or
     ``alternative``) and ``KeyError`` (unsupported container) like the reference.
     """
+    planes, index = _wilcoxon_planes(adata, is_log1p, group_keys, reference, n_threads, batch_size, alternative, use_continuity,
+                                     tie_correct, layer)
+    return _planes_frame(planes, index)
+
+
+def _planes_frame(planes: np.ndarray, index: pd.MultiIndex, **extra) -> pd.DataFrame:
+    """The result DataFrame of the three [G, n_genes] planes (group-major rows), plus any further float64 [G, n_genes] columns."""
+    cols = {"p_value": planes[0].reshape(-1), "statistic": planes[1].reshape(-1), "fold_change": planes[2].reshape(-1)}
+    cols.update({k: v.reshape(-1) for k, v in extra.items()})
+    return pd.DataFrame(cols, index=index, copy=False)
+
+
+def _wilcoxon_planes(adata, is_log1p, group_keys, reference, n_threads, batch_size, alternative, use_continuity, tie_correct,
+                     layer) -> tuple[np.ndarray, pd.MultiIndex]:
+    """The body of ``asymptotic_wilcoxon``: the planes float64 [3, G, n_genes] (p_value, statistic, fold_change) and the
+    (pert, feature) MultiIndex of their G x n_genes rows."""
     X = adata.layers[layer] if layer is not None else adata.X
     data_handler = data_handler_registry.get(X)
 
@@ -163,11 +179,7 @@ def asymptotic_wilcoxon(
     index_thread.join()
     if isinstance(index_box[0], BaseException):
         raise index_box[0]
-    return pd.DataFrame(
-        {"p_value": planes[0].reshape(-1), "statistic": planes[1].reshape(-1), "fold_change": planes[2].reshape(-1)},
-        index=index_box[0],
-        copy=False,
-    )
+    return planes, index_box[0]
 
 
 def _product_index(rows: pd.Series, cols: pd.Series) -> pd.MultiIndex:

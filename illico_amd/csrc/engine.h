@@ -61,6 +61,11 @@ enum {
     KID_CSR_COUNTS,
     KID_DENSIFY,
     KID_GROUP_HISTS,
+    KID_ADJ_VALIDATE, // illico_adjust_pvalues (kernels_adjust.h)
+    KID_ADJ_SORT,
+    KID_ADJ_MERGE,
+    KID_ADJ_SCAN,
+    KID_ADJ_BONF,
     KID_COUNT
 };
 extern const char *const kKernelNames[KID_COUNT];

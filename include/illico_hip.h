@@ -206,6 +206,30 @@ int illico_rank_statistics(illico_ctx *ctx, const void *X, int dtype, int64_t n_
 int illico_planes_to_host(illico_ctx *ctx, const double *dev_p, const double *dev_u, const double *dev_fc, int64_t n_cols,
                           double *out_p, double *out_u, double *out_fc, int64_t out_ld);
 
+/* ---- multiple-testing correction of a p-value plane ---------------------------------------
+ * p: float64 [n_rows][n_cols], row pitch in_ld >= n_cols: one row per group, one column per gene (the out_p plane of the calls
+ * above).  Each row is adjusted on its own, m = n_cols:
+ *   ILLICO_ADJ_BH          Benjamini-Hochberg: adj_(i) = min_{k >= i} p_(k) * (m / k), clipped to 1 -- bit for bit what scipy's
+ *                          stats.false_discovery_control(p, axis=1, method="bh") returns;
+ *   ILLICO_ADJ_BY          Benjamini-Yekutieli: the same with an extra factor c_m = sum_{i <= m} 1 / i, formed on the host in the
+ *                          order numpy's pairwise sum takes (blocks of 8192, its default buffer): scipy's method="by" within a
+ *                          relative 1e-14 -- bit for bit as long as numpy sums that way;
+ *   ILLICO_ADJ_BONFERRONI  min(p * m, 1).
+ * m == 1 returns p unchanged; zeros come out as +0.0.  out_adj: float64 [n_rows][out_ld >= n_cols], or null (top-n only); it may be p
+ * itself (in place, out_ld == in_ld).  n_top > 0: out_top int64 [n_rows][top_ld >= n_top] receives the first n_top columns of the row
+ * sorted ascending by p, ties by ascending column -- numpy's argsort(p + 0.0, kind="stable")[:, :n_top]; n_top == 0: none.
+ * flags: ILLICO_FLAG_INPUT_DEVICE (p on the device), ILLICO_FLAG_OUTPUT_DEVICE (out_adj / out_top on the device).  Host outputs are
+ * complete on return, device outputs are ordered on the context's stream.  A deferred call (ILLICO_FLAG_DEFER) is completed first.
+ * ILLICO_ERR_ARG: null pointers, a pitch below the width, n_top > n_cols, an unknown method, or a p that is NaN or outside [0, 1]
+ * (illico_last_error names the first such (row, column); nothing is written -- except, for a host plane larger than the
+ * "scratch_bytes" cap, the batches of rows before the offending one).  Rows of up to ILLICO_ADJ_LDS_COLS p-values are sorted by one
+ * workgroup in LDS; longer rows through device scratch (the "scratch_bytes" cap; rows are processed in batches). */
+enum { ILLICO_ADJ_BH = 0, ILLICO_ADJ_BY = 1, ILLICO_ADJ_BONFERRONI = 2 };
+enum { ILLICO_ADJ_LDS_COLS = 8192 };
+int illico_adjust_pvalues(illico_ctx *ctx, const double *p, int64_t n_rows, int64_t n_cols, int64_t in_ld,
+                          int method, int flags, double *out_adj, int64_t out_ld,
+                          int64_t n_top, int64_t *out_top, int64_t top_ld);
+
 /* ---- measurement hooks (bench.py roofline leg) ------------------------------------------- */
 int illico_profile_num_kernels(void);
 const char *illico_profile_kernel_name(int kernel_id);
