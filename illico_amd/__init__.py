@@ -6,6 +6,7 @@
 from illico_amd.anndata_lite import AnnDataLite
 from illico_amd.adjust import adjust_pvalues, differential_expression
 from illico_amd.asymptotic_wilcoxon import asymptotic_wilcoxon
+from illico_amd.group_stats import group_statistics
 
-__all__ = ["asymptotic_wilcoxon", "AnnDataLite", "adjust_pvalues", "differential_expression"]
+__all__ = ["asymptotic_wilcoxon", "AnnDataLite", "adjust_pvalues", "differential_expression", "group_statistics"]
 __version__ = "0.1.0"

@@ -37,7 +37,7 @@ SYMBOLS = [
     "illico_run_csr", "illico_csr_indices_sorted", "illico_rank_statistics", "illico_profile_num_kernels", "illico_profile_kernel_name",
     "illico_profile_get", "illico_profile_reset", "illico_version", "illico_csr_bind", "illico_csc_bind", "illico_run_bound",
     "illico_matrix_release", "illico_matrix_touch", "illico_profile_input_bytes", "illico_planes_to_host",
-    "illico_adjust_pvalues",
+    "illico_adjust_pvalues", "illico_group_stats_dense", "illico_group_stats_csc", "illico_group_stats_csr", "illico_group_stats_bound",
 ]
 
 _lib = None
@@ -83,6 +83,10 @@ def load() -> ctypes.CDLL:
         lib.illico_profile_input_bytes.argtypes = [vp, ctypes.POINTER(i64)]
         lib.illico_planes_to_host.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64]
         lib.illico_adjust_pvalues.argtypes = [vp, vp, i64, i64, i64, ci, ci, vp, i64, i64, vp, i64]
+        lib.illico_group_stats_dense.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, vp, vp, vp, vp, i64]
+        for f in (lib.illico_group_stats_csc, lib.illico_group_stats_csr):
+            f.argtypes = [vp, vp, ci, vp, vp, ci, i64, i64, i64, i64, ci, vp, vp, vp, vp, i64]
+        lib.illico_group_stats_bound.argtypes = [vp, vp, i64, i64, ci, vp, vp, vp, vp, i64]
         for name in SYMBOLS:  # fail at load time, not at first use, if the library and the header have drifted
             getattr(lib, name)
         _lib = lib
@@ -430,6 +434,117 @@ class Engine:
                                                        ptr(adj), out_ld, n_top, ptr(top) if n_top else None, max(n_top, 1)))
         return (adj, top) if n_top else adj
 
+    # ---- per-group expression statistics (include/illico_hip.h: illico_group_stats_*) ----
+    def _gs_outputs(self, out, G, W, rest, want_device):
+        """(planes, pointers, output flag, row pitch) of the statistics planes: ``out`` None (allocate nnz int64 / sum float64 [G, W],
+        plus their rest planes with ``rest``) or a tuple of 2 or 4 planes in that order (nnz, sum[, nnz_rest, sum_rest]), each a
+        host ndarray or a CUDA tensor of the right dtype with unit column stride, or None (not computed)."""
+        kinds = (np.int64, np.float64, np.int64, np.float64)
+        if out is None:
+            n = 4 if rest else 2
+            if want_device:
+                import torch
+                tdt = {np.int64: torch.int64, np.float64: torch.float64}
+                planes = tuple(torch.empty((G, W), dtype=tdt[kinds[k]], device=f"cuda:{self.device}") for k in range(n))
+            else:
+                planes = tuple(np.empty((G, W), dtype=kinds[k]) for k in range(n))
+        else:
+            planes = tuple(out)
+            if len(planes) not in (2, 4):
+                raise ValueError("out must hold 2 planes (nnz, sum) or 4 (nnz, sum, nnz_rest, sum_rest)")
+        if all(p is None for p in planes):
+            raise ValueError("at least one output plane is needed")
+        ptrs, side, ld = [], None, None
+        for k, p in enumerate(planes):
+            if p is None:
+                ptrs.append(None)
+                continue
+            if _is_torch_tensor(p):
+                import torch
+                want = torch.int64 if kinds[k] is np.int64 else torch.float64
+                if not p.is_cuda or p.dtype != want or p.dim() != 2 or tuple(p.shape) != (G, W) or (W > 1 and p.stride(1) != 1):
+                    raise ValueError(f"device output plane {k} must be a CUDA {want} [{G}, {W}] tensor with unit column stride")
+                l, dev, ptr = (int(p.stride(0)) if G > 1 else W), True, p.data_ptr()
+            else:
+                if not isinstance(p, np.ndarray) or p.dtype != kinds[k] or p.ndim != 2 or p.shape != (G, W) or \
+                        (W > 1 and p.strides[1] != 8) or (G > 1 and p.strides[0] % 8) or not p.flags.writeable:
+                    raise ValueError(f"output plane {k} must be a writeable {np.dtype(kinds[k])} [{G}, {W}] array with unit column stride")
+                l, dev, ptr = (p.strides[0] // 8 if G > 1 else W), False, p.ctypes.data
+            if side is None:
+                side = dev
+            elif side != dev:
+                raise ValueError("output planes must all live on the same side (host or device)")
+            if ld is None:
+                ld = l
+            elif ld != l:
+                raise ValueError("output planes must share one row stride")
+            ptrs.append(ptr)
+        ptrs += [None] * (4 - len(ptrs))
+        return planes, ptrs, FLAG_OUTPUT_DEVICE if side else 0, int(max(ld or 1, W, 1))
+
+    def group_stats(self, X, col_lb, col_ub, *, is_log1p=False, rest=False, out=None):
+        """Per-group non-zero counts and value sums of the dense columns [col_lb, col_ub) (illico_group_stats_dense).
+
+        ``X``: a row-major numpy array or a CUDA tensor.  Returns ``(nnz, sum)`` -- int64 / float64 ``[G, W]`` -- or, with
+        ``rest=True``, ``(nnz, sum, nnz_rest, sum_rest)``, living where ``X`` lives unless ``out`` (see ``_gs_outputs``) says otherwise."""
+        if _is_torch_tensor(X):
+            if X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1):
+                raise ValueError("X must be row-major 2-D")
+            ptr, on_dev, keep = X.data_ptr(), X.is_cuda, X
+            n_rows, n_cols = int(X.shape[0]), int(X.shape[1])
+            ld = int(X.stride(0)) if n_rows > 1 else n_cols
+            dt = dtype_code(str(X.dtype).replace("torch.", ""))
+        else:
+            X = normalize_values(np.asarray(X))
+            if X.ndim != 2:
+                raise ValueError(f"X must be 2-D, got {X.ndim} dimensions")
+            if (X.shape[1] > 1 and X.strides[1] != X.itemsize) or X.strides[0] % X.itemsize or X.strides[0] < 0:
+                X = np.ascontiguousarray(X)
+            ptr, on_dev, keep = X.ctypes.data, False, X
+            n_rows, n_cols = X.shape
+            ld = X.strides[0] // X.itemsize if n_rows > 1 else n_cols
+            dt = dtype_code(X.dtype)
+        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
+            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        G, W = self.n_groups, col_ub - col_lb
+        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, on_dev)
+        if W == 0:
+            return planes
+        flags = (FLAG_LOG1P if is_log1p else 0) | (FLAG_INPUT_DEVICE if on_dev else 0) | oflag
+        self._bind_torch_stream(keep, *[p for p in planes if p is not None])
+        self._check(self.lib.illico_group_stats_dense(self.h, ptr, dt, n_rows, n_cols, max(ld, n_cols), col_lb, col_ub, flags, *ptrs, out_ld))
+        del keep
+        return planes
+
+    def group_stats_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, *, is_log1p=False, rest=False, out=None):
+        """``group_stats`` of a CSC (``fmt="csc"``) or CSR (``"csr"``) matrix given as its three arrays (numpy or CUDA tensors);
+        CSR rows need not be sorted.  Duplicate entries count once per stored entry."""
+        if fmt not in ("csc", "csr"):
+            raise ValueError(f"fmt must be 'csc' or 'csr', got {fmt!r}")
+        n_rows, n_cols = int(shape[0]), int(shape[1])
+        if _is_torch_tensor(data):
+            d, i, p = _Buf(data), _Buf(indices), _Buf(indptr)
+        else:
+            d = _Buf(normalize_values(np.asarray(data)))
+            idt = np.int32 if (np.asarray(indices).dtype == np.int32 and np.asarray(indptr).dtype == np.int32) else np.int64
+            i, p = _Buf(indices, idt), _Buf(indptr, idt)
+        if i.np_dtype != p.np_dtype or i.np_dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+            raise KeyError(f"Support for index dtypes {i.np_dtype}/{p.np_dtype} is not implemented.")
+        if not (d.on_device == i.on_device == p.on_device):
+            raise ValueError("data, indices and indptr must live on the same side (host or device)")
+        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
+            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        G, W = self.n_groups, col_ub - col_lb
+        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, d.on_device)
+        if W == 0:
+            return planes
+        flags = (FLAG_LOG1P if is_log1p else 0) | (FLAG_INPUT_DEVICE if d.on_device else 0) | oflag
+        fn = self.lib.illico_group_stats_csc if fmt == "csc" else self.lib.illico_group_stats_csr
+        self._bind_torch_stream(d.keep, i.keep, p.keep, *[q for q in planes if q is not None])
+        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, IDX_I32 if i.np_dtype == np.int32 else IDX_I64,
+                       n_rows, n_cols, col_lb, col_ub, flags, *ptrs, out_ld))
+        return planes
+
     def csr_indices_sorted(self, indices, indptr, n_rows) -> bool:
         i, p = _Buf(indices), _Buf(indptr)
         if i.np_dtype != p.np_dtype:
@@ -486,6 +601,20 @@ class BoundMatrix:
         flags = eng._flags(is_log1p, use_continuity, tie_correct) | oflag | (FLAG_DEFER if defer else 0)
         eng._bind_torch_stream(*planes)
         eng._check(eng.lib.illico_run_bound(eng.h, self.h, col_lb, col_ub, flags, alt, ptrs[0], ptrs[1], ptrs[2], out_ld))
+        return planes
+
+    def group_stats(self, col_lb, col_ub, *, is_log1p=False, rest=False, out=None, device_out=False):
+        """``Engine.group_stats`` of the bound matrix (illico_group_stats_bound); host planes unless ``device_out`` or ``out``."""
+        eng = self.engine
+        n_cols = self.shape[1]
+        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
+            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        G, W = eng.n_groups, col_ub - col_lb
+        planes, ptrs, oflag, out_ld = eng._gs_outputs(out, G, W, rest, device_out)
+        if W == 0:
+            return planes
+        eng._bind_torch_stream(*[p for p in planes if p is not None])
+        eng._check(eng.lib.illico_group_stats_bound(eng.h, self.h, col_lb, col_ub, (FLAG_LOG1P if is_log1p else 0) | oflag, *ptrs, out_ld))
         return planes
 
     def touch(self):

@@ -57,16 +57,20 @@ def _check_plane(p):
 
 
 def differential_expression(adata, is_log1p: bool, group_keys: str, reference: str | None = None, *,
-                            corr_method: str = "benjamini-hochberg", n_genes: int | None = None, **kw) -> pd.DataFrame:
+                            corr_method: str = "benjamini-hochberg", n_genes: int | None = None, pts: bool = False, **kw) -> pd.DataFrame:
     """``asymptotic_wilcoxon`` plus the multiple-testing correction that follows it in a DE workflow.
 
     ``kw`` takes the other arguments of ``asymptotic_wilcoxon`` (``batch_size``, ``alternative``, ``layer``, ...).  Returns its
     DataFrame -- the same ``p_value``, ``statistic`` and ``fold_change`` -- plus a float64 ``p_value_adj`` column: ``corr_method``
     applied within each group across all genes of the call.  With ``n_genes``, each group keeps only its ``n_genes`` rows of smallest
     p (ties by gene order), in that order; the groups keep their order.  The reference group's row of a one-versus-one call stays,
-    as ``asymptotic_wilcoxon`` keeps it (its p are 1.0, so are their adjusted values).
+    as ``asymptotic_wilcoxon`` keeps it (its p are 1.0, so are their adjusted values).  ``pts=True`` adds the four columns of
+    ``group_statistics`` (``pct_group``, ``pct_reference``, ``mean_group``, ``mean_reference``) before the ``n_genes`` cut, so they
+    stay on their rows; an in-RAM CSR matrix is uploaded once for both passes.
     """
     code = _method(corr_method)
+    if not isinstance(pts, (bool, np.bool_)):
+        raise ValueError(f"pts must be a bool, got {pts!r}")
     if n_genes is not None and (isinstance(n_genes, bool) or not isinstance(n_genes, (int, np.integer)) or n_genes < 1):
         raise ValueError(f"n_genes must be a positive integer or None, got {n_genes!r}")
     unknown = set(kw) - {"n_threads", "batch_size", "alternative", "use_continuity", "tie_correct", "layer", "precompile"}
@@ -74,7 +78,8 @@ def differential_expression(adata, is_log1p: bool, group_keys: str, reference: s
         raise TypeError(f"differential_expression() got unexpected keyword arguments {sorted(unknown)}")
     args = dict(n_threads=1, batch_size="auto", alternative="two-sided", use_continuity=True, tie_correct=True, layer=None)
     args.update({k: v for k, v in kw.items() if k != "precompile"})
-    planes, index = _wilcoxon_planes(adata, is_log1p, group_keys, reference, **args)
+    inputs: list = []
+    planes, index = _wilcoxon_planes(adata, is_log1p, group_keys, reference, **args, inputs=inputs)
     G, M = planes.shape[1], planes.shape[2]
     n_top = min(int(n_genes), M) if n_genes is not None else 0
     if G and M:
@@ -82,7 +87,12 @@ def differential_expression(adata, is_log1p: bool, group_keys: str, reference: s
         adj, top = res if n_top else (res, None)
     else:
         adj, top = np.empty((G, M), dtype=np.float64), np.empty((G, 0), dtype=np.int64)
-    df = _planes_frame(planes, index, p_value_adj=adj)
+    extra = {}
+    if pts:
+        from illico_amd.group_stats import stat_planes
+        X, handler, group_container = inputs[0]
+        extra = stat_planes(X, handler, group_container, bool(is_log1p))
+    df = _planes_frame(planes, index, p_value_adj=adj, **extra)
     if n_genes is None:
         return df
     rows = (np.arange(G, dtype=np.int64)[:, None] * M + top[:, :n_top]).reshape(-1)

@@ -100,9 +100,10 @@ def _planes_frame(planes: np.ndarray, index: pd.MultiIndex, **extra) -> pd.DataF
 
 
 def _wilcoxon_planes(adata, is_log1p, group_keys, reference, n_threads, batch_size, alternative, use_continuity, tie_correct,
-                     layer) -> tuple[np.ndarray, pd.MultiIndex]:
+                     layer, inputs: list | None = None) -> tuple[np.ndarray, pd.MultiIndex]:
     """The body of ``asymptotic_wilcoxon``: the planes float64 [3, G, n_genes] (p_value, statistic, fold_change) and the
-    (pert, feature) MultiIndex of their G x n_genes rows."""
+    (pert, feature) MultiIndex of their G x n_genes rows.  ``inputs``: a list that receives (X, data handler, GroupContainer) of the
+    call -- the handler of an in-RAM CSR matrix is its device copy, which a later pass over the same matrix can reuse."""
     X = adata.layers[layer] if layer is not None else adata.X
     data_handler = data_handler_registry.get(X)
 
@@ -129,6 +130,8 @@ def _wilcoxon_planes(adata, is_log1p, group_keys, reference, n_threads, batch_si
 
     raw_groups = adata.obs[group_keys]  # a categorical column is encoded from its codes (no pass over N strings)
     unique_raw_groups, group_container = encode_and_count_groups(groups=raw_groups, ref_group=reference)
+    if inputs is not None:
+        inputs.append((X, data_handler, group_container))
     n_genes = X.shape[1]
     n_groups = int(group_container.counts.size)
 

@@ -66,6 +66,12 @@ enum {
     KID_ADJ_MERGE,
     KID_ADJ_SCAN,
     KID_ADJ_BONF,
+    KID_GS_VMAX, // illico_group_stats_* (kernels_group_stats.h)
+    KID_GS_DENSE,
+    KID_GS_CSC,
+    KID_GS_CSR,
+    KID_GS_TOTALS,
+    KID_GS_FINALIZE,
     KID_COUNT
 };
 extern const char *const kKernelNames[KID_COUNT];

@@ -1,0 +1,309 @@
+// illico_group_stats_{dense,csc,csr,bound}: per-(group, gene) non-zero counts and exact value sums, and the same over every other
+// cell (kernels_group_stats.h).  A translation unit of its own: the kernels depend on nothing the Wilcoxon routes use.
+#include "engine.h"
+#include "kernels_group_stats.h"
+
+namespace {
+
+struct GsInput {
+    bool sparse = false, is_csr = false, on_dev = false;
+    const void *X = nullptr; // dense
+    int64_t ld = 0;
+    const void *data = nullptr, *indices = nullptr, *indptr = nullptr; // sparse
+    int idx_dtype = 0;
+    int dtype = 0;
+    int64_t n_rows = 0, n_cols = 0;
+};
+struct GsOutputs {
+    int64_t *nnz, *nnz_rest;
+    double *sum, *sum_rest;
+    int64_t ld;
+};
+
+int gs_check(illico_ctx *c, const GsInput &in, int64_t col_lb, int64_t col_ub, const GsOutputs &o) {
+    if (!c->has_groups) return fail(c, ILLICO_ERR_NO_GROUPS, "illico_set_groups has not been called");
+    if (in.n_rows != c->n_cells)
+        return fail(c, ILLICO_ERR_NO_GROUPS, "X has %lld rows but the groups describe %lld cells", (long long)in.n_rows, (long long)c->n_cells);
+    if (col_lb < 0 || col_ub > in.n_cols || col_lb > col_ub)
+        return fail(c, ILLICO_ERR_BOUNDS, "Invalid chunk bounds: (%lld, %lld) for data with %lld columns.", (long long)col_lb, (long long)col_ub, (long long)in.n_cols);
+    if (in.dtype < 0 || in.dtype > 3) return fail(c, ILLICO_ERR_DTYPE, "unsupported dtype code %d", in.dtype);
+    if (in.sparse && in.idx_dtype != ILLICO_IDX_I32 && in.idx_dtype != ILLICO_IDX_I64)
+        return fail(c, ILLICO_ERR_DTYPE, "unsupported index dtype code %d", in.idx_dtype);
+    if (!o.nnz && !o.sum && !o.nnz_rest && !o.sum_rest) return fail(c, ILLICO_ERR_ARG, "all four output planes are null: nothing to compute");
+    if (o.ld < col_ub - col_lb) return fail(c, ILLICO_ERR_ARG, "out_ld smaller than the chunk width");
+    for (int64_t g = 0; g < c->n_groups; ++g)
+        if (c->h_counts[g] > 2097151)
+            return fail(c, ILLICO_ERR_UNSUPPORTED, "group %lld holds %d cells: the exact per-group sums hold up to 2097151", (long long)g, c->h_counts[g]);
+    return ILLICO_OK;
+}
+
+// the groups' positions in chunks of at most GS_CHUNK (a group of 100 000 cells is spread over ~100 workgroups)
+void gs_chunks(const illico_ctx *c, std::vector<GsChunk> &ch) {
+    ch.clear();
+    int pos = 0;
+    for (int64_t g = 0; g < c->n_groups; ++g) {
+        const int n = c->h_counts[g];
+        for (int p = 0; p < n; p += GS_CHUNK) ch.push_back({(int)g, pos + p, pos + std::min(n, p + GS_CHUNK), n <= GS_CHUNK ? 1 : 0});
+        pos += n;
+    }
+}
+
+template <typename InT>
+int gs_dense_window(illico_ctx *c, const InT *X, int64_t ld, int64_t N, int wn, int dt, int log1p, const GsChunk *d_ch, int n_ch, const GsPlanes &P) {
+    {
+        ProfScope ps(c, KID_GS_VMAX);
+        const int gx = (wn + GS_NT - 1) / GS_NT;
+        const int gy = (int)std::max<int64_t>(1, std::min<int64_t>((N + 63) / 64, (4096 + gx - 1) / gx));
+        hipLaunchKernelGGL(k_gs_dense_vmax<InT>, dim3(gx, gy), dim3(GS_NT), 0, c->stream, X, (long long)ld, (long long)N, wn, dt, log1p, P.vmax, P.nonfin);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (n_ch) {
+        ProfScope ps(c, KID_GS_DENSE);
+        hipLaunchKernelGGL(k_gs_dense<InT>, dim3(n_ch, (wn + GS_TILE - 1) / GS_TILE), dim3(GS_NT), 0, c->stream, X, (long long)ld, wn, c->d_perm, d_ch, dt, log1p, P);
+        HIPCHK(c, hipGetLastError());
+    }
+    return ILLICO_OK;
+}
+
+template <typename InT, typename IdxT>
+int gs_sparse_window(illico_ctx *c, bool is_csr, const void *data, const void *indices, const void *indptr, long long kshift, long long col0, int64_t N,
+                     int wn, int dt, int log1p, const GsChunk *d_ch, int n_ch, const GsPlanes &P) {
+    const int G = (int)c->n_groups;
+    if (!is_csr) {
+        const bool ldsg = G <= GS_CSC_LDS_G;
+        GsCscParams C{data, indices, indptr, kshift, col0, c->d_codes, c->d_codes16, wn, G, dt, log1p};
+        const size_t lds = gs_csc_lds_bytes(G, ldsg);
+        ProfScope ps(c, KID_GS_CSC);
+        const dim3 grid((unsigned)std::min<int64_t>(wn, 1 << 20));
+        if (ldsg) {
+            HIPCHK(c, hipFuncSetAttribute((const void *)k_gs_csc<InT, IdxT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL((k_gs_csc<InT, IdxT, true>), grid, dim3(GS_NT), lds, c->stream, C, P);
+        } else
+            hipLaunchKernelGGL((k_gs_csc<InT, IdxT, false>), grid, dim3(GS_NT), lds, c->stream, C, P);
+        HIPCHK(c, hipGetLastError());
+        return ILLICO_OK;
+    }
+    {
+        ProfScope ps(c, KID_GS_VMAX);
+        const int gy = (wn + GS_VMAX_CW - 1) / GS_VMAX_CW;
+        const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((N + 15) / 16, (2048 + gy - 1) / gy));
+        hipLaunchKernelGGL((k_gs_csr_vmax<InT, IdxT>), dim3(gx, gy), dim3(GS_NT), 0, c->stream, (const InT *)data, (const IdxT *)indices, (const IdxT *)indptr,
+                           kshift, (long long)N, col0, wn, dt, log1p, P.vmax, P.nonfin);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (n_ch) {
+        ProfScope ps(c, KID_GS_CSR);
+        hipLaunchKernelGGL((k_gs_csr<InT, IdxT>), dim3(n_ch, (wn + GS_CSR_CW - 1) / GS_CSR_CW), dim3(GS_NT), 0, c->stream, (const InT *)data, (const IdxT *)indices,
+                           (const IdxT *)indptr, kshift, col0, wn, c->d_perm, d_ch, dt, log1p, P);
+        HIPCHK(c, hipGetLastError());
+    }
+    return ILLICO_OK;
+}
+
+template <typename InT>
+int gs_sparse_any_idx(illico_ctx *c, bool is_csr, int idx_dtype, const void *data, const void *indices, const void *indptr, long long kshift, long long col0,
+                      int64_t N, int wn, int dt, int log1p, const GsChunk *d_ch, int n_ch, const GsPlanes &P) {
+    if (idx_dtype == ILLICO_IDX_I32) return gs_sparse_window<InT, int32_t>(c, is_csr, data, indices, indptr, kshift, col0, N, wn, dt, log1p, d_ch, n_ch, P);
+    return gs_sparse_window<InT, int64_t>(c, is_csr, data, indices, indptr, kshift, col0, N, wn, dt, log1p, d_ch, n_ch, P);
+}
+
+int64_t idx_at(const void *p, int idx_dtype, int64_t i) { return idx_dtype == ILLICO_IDX_I32 ? (int64_t)((const int32_t *)p)[i] : ((const int64_t *)p)[i]; }
+
+int gs_run(illico_ctx *c, const GsInput &in, int64_t col_lb, int64_t col_ub, int flags, const GsOutputs &o) {
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = resolve_pending(c); // a plane written under ILLICO_FLAG_DEFER is complete only after its leftover genes
+    if (rc) return rc;
+    const int64_t W = col_ub - col_lb, G = c->n_groups, N = in.n_rows;
+    if (W == 0) return ILLICO_OK;
+    const bool out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
+    const int log1p = (flags & ILLICO_FLAG_LOG1P) ? 1 : 0, dt = in.dtype;
+    const size_t esz = dtype_size(dt), isz = in.idx_dtype == ILLICO_IDX_I32 ? 4 : 8;
+    void *v = nullptr;
+
+    // chunks of the groups' positions (dense, CSR)
+    std::vector<GsChunk> hch;
+    gs_chunks(c, hch);
+    const int n_ch = (int)hch.size();
+    GsChunk *d_ch = nullptr;
+    if (n_ch) {
+        if ((rc = get_scratch(c, "gs_chunks", hch.size() * sizeof(GsChunk), &v))) return rc;
+        d_ch = (GsChunk *)v;
+        HIPCHK(c, hipMemcpyAsync(d_ch, hch.data(), hch.size() * sizeof(GsChunk), hipMemcpyHostToDevice, c->stream));
+    }
+
+    // host-resident sparse input goes up once: CSC the entries of [col_lb, col_ub), CSR every row
+    const void *data = in.data, *indices = in.indices, *indptr = in.indptr;
+    long long kshift = 0, ptr_col0 = 0; // entry k at data[k - kshift]; the window's first column is indptr[col - ptr_col0]
+    if (in.sparse && !in.on_dev) {
+        const int64_t a = in.is_csr ? 0 : col_lb, b = in.is_csr ? N : col_ub;
+        const int64_t k0 = idx_at(in.indptr, in.idx_dtype, a), k1 = idx_at(in.indptr, in.idx_dtype, b);
+        if (k0 < 0 || k1 < k0) return fail(c, ILLICO_ERR_ARG, "indptr is not non-decreasing");
+        const size_t nnz = (size_t)(k1 - k0), nptr = (size_t)(b - a + 1);
+        if ((rc = get_scratch(c, "gs_upload", std::max<size_t>(nnz, 1) * (esz + isz) + nptr * isz + 64, &v))) return rc;
+        unsigned char *u = (unsigned char *)v;
+        void *dd = u, *di = u + ((nnz * esz + 15) & ~(size_t)15), *dp = (unsigned char *)di + ((nnz * isz + 15) & ~(size_t)15);
+        HIPCHK(c, hipMemcpyAsync(dd, (const unsigned char *)in.data + (size_t)k0 * esz, nnz * esz, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(di, (const unsigned char *)in.indices + (size_t)k0 * isz, nnz * isz, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dp, (const unsigned char *)in.indptr + (size_t)a * isz, nptr * isz, hipMemcpyHostToDevice, c->stream));
+        c->h2d_input_bytes += (int64_t)(nnz * (esz + isz) + nptr * isz);
+        data = dd; indices = di; indptr = dp;
+        kshift = k0;
+        ptr_col0 = a;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (the chunk list and the staged arrays came from pageable host memory)
+
+    // column windows: the [G][wn] planes (+ staged host outputs, + the staged rows of a host dense matrix) fit the scratch cap
+    const int n_out = (o.nnz ? 1 : 0) + (o.sum ? 1 : 0) + (o.nnz_rest ? 1 : 0) + (o.sum_rest ? 1 : 0);
+    const size_t per_col = (size_t)G * 32 + 64 + (out_dev ? 0 : (size_t)G * 8 * n_out) + ((!in.sparse && !in.on_dev) ? (size_t)N * esz : 0);
+    const int64_t WW = std::max<int64_t>(1, std::min<int64_t>({W, (int64_t)((size_t)std::max<int64_t>(c->scratch_bytes, 1) / per_col), (int64_t)1 << 24}));
+    const int n_part = (int)std::min<int64_t>(G, 32);
+    if ((rc = get_scratch(c, "gs_planes", (size_t)WW * per_col + (size_t)n_part * WW * sizeof(GsTotal) + 256, &v))) return rc;
+    unsigned char *base = (unsigned char *)v;
+    GsPlanes P;
+    P.L0 = (long long *)base;
+    P.L1 = P.L0 + (size_t)G * WW;
+    P.cnt = P.L1 + (size_t)G * WW;
+    P.cat = (u64 *)(P.cnt + (size_t)G * WW);
+    P.vmax = P.cat + (size_t)G * WW;
+    P.nonfin = (int *)(P.vmax + WW);
+    GsTotal *part = (GsTotal *)(((uintptr_t)(P.nonfin + WW) + 255) & ~(uintptr_t)255);
+    unsigned char *stage = (unsigned char *)(part + (size_t)n_part * WW);
+    double *st_sum = nullptr, *st_sum_rest = nullptr;
+    long long *st_nnz = nullptr, *st_nnz_rest = nullptr;
+    if (!out_dev) {
+        unsigned char *s = stage;
+        auto take = [&](bool want) { unsigned char *r = want ? s : nullptr; if (want) s += (size_t)G * WW * 8; return r; };
+        st_nnz = (long long *)take(o.nnz != nullptr);
+        st_sum = (double *)take(o.sum != nullptr);
+        st_nnz_rest = (long long *)take(o.nnz_rest != nullptr);
+        st_sum_rest = (double *)take(o.sum_rest != nullptr);
+        stage = s;
+    }
+    void *xwin = stage; // host dense: the window's rows, [N][wn] in the matrix's own type
+
+    for (int64_t w0 = col_lb; w0 < col_ub; w0 += WW) {
+        const int wn = (int)std::min<int64_t>(WW, col_ub - w0);
+        P.W = wn;
+        HIPCHK(c, hipMemsetAsync(P.L0, 0, (size_t)G * wn * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(P.L1, 0, (size_t)G * wn * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(P.cnt, 0, (size_t)G * wn * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(P.cat, 0, (size_t)G * wn * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(P.vmax, 0, (size_t)wn * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(P.nonfin, 0, (size_t)wn * 4, c->stream));
+        if (!in.sparse) {
+            const unsigned char *X = (const unsigned char *)in.X + (size_t)w0 * esz;
+            int64_t ld = in.ld;
+            if (!in.on_dev) {
+                HIPCHK(c, hipMemcpy2DAsync(xwin, (size_t)wn * esz, X, (size_t)in.ld * esz, (size_t)wn * esz, (size_t)N, hipMemcpyHostToDevice, c->stream));
+                c->h2d_input_bytes += (int64_t)((size_t)N * wn * esz);
+                X = (const unsigned char *)xwin;
+                ld = wn;
+            }
+            switch (dt) {
+            case ILLICO_F32: rc = gs_dense_window<float>(c, (const float *)X, ld, N, wn, dt, log1p, d_ch, n_ch, P); break;
+            case ILLICO_F64: rc = gs_dense_window<double>(c, (const double *)X, ld, N, wn, dt, log1p, d_ch, n_ch, P); break;
+            case ILLICO_I32: rc = gs_dense_window<int32_t>(c, (const int32_t *)X, ld, N, wn, dt, log1p, d_ch, n_ch, P); break;
+            default: rc = gs_dense_window<int64_t>(c, (const int64_t *)X, ld, N, wn, dt, log1p, d_ch, n_ch, P); break;
+            }
+        } else {
+            const long long col0 = w0 - ptr_col0;
+            switch (dt) {
+            case ILLICO_F32: rc = gs_sparse_any_idx<float>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, log1p, d_ch, n_ch, P); break;
+            case ILLICO_F64: rc = gs_sparse_any_idx<double>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, log1p, d_ch, n_ch, P); break;
+            case ILLICO_I32: rc = gs_sparse_any_idx<int32_t>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, log1p, d_ch, n_ch, P); break;
+            default: rc = gs_sparse_any_idx<int64_t>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, log1p, d_ch, n_ch, P); break;
+            }
+        }
+        if (rc) return rc;
+        const int gx = (wn + GS_NT - 1) / GS_NT;
+        {
+            ProfScope ps(c, KID_GS_TOTALS);
+            hipLaunchKernelGGL(k_gs_totals, dim3(gx, n_part), dim3(GS_NT), 0, c->stream, P, (int)G, wn, part);
+            HIPCHK(c, hipGetLastError());
+        }
+        GsOut O;
+        const int64_t off = w0 - col_lb;
+        if (out_dev) {
+            O.nnz = o.nnz ? (long long *)o.nnz + off : nullptr;
+            O.sum = o.sum ? o.sum + off : nullptr;
+            O.nnz_rest = o.nnz_rest ? (long long *)o.nnz_rest + off : nullptr;
+            O.sum_rest = o.sum_rest ? o.sum_rest + off : nullptr;
+            O.ld = o.ld;
+        } else {
+            O.nnz = st_nnz; O.sum = st_sum; O.nnz_rest = st_nnz_rest; O.sum_rest = st_sum_rest;
+            O.ld = wn;
+        }
+        {
+            ProfScope ps(c, KID_GS_FINALIZE);
+            const int gy = (int)std::max<int64_t>(1, std::min<int64_t>(G, (8192 + gx - 1) / gx));
+            hipLaunchKernelGGL(k_gs_finalize, dim3(gx, gy), dim3(GS_NT), 0, c->stream, P, (int)G, wn, part, n_part, O);
+            HIPCHK(c, hipGetLastError());
+        }
+        if (!out_dev) {
+            auto down = [&](void *dst, const void *src) -> int {
+                if (dst)
+                    HIPCHK(c, hipMemcpy2DAsync((unsigned char *)dst + (size_t)off * 8, (size_t)o.ld * 8, src, (size_t)wn * 8, (size_t)wn * 8, (size_t)G,
+                                               hipMemcpyDeviceToHost, c->stream));
+                return ILLICO_OK;
+            };
+            if ((rc = down(o.nnz, st_nnz)) || (rc = down(o.sum, st_sum)) || (rc = down(o.nnz_rest, st_nnz_rest)) || (rc = down(o.sum_rest, st_sum_rest)))
+                return rc;
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+    }
+    return ILLICO_OK;
+}
+
+} // namespace
+
+extern "C" int illico_group_stats_dense(illico_ctx *c, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t col_lb, int64_t col_ub,
+                                        int flags, int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest, double *out_sum_rest, int64_t out_ld) {
+    if (!c) return ILLICO_ERR_ARG;
+    CTX_LOCK(c);
+    GsInput in;
+    in.X = X; in.dtype = dtype; in.n_rows = n_rows; in.n_cols = n_cols; in.ld = ld; in.on_dev = flags & ILLICO_FLAG_INPUT_DEVICE;
+    const GsOutputs o{out_nnz, out_nnz_rest, out_sum, out_sum_rest, out_ld};
+    int rc = gs_check(c, in, col_lb, col_ub, o);
+    if (rc) return rc;
+    if (!X) return fail(c, ILLICO_ERR_ARG, "null X");
+    if (ld < n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
+    return gs_run(c, in, col_lb, col_ub, flags, o);
+}
+
+static int group_stats_sparse(illico_ctx *c, bool is_csr, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
+                              int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest,
+                              double *out_sum_rest, int64_t out_ld) {
+    if (!c) return ILLICO_ERR_ARG;
+    CTX_LOCK(c);
+    GsInput in;
+    in.sparse = true; in.is_csr = is_csr; in.data = data; in.indices = indices; in.indptr = indptr; in.idx_dtype = idx_dtype; in.dtype = dtype;
+    in.n_rows = n_rows; in.n_cols = n_cols; in.on_dev = flags & ILLICO_FLAG_INPUT_DEVICE;
+    const GsOutputs o{out_nnz, out_nnz_rest, out_sum, out_sum_rest, out_ld};
+    int rc = gs_check(c, in, col_lb, col_ub, o);
+    if (rc) return rc;
+    if (!data || !indices || !indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
+    return gs_run(c, in, col_lb, col_ub, flags, o);
+}
+
+extern "C" int illico_group_stats_csc(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
+                                      int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest,
+                                      double *out_sum_rest, int64_t out_ld) {
+    return group_stats_sparse(c, false, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, out_nnz, out_sum, out_nnz_rest,
+                              out_sum_rest, out_ld);
+}
+extern "C" int illico_group_stats_csr(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
+                                      int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest,
+                                      double *out_sum_rest, int64_t out_ld) {
+    return group_stats_sparse(c, true, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, out_nnz, out_sum, out_nnz_rest,
+                              out_sum_rest, out_ld);
+}
+extern "C" int illico_group_stats_bound(illico_ctx *c, const illico_matrix *m, int64_t col_lb, int64_t col_ub, int flags, int64_t *out_nnz, double *out_sum,
+                                        int64_t *out_nnz_rest, double *out_sum_rest, int64_t out_ld) {
+    if (!c || !m) return ILLICO_ERR_ARG;
+    CTX_LOCK(c); // (held for the whole call: illico_matrix_release on another thread cannot free the arrays under it)
+    if (m->owner != c || std::find(c->bound.begin(), c->bound.end(), m) == c->bound.end())
+        return fail(c, ILLICO_ERR_ARG, "the matrix handle does not belong to this context (or was released)");
+    return group_stats_sparse(c, m->is_csr, m->d_data, m->dtype, m->d_indices, m->d_indptr, m->idx_dtype, m->n_rows, m->n_cols, col_lb, col_ub,
+                              (flags & (ILLICO_FLAG_LOG1P | ILLICO_FLAG_OUTPUT_DEVICE)) | ILLICO_FLAG_INPUT_DEVICE, out_nnz, out_sum, out_nnz_rest, out_sum_rest,
+                              out_ld);
+}

@@ -230,6 +230,40 @@ int illico_adjust_pvalues(illico_ctx *ctx, const double *p, int64_t n_rows, int6
                           int method, int flags, double *out_adj, int64_t out_ld,
                           int64_t n_top, int64_t *out_top, int64_t top_ld);
 
+/* ---- per-group expression statistics --------------------------------------------------------
+ * For each group g of illico_set_groups and each column j of [col_lb, col_ub) (plane column j - col_lb):
+ *   out_nnz[g][j]       int64: cells of g whose value is non-zero (v != 0: -0.0 and stored explicit zeros do not count, NaN does);
+ *                       sparse input counts stored non-zero ENTRIES, so a duplicate (row, column) entry counts once per entry, as the
+ *                       Wilcoxon routes rank duplicates as separate values;
+ *   out_sum[g][j]       float64: the sum of g's values; under ILLICO_FLAG_LOG1P the sum of expm1(v), the quantity the fold change
+ *                       divides (one-versus-one: (sum[g] / n_g) / (sum[ref] / n_ref) is fold_change[g]);
+ *   out_nnz_rest[g][j], out_sum_rest[g][j]: the same over every cell NOT in g (what one-versus-rest compares against).
+ * Sums are exact-limb sums (kernels_group_stats.h): the correctly rounded sum of the values, whatever the input format or the order
+ * of the stored entries -- byte-identical across dense / CSC / CSR / bound and from run to run; the rest sums are formed exactly
+ * (integer totals minus the group's own), not as a float64 difference.  Values smaller than 2^-83 of the column's largest finite
+ * magnitude are truncated at that unit.  NaN / +inf / -inf (or an expm1 that overflows) make the affected sums NaN / +inf / -inf as
+ * numpy's sum would (+inf and -inf together: NaN); nothing faults.
+ * Planes: row-major [G][out_ld], out_ld >= col_ub - col_lb.  Any of the four pointers may be null (that plane is not produced); at
+ * least one must be given.  flags: ILLICO_FLAG_LOG1P, ILLICO_FLAG_INPUT_DEVICE (X / the sparse arrays on the device),
+ * ILLICO_FLAG_OUTPUT_DEVICE (all four planes on the device, ordered on the context's stream; host planes are complete on return);
+ * other flags are ignored.  Dtypes: the four of ILLICO_F32.., index dtypes ILLICO_IDX_I32 / I64.  CSR rows need not have sorted
+ * column indices.  Host dense input is staged column window by column window (the "scratch_bytes" cap), host CSC uploads the
+ * entries of [col_lb, col_ub) once, host CSR the whole matrix once.  A deferred call (ILLICO_FLAG_DEFER) is completed first.
+ * Errors: ILLICO_ERR_NO_GROUPS (no groups / n_rows mismatch), ILLICO_ERR_BOUNDS, ILLICO_ERR_DTYPE, ILLICO_ERR_ARG (null input,
+ * all outputs null, out_ld or ld too small), ILLICO_ERR_UNSUPPORTED (a group of more than 2097151 cells), ILLICO_ERR_OOM. */
+int illico_group_stats_dense(illico_ctx *ctx, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld,
+                             int64_t col_lb, int64_t col_ub, int flags,
+                             int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest, double *out_sum_rest, int64_t out_ld);
+int illico_group_stats_csc(illico_ctx *ctx, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype,
+                           int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags,
+                           int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest, double *out_sum_rest, int64_t out_ld);
+int illico_group_stats_csr(illico_ctx *ctx, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype,
+                           int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags,
+                           int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest, double *out_sum_rest, int64_t out_ld);
+/* a matrix bound with illico_csr_bind / illico_csc_bind; flags: ILLICO_FLAG_LOG1P, ILLICO_FLAG_OUTPUT_DEVICE */
+int illico_group_stats_bound(illico_ctx *ctx, const illico_matrix *matrix, int64_t col_lb, int64_t col_ub, int flags,
+                             int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest, double *out_sum_rest, int64_t out_ld);
+
 /* ---- measurement hooks (bench.py roofline leg) ------------------------------------------- */
 int illico_profile_num_kernels(void);
 const char *illico_profile_kernel_name(int kernel_id);
