@@ -1,12 +1,13 @@
 """illico_amd -- MI355X-native engine for illico's asymptotic Wilcoxon rank-sum hot path.
 
 ``from illico_amd import asymptotic_wilcoxon`` is a drop-in for ``illico.asymptotic_wilcoxon``; ``adjust_pvalues`` and
-``differential_expression`` add the per-group multiple-testing correction and top-gene ranking that follow it.
+``differential_expression`` add the per-group multiple-testing correction and top-gene ranking that follow it; ``top_by_score``
+ranks a z-score plane.
 """
 from illico_amd.anndata_lite import AnnDataLite
-from illico_amd.adjust import adjust_pvalues, differential_expression
+from illico_amd.adjust import adjust_pvalues, differential_expression, top_by_score
 from illico_amd.asymptotic_wilcoxon import asymptotic_wilcoxon
 from illico_amd.group_stats import group_statistics
 
-__all__ = ["asymptotic_wilcoxon", "AnnDataLite", "adjust_pvalues", "differential_expression", "group_statistics"]
+__all__ = ["asymptotic_wilcoxon", "AnnDataLite", "adjust_pvalues", "differential_expression", "group_statistics", "top_by_score"]
 __version__ = "0.1.0"

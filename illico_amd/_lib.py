@@ -38,6 +38,7 @@ SYMBOLS = [
     "illico_profile_get", "illico_profile_reset", "illico_version", "illico_csr_bind", "illico_csc_bind", "illico_run_bound",
     "illico_matrix_release", "illico_matrix_touch", "illico_profile_input_bytes", "illico_planes_to_host",
     "illico_adjust_pvalues", "illico_group_stats_dense", "illico_group_stats_csc", "illico_group_stats_csr", "illico_group_stats_bound",
+    "illico_run_dense_ex", "illico_run_csc_ex", "illico_run_csr_ex", "illico_run_bound_ex", "illico_top_by_score",
 ]
 
 _lib = None
@@ -87,6 +88,11 @@ def load() -> ctypes.CDLL:
         for f in (lib.illico_group_stats_csc, lib.illico_group_stats_csr):
             f.argtypes = [vp, vp, ci, vp, vp, ci, i64, i64, i64, i64, ci, vp, vp, vp, vp, i64]
         lib.illico_group_stats_bound.argtypes = [vp, vp, i64, i64, ci, vp, vp, vp, vp, i64]
+        lib.illico_run_dense_ex.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, ci, vp, vp, vp, vp, i64]
+        for f in (lib.illico_run_csc_ex, lib.illico_run_csr_ex):
+            f.argtypes = [vp, vp, ci, vp, vp, ci, i64, i64, i64, i64, ci, ci, vp, vp, vp, vp, i64]
+        lib.illico_run_bound_ex.argtypes = [vp, vp, i64, i64, ci, ci, vp, vp, vp, vp, i64]
+        lib.illico_top_by_score.argtypes = [vp, vp, i64, i64, i64, ci, i64, vp, i64]
         for name in SYMBOLS:  # fail at load time, not at first use, if the library and the header have drifted
             getattr(lib, name)
         _lib = lib
@@ -237,17 +243,22 @@ class Engine:
         except KeyError:
             raise ValueError(f"Unsupported alternative hypothesis: {alternative}") from None
 
-    def _outputs(self, out, G, W, want_device):
-        """out: None (allocate host planes), a tuple of three host ndarrays (views with a common row stride are
-        fine) or three device tensors."""
+    def _outputs(self, out, G, W, want_device, scores=False):
+        """out: None (allocate host planes; four with ``scores``), a tuple of three host ndarrays (views with a common row stride
+        are fine) or three device tensors -- or four: the fourth receives the z-score plane."""
+        if not isinstance(scores, (bool, np.bool_)):
+            raise ValueError(f"scores must be a bool, got {scores!r}")
         if out is None:
+            n = 4 if scores else 3
             if want_device:
                 import torch
-                planes = tuple(torch.empty((G, W), dtype=torch.float64, device=f"cuda:{self.device}") for _ in range(3))
+                planes = tuple(torch.empty((G, W), dtype=torch.float64, device=f"cuda:{self.device}") for _ in range(n))
             else:
-                planes = tuple(np.empty((G, W), dtype=np.float64) for _ in range(3))
+                planes = tuple(np.empty((G, W), dtype=np.float64) for _ in range(n))
         else:
             planes = tuple(out)
+            if len(planes) not in (3, 4) or (scores and len(planes) != 4):
+                raise ValueError("out must hold 3 planes (p, U, fold change), or 4 with the z-score plane last (4 with scores=True)")
         if W == 0:  # empty chunk (lb == ub is legal, asymptotic_wilcoxon.py:49): nothing to compute
             return planes, None, 0, 1
         ptrs, flag, ld = [], 0, None
@@ -270,9 +281,10 @@ class Engine:
         return planes, ptrs, flag, int(ld if ld else max(W, 1))
 
     def run_dense(self, X, col_lb, col_ub, *, is_log1p=False, use_continuity=True, tie_correct=True,
-                  alternative="two-sided", out=None, device_out=False, defer=False):
+                  alternative="two-sided", out=None, device_out=False, defer=False, scores=False):
         """``defer=True`` (device input and device planes only): return once the pass is enqueued; the planes are complete
-        after ``synchronize()`` or the next call on this engine (ILLICO_FLAG_DEFER, include/illico_hip.h)."""
+        after ``synchronize()`` or the next call on this engine (ILLICO_FLAG_DEFER, include/illico_hip.h).  ``scores=True``
+        (or a 4-tuple ``out``): a fourth plane, the z-score of every test (include/illico_hip.h: illico_run_dense_ex)."""
         alt = self._alt(alternative)
         if _is_torch_tensor(X):
             if X.dim() != 2 or X.stride(1) != 1:
@@ -291,21 +303,26 @@ class Engine:
         if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
             raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
         G, W = self.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = self._outputs(out, G, W, device_out)
+        planes, ptrs, oflag, out_ld = self._outputs(out, G, W, device_out, scores)
         if ptrs is None:
             return planes
         flags = self._flags(is_log1p, use_continuity, tie_correct) | (FLAG_INPUT_DEVICE if on_dev else 0) | oflag | \
             (FLAG_DEFER if defer else 0)
         self._bind_torch_stream(keep, *planes)
-        self._check(self.lib.illico_run_dense(self.h, buf_ptr, dt, n_rows, n_cols, ld, col_lb, col_ub, flags, alt,
-                                              ptrs[0], ptrs[1], ptrs[2], out_ld))
+        if len(ptrs) == 4:
+            self._check(self.lib.illico_run_dense_ex(self.h, buf_ptr, dt, n_rows, n_cols, ld, col_lb, col_ub, flags, alt,
+                                                     ptrs[0], ptrs[1], ptrs[2], ptrs[3], out_ld))
+        else:
+            self._check(self.lib.illico_run_dense(self.h, buf_ptr, dt, n_rows, n_cols, ld, col_lb, col_ub, flags, alt,
+                                                  ptrs[0], ptrs[1], ptrs[2], out_ld))
         del keep
         return planes
 
     def run_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, *, is_log1p=False, use_continuity=True,
-                   tie_correct=True, alternative="two-sided", out=None, device_out=False, defer=False):
+                   tie_correct=True, alternative="two-sided", out=None, device_out=False, defer=False, scores=False):
         """``defer=True`` (device-resident CSC arrays and device planes only; ignored elsewhere): return once the count-valued
-        pass is enqueued; the planes are complete after ``synchronize()`` or the next call on this engine."""
+        pass is enqueued; the planes are complete after ``synchronize()`` or the next call on this engine.  ``scores``: as in
+        ``run_dense``."""
         alt = self._alt(alternative)
         n_rows, n_cols = int(shape[0]), int(shape[1])
         if _is_torch_tensor(data):
@@ -321,15 +338,18 @@ class Engine:
         if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
             raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
         G, W = self.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = self._outputs(out, G, W, device_out)
+        planes, ptrs, oflag, out_ld = self._outputs(out, G, W, device_out, scores)
         if ptrs is None:
             return planes
         flags = self._flags(is_log1p, use_continuity, tie_correct) | (FLAG_INPUT_DEVICE if d.on_device else 0) | oflag | \
             (FLAG_DEFER if defer else 0)
-        fn = self.lib.illico_run_csc if fmt == "csc" else self.lib.illico_run_csr
+        if len(ptrs) == 4:
+            fn = self.lib.illico_run_csc_ex if fmt == "csc" else self.lib.illico_run_csr_ex
+        else:
+            fn = self.lib.illico_run_csc if fmt == "csc" else self.lib.illico_run_csr
         self._bind_torch_stream(d.keep, i.keep, p.keep, *planes)
         self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, IDX_I32 if i.np_dtype == np.int32 else IDX_I64,
-                       n_rows, n_cols, col_lb, col_ub, flags, alt, ptrs[0], ptrs[1], ptrs[2], out_ld))
+                       n_rows, n_cols, col_lb, col_ub, flags, alt, *ptrs, out_ld))
         return planes
 
     def bind_sparse(self, fmt, data, indices, indptr, shape):
@@ -433,6 +453,24 @@ class Engine:
             self._check(self.lib.illico_adjust_pvalues(self.h, ptr(p), G, M, ld, code, (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0,
                                                        ptr(adj), out_ld, n_top, ptr(top) if n_top else None, max(n_top, 1)))
         return (adj, top) if n_top else adj
+
+    def top_by_score(self, x, n_top, *, out=None):
+        """Each row's first ``n_top`` columns by DESCENDING score, ties by column (include/illico_hip.h: illico_top_by_score) --
+        ``np.argsort(-(x + 0.0), axis=1, kind="stable")[:, :n_top]``.  ``x``: float64 ``[G, M]``, numpy or CUDA tensor with unit
+        column stride (a z-score plane); the int64 ``[G, n_top]`` result lives where ``x`` lives.  ``ValueError`` for a NaN."""
+        x, G, M, ld, on_dev = _adjust_plane(x, "x", copy_ok=True)
+        n_top = _adjust_n_top(n_top, M)
+        if on_dev:
+            import torch
+            top = torch.empty((G, n_top), dtype=torch.int64, device=x.device) if out is None else out
+        else:
+            top = np.empty((G, n_top), dtype=np.int64) if out is None else out
+        if G and M and n_top:
+            self._bind_torch_stream(x, top)
+            ptr = (lambda a: a.data_ptr()) if on_dev else (lambda a: a.ctypes.data)
+            self._check(self.lib.illico_top_by_score(self.h, ptr(x), G, M, ld, (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0,
+                                                     n_top, ptr(top), n_top))
+        return top
 
     # ---- per-group expression statistics (include/illico_hip.h: illico_group_stats_*) ----
     def _gs_outputs(self, out, G, W, rest, want_device):
@@ -588,19 +626,24 @@ class BoundMatrix:
         self.engine, self.h, self.shape, self._keep = engine, handle, shape, keep
 
     def run(self, col_lb, col_ub, *, is_log1p=False, use_continuity=True, tie_correct=True, alternative="two-sided", out=None,
-            device_out=False, defer=False):
+            device_out=False, defer=False, scores=False):
+        """``scores``: as in ``Engine.run_dense``.  A call with the z-score plane computes its chunk directly: the windows of
+        the option "bound_ahead_genes" are neither used nor replaced by it (include/illico_hip.h: illico_run_bound_ex)."""
         eng = self.engine
         alt = eng._alt(alternative)
         n_cols = self.shape[1]
         if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
             raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
         G, W = eng.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = eng._outputs(out, G, W, device_out)
+        planes, ptrs, oflag, out_ld = eng._outputs(out, G, W, device_out, scores)
         if ptrs is None:
             return planes
         flags = eng._flags(is_log1p, use_continuity, tie_correct) | oflag | (FLAG_DEFER if defer else 0)
         eng._bind_torch_stream(*planes)
-        eng._check(eng.lib.illico_run_bound(eng.h, self.h, col_lb, col_ub, flags, alt, ptrs[0], ptrs[1], ptrs[2], out_ld))
+        if len(ptrs) == 4:
+            eng._check(eng.lib.illico_run_bound_ex(eng.h, self.h, col_lb, col_ub, flags, alt, *ptrs, out_ld))
+        else:
+            eng._check(eng.lib.illico_run_bound(eng.h, self.h, col_lb, col_ub, flags, alt, ptrs[0], ptrs[1], ptrs[2], out_ld))
         return planes
 
     def group_stats(self, col_lb, col_ub, *, is_log1p=False, rest=False, out=None, device_out=False):

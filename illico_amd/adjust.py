@@ -13,7 +13,10 @@ import pandas as pd
 from illico_amd import _lib
 from illico_amd.asymptotic_wilcoxon import _planes_frame, _wilcoxon_planes
 
-__all__ = ["adjust_pvalues", "differential_expression"]
+__all__ = ["adjust_pvalues", "differential_expression", "top_by_score"]
+
+#: what ``differential_expression`` can order each group's rows by for its ``n_genes`` cut
+RANK_BY = ("p_value", "z_score")
 
 #: method names -> the engine's codes (include/illico_hip.h: ILLICO_ADJ_*)
 METHODS = {"bh": "bh", "benjamini-hochberg": "bh", "by": "by", "benjamini-yekutieli": "by", "bonferroni": "bonferroni"}
@@ -42,22 +45,35 @@ def adjust_pvalues(p, method: str = "benjamini-hochberg", *, n_top: int = 0):
     return _lib.get_engine(device).adjust_pvalues(p, code, n_top=n_top)
 
 
-def _check_plane(p):
+def top_by_score(z, n_top: int):
+    """Each row's first ``n_top`` columns by descending score, ties by column: ``np.argsort(-(z + 0.0), axis=1, kind="stable")[:, :n_top]``.
+
+    ``z``: float64 ``[G, M]`` numpy array or CUDA tensor with unit column stride -- a z-score plane (``Engine.run_dense(scores=True)``).
+    Returns int64 ``[G, n_top]`` where ``z`` lives.  ``-0.0`` and ``+0.0`` tie, ``+inf`` comes first, ``-inf`` last; a NaN raises
+    ``ValueError`` naming its position."""
+    _check_plane(z, "z")
+    n_top = _lib._adjust_n_top(n_top, int(z.shape[1]))
+    device = z.device.index if _lib._is_torch_tensor(z) else None
+    return _lib.get_engine(device).top_by_score(z, n_top)
+
+
+def _check_plane(p, what="p"):
     """The dtype / rank / residency checks of Engine.adjust_pvalues, before any engine exists."""
     if _lib._is_torch_tensor(p):
         import torch
         if not p.is_cuda:
-            raise ValueError("p must be a numpy array or a CUDA tensor (got a CPU tensor)")
+            raise ValueError(f"{what} must be a numpy array or a CUDA tensor (got a CPU tensor)")
         if p.dtype != torch.float64 or p.dim() != 2:
-            raise ValueError(f"p must be a float64 2-D tensor, got {p.dtype} with {p.dim()} dimensions")
+            raise ValueError(f"{what} must be a float64 2-D tensor, got {p.dtype} with {p.dim()} dimensions")
     elif not isinstance(p, np.ndarray):
-        raise ValueError(f"p must be a numpy array or a CUDA tensor, got {type(p).__name__}")
+        raise ValueError(f"{what} must be a numpy array or a CUDA tensor, got {type(p).__name__}")
     elif p.dtype != np.float64 or p.ndim != 2:
-        raise ValueError(f"p must be a float64 2-D array, got {p.dtype} with {p.ndim} dimensions")
+        raise ValueError(f"{what} must be a float64 2-D array, got {p.dtype} with {p.ndim} dimensions")
 
 
 def differential_expression(adata, is_log1p: bool, group_keys: str, reference: str | None = None, *,
-                            corr_method: str = "benjamini-hochberg", n_genes: int | None = None, pts: bool = False, **kw) -> pd.DataFrame:
+                            corr_method: str = "benjamini-hochberg", n_genes: int | None = None, pts: bool = False,
+                            scores: bool = False, rank_by: str = "p_value", **kw) -> pd.DataFrame:
     """``asymptotic_wilcoxon`` plus the multiple-testing correction that follows it in a DE workflow.
 
     ``kw`` takes the other arguments of ``asymptotic_wilcoxon`` (``batch_size``, ``alternative``, ``layer``, ...).  Returns its
@@ -66,11 +82,20 @@ def differential_expression(adata, is_log1p: bool, group_keys: str, reference: s
     p (ties by gene order), in that order; the groups keep their order.  The reference group's row of a one-versus-one call stays,
     as ``asymptotic_wilcoxon`` keeps it (its p are 1.0, so are their adjusted values).  ``pts=True`` adds the four columns of
     ``group_statistics`` (``pct_group``, ``pct_reference``, ``mean_group``, ``mean_reference``) before the ``n_genes`` cut, so they
-    stay on their rows; an in-RAM CSR matrix is uploaded once for both passes.
+    stay on their rows; an in-RAM CSR matrix is uploaded once for both passes.  ``scores=True`` adds a float64 ``z_score`` column: the
+    test's z, positive when the group ranks above its reference (scanpy's ``scores``; include/illico_hip.h: illico_run_dense_ex).
+    ``rank_by="z_score"`` orders each group's rows by descending z for the ``n_genes`` cut -- scanpy's order, and the one that still
+    separates genes whose p has underflowed to 0 -- and implies ``scores=True``; ``rank_by="p_value"`` (the default) orders by p.
     """
     code = _method(corr_method)
     if not isinstance(pts, (bool, np.bool_)):
         raise ValueError(f"pts must be a bool, got {pts!r}")
+    if not isinstance(scores, (bool, np.bool_)):
+        raise ValueError(f"scores must be a bool, got {scores!r}")
+    if not isinstance(rank_by, str) or rank_by not in RANK_BY:
+        raise ValueError(f"rank_by must be one of {RANK_BY}, got {rank_by!r}")
+    by_z = rank_by == "z_score"
+    scores = bool(scores) or by_z
     if n_genes is not None and (isinstance(n_genes, bool) or not isinstance(n_genes, (int, np.integer)) or n_genes < 1):
         raise ValueError(f"n_genes must be a positive integer or None, got {n_genes!r}")
     unknown = set(kw) - {"n_threads", "batch_size", "alternative", "use_continuity", "tie_correct", "layer", "precompile"}
@@ -79,20 +104,23 @@ def differential_expression(adata, is_log1p: bool, group_keys: str, reference: s
     args = dict(n_threads=1, batch_size="auto", alternative="two-sided", use_continuity=True, tie_correct=True, layer=None)
     args.update({k: v for k, v in kw.items() if k != "precompile"})
     inputs: list = []
-    planes, index = _wilcoxon_planes(adata, is_log1p, group_keys, reference, **args, inputs=inputs)
+    planes, index = _wilcoxon_planes(adata, is_log1p, group_keys, reference, **args, inputs=inputs, scores=scores)
     G, M = planes.shape[1], planes.shape[2]
     n_top = min(int(n_genes), M) if n_genes is not None else 0
     if G and M:
-        res = _lib.get_engine().adjust_pvalues(planes[0], code, n_top=n_top)
-        adj, top = res if n_top else (res, None)
+        eng = _lib.get_engine()
+        res = eng.adjust_pvalues(planes[0], code, n_top=0 if by_z else n_top)
+        adj, top = res if (n_top and not by_z) else (res, None)
+        if n_top and by_z:
+            top = eng.top_by_score(planes[3], n_top)
     else:
         adj, top = np.empty((G, M), dtype=np.float64), np.empty((G, 0), dtype=np.int64)
-    extra = {}
+    extra = {"z_score": planes[3]} if scores else {}
     if pts:
         from illico_amd.group_stats import stat_planes
         X, handler, group_container = inputs[0]
-        extra = stat_planes(X, handler, group_container, bool(is_log1p))
-    df = _planes_frame(planes, index, p_value_adj=adj, **extra)
+        extra.update(stat_planes(X, handler, group_container, bool(is_log1p)))
+    df = _planes_frame(planes[:3], index, p_value_adj=adj, **extra)
     if n_genes is None:
         return df
     rows = (np.arange(G, dtype=np.int64)[:, None] * M + top[:, :n_top]).reshape(-1)

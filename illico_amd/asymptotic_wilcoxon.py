@@ -51,9 +51,8 @@ def operator(data_handler: DataHandler, lb: int, ub: int, group_container: Group
     fetched_data, bounds = data_handler.fetch(lb, ub)
     X = data_handler.to_nb(fetched_data)
     kw = {} if out is None else {"out": out}
-    pvalues, statistics, fold_change = dispatcher(X, *bounds, group_container, is_log1p, use_continuity, tie_correct,
-                                                  alternative, **kw)
-    return (pvalues, statistics, fold_change), (lb, ub)
+    planes = dispatcher(X, *bounds, group_container, is_log1p, use_continuity, tie_correct, alternative, **kw)
+    return tuple(planes), (lb, ub)
 
 
 def asymptotic_wilcoxon(
@@ -100,10 +99,11 @@ def _planes_frame(planes: np.ndarray, index: pd.MultiIndex, **extra) -> pd.DataF
 
 
 def _wilcoxon_planes(adata, is_log1p, group_keys, reference, n_threads, batch_size, alternative, use_continuity, tie_correct,
-                     layer, inputs: list | None = None) -> tuple[np.ndarray, pd.MultiIndex]:
-    """The body of ``asymptotic_wilcoxon``: the planes float64 [3, G, n_genes] (p_value, statistic, fold_change) and the
-    (pert, feature) MultiIndex of their G x n_genes rows.  ``inputs``: a list that receives (X, data handler, GroupContainer) of the
-    call -- the handler of an in-RAM CSR matrix is its device copy, which a later pass over the same matrix can reuse."""
+                     layer, inputs: list | None = None, scores: bool = False) -> tuple[np.ndarray, pd.MultiIndex]:
+    """The body of ``asymptotic_wilcoxon``: the planes float64 [3, G, n_genes] (p_value, statistic, fold_change) -- [4, G, n_genes]
+    with ``scores``, the z-score plane last -- and the (pert, feature) MultiIndex of their G x n_genes rows.  ``inputs``: a list that
+    receives (X, data handler, GroupContainer) of the call -- the handler of an in-RAM CSR matrix is its device copy, which a later
+    pass over the same matrix can reuse."""
     X = adata.layers[layer] if layer is not None else adata.X
     data_handler = data_handler_registry.get(X)
 
@@ -153,8 +153,8 @@ def _wilcoxon_planes(adata, is_log1p, group_keys, reference, n_threads, batch_si
     else:
         raise ValueError(f"Invalid batch_size value: {batch_size}. Must be 'auto' or an integer.")
 
-    # three [G, n_genes] planes; each chunk writes its [:, lb:ub] window in place
-    planes = np.empty((3, n_groups, n_genes), dtype=np.float64)
+    # three (four) [G, n_genes] planes; each chunk writes its [:, lb:ub] window in place
+    planes = np.empty((4 if scores else 3, n_groups, n_genes), dtype=np.float64)
     iterator = [(lb, ub) for lb, ub in iterator if ub > lb]
     # the G x M row index of the result (asymptotic_wilcoxon.py:252-256) does not depend on the statistics: it is built on a thread of
     # its own while the engine works (numpy releases the GIL in repeat / tile, ctypes releases it in the engine calls) -- 15 - 30 ms of
@@ -176,7 +176,7 @@ def _wilcoxon_planes(adata, is_log1p, group_keys, reference, n_threads, batch_si
         run_streaming(data_handler, iterator, group_container, is_log1p, use_continuity, alternative, tie_correct, planes)
     else:
         for lb, ub in iterator:
-            out = tuple(planes[k][:, lb:ub] for k in range(3))
+            out = tuple(planes[k][:, lb:ub] for k in range(planes.shape[0]))
             operator(data_handler, lb, ub, group_container, is_log1p, use_continuity, alternative, tie_correct, out=out)
 
     index_thread.join()

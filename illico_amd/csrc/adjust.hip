@@ -40,16 +40,18 @@ static double harmonic(int64_t m) {
     return acc;
 }
 
-// the first invalid p of rows [row0, row0 + nb) (p points at row row0): ILLICO_ERR_ARG naming it, or OK
+// the first invalid p of rows [row0, row0 + nb) (p points at row row0): ILLICO_ERR_ARG naming it, or OK.  score: the first NaN of a
+// score plane (illico_top_by_score)
 static int adj_validate(illico_ctx *c, const double *p, int64_t ld, int64_t nb, int64_t m, int64_t row0, u64 *d_err, const double *host_p,
-                        int64_t host_ld) {
+                        int64_t host_ld, bool score = false) {
     HIPCHK(c, hipMemsetAsync(d_err, 0xFF, 8, c->stream));
     {
-        ProfScope ps(c, KID_ADJ_VALIDATE);
+        ProfScope ps(c, score ? KID_TOP_VALIDATE : KID_ADJ_VALIDATE);
         const int gx = (int)std::min<int64_t>((m + 255) / 256, 64);
         for (int64_t r = 0; r < nb; r += 65535) {
             const int ny = (int)std::min<int64_t>(65535, nb - r);
-            hipLaunchKernelGGL(k_adj_validate, dim3(gx, ny), dim3(256), 0, c->stream, p + r * ld, (long long)ld, (int)m, (long long)(row0 + r), d_err);
+            hipLaunchKernelGGL(score ? k_top_validate : k_adj_validate, dim3(gx, ny), dim3(256), 0, c->stream, p + r * ld, (long long)ld, (int)m,
+                               (long long)(row0 + r), d_err);
         }
         HIPCHK(c, hipGetLastError());
     }
@@ -61,14 +63,16 @@ static int adj_validate(illico_ctx *c, const double *p, int64_t ld, int64_t nb, 
     double v = 0.0;
     if (host_p) v = host_p[r * host_ld + col];
     else HIPCHK(c, hipMemcpy(&v, p + (r - row0) * ld + col, 8, hipMemcpyDeviceToHost));
+    if (score) return fail(c, ILLICO_ERR_ARG, "score at (row %lld, column %lld) is NaN", (long long)r, (long long)col);
     return fail(c, ILLICO_ERR_ARG, "p-value at (row %lld, column %lld) is %.17g: p-values must lie in [0, 1]", (long long)r, (long long)col, v);
 }
 
-extern "C" int illico_adjust_pvalues(illico_ctx *c, const double *p, int64_t n_rows, int64_t n_cols, int64_t in_ld, int method, int flags,
-                                     double *out_adj, int64_t out_ld, int64_t n_top, int64_t *out_top, int64_t top_ld) {
+// illico_adjust_pvalues, and (score) illico_top_by_score: the same batches, sorts and merges on the keys of -x, top-n only
+static int adjust_or_top(illico_ctx *c, const double *p, int64_t n_rows, int64_t n_cols, int64_t in_ld, int method, int flags,
+                         double *out_adj, int64_t out_ld, int64_t n_top, int64_t *out_top, int64_t top_ld, bool score) {
     if (!c) return ILLICO_ERR_ARG;
     CTX_LOCK(c);
-    if (!p) return fail(c, ILLICO_ERR_ARG, "null p");
+    if (!p) return fail(c, ILLICO_ERR_ARG, score ? "null x" : "null p");
     if (n_rows < 0 || n_cols < 0) return fail(c, ILLICO_ERR_ARG, "negative shape (%lld, %lld)", (long long)n_rows, (long long)n_cols);
     if (in_ld < n_cols) return fail(c, ILLICO_ERR_ARG, "in_ld %lld smaller than n_cols %lld", (long long)in_ld, (long long)n_cols);
     if (method != ILLICO_ADJ_BH && method != ILLICO_ADJ_BY && method != ILLICO_ADJ_BONFERRONI)
@@ -111,7 +115,7 @@ extern "C" int illico_adjust_pvalues(illico_ctx *c, const double *p, int64_t n_r
 
     // device input is looked at whole before anything is written (in place or not, an invalid plane leaves every output untouched);
     // host input batch by batch, as it arrives (a plane larger than the scratch cap may then have earlier batches written)
-    if (in_dev && (rc = adj_validate(c, p, in_ld, n_rows, m, 0, d_err, nullptr, 0))) return rc;
+    if (in_dev && (rc = adj_validate(c, p, in_ld, n_rows, m, 0, d_err, nullptr, 0, score))) return rc;
     const double cm = method == ILLICO_ADJ_BY ? harmonic(m) : 0.0;
     const int gx = (int)std::min<int64_t>((m + 255) / 256, 64);
 
@@ -123,7 +127,7 @@ extern "C" int illico_adjust_pvalues(illico_ctx *c, const double *p, int64_t n_r
             HIPCHK(c, hipMemcpy2DAsync(d_in, (size_t)m * 8, dp, (size_t)in_ld * 8, (size_t)m * 8, (size_t)nb, hipMemcpyHostToDevice, c->stream));
             dp = d_in;
             dld = m;
-            if ((rc = adj_validate(c, dp, dld, nb, m, r0, d_err, p, in_ld))) return rc;
+            if ((rc = adj_validate(c, dp, dld, nb, m, r0, d_err, p, in_ld, score))) return rc;
         }
         double *dout = out_adj ? (out_dev ? out_adj + r0 * out_ld : d_out) : nullptr;
         const int64_t dold = out_dev ? out_ld : m;
@@ -146,9 +150,10 @@ extern "C" int illico_adjust_pvalues(illico_ctx *c, const double *p, int64_t n_r
                 P.n2 = (int)std::max<int64_t>(128, next_pow2(m));
                 const int nt = std::min(1024, P.n2 / 2);
                 const size_t lds = (size_t)P.n2 * 12 + 16 * 8;
-                ProfScope ps(c, KID_ADJ_SORT);
-                HIPCHK(c, hipFuncSetAttribute((const void *)k_adj_sort_lds<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(k_adj_sort_lds<true>, dim3(1, (int)nb), dim3(nt), lds, c->stream, P);
+                ProfScope ps(c, score ? KID_TOP_SORT : KID_ADJ_SORT);
+                auto kern = score ? k_top_sort_lds<true> : k_adj_sort_lds<true>;
+                HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hipLaunchKernelGGL(kern, dim3(1, (int)nb), dim3(nt), lds, c->stream, P);
                 HIPCHK(c, hipGetLastError());
             } else {
                 // runs of ADJ_LDS_COLS sorted in LDS, merged pairwise through HBM, then scanned row by row
@@ -157,21 +162,22 @@ extern "C" int illico_adjust_pvalues(illico_ctx *c, const double *p, int64_t n_r
                 P.sidx = run_i[0];
                 const size_t lds = (size_t)P.n2 * 12 + 16 * 8;
                 {
-                    ProfScope ps(c, KID_ADJ_SORT);
-                    HIPCHK(c, hipFuncSetAttribute((const void *)k_adj_sort_lds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL(k_adj_sort_lds<false>, dim3((int)((m + ADJ_LDS_COLS - 1) / ADJ_LDS_COLS), (int)nb), dim3(1024), lds, c->stream, P);
+                    ProfScope ps(c, score ? KID_TOP_SORT : KID_ADJ_SORT);
+                    auto kern = score ? k_top_sort_lds<false> : k_adj_sort_lds<false>;
+                    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                    hipLaunchKernelGGL(kern, dim3((int)((m + ADJ_LDS_COLS - 1) / ADJ_LDS_COLS), (int)nb), dim3(1024), lds, c->stream, P);
                     HIPCHK(c, hipGetLastError());
                 }
                 int cur = 0;
                 for (int64_t w = ADJ_LDS_COLS; w < m; w *= 2, cur ^= 1) {
-                    ProfScope ps(c, KID_ADJ_MERGE);
+                    ProfScope ps(c, score ? KID_TOP_MERGE : KID_ADJ_MERGE);
                     hipLaunchKernelGGL(k_adj_merge, dim3((int)((m + 255) / 256), (int)nb), dim3(256), 0, c->stream, run_k[cur], run_i[cur],
                                        run_k[cur ^ 1], run_i[cur ^ 1], (int)m, (int)w);
                     HIPCHK(c, hipGetLastError());
                 }
                 P.skey = run_k[cur];
                 P.sidx = run_i[cur];
-                ProfScope ps(c, KID_ADJ_SCAN);
+                ProfScope ps(c, score ? KID_TOP_SCAN : KID_ADJ_SCAN);
                 hipLaunchKernelGGL(k_adj_scan, dim3(1, (int)nb), dim3(ADJ_SCAN_NT), 0, c->stream, P);
                 HIPCHK(c, hipGetLastError());
             }
@@ -192,4 +198,17 @@ extern "C" int illico_adjust_pvalues(illico_ctx *c, const double *p, int64_t n_r
         }
     }
     return ILLICO_OK;
+}
+
+extern "C" int illico_adjust_pvalues(illico_ctx *c, const double *p, int64_t n_rows, int64_t n_cols, int64_t in_ld, int method, int flags,
+                                     double *out_adj, int64_t out_ld, int64_t n_top, int64_t *out_top, int64_t top_ld) {
+    return adjust_or_top(c, p, n_rows, n_cols, in_ld, method, flags, out_adj, out_ld, n_top, out_top, top_ld, false);
+}
+
+extern "C" int illico_top_by_score(illico_ctx *c, const double *x, int64_t n_rows, int64_t n_cols, int64_t in_ld, int flags, int64_t n_top,
+                                   int64_t *out_top, int64_t top_ld) {
+    if (!c) return ILLICO_ERR_ARG;
+    if (n_top < 1 && n_rows > 0 && n_cols > 0) return fail(c, ILLICO_ERR_ARG, "n_top %lld: at least 1 is needed", (long long)n_top);
+    // method ADJ_M_NONE through "no out_adj": only the order and the top-n are formed (the sort kernels' FINAL path and k_adj_scan)
+    return adjust_or_top(c, x, n_rows, n_cols, in_ld, ILLICO_ADJ_BH, flags, nullptr, 0, n_top, out_top, top_ld, true);
 }

@@ -6,7 +6,8 @@
 const char *const kKernelNames[KID_COUNT] = {"k_transpose_permute", "k_ovo_rank", "k_ovo_counts", "k_ovo_fused", "k_ovr_fused",
                                               "k_fused_tables", "k_finalize", "k_ovr_gene", "k_sparse_seg", "k_csc_gene", "k_gene_totals", "k_csc_counts", "k_csc_ovr_gene", "k_ovr_partition", "k_ovr_rank_parts", "k_value_sums", "k_ovo_fused_wide", "k_group_compact", "k_ovo_rank_compact", "k_ovr_counts", "k_gather_columns", "k_csr_counts", "k_densify", "k_group_value_hists",
                                               "k_adj_validate", "k_adj_sort_lds", "k_adj_merge", "k_adj_scan", "k_adj_bonferroni",
-                                              "k_gs_vmax", "k_gs_dense", "k_gs_csc", "k_gs_csr", "k_gs_totals", "k_gs_finalize"};
+                                              "k_gs_vmax", "k_gs_dense", "k_gs_csc", "k_gs_csr", "k_gs_totals", "k_gs_finalize",
+                                              "k_finalize_z", "k_top_validate", "k_top_sort", "k_top_merge", "k_top_scan"};
 
 // The message of a failed call is kept per calling thread (and in the context, for single-threaded callers): a second
 // thread's failure must not replace the text the first is about to read through illico_last_error.
@@ -510,8 +511,8 @@ bool fused_path_allowed(const illico_ctx *c, int flags) {
 }
 
 int launch_finalize(illico_ctx *c, const long long *s2u, const u64 *stie, const double *ssum, const double *gene_total,
-                           int nb, int flags, int alternative, double *out_p, double *out_u, double *out_fc, int64_t out_ld,
-                           int64_t col_off, const int *col_map, bool packed, bool tie_f64) {
+                           int nb, int flags, int alternative, const OutPlanes &o, int64_t col_off, const int *col_map, bool packed,
+                           bool tie_f64) {
     FinalizeParams F;
     F.col_map = col_map;
     F.packed = packed ? 1 : 0;
@@ -521,24 +522,27 @@ int launch_finalize(illico_ctx *c, const long long *s2u, const u64 *stie, const 
     F.use_continuity = (flags & ILLICO_FLAG_CONTINUITY) ? 1 : 0;
     F.tie_correct = (flags & ILLICO_FLAG_TIE_CORRECT) ? 1 : 0;
     F.alternative = alternative;
-    F.out_p = out_p + col_off; F.out_u = out_u + col_off; F.out_fc = out_fc + col_off; F.out_ld = out_ld;
-    ProfScope ps(c, KID_FINALIZE);
+    F.out_p = o.p + col_off; F.out_u = o.u + col_off; F.out_fc = o.fc + col_off; F.out_ld = o.ld;
+    F.out_z = o.z ? o.z + col_off : nullptr;
+    ProfScope ps(c, o.z ? KID_FINALIZE_Z : KID_FINALIZE);
     dim3 grid((nb + 31) / 32, ((int)c->n_groups + 31) / 32);
-    hipLaunchKernelGGL(k_finalize, grid, dim3(256), 0, c->stream, F);
+    if (o.z) hipLaunchKernelGGL(k_finalize<true>, grid, dim3(256), 0, c->stream, F); // (a fourth LDS tile: its own instantiation)
+    else hipLaunchKernelGGL(k_finalize<false>, grid, dim3(256), 0, c->stream, F);
     HIPCHK(c, hipGetLastError());
     return ILLICO_OK;
 }
-static int begin_outputs(illico_ctx *c, int flags, int64_t W, double *out_p, double *out_u, double *out_fc, int64_t out_ld, OutPlanes *o) {
+static int begin_outputs(illico_ctx *c, int flags, int64_t W, double *out_p, double *out_u, double *out_fc, int64_t out_ld, OutPlanes *o,
+                         double *out_z = nullptr) {
     if (flags & ILLICO_FLAG_OUTPUT_DEVICE) {
-        *o = {out_p, out_u, out_fc, out_ld, false};
+        *o = {out_p, out_u, out_fc, out_ld, false, out_z};
         return ILLICO_OK;
     }
     void *buf;
     size_t plane = (size_t)c->n_groups * (size_t)W;
-    int rc = get_scratch(c, "out_planes", plane * 3 * sizeof(double), &buf);
+    int rc = get_scratch(c, "out_planes", plane * (out_z ? 4 : 3) * sizeof(double), &buf);
     if (rc) return rc;
     double *b = (double *)buf;
-    *o = {b, b + plane, b + 2 * plane, W, true};
+    *o = {b, b + plane, b + 2 * plane, W, true, out_z ? b + 3 * plane : nullptr};
     return ILLICO_OK;
 }
 
@@ -547,16 +551,17 @@ static int begin_outputs(illico_ctx *c, int flags, int64_t W, double *out_p, dou
 // page of the three destination windows (read and written back: contents are preserved) while the uploads and the kernels run.
 struct PlaneTouch {
     std::vector<std::thread> pool;
-    void start(double *const planes[3], size_t n_rows, size_t row_bytes, size_t pitch_bytes) {
-        if (3 * n_rows * row_bytes < ((size_t)64 << 20)) return;
+    void start(double *const planes[4], size_t n_rows, size_t row_bytes, size_t pitch_bytes) { // (planes[3] may be null: three planes)
+        const size_t np = planes[3] ? 4 : 3;
+        if (np * n_rows * row_bytes < ((size_t)64 << 20)) return;
         const int T = 8;
-        double *p0 = planes[0], *p1 = planes[1], *p2 = planes[2];
+        double *p0 = planes[0], *p1 = planes[1], *p2 = planes[2], *p3 = planes[3];
         const bool dbg = getenv("ILLICO_HS_DEBUG") != nullptr;
         for (int t = 0; t < T; ++t)
             pool.emplace_back([=]() {
                 const auto t0 = std::chrono::steady_clock::now();
-                double *const pl[3] = {p0, p1, p2};
-                for (size_t r = 3 * n_rows * t / T; r < 3 * n_rows * (t + 1) / T; ++r) {
+                double *const pl[4] = {p0, p1, p2, p3};
+                for (size_t r = np * n_rows * t / T; r < np * n_rows * (t + 1) / T; ++r) {
                     char *row = (char *)pl[r / n_rows] + (r % n_rows) * pitch_bytes; // (8-byte aligned: a row of doubles)
                     // (volatile read + write-back: the page is faulted in for writing, its contents stay; an atomic add of 0 is
                     // folded into a load by the compiler.  Nobody else touches the planes before join().)
@@ -576,14 +581,16 @@ struct PlaneTouch {
 // Host planes: the device staging planes come back through two pinned 32-MB buffers (row blocks of the three planes in turn:
 // block i is copied down at the link's rate while block i - 1 is scattered into the caller's planes by a few host threads).  A
 // pageable destination made the driver stage the 24 bytes per test itself: 20 - 40 ms for C2's 384 MB, against ~10 ms.
-static int end_outputs(illico_ctx *c, const OutPlanes &o, int64_t W, double *out_p, double *out_u, double *out_fc, int64_t out_ld) {
+static int end_outputs(illico_ctx *c, const OutPlanes &o, int64_t W, double *out_p, double *out_u, double *out_fc, int64_t out_ld,
+                       double *out_z = nullptr) {
     if (!o.staged) return ILLICO_OK;
-    const size_t G = (size_t)c->n_groups, row = (size_t)W * 8;
-    const size_t total = 3 * G * row;
-    if (total < ((size_t)8 << 20)) { // small results: three strided copies
+    const size_t G = (size_t)c->n_groups, row = (size_t)W * 8, NP = out_z ? 4 : 3;
+    const size_t total = NP * G * row;
+    if (total < ((size_t)8 << 20)) { // small results: three (four) strided copies
         HIPCHK(c, hipMemcpy2DAsync(out_p, out_ld * 8, o.p, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpy2DAsync(out_u, out_ld * 8, o.u, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpy2DAsync(out_fc, out_ld * 8, o.fc, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
+        if (out_z) HIPCHK(c, hipMemcpy2DAsync(out_z, out_ld * 8, o.z, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return ILLICO_OK;
     }
@@ -595,16 +602,17 @@ static int end_outputs(illico_ctx *c, const OutPlanes &o, int64_t W, double *out
         for (int k = 0; k < 2; ++k) if (!c->out_ev[k]) HIPCHK(c, hipEventCreateWithFlags(&c->out_ev[k], hipEventDisableTiming));
         c->out_pin_bytes = buf;
     }
-    const size_t rows_per = std::max<size_t>(1, buf / row), n_rows = 3 * G; // rows of the three planes, one after the other
+    const size_t rows_per = std::max<size_t>(1, buf / row), n_rows = NP * G; // rows of the three (four) planes, one after the other
     if (row > buf) { // (a window too wide for the buffers: the plain copies)
         HIPCHK(c, hipMemcpy2DAsync(out_p, out_ld * 8, o.p, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpy2DAsync(out_u, out_ld * 8, o.u, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpy2DAsync(out_fc, out_ld * 8, o.fc, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
+        if (out_z) HIPCHK(c, hipMemcpy2DAsync(out_z, out_ld * 8, o.z, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return ILLICO_OK;
     }
-    const double *src[3] = {o.p, o.u, o.fc};
-    double *dst[3] = {out_p, out_u, out_fc};
+    const double *src[4] = {o.p, o.u, o.fc, o.z};
+    double *dst[4] = {out_p, out_u, out_fc, out_z};
     auto scatter = [&](int k, size_t r0, size_t r1) { // rows [r0, r1) of the concatenated planes, from pinned buffer k
         const char *from = (const char *)c->out_pin[k];
         const int T = (r1 - r0) * row >= ((size_t)4 << 20) ? 4 : 1;
@@ -697,7 +705,7 @@ static int resolve_pending(illico_ctx *c, PendingDense q) {
     if (q.kind == 1) return resolve_pending_csc(c, q);
     const u32 *hf = (const u32 *)c->pend_pinned[q.slot];
     const bool skipped = hf[q.col_ub - q.col_lb] != 0u; // the 256-value stage was left to run_leftovers (k_wide_decide)
-    const OutPlanes o{q.p, q.u, q.fc, q.out_ld, false};
+    const OutPlanes o{q.p, q.u, q.fc, q.out_ld, false, q.z};
     switch (q.dtype) {
     case ILLICO_F32: return run_leftovers<float, u32>(c, q.X, q.dtype, q.N, q.ld, q.col_lb, q.col_ub, q.flags, q.alternative, o, hf, skipped);
 #ifndef ILLICO_DEV_F32_ONLY
@@ -729,9 +737,9 @@ static int run_dense_any(illico_ctx *c, const void *X, int dtype, int64_t n_rows
     }
 }
 
-extern "C" int illico_run_dense(illico_ctx *c, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld,
-                                int64_t col_lb, int64_t col_ub, int flags, int alternative, double *out_p, double *out_u,
-                                double *out_fc, int64_t out_ld) {
+extern "C" int illico_run_dense_ex(illico_ctx *c, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld,
+                                   int64_t col_lb, int64_t col_ub, int flags, int alternative, double *out_p, double *out_u,
+                                   double *out_fc, double *out_z, int64_t out_ld) {
     if (!c) return ILLICO_ERR_ARG;
     CTX_LOCK(c);
     int rc = check_common(c, n_rows, n_cols, col_lb, col_ub, alternative, out_p, out_u, out_fc, out_ld);
@@ -752,20 +760,26 @@ extern "C" int illico_run_dense(illico_ctx *c, const void *X, int dtype, int64_t
         const size_t span = (size_t)(c->n_groups - 1) * (size_t)out_ld + (size_t)W, pspan = (size_t)(c->n_groups - 1) * (size_t)prev.out_ld + (size_t)(prev.col_ub - prev.col_lb);
         auto apart = [](const double *a, size_t na, const double *b, size_t nb) { return a + na <= b || b + nb <= a; };
         later = true;
-        for (const double *a : {out_p, out_u, out_fc})
-            for (const double *b : {prev.p, prev.u, prev.fc}) later = later && apart(a, span, b, pspan);
+        for (const double *a : {out_p, out_u, out_fc, out_z})
+            for (const double *b : {prev.p, prev.u, prev.fc, prev.z}) later = later && (!a || !b || apart(a, span, b, pspan));
     }
     if (!later && (rc = resolve_pending(c, prev))) return rc;
     if (W == 0) return later ? resolve_pending(c, prev) : ILLICO_OK;
     OutPlanes o;
-    if ((rc = begin_outputs(c, flags, W, out_p, out_u, out_fc, out_ld, &o))) { if (later) resolve_pending(c, prev); return rc; }
+    if ((rc = begin_outputs(c, flags, W, out_p, out_u, out_fc, out_ld, &o, out_z))) { if (later) resolve_pending(c, prev); return rc; }
     PlaneTouch touch; // (joined before the first result is scattered, and on every way out)
-    if (o.staged) { double *const dst[3] = {out_p, out_u, out_fc}; touch.start(dst, (size_t)c->n_groups, (size_t)W * 8, (size_t)out_ld * 8); }
+    if (o.staged) { double *const dst[4] = {out_p, out_u, out_fc, out_z}; touch.start(dst, (size_t)c->n_groups, (size_t)W * 8, (size_t)out_ld * 8); }
     rc = run_dense_any(c, X, dtype, n_rows, ld, col_lb, col_ub, flags, alternative, o);
     if (later) { const int rc2 = resolve_pending(c, prev); if (!rc) rc = rc2; }
     if (rc) return rc;
     touch.join();
-    return end_outputs(c, o, W, out_p, out_u, out_fc, out_ld);
+    return end_outputs(c, o, W, out_p, out_u, out_fc, out_ld, out_z);
+}
+
+extern "C" int illico_run_dense(illico_ctx *c, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld,
+                                int64_t col_lb, int64_t col_ub, int flags, int alternative, double *out_p, double *out_u,
+                                double *out_fc, int64_t out_ld) {
+    return illico_run_dense_ex(c, X, dtype, n_rows, n_cols, ld, col_lb, col_ub, flags, alternative, out_p, out_u, out_fc, nullptr, out_ld);
 }
 
 extern "C" int illico_planes_to_host(illico_ctx *c, const double *dev_p, const double *dev_u, const double *dev_fc, int64_t n_cols, double *out_p,
@@ -780,7 +794,7 @@ extern "C" int illico_planes_to_host(illico_ctx *c, const double *dev_p, const d
     if (rc || n_cols == 0) return rc;
     const OutPlanes o{const_cast<double *>(dev_p), const_cast<double *>(dev_u), const_cast<double *>(dev_fc), n_cols, true};
     PlaneTouch touch;
-    { double *const dst[3] = {out_p, out_u, out_fc}; touch.start(dst, (size_t)c->n_groups, (size_t)n_cols * 8, (size_t)out_ld * 8); }
+    { double *const dst[4] = {out_p, out_u, out_fc, nullptr}; touch.start(dst, (size_t)c->n_groups, (size_t)n_cols * 8, (size_t)out_ld * 8); }
     touch.join();
     return end_outputs(c, o, n_cols, out_p, out_u, out_fc, out_ld);
 }
@@ -844,14 +858,14 @@ static int resolve_pending_csc(illico_ctx *c, const PendingDense &q) {
         int64_t n_flagged = 0;
         for (int64_t j = 0; j < W; ++j) n_flagged += hf[j] ? 1 : 0;
         if ((double)vd[0] > 0.02 * (double)vd[2] || (double)vd[1] > 0.005 * (double)vd[2] || vd[3] != 0u || n_flagged * 16 > W) { // not a matrix for the route (or many genes left it): all of it
-            const OutPlanes o{q.p, q.u, q.fc, q.out_ld, false};
+            const OutPlanes o{q.p, q.u, q.fc, q.out_ld, false, q.z};
             return run_sparse_inner(c, true, q.sp_data, q.dtype, q.sp_indices, q.sp_indptr, q.idx_dtype, q.N, q.n_cols, q.col_lb, q.col_ub, q.flags, q.alternative, o);
         }
         for (int64_t j = 0; j < W;) { // runs of flagged genes (closer than 32 genes: one run)
             if (!hf[j]) { ++j; continue; }
             int64_t last = j;
             for (int64_t e = j + 1; e < W && e - last <= 32; ++e) if (hf[e]) last = e;
-            const OutPlanes o{q.p + j, q.u + j, q.fc + j, q.out_ld, false};
+            const OutPlanes o = OutPlanes{q.p, q.u, q.fc, q.out_ld, false, q.z}.shifted(j);
             const int rc = run_sparse_inner(c, true, q.sp_data, q.dtype, q.sp_indices, q.sp_indptr, q.idx_dtype, q.N, q.n_cols, q.col_lb + j, q.col_lb + last + 1,
                                             q.flags, q.alternative, o);
             if (rc) return rc;
@@ -867,7 +881,7 @@ static int resolve_pending_csc(illico_ctx *c, const PendingDense &q) {
         for (int64_t j = 0; j < W; ++j)
             if (hf[j]) { if (j == 0 || !hf[j - 1]) ++runs; if (first < 0) first = j; last = j; }
         if (runs > 8) {
-            const OutPlanes o{q.p + first, q.u + first, q.fc + first, q.out_ld, false};
+            const OutPlanes o = OutPlanes{q.p, q.u, q.fc, q.out_ld, false, q.z}.shifted(first);
             return run_sparse_inner(c, false, q.sp_data, q.dtype, q.sp_indices, q.sp_indptr, q.idx_dtype, q.N, q.n_cols, q.col_lb + first,
                                     q.col_lb + last + 1, q.flags, q.alternative, o);
         }
@@ -876,7 +890,7 @@ static int resolve_pending_csc(illico_ctx *c, const PendingDense &q) {
         if (!hf[j]) { ++j; continue; }
         int64_t e = j;
         while (e < W && hf[e]) ++e;
-        const OutPlanes o{q.p + j, q.u + j, q.fc + j, q.out_ld, false};
+        const OutPlanes o = OutPlanes{q.p, q.u, q.fc, q.out_ld, false, q.z}.shifted(j);
         const int rc = run_sparse_inner(c, false, q.sp_data, q.dtype, q.sp_indices, q.sp_indptr, q.idx_dtype, q.N, q.n_cols, q.col_lb + j,
                                         q.col_lb + e, q.flags, q.alternative, o);
         if (rc) return rc;
@@ -887,7 +901,7 @@ static int resolve_pending_csc(illico_ctx *c, const PendingDense &q) {
 
 static int run_sparse(illico_ctx *c, bool is_csr, const void *data, int dtype, const void *indices, const void *indptr,
                       int idx_dtype, int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, int alternative,
-                      double *out_p, double *out_u, double *out_fc, int64_t out_ld) {
+                      double *out_p, double *out_u, double *out_fc, int64_t out_ld, double *out_z = nullptr) {
     if (!c) return ILLICO_ERR_ARG;
     CTX_LOCK(c);
     int rc = check_common(c, n_rows, n_cols, col_lb, col_ub, alternative, out_p, out_u, out_fc, out_ld);
@@ -907,15 +921,15 @@ static int run_sparse(illico_ctx *c, bool is_csr, const void *data, int dtype, c
         const size_t span = (size_t)(c->n_groups - 1) * (size_t)out_ld + (size_t)W, pspan = (size_t)(c->n_groups - 1) * (size_t)prev.out_ld + (size_t)(prev.col_ub - prev.col_lb);
         auto apart = [](const double *a, size_t na, const double *b, size_t nb) { return a + na <= b || b + nb <= a; };
         later = true;
-        for (const double *a : {out_p, out_u, out_fc})
-            for (const double *b : {prev.p, prev.u, prev.fc}) later = later && apart(a, span, b, pspan);
+        for (const double *a : {out_p, out_u, out_fc, out_z})
+            for (const double *b : {prev.p, prev.u, prev.fc, prev.z}) later = later && (!a || !b || apart(a, span, b, pspan));
     }
     if (!later && (rc = resolve_pending(c, prev))) return rc;
     if (W == 0) return later ? resolve_pending(c, prev) : ILLICO_OK;
     OutPlanes o;
-    if ((rc = begin_outputs(c, flags, W, out_p, out_u, out_fc, out_ld, &o))) { if (later) resolve_pending(c, prev); return rc; }
+    if ((rc = begin_outputs(c, flags, W, out_p, out_u, out_fc, out_ld, &o, out_z))) { if (later) resolve_pending(c, prev); return rc; }
     PlaneTouch touch;
-    if (o.staged) { double *const dst[3] = {out_p, out_u, out_fc}; touch.start(dst, (size_t)c->n_groups, (size_t)W * 8, (size_t)out_ld * 8); }
+    if (o.staged) { double *const dst[4] = {out_p, out_u, out_fc, out_z}; touch.start(dst, (size_t)c->n_groups, (size_t)W * 8, (size_t)out_ld * 8); }
     rc = run_sparse_inner(c, is_csr, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, alternative, o);
     if (later) { // (the earlier call's leftovers run on the ordinary routes; this call's own pending state must survive them)
         const PendingDense mine = c->pend;
@@ -926,9 +940,21 @@ static int run_sparse(illico_ctx *c, bool is_csr, const void *data, int dtype, c
     }
     if (rc) return rc;
     touch.join();
-    return end_outputs(c, o, W, out_p, out_u, out_fc, out_ld);
+    return end_outputs(c, o, W, out_p, out_u, out_fc, out_ld, out_z);
 }
 
+extern "C" int illico_run_csc_ex(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr,
+                                 int idx_dtype, int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags,
+                                 int alternative, double *out_p, double *out_u, double *out_fc, double *out_z, int64_t out_ld) {
+    return run_sparse(c, false, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, alternative,
+                      out_p, out_u, out_fc, out_ld, out_z);
+}
+extern "C" int illico_run_csr_ex(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr,
+                                 int idx_dtype, int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags,
+                                 int alternative, double *out_p, double *out_u, double *out_fc, double *out_z, int64_t out_ld) {
+    return run_sparse(c, true, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, alternative,
+                      out_p, out_u, out_fc, out_ld, out_z);
+}
 extern "C" int illico_run_csc(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr,
                               int idx_dtype, int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags,
                               int alternative, double *out_p, double *out_u, double *out_fc, int64_t out_ld) {
@@ -1083,8 +1109,8 @@ static int run_bound_ahead(illico_ctx *c, const illico_matrix *m, int64_t col_lb
     return end_outputs(c, o, W, out_p, out_u, out_fc, out_ld);
 }
 
-extern "C" int illico_run_bound(illico_ctx *c, const illico_matrix *m, int64_t col_lb, int64_t col_ub, int flags, int alternative,
-                                double *out_p, double *out_u, double *out_fc, int64_t out_ld) {
+extern "C" int illico_run_bound_ex(illico_ctx *c, const illico_matrix *m, int64_t col_lb, int64_t col_ub, int flags, int alternative,
+                                   double *out_p, double *out_u, double *out_fc, double *out_z, int64_t out_ld) {
     if (!c || !m) return ILLICO_ERR_ARG;
     CTX_LOCK(c); // (recursive: held for the whole call, so that illico_matrix_release on another thread cannot free the arrays under it)
     if (m->owner != c || std::find(c->bound.begin(), c->bound.end(), m) == c->bound.end())
@@ -1098,14 +1124,18 @@ extern "C" int illico_run_bound(illico_ctx *c, const illico_matrix *m, int64_t c
     int rc;
     const int64_t A = c->bound_ahead_genes;
     if (A > 0 && m->is_csr && !c->tap && c->has_groups && col_lb >= 0 && col_lb < col_ub && col_ub <= m->n_cols && col_ub - col_lb < A && col_ub - col_lb < m->n_cols &&
-        out_p && out_u && out_fc && out_ld >= col_ub - col_lb)
+        out_p && out_u && out_fc && !out_z && out_ld >= col_ub - col_lb) // (a call with z computes its chunk directly: the windows hold three planes)
         rc = run_bound_ahead(c, m, col_lb, col_ub, flags & keep, alternative, out_p, out_u, out_fc, out_ld);
     else
         rc = run_sparse(c, m->is_csr, m->d_data, m->dtype, m->d_indices, m->d_indptr, m->idx_dtype, m->n_rows, m->n_cols, col_lb, col_ub,
-                        (flags & keep) | ILLICO_FLAG_INPUT_DEVICE, alternative, out_p, out_u, out_fc, out_ld);
+                        (flags & keep) | ILLICO_FLAG_INPUT_DEVICE, alternative, out_p, out_u, out_fc, out_ld, out_z);
     c->cur_sorted_known = false;
     c->hold_csr_counts = hold0;
     return rc;
+}
+extern "C" int illico_run_bound(illico_ctx *c, const illico_matrix *m, int64_t col_lb, int64_t col_ub, int flags, int alternative,
+                                double *out_p, double *out_u, double *out_fc, int64_t out_ld) {
+    return illico_run_bound_ex(c, m, col_lb, col_ub, flags, alternative, out_p, out_u, out_fc, nullptr, out_ld);
 }
 extern "C" int illico_matrix_release(illico_ctx *c, illico_matrix *m) {
     if (!c || !m) return ILLICO_ERR_ARG;

@@ -214,6 +214,8 @@ int run_fused_ovo(illico_ctx *c, const void *X, int64_t ld, int64_t b0, int nb, 
     P.tie_correct = (flags & ILLICO_FLAG_TIE_CORRECT) ? 1 : 0;
     P.alternative = alternative;
     P.out_p = o.p + col_off; P.out_u = o.u + col_off; P.out_fc = o.fc + col_off; P.out_ld = o.ld;
+    P.out_z = o.z ? o.z + col_off : nullptr;
+    const bool zp = o.z != nullptr; // the z-score plane: the kernels' Z = true instantiations
     const int tiles = (nb + 63) / 64;
     int gpw = c->fused_groups_per_wg;
     if (gpw <= 0) { // 8 groups per workgroup (two per wavefront) measured best at C2 (4: +2 %, 16: +1 %, 32: +3 %: shorter
@@ -278,14 +280,15 @@ int run_fused_ovo(illico_ctx *c, const void *X, int64_t ld, int64_t b0, int nb, 
         } else hipLaunchKernelGGL((k_group_hists_to_column<RT, false>), dim3(tiles), dim3(256), 0, c->stream, P, (const u32 *)H);
         hipLaunchKernelGGL((k_fused_tables_all<RT>), dim3((nb + 255) / 256), dim3(256), 0, c->stream, P);
         const dim3 ge(tiles, ((int)c->n_groups + 3) / 4);
-        if (ovr) hipLaunchKernelGGL((k_emit_from_group_hists<RT, true>), ge, dim3(256), 0, c->stream, P, (const u32 *)H);
-        else hipLaunchKernelGGL((k_emit_from_group_hists<RT, false>), ge, dim3(256), 0, c->stream, P, (const u32 *)H);
+        auto emit = ovr ? (zp ? k_emit_from_group_hists<RT, true, true> : k_emit_from_group_hists<RT, true>)
+                        : (zp ? k_emit_from_group_hists<RT, false, true> : k_emit_from_group_hists<RT, false>);
+        hipLaunchKernelGGL(emit, ge, dim3(256), 0, c->stream, P, (const u32 *)H);
         HIPCHK(c, hipGetLastError());
     } else if (!ovr) {
         if (wide_only) {
         } else if (tiles >= 100) { // one 1024-thread workgroup per tile builds the tables (C2: 125 tiles, 0.074 ms)
             ProfScope ps(c, KID_FUSED_REF);
-            auto kern = k_fused_ref<InT, RT>;
+            auto kern = zp ? k_fused_ref<InT, RT, false, true> : k_fused_ref<InT, RT>;
             hipLaunchKernelGGL(kern, dim3(tiles), dim3(FUSED_REF_NT), fused_ref_lds_bytes(RT), c->stream, P);
             HIPCHK(c, hipGetLastError());
         } else { // few tiles (a C5 shard: 59): the reference rows split over (tiles, row chunks), then one thread per gene for
@@ -303,10 +306,11 @@ int run_fused_ovo(illico_ctx *c, const void *X, int64_t ld, int64_t b0, int nb, 
         if (!wide_only) {
             ProfScope ps(c, KID_OVO_FUSED);
             if (c->max_nonref <= 255) // 8-bit running multiplicities: 34 KB of LDS per workgroup instead of 50 KB
-                hipLaunchKernelGGL((k_ovo_fused<InT, RT, false, 8>), main_grid, dim3(FUSED_NT), lds8, c->stream, P);
-            else if (c->max_nonref <= 65535) hipLaunchKernelGGL((k_ovo_fused<InT, RT, false, 16>), main_grid, dim3(FUSED_NT), lds16, c->stream, P);
+                hipLaunchKernelGGL((zp ? k_ovo_fused<InT, RT, false, 8, FUSED_U, false, true> : k_ovo_fused<InT, RT, false, 8>), main_grid, dim3(FUSED_NT), lds8, c->stream, P);
+            else if (c->max_nonref <= 65535)
+                hipLaunchKernelGGL((zp ? k_ovo_fused<InT, RT, false, 16, FUSED_U, false, true> : k_ovo_fused<InT, RT, false, 16>), main_grid, dim3(FUSED_NT), lds16, c->stream, P);
             else { // clusters of more than 65535 cells: 32-bit multiplicities (82 KB: one workgroup per CU)
-                auto kern = k_ovo_fused<InT, RT, false, 32>;
+                auto kern = zp ? k_ovo_fused<InT, RT, false, 32, FUSED_U, false, true> : k_ovo_fused<InT, RT, false, 32>;
                 const size_t lds32 = fused_main_lds_bytes<RT, false, 32>();
                 HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32));
                 hipLaunchKernelGGL(kern, main_grid, dim3(FUSED_NT), lds32, c->stream, P);
@@ -330,13 +334,13 @@ int run_fused_ovo(illico_ctx *c, const void *X, int64_t ld, int64_t b0, int nb, 
             HIPCHK(c, hipMemsetAsync(Q.wide_tiles, 0, 4, c->stream));
             {
                 ProfScope ps(c, KID_FUSED_REF);
-                auto kern = k_fused_ref<InT, WRT, true>;
+                auto kern = zp ? k_fused_ref<InT, WRT, true, true> : k_fused_ref<InT, WRT, true>;
                 HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_ref_lds_bytes(WRT)));
                 hipLaunchKernelGGL(kern, dim3(tiles), dim3(FUSED_REF_NT), fused_ref_lds_bytes(WRT), c->stream, Q);
                 HIPCHK(c, hipGetLastError());
             }
             ProfScope ps(c, KID_OVO_FUSED_WIDE);
-            auto kern = k_ovo_fused<InT, WRT, false, 8, FUSED_U, true>;
+            auto kern = zp ? k_ovo_fused<InT, WRT, false, 8, FUSED_U, true, true> : k_ovo_fused<InT, WRT, false, 8, FUSED_U, true>;
             const size_t lds = fused_main_lds_bytes<WRT, false, 8>();
             HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             int n_cu = 256;
@@ -371,10 +375,9 @@ int run_fused_ovo(illico_ctx *c, const void *X, int64_t ld, int64_t b0, int nb, 
             while (P2.groups_per_wg > 8 && (int64_t)tiles * ((c->n_groups + P2.groups_per_wg - 1) / P2.groups_per_wg) < 2048) P2.groups_per_wg >>= 1;
             const dim3 grid2(tiles, ((int)c->n_groups + P2.groups_per_wg - 1) / P2.groups_per_wg);
             const bool np3 = c->n_cells < (1ll << 23); // s < 2^24: three byte planes
-            if (cbits == 8 && np3) hipLaunchKernelGGL((k_ovr_from_hists<RT, 8, 3>), grid2, dim3(FUSED_NT), 0, c->stream, P2);
-            else if (cbits == 8) hipLaunchKernelGGL((k_ovr_from_hists<RT, 8, 4>), grid2, dim3(FUSED_NT), 0, c->stream, P2);
-            else if (np3) hipLaunchKernelGGL((k_ovr_from_hists<RT, 0, 3>), grid2, dim3(FUSED_NT), 0, c->stream, P2);
-            else hipLaunchKernelGGL((k_ovr_from_hists<RT, 0, 4>), grid2, dim3(FUSED_NT), 0, c->stream, P2);
+            auto k_from = cbits == 8 ? (np3 ? (zp ? k_ovr_from_hists<RT, 8, 3, true> : k_ovr_from_hists<RT, 8, 3>) : (zp ? k_ovr_from_hists<RT, 8, 4, true> : k_ovr_from_hists<RT, 8, 4>))
+                                     : (np3 ? (zp ? k_ovr_from_hists<RT, 0, 3, true> : k_ovr_from_hists<RT, 0, 3>) : (zp ? k_ovr_from_hists<RT, 0, 4, true> : k_ovr_from_hists<RT, 0, 4>));
+            hipLaunchKernelGGL(k_from, grid2, dim3(FUSED_NT), 0, c->stream, P2);
             HIPCHK(c, hipGetLastError());
         } else {
             {
@@ -385,7 +388,7 @@ int run_fused_ovo(illico_ctx *c, const void *X, int64_t ld, int64_t b0, int nb, 
                 HIPCHK(c, hipGetLastError());
             }
             ProfScope ps(c, KID_OVR_FUSED);
-            hipLaunchKernelGGL((k_ovo_fused<InT, RT, true, 16>), main_grid, dim3(FUSED_NT), lds_ovr, c->stream, P);
+            hipLaunchKernelGGL((zp ? k_ovo_fused<InT, RT, true, 16, FUSED_U, false, true> : k_ovo_fused<InT, RT, true, 16>), main_grid, dim3(FUSED_NT), lds_ovr, c->stream, P);
             HIPCHK(c, hipGetLastError());
         }
     }
@@ -416,7 +419,7 @@ int run_fused_ovo(illico_ctx *c, const void *X, int64_t ld, int64_t b0, int nb, 
             HIPCHK(c, hipGetLastError());
         }
         ProfScope ps(c, KID_OVO_FUSED_WIDE);
-        auto kern = k_ovo_fused<InT, WRT, true, 16, FUSED_U, true>;
+        auto kern = zp ? k_ovo_fused<InT, WRT, true, 16, FUSED_U, true, true> : k_ovo_fused<InT, WRT, true, 16, FUSED_U, true>;
         const size_t lds = fused_main_lds_bytes<WRT, true, 16>();
         HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         int n_cu = 256;
@@ -776,9 +779,9 @@ static int leftovers_on_narrow(illico_ctx *c, InT *xl, int dtype, int64_t N, int
         bool any = false;
         for (int64_t j = 0; j < n; ++j) any = any || init[j] == 1u;
         if (any) {
-            if ((rc = get_scratch(c, "wide_tmp", (size_t)3 * G * (size_t)n_pad * 8, &v))) return rc;
+            if ((rc = get_scratch(c, "wide_tmp", (size_t)(o.z ? 4 : 3) * G * (size_t)n_pad * 8, &v))) return rc;
             double *tp = (double *)v;
-            const OutPlanes ot{tp, tp + (size_t)G * n_pad, tp + (size_t)2 * G * n_pad, n_pad, false};
+            const OutPlanes ot{tp, tp + (size_t)G * n_pad, tp + (size_t)2 * G * n_pad, n_pad, false, o.z ? tp + (size_t)3 * G * n_pad : nullptr};
             if ((rc = run_fused_ovo<InT>(c, xl, n_pad, 0, (int)n, lflags, alternative, ot, 0, hf2, -1, false, 0, init.data()))) return rc;
             HIPCHK(c, hipMemcpyAsync(d_flags2, hf2.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
             {
@@ -786,6 +789,8 @@ static int leftovers_on_narrow(illico_ctx *c, InT *xl, int dtype, int64_t N, int
                 const dim3 grid((unsigned)((n + 255) / 256), (unsigned)std::min(G, 1024));
                 hipLaunchKernelGGL(k_scatter_planes, grid, dim3(256), 0, c->stream, (const double *)ot.p, (const double *)ot.u, (const double *)ot.fc, (long long)n_pad,
                                    (const int *)d_dst, (const u32 *)d_flags2, 2u, (int)n, G, o.p, o.u, o.fc, (long long)o.ld);
+                if (o.z) hipLaunchKernelGGL(k_scatter_plane, grid, dim3(256), 0, c->stream, (const double *)ot.z, (long long)n_pad, (const int *)d_dst,
+                                            (const u32 *)d_flags2, 2u, (int)n, G, o.z, (long long)o.ld);
                 HIPCHK(c, hipGetLastError());
             }
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -882,7 +887,7 @@ int run_dense_t(illico_ctx *c, const void *X, int dtype, int64_t N, int64_t ld, 
             c->pend_next ^= 1;
             PendingDense &q = c->pend;
             q.on = true; q.kind = 0; q.X = X; q.dtype = dtype; q.flags = flags & ~ILLICO_FLAG_DEFER; q.alternative = alternative; q.slot = slot;
-            q.N = N; q.ld = ld; q.col_lb = col_lb; q.col_ub = col_ub; q.out_ld = o.ld; q.p = o.p; q.u = o.u; q.fc = o.fc;
+            q.N = N; q.ld = ld; q.col_lb = col_lb; q.col_ub = col_ub; q.out_ld = o.ld; q.p = o.p; q.u = o.u; q.fc = o.fc; q.z = o.z;
             return ILLICO_OK;
         }
         if ((rc = run_fused_ovo<InT>(c, X, ld, col_lb, (int)W, flags, alternative, o, 0, hf, -1, ovr, max_gather))) return rc;
@@ -1006,7 +1011,7 @@ static int run_dense_twopass(illico_ctx *c, const void *X, int dtype, int64_t N,
                 HIPCHK(c, hipStreamSynchronize(c->stream));
                 continue;
             }
-            if ((rc = launch_finalize(c, s2u, stie, ssum, nullptr, nb, flags, alternative, o.p, o.u, o.fc, o.ld, cmap ? 0 : b0 - col_lb, cmap ? cmap + (b0 - col_lb) : nullptr))) return rc;
+            if ((rc = launch_finalize(c, s2u, stie, ssum, nullptr, nb, flags, alternative, o, cmap ? 0 : b0 - col_lb, cmap ? cmap + (b0 - col_lb) : nullptr))) return rc;
             continue;
         }
         OvrPackedInput pki;
@@ -1052,7 +1057,7 @@ static int run_dense_twopass(illico_ctx *c, const void *X, int dtype, int64_t N,
                 HIPCHK(c, hipStreamSynchronize(c->stream));
                 continue;
             }
-            if ((rc = launch_finalize(c, s2u, stie, ssum, nullptr, nb, flags, alternative, o.p, o.u, o.fc, o.ld, cmap ? 0 : b0 - col_lb, cmap ? cmap + (b0 - col_lb) : nullptr))) return rc;
+            if ((rc = launch_finalize(c, s2u, stie, ssum, nullptr, nb, flags, alternative, o, cmap ? 0 : b0 - col_lb, cmap ? cmap + (b0 - col_lb) : nullptr))) return rc;
         } else if (ovr_counts) {
             // count-like leftovers: the column-histogram kernel takes every integer gene below OVRC_R; the value-range parts /
             // the general route only see the runs of genes it flags
@@ -1081,7 +1086,7 @@ static int run_dense_twopass(illico_ctx *c, const void *X, int dtype, int64_t N,
                                                              stie + (size_t)j * G, ssum + (size_t)j * G, gtot + j, false))) return rc;
                 j = e;
             }
-            if ((rc = launch_finalize(c, s2u, stie, ssum, gtot, nb, flags, alternative, o.p, o.u, o.fc, o.ld, cmap ? 0 : b0 - col_lb, cmap ? cmap + (b0 - col_lb) : nullptr))) return rc;
+            if ((rc = launch_finalize(c, s2u, stie, ssum, gtot, nb, flags, alternative, o, cmap ? 0 : b0 - col_lb, cmap ? cmap + (b0 - col_lb) : nullptr))) return rc;
         } else {
             bool done = false;
             if ((rc = run_ovr_dense_parts<KeyT>(c, Xt, stride, nb, (int)N, dtype, flags, s2u, stie, ssum, gtot, &done, padded, ovr_packed ? &pki : nullptr))) return rc;
@@ -1097,7 +1102,7 @@ static int run_dense_twopass(illico_ctx *c, const void *X, int dtype, int64_t N,
                 HIPCHK(c, hipStreamSynchronize(c->stream));
                 continue;
             }
-            if ((rc = launch_finalize(c, s2u, stie, ssum, gtot, nb, flags, alternative, o.p, o.u, o.fc, o.ld, cmap ? 0 : b0 - col_lb, cmap ? cmap + (b0 - col_lb) : nullptr))) return rc;
+            if ((rc = launch_finalize(c, s2u, stie, ssum, gtot, nb, flags, alternative, o, cmap ? 0 : b0 - col_lb, cmap ? cmap + (b0 - col_lb) : nullptr))) return rc;
         }
     }
     if (!redo_runs.empty()) { // (tie-heavy columns of a matrix with groups above 1024 cells: transposition + the general sort route)

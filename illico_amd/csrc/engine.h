@@ -72,6 +72,11 @@ enum {
     KID_GS_CSR,
     KID_GS_TOTALS,
     KID_GS_FINALIZE,
+    KID_FINALIZE_Z, // k_finalize<true>, profiled as "k_finalize_z": with the z-score plane
+    KID_TOP_VALIDATE, // illico_top_by_score (kernels_adjust.h)
+    KID_TOP_SORT,
+    KID_TOP_MERGE,
+    KID_TOP_SCAN,
     KID_COUNT
 };
 extern const char *const kKernelNames[KID_COUNT];
@@ -90,6 +95,7 @@ struct PendingDense {
     bool sorted_known = false;    // kind 1, CSR: the matrix was bound and its rows found in order (illico_ctx::cur_sorted_known when the call was made)
     int64_t N = 0, ld = 0, col_lb = 0, col_ub = 0, out_ld = 0;
     double *p = nullptr, *u = nullptr, *fc = nullptr;
+    double *z = nullptr;          // the call's z-score plane (null: none): complete exactly when p is
 };
 
 // a sparse matrix bound to a context (illico_csr_bind / illico_csc_bind): device arrays, owned or adopted
@@ -300,6 +306,8 @@ struct OutPlanes {
     double *p, *u, *fc; // device
     int64_t ld;
     bool staged;
+    double *z = nullptr; // device z-score plane (the *_ex entry points), null = none
+    OutPlanes shifted(int64_t j) const { return {p + j, u + j, fc + j, ld, staged, z ? z + j : nullptr}; } // column j on
 };
 
 // pinned slots / copy stream of the host-window pipeline (dense_driver.h: host_windows_pipeline); one per context, freed with it
@@ -322,8 +330,7 @@ int ovo_counts_limit(const illico_ctx *c);           // table size of the two-pa
 bool counts_path_allowed(const illico_ctx *c, int flags);
 bool fused_path_allowed(const illico_ctx *c, int flags);
 int launch_finalize(illico_ctx *c, const long long *s2u, const u64 *stie, const double *ssum, const double *gene_total, int nb, int flags,
-                    int alternative, double *out_p, double *out_u, double *out_fc, int64_t out_ld, int64_t col_off, const int *col_map = nullptr,
-                    bool packed = false, bool tie_f64 = false);
+                    int alternative, const OutPlanes &o, int64_t col_off, const int *col_map = nullptr, bool packed = false, bool tie_f64 = false);
 int launch_gene_totals(illico_ctx *c, const double *ssum, int G, int nb, double *gtot);
 void flagged_runs(const u32 *hf, int64_t wn, int64_t w0, std::vector<std::pair<int64_t, int64_t>> &runs);
 

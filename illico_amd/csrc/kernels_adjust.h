@@ -31,6 +31,13 @@
 enum { ADJ_M_BH = 0, ADJ_M_BY = 1, ADJ_M_NONE = 2 }; // what the sort kernels form besides the order (NONE: top-n only)
 
 __device__ __forceinline__ u64 adj_key(double p) { return (u64)__double_as_longlong(p + 0.0); }
+// illico_top_by_score: the order-preserving u64 of -x + 0.0 (sign bit set: all bits flipped, else the sign bit set), so that keys ascend as
+// x descends; -0.0 and +0.0 share a key, +inf sorts first, -inf last -- at 0xFFF0000000000000, still below the padding key ~0.  (NaN is
+// refused before: k_top_validate.)
+__device__ __forceinline__ u64 score_key(double x) {
+    const u64 b = (u64)__double_as_longlong(-x + 0.0);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
 
 struct AdjParams {
     const double *p;        // first row of the batch
@@ -86,6 +93,13 @@ __global__ __launch_bounds__(256) void k_adj_validate(const double *__restrict__
         if (adj_key(row[c]) > ADJ_KEY_MAX) atomicMin(err, (u64)(row0 + blockIdx.y) * (u64)m + (u64)c);
 }
 
+// illico_top_by_score: the first NaN, as k_adj_validate
+__global__ __launch_bounds__(256) void k_top_validate(const double *__restrict__ x, long long ld, int m, long long row0, u64 *__restrict__ err) {
+    const double *row = x + (size_t)blockIdx.y * ld;
+    for (int c = blockIdx.x * 256 + (int)threadIdx.x; c < m; c += gridDim.x * 256)
+        if (isnan(row[c])) atomicMin(err, (u64)(row0 + blockIdx.y) * (u64)m + (u64)c);
+}
+
 // grid (column blocks, rows)
 __global__ __launch_bounds__(256) void k_adj_bonferroni(const double *__restrict__ p, long long ld, int m, double *__restrict__ out,
                                                         long long out_ld) {
@@ -96,8 +110,9 @@ __global__ __launch_bounds__(256) void k_adj_bonferroni(const double *__restrict
 
 // grid (segments, rows), blockDim = min(1024, n2 / 2) (n2 a power of two, at least 128); dynamic LDS 12 * n2 + 8 * 16 bytes.
 // FINAL: grid.x == 1 and m <= n2.  Otherwise segment s holds columns [s * n2, min((s + 1) * n2, m)) and is written, sorted, to skey / sidx.
-template <bool FINAL>
-__global__ __launch_bounds__(1024) void k_adj_sort_lds(AdjParams P) {
+// SCORE (k_top_sort_lds): the keys of illico_top_by_score; only the order and the top-n are formed (method ADJ_M_NONE).
+template <bool FINAL, bool SCORE>
+__device__ __forceinline__ void adj_sort_lds_body(const AdjParams &P) {
     extern __shared__ __align__(16) unsigned char adj_lds[];
     const int n2 = P.n2, nt = blockDim.x, tid = threadIdx.x;
     u64 *key = (u64 *)adj_lds;
@@ -108,7 +123,7 @@ __global__ __launch_bounds__(1024) void k_adj_sort_lds(AdjParams P) {
     const int valid = min(n2, P.m - c0);
     const double *prow = P.p + row * P.in_ld + c0;
     for (int i = tid; i < n2; i += nt) {
-        key[i] = i < valid ? adj_key(prow[i]) : ~0ull; // padding sorts last (every valid key is at most ADJ_KEY_MAX)
+        key[i] = i < valid ? (SCORE ? score_key(prow[i]) : adj_key(prow[i])) : ~0ull; // padding sorts last (every valid key is below ~0)
         idx[i] = i < valid ? (u32)(c0 + i) : 0xFFFFFFFFu;
     }
     __syncthreads();
@@ -159,6 +174,10 @@ __global__ __launch_bounds__(1024) void k_adj_sort_lds(AdjParams P) {
         }
     }
 }
+template <bool FINAL>
+__global__ __launch_bounds__(1024) void k_adj_sort_lds(AdjParams P) { adj_sort_lds_body<FINAL, false>(P); }
+template <bool FINAL>
+__global__ __launch_bounds__(1024) void k_top_sort_lds(AdjParams P) { adj_sort_lds_body<FINAL, true>(P); }
 
 // grid (ceil(m / 256), rows): runs of w sorted slots -> runs of 2w
 __global__ __launch_bounds__(256) void k_adj_merge(const u64 *__restrict__ sk, const u32 *__restrict__ si, u64 *__restrict__ dk,

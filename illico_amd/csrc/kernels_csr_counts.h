@@ -68,6 +68,7 @@ struct CsrCountsParams {
     const int *big_groups;               // [n_big] group numbers
     int n_big;
     int abl;                             // timing experiments only (tools/ab.py csr_counts_abl): 1 no entry loop, 2 no sweep, 4 no LDS atomics, 8 no p-values
+    double *out_z;                       // [G][out_ld] z-score plane (zscore_device_pre), offset like out_p; null = none
 };
 
 // {non-integer samples, samples beyond the table, samples, rows out of order}: more than 2 % / 0.5 % of the samples, or any row out of
@@ -390,7 +391,9 @@ static inline size_t csrh_lds_bytes(int Wg) { return (size_t)Wg * CSRH_WPG * 4; 
 
 // The sweep of one (group, gene window): one thread per gene.  word(i, j, live) = word i of gene j's cells -- from LDS behind the entry
 // loop (OVO), or from the dump of the OVR count pass.
-template <bool OVR, bool PRELOAD = false, typename WordFn>
+// Z: the z-score plane too, when P.out_z is set (k_csr_counts: one instantiation for both, its resources are the same; k_csr_ovr_sweep
+// has one without the z code for the calls without z)
+template <bool OVR, bool PRELOAD = false, bool Z = true, typename WordFn>
 __device__ __forceinline__ void csrc_sweep(const CsrCountsParams &P, int g, int n_g, int w, int wcols, bool is_ref, int tid, WordFn word) {
     const int Wg = P.Wg;
     const double cc = P.use_continuity ? 0.5 : 0.0;
@@ -409,7 +412,7 @@ __device__ __forceinline__ void csrc_sweep(const CsrCountsParams &P, int g, int 
         const uint4 gi = P.ginfo[jc];
         const double gt = P.gene_total[jc]; // OVO: the reference group's mean; OVR: the column's value sum
         const u64 T_sel = (u64)gi.x | ((u64)gi.y << 32), zsel = gi.z;
-        double p, U, fc;
+        double p, U, fc, z = 0.0;
         if (is_ref) { // sparse_ovo.py:140-143
             p = 1.0; U = -1.0;
             fc = (gt == 0.0) ? inf : gt / gt;
@@ -477,6 +480,7 @@ __device__ __forceinline__ void csrc_sweep(const CsrCountsParams &P, int g, int 
             U = 0.5 * (double)two_u;
             const double tie_d = !P.tie_correct ? 0.0 : (OVR ? __longlong_as_double((long long)tie_sum) : (double)tie_sum);
             p = (P.abl & 8) ? tie_d : pval_device_pre(nnn, var0, n12, tie_d, U, mu, cc, P.alternative);
+            if (Z && P.out_z) z = zscore_device_pre(nnn, var0, tie_d, U, mu); // (uniform branch)
             // fold change, math.py:181-192 (integer value sums: exact)
             const double sum_g = (double)vsum;
             if (OVR) fc = fold_change_device(sum_g, gt - sum_g, gc);
@@ -490,6 +494,7 @@ __device__ __forceinline__ void csrc_sweep(const CsrCountsParams &P, int g, int 
             P.out_p[o] = p;
             P.out_u[o] = U;
             P.out_fc[o] = fc;
+            if (Z && P.out_z) P.out_z[o] = z;
         }
     }
 }
@@ -542,6 +547,7 @@ __global__ __launch_bounds__(CSRC_NT, 4) void k_csr_counts(CsrCountsParams P) {
 }
 
 // OVR, second pass: every (group, window) from its dumped cells.  grid (windows, groups)
+template <bool Z = false>
 static __global__ __launch_bounds__(CSRC_NT) void k_csr_ovr_sweep(CsrCountsParams P) {
     if (csrc_verdict_bad(P.verdict)) return;
     const int Wg = P.Wg, w = blockIdx.x, g = blockIdx.y;
@@ -549,7 +555,7 @@ static __global__ __launch_bounds__(CSRC_NT) void k_csr_ovr_sweep(CsrCountsParam
     const int n_g = P.pos_ptr[g + 1] - P.pos_ptr[g];
     if (n_g > 255) return; // (k_csr_big_sweep)
     const u32 *src = P.dump + ((size_t)g * gridDim.x + w) * CSRC_WPG * Wg;
-    csrc_sweep<true, true>(P, g, n_g, w, wcols, false, threadIdx.x, [&](int i, int j, bool live) { return live ? src[i * Wg + j] : 0u; });
+    csrc_sweep<true, true, Z>(P, g, n_g, w, wcols, false, threadIdx.x, [&](int i, int j, bool live) { return live ? src[i * Wg + j] : 0u; });
 }
 
 // OVR: the column histograms from the dump -- one thread per (gene, slice of the groups): the cells of its groups added up in registers,
@@ -581,7 +587,7 @@ static __global__ __launch_bounds__(256) void k_csr_colhist(CsrCountsParams P, i
 
 // ---- groups of more than 255 cells: their histograms were added up chunk by chunk (k_csr_hist, slab 1 + k); one thread per (big
 // group, gene) turns them into the statistics with 64-bit terms.  grid (gene blocks of 256, big groups)
-template <bool OVR>
+template <bool OVR, bool Z = false> // (Z: the z-score plane too)
 __global__ __launch_bounds__(256) void k_csr_big_sweep(CsrCountsParams P) {
     if (csrc_verdict_bad(P.verdict)) return;
     const int jc = blockIdx.x * blockDim.x + threadIdx.x;
@@ -634,4 +640,5 @@ __global__ __launch_bounds__(256) void k_csr_big_sweep(CsrCountsParams P) {
     P.out_p[o] = p;
     P.out_u[o] = U;
     P.out_fc[o] = fc;
+    if constexpr (Z) P.out_z[o] = zscore_device_pre(gc.nnn, gc.var0, !P.tie_correct ? 0.0 : (OVR ? __longlong_as_double((long long)tie_sum) : (double)tie_sum), U, gc.mu);
 }

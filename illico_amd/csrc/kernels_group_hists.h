@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void k_group_hists_to_column(FusedParams P, co
 }
 
 // grid (tiles, ceil(G / 4)): one wavefront per (group, tile), lane = gene
-template <int RT, bool OVR>
+template <int RT, bool OVR, bool Z = false> // (Z: as k_ovo_fused)
 __global__ __launch_bounds__(256) void k_emit_from_group_hists(FusedParams P, const u32 *__restrict__ H) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tile = blockIdx.x, tiles = gridDim.x, gene = tile * 64 + lane;
@@ -128,12 +128,12 @@ __global__ __launch_bounds__(256) void k_emit_from_group_hists(FusedParams P, co
     const double ref_sum = (double)P.ref_sum[gene];
     const double cc = P.use_continuity ? 0.5 : 0.0;
     const GroupConst gc = P.gconst[g];
-    double pv, Ustat, fc;
+    double pv, Ustat, fc, tie;
     if (OVR) { // as k_ovo_fused's emit (dense_ovr.py:57-75)
         const long long n_rest = P.n_cells - n_tgt;
         const long long two_u = 2ll * n_rest * n_tgt + n_tgt * (n_tgt + 1) - ((long long)S2 + n_tgt);
         Ustat = 0.5 * (double)two_u;
-        const double tie = !P.tie_correct ? 0.0 : (P.tie_mode ? __longlong_as_double((long long)T_A) : (double)T_A);
+        tie =!P.tie_correct ? 0.0 : (P.tie_mode ? __longlong_as_double((long long)T_A) : (double)T_A);
         pv = pval_device_pre(gc.nnn, gc.var0, gc.n12, tie, Ustat, gc.mu, cc, P.alternative);
         fc = fold_change_device((double)vsum, ref_sum - (double)vsum, gc);
     } else {
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void k_emit_from_group_hists(FusedParams P, co
         const u64 tie_i = T_A + 3ull * TT;
         const long long two_u = 2ll * n_ref * n_tgt - (long long)S2;
         Ustat = 0.5 * (double)two_u;
-        const double tie = P.tie_correct ? (double)tie_i : 0.0;
+        tie = P.tie_correct ? (double)tie_i : 0.0;
         pv = pval_device_pre(gc.nnn, gc.var0, gc.n12, tie, Ustat, gc.mu, cc, P.alternative);
         fc = (mu_ref_ovo == 0.0) ? __longlong_as_double(0x7FF0000000000000ll) : ((double)vsum / gc.d_tgt) / mu_ref_ovo;
     }
@@ -150,4 +150,5 @@ __global__ __launch_bounds__(256) void k_emit_from_group_hists(FusedParams P, co
     P.out_p[o] = pv;
     P.out_u[o] = Ustat;
     P.out_fc[o] = fc;
+    if constexpr (Z) P.out_z[o] = zscore_device_pre(gc.nnn, gc.var0, tie, Ustat, gc.mu);
 }

@@ -55,6 +55,14 @@ static __global__ __launch_bounds__(256) void k_scatter_planes(const double *__r
         ofc[o] = fc[i];
     }
 }
+// the same for one plane (the z-score plane of a call that asks for it)
+static __global__ __launch_bounds__(256) void k_scatter_plane(const double *__restrict__ z, long long ld, const int *__restrict__ map,
+                                                       const u32 *__restrict__ flags, u32 want, int n, int G, double *oz, long long out_ld) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n || flags[j] != want) return;
+    const long long dst = map[j];
+    for (int g = blockIdx.y; g < G; g += gridDim.y) oz[(size_t)g * out_ld + dst] = z[(size_t)g * ld + j];
+}
 
 #define OVRC_R 32768
 #define OVRC_NT 1024

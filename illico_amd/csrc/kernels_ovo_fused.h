@@ -59,6 +59,7 @@ struct FusedParams {
     unsigned char *hist_words; // OVR one pass: [G][tiles] words of a (group, tile) histogram that were written (the rest are zero)
     const u32 *wide_skip;     // WIDE: *wide_skip != 0 (k_wide_decide): the 256-value stage is left to the host (every WIDE kernel returns at once)
     const u32 *hist_off;      // OVR one-pass form, mixed cell widths: [G + 1] words per lane before group g (16 for a group of <= 255 cells, else 32)
+    double *out_z;            // [G][out_ld] z-score plane (zscore_device_pre), offset like out_p; null = none
 };
 
 // Table index of a value, clamped into [0, RT-1], and whether the value IS that integer (else the gene leaves
@@ -265,7 +266,8 @@ static __global__ __launch_bounds__(1024) void k_wide_decide(const u32 *__restri
 #define FUSED_REF_NT 1024
 #define FUSED_WIDE_RT 256
 static inline size_t fused_ref_lds_bytes(int rt) { return (size_t)64 * (rt + 1) * 4; }
-template <typename InT, int RT, bool WIDE = false>
+// Z: also the reference row of the z-score plane (zeros).  The calls without z run the instantiations that have no z code (Z = false).
+template <typename InT, int RT, bool WIDE = false, bool Z = false>
 __global__ __launch_bounds__(FUSED_REF_NT) void k_fused_ref(FusedParams P) {
     constexpr int NW = FUSED_REF_NT / 64, STR = RT + 1, UR = 16;
     extern __shared__ __align__(16) u32 h[]; // [64 * STR]
@@ -331,6 +333,7 @@ __global__ __launch_bounds__(FUSED_REF_NT) void k_fused_ref(FusedParams P) {
         P.out_p[o] = 1.0;                                                            // sparse_ovo.py:140-143
         P.out_u[o] = -1.0;
         P.out_fc[o] = (sum == 0) ? __longlong_as_double(0x7FF0000000000000ll) : 1.0; // math.py:190-192 with mu_tgt == mu_ref
+        if constexpr (Z) P.out_z[o] = 0.0;
         }
     }
     __syncthreads();
@@ -491,6 +494,7 @@ template <int RT, bool WIDE = false> __global__ void k_fused_tables_all(FusedPar
         P.out_p[o] = 1.0;                                                            // sparse_ovo.py:140-143
         P.out_u[o] = -1.0;
         P.out_fc[o] = (sum == 0) ? __longlong_as_double(0x7FF0000000000000ll) : 1.0; // math.py:190-192 with mu_tgt == mu_ref
+        if (P.out_z) P.out_z[o] = 0.0;
     }
 }
 
@@ -503,7 +507,8 @@ template <int RT, bool WIDE = false> __global__ void k_fused_tables_all(FusedPar
 template <int RT, bool OVR, int CB> static inline size_t fused_main_lds_bytes() {
     return (size_t)(RT + 1) * 64 * 4 + (size_t)(FUSED_NT / 64) * (OVR ? 1 : RT * CB / 32) * 64 * 4;
 }
-template <typename InT, int RT, bool OVR, int CB, int U = FUSED_U, bool WIDE = false>
+// Z: also the z-score plane (zscore_device_pre); Z = false has no z code (the calls without z).
+template <typename InT, int RT, bool OVR, int CB, int U = FUSED_U, bool WIDE = false, bool Z = false>
 __global__ __launch_bounds__(FUSED_NT, WIDE ? (OVR ? 2 : 1) : ((OVR || CB == 8) ? 4 : 3)) void k_ovo_fused(FusedParams P) {
     constexpr int NT = FUSED_NT, NW = NT / 64, CSTR = RT + 1, BW = OVR ? 1 : RT * CB / 32;
     // Both tables are laid out [value][lane]: the LDS bank of a lookup is set by the lane alone, whatever the values
@@ -560,21 +565,21 @@ __global__ __launch_bounds__(FUSED_NT, WIDE ? (OVR ? 2 : 1) : ((OVR || CB == 8) 
     // ---- this lane's (group, gene) result from the group's integer statistics ----
     auto emit = [&](int g, long long n_tgt, u64 S2, u64 TT, u32 vsum) {
         if (!act) return;
-        double pv, Ustat, fc;
+        double pv, Ustat, fc, tie;
         const GroupConst gc = P.gconst[g]; // (uniform address: one scalar load per group)
         if (OVR) { // dense_ovr.py:57-75: the "reference" of group g is every other cell
             const long long n_rest = P.n_cells - n_tgt;
             // 2*ranksum = S2 + n_tgt (2 rank = 2 #less + #equal + 1);  U = n_rest n_tgt + n_tgt(n_tgt+1)/2 - ranksum
             const long long two_u = 2ll * n_rest * n_tgt + n_tgt * (n_tgt + 1) - ((long long)S2 + n_tgt);
             Ustat = 0.5 * (double)two_u;
-            const double tie = !P.tie_correct ? 0.0 : (P.tie_mode ? __longlong_as_double((long long)T_A) : (double)T_A);
+            tie = !P.tie_correct ? 0.0 : (P.tie_mode ? __longlong_as_double((long long)T_A) : (double)T_A);
             pv = pval_device_pre(gc.nnn, gc.var0, gc.n12, tie, Ustat, gc.mu, cc, P.alternative);
             fc = fold_change_device((double)vsum, ref_sum - (double)vsum, gc); // math.py:185-188
         } else {
             const u64 tie_i = T_A + 3ull * TT;
             const long long two_u = 2ll * n_ref * n_tgt - (long long)S2;
             Ustat = 0.5 * (double)two_u;
-            const double tie = P.tie_correct ? (double)tie_i : 0.0;
+            tie = P.tie_correct ? (double)tie_i : 0.0;
             pv = pval_device_pre(gc.nnn, gc.var0, gc.n12, tie, Ustat, gc.mu, cc, P.alternative);
             fc = (mu_ref_ovo == 0.0) ? __longlong_as_double(0x7FF0000000000000ll) : ((double)vsum / gc.d_tgt) / mu_ref_ovo;
         }
@@ -582,6 +587,7 @@ __global__ __launch_bounds__(FUSED_NT, WIDE ? (OVR ? 2 : 1) : ((OVR || CB == 8) 
         P.out_p[o] = pv;
         P.out_u[o] = Ustat;
         P.out_fc[o] = fc;
+        if constexpr (Z) P.out_z[o] = zscore_device_pre(gc.nnn, gc.var0, tie, Ustat, gc.mu);
     };
 
     // Scalar row addressing and read/write counters (gather_rows / consume_rmw).  The p-values are evaluated here:
@@ -754,7 +760,7 @@ __global__ __launch_bounds__(FUSED_NT, 4) void k_ovr_group_hists(FusedParams P) 
 // 16 histogram words are requested BEFORE this group's p-value is evaluated (~900 instructions with nothing in flight otherwise).
 // CB == 0: histogram width per group; a group of more than 255 cells (16-bit cells, 32 words) is the rare case and reads s[c] back
 // from the cumulative table in global memory instead of keeping a second register copy.
-template <int RT, int CB, int NPL = 4>
+template <int RT, int CB, int NPL = 4, bool Z = false> // (Z: as k_ovo_fused)
 __global__ __launch_bounds__(FUSED_NT, NPL == 3 ? 3 : 2) void k_ovr_from_hists(FusedParams P) {
     static_assert(CB == 8 || CB == 0, "8-bit cells throughout, or the width per group");
     constexpr int NW = FUSED_NT / 64, CSTR = RT + 1, BW8 = RT / 4;
@@ -867,5 +873,6 @@ __global__ __launch_bounds__(FUSED_NT, NPL == 3 ? 3 : 2) void k_ovr_from_hists(F
         P.out_p[o] = pv;
         P.out_u[o] = Ustat;
         P.out_fc[o] = fc;
+        if constexpr (Z) P.out_z[o] = zscore_device_pre(gc.nnn, gc.var0, tie, Ustat, gc.mu);
     }
 }

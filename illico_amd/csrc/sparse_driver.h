@@ -207,8 +207,8 @@ static int run_csc_counts_route(illico_ctx *c, const InT *d_data, const IdxT *d_
                 if (mixed) { if ((rc = launch_csc_counts<InT, IdxT, true>(c, P, rt, n_big > 0, ovr, lds))) return rc; }
                 else if ((rc = launch_csc_counts<InT, IdxT, false>(c, P, rt, n_big > 0, ovr, lds, w16))) return rc;
             }
-            if (d_cols) { if ((rc = launch_finalize(c, s2u, stie, ssum, ovr ? gtot : nullptr, nb, flags, alternative, o.p, o.u, o.fc, o.ld, -col_lb, d_cols + b0, pack16, ovr))) return rc; }
-            else if ((rc = launch_finalize(c, s2u, stie, ssum, ovr ? gtot : nullptr, nb, flags, alternative, o.p, o.u, o.fc, o.ld, cols[b0] - col_lb, nullptr, pack16, ovr))) return rc;
+            if (d_cols) { if ((rc = launch_finalize(c, s2u, stie, ssum, ovr ? gtot : nullptr, nb, flags, alternative, o, -col_lb, d_cols + b0, pack16, ovr))) return rc; }
+            else if ((rc = launch_finalize(c, s2u, stie, ssum, ovr ? gtot : nullptr, nb, flags, alternative, o, cols[b0] - col_lb, nullptr, pack16, ovr))) return rc;
             if (c->pinned_bytes < (size_t)nb * 4) {
                 if (c->pinned) hipHostFree(c->pinned);
                 c->pinned = nullptr; c->pinned_bytes = 0;
@@ -292,7 +292,7 @@ static int run_csc_counts_deferred(illico_ctx *c, const void *data, const void *
             if (mixed) { if ((rc = launch_csc_counts<InT, IdxT, true>(c, P, rt, n_big > 0, ovr, lds))) return rc; }
             else if ((rc = launch_csc_counts<InT, IdxT, false>(c, P, rt, n_big > 0, ovr, lds, w16))) return rc;
         }
-        if ((rc = launch_finalize(c, s2u, stie, ssum, ovr ? gtot : nullptr, nb, flags, alternative, o.p, o.u, o.fc, o.ld, b0, nullptr, pack16, ovr))) return rc;
+        if ((rc = launch_finalize(c, s2u, stie, ssum, ovr ? gtot : nullptr, nb, flags, alternative, o, b0, nullptr, pack16, ovr))) return rc;
     }
     const int slot = c->pend_next;
     void *&pin = c->pend_pinned[slot];
@@ -311,7 +311,7 @@ static int run_csc_counts_deferred(illico_ctx *c, const void *data, const void *
     q = PendingDense();
     q.on = true; q.kind = 1; q.sp_data = data; q.sp_indices = indices; q.sp_indptr = indptr; q.idx_dtype = idx_dtype; q.n_cols = n_cols;
     q.dtype = dtype; q.flags = flags & ~ILLICO_FLAG_DEFER; q.alternative = alternative; q.slot = slot; q.N = n_rows;
-    q.col_lb = col_lb; q.col_ub = col_ub; q.out_ld = o.ld; q.p = o.p; q.u = o.u; q.fc = o.fc;
+    q.col_lb = col_lb; q.col_ub = col_ub; q.out_ld = o.ld; q.p = o.p; q.u = o.u; q.fc = o.fc; q.z = o.z;
     return ILLICO_OK;
 }
 
@@ -374,8 +374,8 @@ static int run_csc_gene_route(illico_ctx *c, const InT *d_data, const IdxT *d_in
         // the kernel adds a group's values in the order its LDS regroup happened to leave them: replace its sums by the
         // order-independent ones
         if ((rc = launch_csc_value_sums<InT, IdxT>(c, d_data, d_indices, d_indptr, kshift, cols[b0], d_cols ? d_cols + b0 : nullptr, d_codes, nb, dtype, flags, ssum))) return rc;
-        if (d_cols) { if ((rc = launch_finalize(c, s2u, stie, ssum, nullptr, nb, flags, alternative, o.p, o.u, o.fc, o.ld, -col_lb, d_cols + b0))) return rc; }
-        else if ((rc = launch_finalize(c, s2u, stie, ssum, nullptr, nb, flags, alternative, o.p, o.u, o.fc, o.ld, cols[b0] - col_lb))) return rc;
+        if (d_cols) { if ((rc = launch_finalize(c, s2u, stie, ssum, nullptr, nb, flags, alternative, o, -col_lb, d_cols + b0))) return rc; }
+        else if ((rc = launch_finalize(c, s2u, stie, ssum, nullptr, nb, flags, alternative, o, cols[b0] - col_lb))) return rc;
         h_fb.resize(nb);
         HIPCHK(c, hipMemcpyAsync(h_fb.data(), fb, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -465,8 +465,8 @@ static int run_csc_ovr_route(illico_ctx *c, const InT *d_data, const IdxT *d_ind
         }
         if ((rc = launch_csc_value_sums<InT, IdxT>(c, d_data, d_indices, d_indptr, kshift, cols[b0], d_cols ? d_cols + b0 : nullptr, d_codes, nb, dtype, flags, ssum))) return rc;
         if ((rc = launch_gene_totals(c, ssum, G, nb, gtot))) return rc;
-        if (d_cols) { if ((rc = launch_finalize(c, s2u, stie, ssum, gtot, nb, flags, alternative, o.p, o.u, o.fc, o.ld, -col_lb, d_cols + b0, false, true))) return rc; }
-        else if ((rc = launch_finalize(c, s2u, stie, ssum, gtot, nb, flags, alternative, o.p, o.u, o.fc, o.ld, cols[b0] - col_lb, nullptr, false, true))) return rc;
+        if (d_cols) { if ((rc = launch_finalize(c, s2u, stie, ssum, gtot, nb, flags, alternative, o, -col_lb, d_cols + b0, false, true))) return rc; }
+        else if ((rc = launch_finalize(c, s2u, stie, ssum, gtot, nb, flags, alternative, o, cols[b0] - col_lb, nullptr, false, true))) return rc;
         if (c->pinned_bytes < (size_t)nb * 4) {
             if (c->pinned) hipHostFree(c->pinned);
             c->pinned = nullptr; c->pinned_bytes = 0;
@@ -528,7 +528,7 @@ static int launch_csr_counts_route(illico_ctx *c, const InT *d_data, const IdxT 
     P.G = G; P.ref = (int)c->ref; P.n_cells = n_rows; P.col_lb = col_lb; P.W = (int)W; P.Wg = Wg; P.bounds = bounds; P.bstep = 1; P.n_bnd = n_bnd;
     P.tab = tab; P.ginfo = ginfo; P.gene_total = gtot; P.Wpad = Wpad; P.gene_flags = d_flags; P.verdict = d_verdict; P.unsorted = d_verdict + 3;
     P.use_continuity = (flags & ILLICO_FLAG_CONTINUITY) ? 1 : 0; P.tie_correct = (flags & ILLICO_FLAG_TIE_CORRECT) ? 1 : 0; P.alternative = alternative;
-    P.out_p = o.p; P.out_u = o.u; P.out_fc = o.fc; P.out_ld = o.ld; P.hist = hist;
+    P.out_p = o.p; P.out_u = o.u; P.out_fc = o.fc; P.out_z = o.z; P.out_ld = o.ld; P.hist = hist;
     P.chunk_p0 = c->d_csr_chunks; P.chunk_n = c->d_csr_chunks + n_chunks; P.chunk_slab = c->d_csr_chunks + 2 * n_chunks;
     P.big_groups = c->d_csr_chunks + 3 * n_chunks; P.n_big = n_big; P.abl = c->csr_counts_abl;
     {
@@ -567,15 +567,15 @@ static int launch_csr_counts_route(illico_ctx *c, const InT *d_data, const IdxT 
             HIPCHK(c, hipGetLastError());
         }
         ProfScope ps(c, KID_OVR_SCAN);
-        hipLaunchKernelGGL(k_csr_ovr_sweep, dim3(n_win, G), dim3(CSRC_NT), 0, c->stream, P);
-        if (n_big > 0) hipLaunchKernelGGL((k_csr_big_sweep<true>), dim3((unsigned)((W + 255) / 256), n_big), dim3(256), 0, c->stream, P);
+        hipLaunchKernelGGL((o.z ? k_csr_ovr_sweep<true> : k_csr_ovr_sweep<false>), dim3(n_win, G), dim3(CSRC_NT), 0, c->stream, P);
+        if (n_big > 0) hipLaunchKernelGGL((o.z ? k_csr_big_sweep<true, true> : k_csr_big_sweep<true>), dim3((unsigned)((W + 255) / 256), n_big), dim3(256), 0, c->stream, P);
         HIPCHK(c, hipGetLastError());
     } else {
         ProfScope ps(c, KID_CSR_COUNTS);
         auto kern = k_csr_counts<InT, IdxT, false>;
         HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(n_win, G), dim3(CSRC_NT), lds, c->stream, P);
-        if (n_big > 0) hipLaunchKernelGGL((k_csr_big_sweep<false>), dim3((unsigned)((W + 255) / 256), n_big), dim3(256), 0, c->stream, P);
+        if (n_big > 0) hipLaunchKernelGGL((o.z ? k_csr_big_sweep<false, true> : k_csr_big_sweep<false>), dim3((unsigned)((W + 255) / 256), n_big), dim3(256), 0, c->stream, P);
         HIPCHK(c, hipGetLastError());
     }
     return ILLICO_OK;
@@ -757,7 +757,7 @@ int run_sparse_t(illico_ctx *c, bool is_csr, const void *data, const void *indic
         q.sorted_known = c->cur_sorted_known;
         q.idx_dtype = (int)(sizeof(IdxT) == 4 ? ILLICO_IDX_I32 : ILLICO_IDX_I64); q.n_cols = n_cols;
         q.dtype = dtype; q.flags = flags & ~ILLICO_FLAG_DEFER; q.alternative = alternative; q.slot = slot; q.N = n_rows;
-        q.col_lb = col_lb; q.col_ub = col_ub; q.out_ld = o.ld; q.p = o.p; q.u = o.u; q.fc = o.fc;
+        q.col_lb = col_lb; q.col_ub = col_ub; q.out_ld = o.ld; q.p = o.p; q.u = o.u; q.fc = o.fc; q.z = o.z;
         return ILLICO_OK;
     }
 
@@ -868,8 +868,7 @@ int run_sparse_t(illico_ctx *c, bool is_csr, const void *data, const void *indic
                 if (!hf[j]) { ++j; continue; }
                 int64_t last = j;
                 for (int64_t e = j + 1; e < W && e - last <= 32; ++e) if (hf[e]) last = e;
-                OutPlanes o2 = o;
-                o2.p += j; o2.u += j; o2.fc += j;
+                const OutPlanes o2 = o.shifted(j);
                 if ((rc = run_sparse_t<InT, IdxT, KeyT>(c, is_csr, data, indices, indptr, dtype, n_rows, n_cols, col_lb + j, col_lb + last + 1, flags,
                                                         alternative, o2, false, true, false, false))) return rc;
                 j = last + 1;
@@ -927,8 +926,7 @@ int run_sparse_t(illico_ctx *c, bool is_csr, const void *data, const void *indic
         if (bad_lo < 0) return ILLICO_OK;
         // genes the fused kernels could not take (values outside the small-integer table): the exact sparse route
         // over the column window that covers them (it recomputes, identically, the good genes in between)
-        OutPlanes o2 = o;
-        o2.p += bad_lo - col_lb; o2.u += bad_lo - col_lb; o2.fc += bad_lo - col_lb;
+        const OutPlanes o2 = o.shifted(bad_lo - col_lb);
         return run_sparse_t<InT, IdxT, KeyT>(c, is_csr, data, indices, indptr, dtype, n_rows, n_cols, bad_lo, bad_hi + 1, flags,
                                              alternative, o2, false, true, false, false);
     }
@@ -981,8 +979,7 @@ int run_sparse_t(illico_ctx *c, bool is_csr, const void *data, const void *indic
                                    (int)n_rows, (long long)w0, (int)wn, (InT *)v, (long long)ldD);
                 HIPCHK(c, hipGetLastError());
             }
-            OutPlanes o2 = o;
-            o2.p += w0 - col_lb; o2.u += w0 - col_lb; o2.fc += w0 - col_lb;
+            const OutPlanes o2 = o.shifted(w0 - col_lb);
             if ((rc = run_dense_t<InT, KeyT>(c, v, dtype, n_rows, ldD, 0, wn, (flags | ILLICO_FLAG_INPUT_DEVICE) & ~ILLICO_FLAG_DEFER, alternative, o2))) return rc;
         }
         return ILLICO_OK;
@@ -1075,8 +1072,7 @@ int run_sparse_t(illico_ctx *c, bool is_csr, const void *data, const void *indic
                                    d_indptr, (int)n_rows, RB, (long long)w0, (int)wn, (const u32 *)counts, (const u32 *)col_ptr, (const int *)c->d_codes, t_data, t_rows);
                 HIPCHK(c, hipGetLastError());
             }
-            OutPlanes o2 = o;
-            o2.p += w0 - col_lb; o2.u += w0 - col_lb; o2.fc += w0 - col_lb;
+            const OutPlanes o2 = o.shifted(w0 - col_lb);
             if ((rc = run_sparse_t<InT, int32_t, KeyT>(c, false, t_data, t_rows, col_ptr, dtype, n_rows, wn, 0, wn,
                                                        flags | ILLICO_FLAG_INPUT_DEVICE, alternative, o2, false, false, true, false)))
                 return rc;
@@ -1186,8 +1182,7 @@ int run_sparse_t(illico_ctx *c, bool is_csr, const void *data, const void *indic
                                        (long long)w0, (int)wn, (int)n_rows, (InT *)v, (long long)ldD);
                     HIPCHK(c, hipGetLastError());
                 }
-                OutPlanes o2 = o;
-                o2.p += w0 - col_lb; o2.u += w0 - col_lb; o2.fc += w0 - col_lb;
+                const OutPlanes o2 = o.shifted(w0 - col_lb);
                 if ((rc = run_dense_t<InT, KeyT>(c, v, dtype, n_rows, ldD, 0, wn, (flags | ILLICO_FLAG_INPUT_DEVICE) & ~ILLICO_FLAG_DEFER, alternative, o2))) return rc;
             }
             return ILLICO_OK;
@@ -1398,7 +1393,7 @@ int run_sparse_t(illico_ctx *c, bool is_csr, const void *data, const void *indic
                 if ((rc = launch_ovo<KeyT>(c, P, ref_cap_b, grp_cap_b, route_flags, &gb, true, route))) return rc;
             } else
             if ((rc = launch_ovo<KeyT>(c, P, ref_cap_b, grp_cap_b, route_flags, &gb, true))) return rc;
-            if ((rc = launch_finalize(c, s2u, stie, ssum, nullptr, nb, flags, alternative, o.p, o.u, o.fc, o.ld, fin_off, d_cols))) return rc;
+            if ((rc = launch_finalize(c, s2u, stie, ssum, nullptr, nb, flags, alternative, o, fin_off, d_cols))) return rc;
         } else {
             OvrParams P;
             P.keys_a = Xs; P.keys_b = kb; P.vals_a = va; P.vals_b = vb; P.code_by_pos = nullptr; P.seg_ptr = seg;
@@ -1409,7 +1404,7 @@ int run_sparse_t(illico_ctx *c, bool is_csr, const void *data, const void *indic
             else if ((rc = launch_seg_value_sums<KeyT>(c, Xs, seg, nb, dtype, flags, ssum))) return rc;
             if ((rc = launch_ovr_gene<KeyT, true>(c, P))) return rc;
             if ((rc = launch_gene_totals(c, ssum, G, nb, gtot))) return rc;
-            if ((rc = launch_finalize(c, s2u, stie, ssum, gtot, nb, flags, alternative, o.p, o.u, o.fc, o.ld, fin_off, d_cols, false, true))) return rc;
+            if ((rc = launch_finalize(c, s2u, stie, ssum, gtot, nb, flags, alternative, o, fin_off, d_cols, false, true))) return rc;
         }
     }
     }

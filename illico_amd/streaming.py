@@ -51,7 +51,8 @@ class _Slot:
 
 
 def run_streaming(data_handler, iterator, group_container, is_log1p, use_continuity, alternative, tie_correct, planes):
-    """Stream the gene chunks ``iterator`` of a backed container through the engine; ``planes`` is the [3, G, n_genes] result."""
+    """Stream the gene chunks ``iterator`` of a backed container through the engine; ``planes`` is the [3, G, n_genes] result (or
+    [4, G, n_genes]: the fourth plane receives the z-scores)."""
     import torch
 
     from illico_amd._lib import get_engine, normalize_values
@@ -93,6 +94,6 @@ def run_streaming(data_handler, iterator, group_container, is_log1p, use_continu
             if k + 1 < len(iterator):
                 nxt = pool.submit(prefetch, k + 1)
             torch.cuda.current_stream(device).wait_event(ev)
-            out = tuple(planes[j][:, lb:ub] for j in range(3))
+            out = tuple(planes[j][:, lb:ub] for j in range(len(planes)))
             dispatcher(staged, *local, group_container, is_log1p, use_continuity, tie_correct, alternative, out=out, engine=eng)
             del staged

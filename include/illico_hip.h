@@ -149,6 +149,20 @@ int illico_run_csc(illico_ctx *ctx, const void *data, int dtype, const void *ind
 int illico_run_csr(illico_ctx *ctx, const void *data, int dtype, const void *indices, const void *indptr,
                    int idx_dtype, int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags,
                    int alternative, double *out_p, double *out_u, double *out_fc, int64_t out_ld);
+/* The same three with a fourth plane: out_z receives the z-score of every test, (mu - U) / sigma with mu = n_ref n_tgt / 2 and sigma
+ * formed exactly as the p-value forms it (tie-corrected under ILLICO_FLAG_TIE_CORRECT, never continuity-corrected, whatever the
+ * alternative): positive when the group ranks above its reference -- scanpy's "scores".  0.0 on a constant column (where p is 1 through
+ * the tie correction) and on the reference group's row of an OVO call.  out_z may be null (the calls above are these with null); it
+ * shares out_ld and the residency flags with the other planes, and the p, U and fold-change planes are the same bytes either way. */
+int illico_run_dense_ex(illico_ctx *ctx, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld,
+                        int64_t col_lb, int64_t col_ub, int flags, int alternative, double *out_p, double *out_u,
+                        double *out_fc, double *out_z, int64_t out_ld);
+int illico_run_csc_ex(illico_ctx *ctx, const void *data, int dtype, const void *indices, const void *indptr,
+                      int idx_dtype, int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags,
+                      int alternative, double *out_p, double *out_u, double *out_fc, double *out_z, int64_t out_ld);
+int illico_run_csr_ex(illico_ctx *ctx, const void *data, int dtype, const void *indices, const void *indptr,
+                      int idx_dtype, int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags,
+                      int alternative, double *out_p, double *out_u, double *out_fc, double *out_z, int64_t out_ld);
 /* ---- a sparse matrix bound once, computed chunk by chunk -------------------------------------
  * The reference's driver calls a dispatcher once per gene chunk with the SAME matrix (illico/asymptotic_wilcoxon.py:236-241:
  * 32 calls at 8000 genes and batch_size 256); CSR rows span every gene, so illico_run_csr on HOST arrays has to move the whole
@@ -165,6 +179,10 @@ int illico_csc_bind(illico_ctx *ctx, const void *data, int dtype, const void *in
                     int64_t n_rows, int64_t n_cols, int flags, illico_matrix **out_matrix);
 int illico_run_bound(illico_ctx *ctx, const illico_matrix *matrix, int64_t col_lb, int64_t col_ub, int flags, int alternative,
                      double *out_p, double *out_u, double *out_fc, int64_t out_ld);
+/* with the z-score plane (see the _ex calls above).  A call with out_z != null computes its chunk directly, whatever
+ * "bound_ahead_genes" says: the windows computed ahead hold three planes; they are neither used nor replaced by it. */
+int illico_run_bound_ex(illico_ctx *ctx, const illico_matrix *matrix, int64_t col_lb, int64_t col_ub, int flags, int alternative,
+                        double *out_p, double *out_u, double *out_fc, double *out_z, int64_t out_ld);
 int illico_matrix_release(illico_ctx *ctx, illico_matrix *matrix);
 /* Adopted device arrays (ILLICO_FLAG_INPUT_DEVICE) stay the caller's: they must not change while a call on them is in flight, and what
  * the context remembers about a bound matrix -- whether its CSR rows are in order (looked at once, at bind time) and, with the option
@@ -229,6 +247,13 @@ enum { ILLICO_ADJ_LDS_COLS = 8192 };
 int illico_adjust_pvalues(illico_ctx *ctx, const double *p, int64_t n_rows, int64_t n_cols, int64_t in_ld,
                           int method, int flags, double *out_adj, int64_t out_ld,
                           int64_t n_top, int64_t *out_top, int64_t top_ld);
+/* Top columns by score: for each row of x (float64 [n_rows][in_ld >= n_cols], a z-score plane), out_top int64 [n_rows][top_ld >= n_top]
+ * receives the first n_top columns sorted DESCENDING by x, ties by ascending column -- numpy's
+ * argsort(-(x + 0.0), kind="stable")[:, :n_top] (-0.0 and +0.0 tie; +inf first, -inf last).  1 <= n_top <= n_cols.  The sort and merge
+ * kernels of the adjustment above, on the order-preserving key of -x + 0.0.  ILLICO_ERR_ARG for a NaN, naming the first (row, column),
+ * before anything is written.  flags, residency, batches and a deferred call: as for the adjustment. */
+int illico_top_by_score(illico_ctx *ctx, const double *x, int64_t n_rows, int64_t n_cols, int64_t in_ld, int flags,
+                        int64_t n_top, int64_t *out_top, int64_t top_ld);
 
 /* ---- per-group expression statistics --------------------------------------------------------
  * For each group g of illico_set_groups and each column j of [col_lb, col_ub) (plane column j - col_lb):
