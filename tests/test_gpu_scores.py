@@ -1,6 +1,4 @@
 """The z-score plane of the Wilcoxon routes (illico_run_*_ex) and top_by_score, against a float64 numpy restatement on the host."""
-import math
-
 import numpy as np
 import pandas as pd
 import pytest
@@ -10,6 +8,7 @@ from scipy.special import erfc
 import oracle
 from conftest import make_counts, make_labels
 from illico_amd import AnnDataLite, asymptotic_wilcoxon, differential_expression, top_by_score
+from threshold_cases import z_want
 
 pytestmark = pytest.mark.gpu
 
@@ -24,40 +23,6 @@ def engine():
 
 def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def z_want(X, g, U, tie_correct=True):
-    """(mu - U) / sqrt(var0 * tie_corr) as pval_device_pre forms sigma (kernels_finalize.h), one IEEE operation at a time."""
-    X = np.asarray(X, dtype=np.float64)
-    N, M = X.shape
-    codes, counts, ref = g.encoded_groups, g.counts, g.encoded_ref_group
-    Z = np.zeros((counts.size, M))
-    col_tie = None
-    if ref < 0:
-        col_tie = [sum(int(t) ** 3 - int(t) for t in np.unique(X[:, j], return_counts=True)[1]) for j in range(M)]
-    for gi in range(counts.size):
-        if gi == ref:
-            continue
-        n_tgt = int(counts[gi])
-        if ref >= 0:
-            n_ref = int(counts[ref])
-            n = n_ref + n_tgt
-            cells = (codes == ref) | (codes == gi)
-        else:
-            n_ref, n, cells = N - n_tgt, N, None
-        nnn = float(n * (n - 1) * (n + 1))
-        var0 = float(n_ref * n_tgt * (n_ref + n_tgt + 1)) / 12.0
-        mu = float(n_ref * n_tgt) / 2.0
-        for j in range(M):
-            if not tie_correct:
-                tie = 0.0
-            elif cells is None:
-                tie = float(col_tie[j])
-            else:
-                tie = float(sum(int(t) ** 3 - int(t) for t in np.unique(X[cells, j], return_counts=True)[1]))
-            tc = 1.0 - tie / nnn
-            Z[gi, j] = (mu - float(U[gi, j])) / math.sqrt(var0 * tc) if tc > 1.0e-9 else 0.0
-    return Z
 
 
 def _data(seed=5, n=700, m=70, G=6, n_ref=150):
