@@ -28,6 +28,11 @@ ADJUST_METHODS = {"bh": ADJ_BH, "by": ADJ_BY, "bonferroni": ADJ_BONFERRONI}
 #: longest row of p-values one workgroup sorts in LDS (ILLICO_ADJ_LDS_COLS); longer rows take the route through device scratch
 ADJUST_LDS_COLS = 8192
 
+TT_WELCH, TT_OVERESTIM_VAR = 0, 1
+TT_VARIANTS = {"welch": TT_WELCH, "overestim_var": TT_OVERESTIM_VAR}
+#: the planes illico_ttest_from_moments can write, in the order of its output arguments
+TT_OUTPUTS = ("p", "t", "df", "mean", "var", "mean_ref", "var_ref")
+
 _DTYPES = {np.dtype(np.float32): F32, np.dtype(np.float64): F64, np.dtype(np.int32): I32, np.dtype(np.int64): I64}
 
 # every symbol include/illico_hip.h declares
@@ -39,6 +44,8 @@ SYMBOLS = [
     "illico_matrix_release", "illico_matrix_touch", "illico_profile_input_bytes", "illico_planes_to_host",
     "illico_adjust_pvalues", "illico_group_stats_dense", "illico_group_stats_csc", "illico_group_stats_csr", "illico_group_stats_bound",
     "illico_run_dense_ex", "illico_run_csc_ex", "illico_run_csr_ex", "illico_run_bound_ex", "illico_top_by_score",
+    "illico_group_moments_dense", "illico_group_moments_csc", "illico_group_moments_csr", "illico_group_moments_bound",
+    "illico_ttest_from_moments", "illico_student_t_pvalues",
 ]
 
 _lib = None
@@ -93,6 +100,12 @@ def load() -> ctypes.CDLL:
             f.argtypes = [vp, vp, ci, vp, vp, ci, i64, i64, i64, i64, ci, ci, vp, vp, vp, vp, i64]
         lib.illico_run_bound_ex.argtypes = [vp, vp, i64, i64, ci, ci, vp, vp, vp, vp, i64]
         lib.illico_top_by_score.argtypes = [vp, vp, i64, i64, i64, ci, i64, vp, i64]
+        lib.illico_group_moments_dense.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, vp, vp, vp, vp, i64]
+        for f in (lib.illico_group_moments_csc, lib.illico_group_moments_csr):
+            f.argtypes = [vp, vp, ci, vp, vp, ci, i64, i64, i64, i64, ci, vp, vp, vp, vp, i64]
+        lib.illico_group_moments_bound.argtypes = [vp, vp, i64, i64, ci, vp, vp, vp, vp, i64]
+        lib.illico_ttest_from_moments.argtypes = [vp, vp, vp, vp, vp, i64, i64, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, i64]
+        lib.illico_student_t_pvalues.argtypes = [vp, vp, vp, i64, ci, ci, vp]
         for name in SYMBOLS:  # fail at load time, not at first use, if the library and the header have drifted
             getattr(lib, name)
         _lib = lib
@@ -473,11 +486,12 @@ class Engine:
         return top
 
     # ---- per-group expression statistics (include/illico_hip.h: illico_group_stats_*) ----
-    def _gs_outputs(self, out, G, W, rest, want_device):
+    def _gs_outputs(self, out, G, W, rest, want_device, kinds=(np.int64, np.float64, np.int64, np.float64),
+                    names="(nnz, sum) or 4 (nnz, sum, nnz_rest, sum_rest)"):
         """(planes, pointers, output flag, row pitch) of the statistics planes: ``out`` None (allocate nnz int64 / sum float64 [G, W],
         plus their rest planes with ``rest``) or a tuple of 2 or 4 planes in that order (nnz, sum[, nnz_rest, sum_rest]), each a
-        host ndarray or a CUDA tensor of the right dtype with unit column stride, or None (not computed)."""
-        kinds = (np.int64, np.float64, np.int64, np.float64)
+        host ndarray or a CUDA tensor of the right dtype with unit column stride, or None (not computed).  ``kinds`` / ``names``: the
+        four planes' dtypes and what the error message calls them (the moment planes are four float64 ones)."""
         if out is None:
             n = 4 if rest else 2
             if want_device:
@@ -489,7 +503,7 @@ class Engine:
         else:
             planes = tuple(out)
             if len(planes) not in (2, 4):
-                raise ValueError("out must hold 2 planes (nnz, sum) or 4 (nnz, sum, nnz_rest, sum_rest)")
+                raise ValueError(f"out must hold 2 planes {names}")
         if all(p is None for p in planes):
             raise ValueError("at least one output plane is needed")
         ptrs, side, ld = [], None, None
@@ -583,6 +597,164 @@ class Engine:
                        n_rows, n_cols, col_lb, col_ub, flags, *ptrs, out_ld))
         return planes
 
+    # ---- per-group moments and Welch's t-test (include/illico_hip.h: illico_group_moments_*, illico_ttest_from_moments) ----
+    _GM_KINDS = (np.float64, np.float64, np.float64, np.float64)
+    _GM_NAMES = "(sum, sumsq) or 4 (sum, sumsq, sum_rest, sumsq_rest)"
+
+    def group_moments(self, X, col_lb, col_ub, *, rest=False, out=None):
+        """Per-group exact sums of the values and of their squares over the dense columns [col_lb, col_ub) (illico_group_moments_dense).
+
+        ``X``: a row-major numpy array or a CUDA tensor.  Returns ``(sum, sumsq)`` -- float64 ``[G, W]`` -- or, with ``rest=True``,
+        ``(sum, sumsq, sum_rest, sumsq_rest)``, living where ``X`` lives unless ``out`` (2 or 4 planes in that order, each a host
+        ndarray, a CUDA tensor or None) says otherwise.  The values are taken as given: there is no ``is_log1p``."""
+        if _is_torch_tensor(X):
+            if X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1):
+                raise ValueError("X must be row-major 2-D")
+            ptr, on_dev, keep = X.data_ptr(), X.is_cuda, X
+            n_rows, n_cols = int(X.shape[0]), int(X.shape[1])
+            ld = int(X.stride(0)) if n_rows > 1 else n_cols
+            dt = dtype_code(str(X.dtype).replace("torch.", ""))
+        else:
+            X = normalize_values(np.asarray(X))
+            if X.ndim != 2:
+                raise ValueError(f"X must be 2-D, got {X.ndim} dimensions")
+            if (X.shape[1] > 1 and X.strides[1] != X.itemsize) or X.strides[0] % X.itemsize or X.strides[0] < 0:
+                X = np.ascontiguousarray(X)
+            ptr, on_dev, keep = X.ctypes.data, False, X
+            n_rows, n_cols = X.shape
+            ld = X.strides[0] // X.itemsize if n_rows > 1 else n_cols
+            dt = dtype_code(X.dtype)
+        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
+            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        G, W = self.n_groups, col_ub - col_lb
+        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, on_dev, self._GM_KINDS, self._GM_NAMES)
+        if W == 0:
+            return planes
+        flags = (FLAG_INPUT_DEVICE if on_dev else 0) | oflag
+        self._bind_torch_stream(keep, *[p for p in planes if p is not None])
+        self._check(self.lib.illico_group_moments_dense(self.h, ptr, dt, n_rows, n_cols, max(ld, n_cols), col_lb, col_ub, flags, *ptrs, out_ld))
+        del keep
+        return planes
+
+    def group_moments_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, *, rest=False, out=None):
+        """``group_moments`` of a CSC (``fmt="csc"``) or CSR (``"csr"``) matrix given as its three arrays (numpy or CUDA tensors);
+        CSR rows need not be sorted.  Duplicate entries count as separate values."""
+        if fmt not in ("csc", "csr"):
+            raise ValueError(f"fmt must be 'csc' or 'csr', got {fmt!r}")
+        n_rows, n_cols = int(shape[0]), int(shape[1])
+        if _is_torch_tensor(data):
+            d, i, p = _Buf(data), _Buf(indices), _Buf(indptr)
+        else:
+            d = _Buf(normalize_values(np.asarray(data)))
+            idt = np.int32 if (np.asarray(indices).dtype == np.int32 and np.asarray(indptr).dtype == np.int32) else np.int64
+            i, p = _Buf(indices, idt), _Buf(indptr, idt)
+        if i.np_dtype != p.np_dtype or i.np_dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+            raise KeyError(f"Support for index dtypes {i.np_dtype}/{p.np_dtype} is not implemented.")
+        if not (d.on_device == i.on_device == p.on_device):
+            raise ValueError("data, indices and indptr must live on the same side (host or device)")
+        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
+            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        G, W = self.n_groups, col_ub - col_lb
+        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, d.on_device, self._GM_KINDS, self._GM_NAMES)
+        if W == 0:
+            return planes
+        flags = (FLAG_INPUT_DEVICE if d.on_device else 0) | oflag
+        fn = self.lib.illico_group_moments_csc if fmt == "csc" else self.lib.illico_group_moments_csr
+        self._bind_torch_stream(d.keep, i.keep, p.keep, *[q for q in planes if q is not None])
+        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, IDX_I32 if i.np_dtype == np.int32 else IDX_I64,
+                       n_rows, n_cols, col_lb, col_ub, flags, *ptrs, out_ld))
+        return planes
+
+    def ttest_from_moments(self, sum, sumsq, sum_rest=None, sumsq_rest=None, *, variant="welch", alternative="two-sided",
+                           want=("p", "t"), out=None):
+        """Welch's t-test of every (group, gene) from moment planes (illico_ttest_from_moments), for the engine's current groups.
+
+        ``sum`` / ``sumsq`` (and, one-versus-rest, ``sum_rest`` / ``sumsq_rest``): float64 ``[G, M]`` numpy arrays or CUDA tensors with
+        unit column stride and one row stride, all on one side.  ``variant``: ``"welch"`` or ``"overestim_var"``.  ``want``: which of
+        ``TT_OUTPUTS`` (``"p"``, ``"t"``, ``"df"``, ``"mean"``, ``"var"``, ``"mean_ref"``, ``"var_ref"``) to compute.  Returns a tuple of
+        float64 ``[G, M]`` planes in the order of ``want``, living where the inputs live; ``out``: a tuple of as many planes to write."""
+        try:
+            var = TT_VARIANTS[variant]
+        except (KeyError, TypeError):
+            raise ValueError(f"Unknown t-test variant {variant!r}: one of {sorted(TT_VARIANTS)}") from None
+        alt = self._alt(alternative)
+        want = tuple(want)
+        if not want or any(w not in TT_OUTPUTS for w in want) or len(set(want)) != len(want):
+            raise ValueError(f"want must name distinct planes of {TT_OUTPUTS}, got {want!r}")
+        ins, lds, G, M, on_dev = [], set(), None, None, None
+        for name, x in (("sum", sum), ("sumsq", sumsq), ("sum_rest", sum_rest), ("sumsq_rest", sumsq_rest)):
+            if x is None:
+                if name in ("sum", "sumsq"):
+                    raise ValueError(f"{name} is required")
+                ins.append(None)
+                continue
+            x, g, m, l, dev = _adjust_plane(x, name, copy_ok=True)
+            if G is None:
+                G, M, on_dev = g, m, dev
+            elif (g, m, dev) != (G, M, on_dev):
+                raise ValueError("the moment planes must share one shape and live on the same side (host or device)")
+            lds.add(l)
+            ins.append(x)
+        if len(lds) > 1:
+            if on_dev:
+                raise ValueError("device moment planes must share one row stride")
+            ins, lds = [None if q is None else np.ascontiguousarray(q) for q in ins], {M}
+        ld = max(lds.pop(), M, 1)
+        if G != getattr(self, "n_groups", None):
+            raise ValueError(f"the moment planes have {G} rows but the engine's groups number {getattr(self, 'n_groups', None)}")
+        if out is None:
+            if on_dev:
+                import torch
+                planes = tuple(torch.empty((G, M), dtype=torch.float64, device=ins[0].device) for _ in want)
+            else:
+                planes = tuple(np.empty((G, M), dtype=np.float64) for _ in want)
+        else:
+            planes = tuple(out)
+            if len(planes) != len(want):
+                raise ValueError(f"out must hold {len(want)} planes, one per entry of want")
+        ptr = (lambda a: a.data_ptr()) if on_dev else (lambda a: a.ctypes.data)
+        optrs, out_ld = [None] * len(TT_OUTPUTS), None
+        for w, pl in zip(want, planes):
+            pl2, g, m, l, dev = _adjust_plane(pl, f"out[{w}]", copy_ok=False)
+            if (g, m, dev) != (G, M, on_dev) or (not dev and not pl.flags.writeable):
+                raise ValueError(f"out[{w}] must be a writeable float64 [{G}, {M}] plane on the same side as the moments")
+            if out_ld is None:
+                out_ld = l
+            elif out_ld != l:
+                raise ValueError("output planes must share one row stride")
+            optrs[TT_OUTPUTS.index(w)] = ptr(pl)
+        if G and M:
+            self._bind_torch_stream(*[q for q in ins if q is not None], *planes)
+            flags = (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0
+            self._check(self.lib.illico_ttest_from_moments(self.h, *[None if q is None else ptr(q) for q in ins], M, ld, var, alt, flags,
+                                                           *optrs, out_ld))
+        return planes
+
+    def student_t_pvalues(self, t, df, alternative="two-sided"):
+        """Student's t tail of every (t, df) pair, elementwise (illico_student_t_pvalues): two-sided ``2 sf(|t|, df)``, ``"greater"``
+        ``sf(t, df)``, ``"less"`` ``sf(-t, df)``.  ``t`` / ``df``: float64 numpy arrays or contiguous CUDA tensors of one shape; the
+        result lives where they live.  NaN where the evaluation did not converge (or ``t`` is NaN)."""
+        alt = self._alt(alternative)
+        if _is_torch_tensor(t) != _is_torch_tensor(df):
+            raise ValueError("t and df must both be numpy arrays or both CUDA tensors")
+        if _is_torch_tensor(t):
+            import torch
+            if not (t.is_cuda and df.is_cuda) or t.dtype != torch.float64 or df.dtype != torch.float64 or t.shape != df.shape:
+                raise ValueError("t and df must be float64 CUDA tensors of one shape")
+            t, df = t.contiguous(), df.contiguous()
+            p = torch.empty_like(t)
+            n, flags, ptr = t.numel(), FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE, (lambda a: a.data_ptr())
+        else:
+            t, df = np.ascontiguousarray(t, dtype=np.float64), np.ascontiguousarray(df, dtype=np.float64)
+            if t.shape != df.shape:
+                raise ValueError(f"t and df must have one shape, got {t.shape} and {df.shape}")
+            p = np.empty_like(t)
+            n, flags, ptr = t.size, 0, (lambda a: a.ctypes.data)
+        if n:
+            self._bind_torch_stream(t, df, p)
+            self._check(self.lib.illico_student_t_pvalues(self.h, ptr(t), ptr(df), n, alt, flags, ptr(p)))
+        return p
+
     def csr_indices_sorted(self, indices, indptr, n_rows) -> bool:
         i, p = _Buf(indices), _Buf(indptr)
         if i.np_dtype != p.np_dtype:
@@ -658,6 +830,20 @@ class BoundMatrix:
             return planes
         eng._bind_torch_stream(*[p for p in planes if p is not None])
         eng._check(eng.lib.illico_group_stats_bound(eng.h, self.h, col_lb, col_ub, (FLAG_LOG1P if is_log1p else 0) | oflag, *ptrs, out_ld))
+        return planes
+
+    def group_moments(self, col_lb, col_ub, *, rest=False, out=None, device_out=False):
+        """``Engine.group_moments`` of the bound matrix (illico_group_moments_bound); host planes unless ``device_out`` or ``out``."""
+        eng = self.engine
+        n_cols = self.shape[1]
+        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
+            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        G, W = eng.n_groups, col_ub - col_lb
+        planes, ptrs, oflag, out_ld = eng._gs_outputs(out, G, W, rest, device_out, eng._GM_KINDS, eng._GM_NAMES)
+        if W == 0:
+            return planes
+        eng._bind_torch_stream(*[p for p in planes if p is not None])
+        eng._check(eng.lib.illico_group_moments_bound(eng.h, self.h, col_lb, col_ub, oflag, *ptrs, out_ld))
         return planes
 
     def touch(self):

@@ -17,6 +17,10 @@ __all__ = ["adjust_pvalues", "differential_expression", "top_by_score"]
 
 #: what ``differential_expression`` can order each group's rows by for its ``n_genes`` cut
 RANK_BY = ("p_value", "z_score")
+#: ... with a t-test method: the statistic column (t) is the score
+RANK_BY_TTEST = ("p_value", "statistic")
+#: the tests ``differential_expression`` runs (scanpy's names) -> the variant of ``welch_ttest``, None for the Wilcoxon engine
+DE_METHODS = {"wilcoxon": None, "t-test": "welch", "t-test_overestim_var": "overestim_var"}
 
 #: method names -> the engine's codes (include/illico_hip.h: ILLICO_ADJ_*)
 METHODS = {"bh": "bh", "benjamini-hochberg": "bh", "by": "by", "benjamini-yekutieli": "by", "bonferroni": "bonferroni"}
@@ -73,7 +77,7 @@ def _check_plane(p, what="p"):
 
 def differential_expression(adata, is_log1p: bool, group_keys: str, reference: str | None = None, *,
                             corr_method: str = "benjamini-hochberg", n_genes: int | None = None, pts: bool = False,
-                            scores: bool = False, rank_by: str = "p_value", **kw) -> pd.DataFrame:
+                            scores: bool = False, rank_by: str = "p_value", method: str = "wilcoxon", **kw) -> pd.DataFrame:
     """``asymptotic_wilcoxon`` plus the multiple-testing correction that follows it in a DE workflow.
 
     ``kw`` takes the other arguments of ``asymptotic_wilcoxon`` (``batch_size``, ``alternative``, ``layer``, ...).  Returns its
@@ -86,8 +90,20 @@ def differential_expression(adata, is_log1p: bool, group_keys: str, reference: s
     test's z, positive when the group ranks above its reference (scanpy's ``scores``; include/illico_hip.h: illico_run_dense_ex).
     ``rank_by="z_score"`` orders each group's rows by descending z for the ``n_genes`` cut -- scanpy's order, and the one that still
     separates genes whose p has underflowed to 0 -- and implies ``scores=True``; ``rank_by="p_value"`` (the default) orders by p.
+
+    ``method``: ``"wilcoxon"`` (the default: everything above), ``"t-test"`` or ``"t-test_overestim_var"`` -- scanpy's names for Welch's
+    t-test and its variant (``illico_amd.welch_ttest``).  With a t-test ``p_value``, ``statistic`` (t) and ``fold_change`` are
+    ``welch_ttest``'s; ``p_value_adj``, ``n_genes`` and ``pts`` work as above; ``rank_by="statistic"`` orders each group's rows by
+    descending t (valid with a t-test only).  The statistic column is the score, so ``scores=True`` and ``rank_by="z_score"`` raise
+    ``ValueError``; ``use_continuity`` / ``tie_correct`` mean nothing to a t-test and raise ``TypeError``; ``n_threads``,
+    ``batch_size`` and ``precompile`` are accepted and ignored.
     """
     code = _method(corr_method)
+    if not isinstance(method, str) or method not in DE_METHODS:
+        raise ValueError(f"method must be one of {tuple(DE_METHODS)}, got {method!r}")
+    if DE_METHODS[method] is not None:
+        return _differential_expression_ttest(adata, is_log1p, group_keys, reference, code, n_genes, pts, scores, rank_by,
+                                              DE_METHODS[method], kw)
     if not isinstance(pts, (bool, np.bool_)):
         raise ValueError(f"pts must be a bool, got {pts!r}")
     if not isinstance(scores, (bool, np.bool_)):
@@ -121,6 +137,50 @@ def differential_expression(adata, is_log1p: bool, group_keys: str, reference: s
         X, handler, group_container = inputs[0]
         extra.update(stat_planes(X, handler, group_container, bool(is_log1p)))
     df = _planes_frame(planes[:3], index, p_value_adj=adj, **extra)
+    if n_genes is None:
+        return df
+    rows = (np.arange(G, dtype=np.int64)[:, None] * M + top[:, :n_top]).reshape(-1)
+    return df.iloc[rows]
+
+
+def _differential_expression_ttest(adata, is_log1p, group_keys, reference, code, n_genes, pts, scores, rank_by, variant, kw) -> pd.DataFrame:
+    """``differential_expression(method="t-test" / "t-test_overestim_var")``: ``welch_ttest``, then the same correction and cut."""
+    from illico_amd import ttest
+    if not isinstance(pts, (bool, np.bool_)):
+        raise ValueError(f"pts must be a bool, got {pts!r}")
+    if not isinstance(scores, (bool, np.bool_)):
+        raise ValueError(f"scores must be a bool, got {scores!r}")
+    if scores:
+        raise ValueError("scores=True belongs to method='wilcoxon': a t-test's statistic column is its score")
+    if not isinstance(rank_by, str) or rank_by not in RANK_BY_TTEST:
+        raise ValueError(f"rank_by must be one of {RANK_BY_TTEST} with a t-test method, got {rank_by!r}")
+    if n_genes is not None and (isinstance(n_genes, bool) or not isinstance(n_genes, (int, np.integer)) or n_genes < 1):
+        raise ValueError(f"n_genes must be a positive integer or None, got {n_genes!r}")
+    wilcoxon_only = set(kw) & {"use_continuity", "tie_correct"}
+    if wilcoxon_only:
+        raise TypeError(f"differential_expression(method='t-test...') got Wilcoxon-only keyword arguments {sorted(wilcoxon_only)}")
+    unknown = set(kw) - {"n_threads", "batch_size", "alternative", "layer", "precompile"}
+    if unknown:
+        raise TypeError(f"differential_expression() got unexpected keyword arguments {sorted(unknown)}")
+    alternative, layer = kw.get("alternative", "two-sided"), kw.get("layer")
+    ttest._check_arguments(is_log1p, variant, alternative)
+    planes, index, (X, handler, group_container) = ttest._ttest_frame_inputs(adata, is_log1p, group_keys, reference, variant, alternative, layer)
+    G, M = planes.shape[1], planes.shape[2]
+    n_top = min(int(n_genes), M) if n_genes is not None else 0
+    by_t = rank_by == "statistic"
+    if G and M:
+        eng = _lib.get_engine()
+        res = eng.adjust_pvalues(planes[0], code, n_top=0 if by_t else n_top)
+        adj, top = res if (n_top and not by_t) else (res, None)
+        if n_top and by_t:
+            top = eng.top_by_score(planes[1], n_top)
+    else:
+        adj, top = np.empty((G, M), dtype=np.float64), np.empty((G, 0), dtype=np.int64)
+    extra = {}
+    if pts:
+        from illico_amd.group_stats import stat_planes
+        extra.update(stat_planes(X, handler, group_container, bool(is_log1p)))
+    df = _planes_frame(planes, index, p_value_adj=adj, **extra)
     if n_genes is None:
         return df
     rows = (np.arange(G, dtype=np.int64)[:, None] * M + top[:, :n_top]).reshape(-1)

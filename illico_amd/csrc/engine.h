@@ -77,6 +77,13 @@ enum {
     KID_TOP_SORT,
     KID_TOP_MERGE,
     KID_TOP_SCAN,
+    KID_GM_VMAX, // illico_group_moments_* (kernels_group_moments.h)
+    KID_GM_DENSE,
+    KID_GM_CSC,
+    KID_GM_CSR,
+    KID_GM_TOTALS,
+    KID_GM_FINALIZE,
+    KID_TTEST, // illico_ttest_from_moments / illico_student_t_pvalues (kernels_ttest.h)
     KID_COUNT
 };
 extern const char *const kKernelNames[KID_COUNT];

@@ -1,0 +1,422 @@
+// illico_group_moments_{dense,csc,csr,bound}: per-(group, gene) exact sums of the values and of their squares, and the same over
+// every other cell (kernels_group_moments.h); illico_ttest_from_moments / illico_student_t_pvalues: Welch's t-test from those
+// planes (kernels_ttest.h).  A translation unit of its own: the kernels depend on nothing the other routes use.
+#include "engine.h"
+#include "kernels_group_moments.h"
+#include "kernels_ttest.h"
+
+namespace {
+
+struct GmInput {
+    bool sparse = false, is_csr = false, on_dev = false;
+    const void *X = nullptr; // dense
+    int64_t ld = 0;
+    const void *data = nullptr, *indices = nullptr, *indptr = nullptr; // sparse
+    int idx_dtype = 0;
+    int dtype = 0;
+    int64_t n_rows = 0, n_cols = 0;
+};
+struct GmOutputs {
+    double *sum, *sumsq, *sum_rest, *sumsq_rest;
+    int64_t ld;
+};
+
+int gm_check(illico_ctx *c, const GmInput &in, int64_t col_lb, int64_t col_ub, int flags, const GmOutputs &o) {
+    if (!c->has_groups) return fail(c, ILLICO_ERR_NO_GROUPS, "illico_set_groups has not been called");
+    if (in.n_rows != c->n_cells)
+        return fail(c, ILLICO_ERR_NO_GROUPS, "X has %lld rows but the groups describe %lld cells", (long long)in.n_rows, (long long)c->n_cells);
+    if (col_lb < 0 || col_ub > in.n_cols || col_lb > col_ub)
+        return fail(c, ILLICO_ERR_BOUNDS, "Invalid chunk bounds: (%lld, %lld) for data with %lld columns.", (long long)col_lb, (long long)col_ub, (long long)in.n_cols);
+    if (in.dtype < 0 || in.dtype > 3) return fail(c, ILLICO_ERR_DTYPE, "unsupported dtype code %d", in.dtype);
+    if (in.sparse && in.idx_dtype != ILLICO_IDX_I32 && in.idx_dtype != ILLICO_IDX_I64)
+        return fail(c, ILLICO_ERR_DTYPE, "unsupported index dtype code %d", in.idx_dtype);
+    if (flags & ILLICO_FLAG_LOG1P)
+        return fail(c, ILLICO_ERR_ARG, "ILLICO_FLAG_LOG1P: the moments are those of the values as given (the t-test is a test on the log values)");
+    if (!o.sum && !o.sumsq && !o.sum_rest && !o.sumsq_rest) return fail(c, ILLICO_ERR_ARG, "all four output planes are null: nothing to compute");
+    if (o.ld < col_ub - col_lb) return fail(c, ILLICO_ERR_ARG, "out_ld smaller than the chunk width");
+    for (int64_t g = 0; g < c->n_groups; ++g)
+        if (c->h_counts[g] > 2097151)
+            return fail(c, ILLICO_ERR_UNSUPPORTED, "group %lld holds %d cells: the exact per-group sums hold up to 2097151", (long long)g, c->h_counts[g]);
+    return ILLICO_OK;
+}
+
+// the groups' positions in chunks of at most GM_CHUNK (a group of 100 000 cells is spread over ~100 workgroups)
+void gm_chunks(const illico_ctx *c, std::vector<GmChunk> &ch) {
+    ch.clear();
+    int pos = 0;
+    for (int64_t g = 0; g < c->n_groups; ++g) {
+        const int n = c->h_counts[g];
+        for (int p = 0; p < n; p += GM_CHUNK) ch.push_back({(int)g, pos + p, pos + std::min(n, p + GM_CHUNK), n <= GM_CHUNK ? 1 : 0});
+        pos += n;
+    }
+}
+
+template <typename InT>
+int gm_dense_window(illico_ctx *c, const InT *X, int64_t ld, int64_t N, int wn, const GmChunk *d_ch, int n_ch, const GmPlanes &P) {
+    {
+        ProfScope ps(c, KID_GM_VMAX);
+        const int gx = (wn + GM_NT - 1) / GM_NT;
+        const int gy = (int)std::max<int64_t>(1, std::min<int64_t>((N + 63) / 64, (4096 + gx - 1) / gx));
+        hipLaunchKernelGGL(k_gm_dense_vmax<InT>, dim3(gx, gy), dim3(GM_NT), 0, c->stream, X, (long long)ld, (long long)N, wn, P.vmax, P.vmaxq, P.nonfin);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (n_ch) {
+        ProfScope ps(c, KID_GM_DENSE);
+        hipLaunchKernelGGL(k_gm_dense<InT>, dim3(n_ch, (wn + GM_TILE - 1) / GM_TILE), dim3(GM_NT), 0, c->stream, X, (long long)ld, wn, c->d_perm, d_ch, P);
+        HIPCHK(c, hipGetLastError());
+    }
+    return ILLICO_OK;
+}
+
+template <typename InT, typename IdxT>
+int gm_sparse_window(illico_ctx *c, bool is_csr, const void *data, const void *indices, const void *indptr, long long kshift, long long col0, int64_t N,
+                     int wn, int dt, const GmChunk *d_ch, int n_ch, const GmPlanes &P) {
+    const int G = (int)c->n_groups;
+    if (!is_csr) {
+        const bool ldsg = G <= GM_CSC_LDS_G;
+        GmCscParams C{data, indices, indptr, kshift, col0, c->d_codes, c->d_codes16, wn, G, dt};
+        const size_t lds = gm_csc_lds_bytes(G, ldsg);
+        ProfScope ps(c, KID_GM_CSC);
+        const dim3 grid((unsigned)std::min<int64_t>(wn, 1 << 20));
+        if (ldsg) {
+            HIPCHK(c, hipFuncSetAttribute((const void *)k_gm_csc<InT, IdxT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL((k_gm_csc<InT, IdxT, true>), grid, dim3(GM_NT), lds, c->stream, C, P);
+        } else
+            hipLaunchKernelGGL((k_gm_csc<InT, IdxT, false>), grid, dim3(GM_NT), lds, c->stream, C, P);
+        HIPCHK(c, hipGetLastError());
+        return ILLICO_OK;
+    }
+    {
+        ProfScope ps(c, KID_GM_VMAX);
+        const int gy = (wn + GM_VMAX_CW - 1) / GM_VMAX_CW;
+        const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((N + 15) / 16, (2048 + gy - 1) / gy));
+        hipLaunchKernelGGL((k_gm_csr_vmax<InT, IdxT>), dim3(gx, gy), dim3(GM_NT), 0, c->stream, (const InT *)data, (const IdxT *)indices, (const IdxT *)indptr,
+                           kshift, (long long)N, col0, wn, P.vmax, P.vmaxq, P.nonfin);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (n_ch) {
+        ProfScope ps(c, KID_GM_CSR);
+        hipLaunchKernelGGL((k_gm_csr<InT, IdxT>), dim3(n_ch, (wn + GM_CSR_CW - 1) / GM_CSR_CW), dim3(GM_NT), 0, c->stream, (const InT *)data, (const IdxT *)indices,
+                           (const IdxT *)indptr, kshift, col0, wn, c->d_perm, d_ch, P);
+        HIPCHK(c, hipGetLastError());
+    }
+    return ILLICO_OK;
+}
+
+template <typename InT>
+int gm_sparse_any_idx(illico_ctx *c, bool is_csr, int idx_dtype, const void *data, const void *indices, const void *indptr, long long kshift, long long col0,
+                      int64_t N, int wn, int dt, const GmChunk *d_ch, int n_ch, const GmPlanes &P) {
+    if (idx_dtype == ILLICO_IDX_I32) return gm_sparse_window<InT, int32_t>(c, is_csr, data, indices, indptr, kshift, col0, N, wn, dt, d_ch, n_ch, P);
+    return gm_sparse_window<InT, int64_t>(c, is_csr, data, indices, indptr, kshift, col0, N, wn, dt, d_ch, n_ch, P);
+}
+
+int64_t gm_idx_at(const void *p, int idx_dtype, int64_t i) { return idx_dtype == ILLICO_IDX_I32 ? (int64_t)((const int32_t *)p)[i] : ((const int64_t *)p)[i]; }
+
+int gm_run(illico_ctx *c, const GmInput &in, int64_t col_lb, int64_t col_ub, int flags, const GmOutputs &o) {
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = resolve_pending(c); // a plane written under ILLICO_FLAG_DEFER is complete only after its leftover genes
+    if (rc) return rc;
+    const int64_t W = col_ub - col_lb, G = c->n_groups, N = in.n_rows;
+    if (W == 0) return ILLICO_OK;
+    const bool out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
+    const int dt = in.dtype;
+    const size_t esz = dtype_size(dt), isz = in.idx_dtype == ILLICO_IDX_I32 ? 4 : 8;
+    void *v = nullptr;
+
+    // chunks of the groups' positions (dense, CSR)
+    std::vector<GmChunk> hch;
+    gm_chunks(c, hch);
+    const int n_ch = (int)hch.size();
+    GmChunk *d_ch = nullptr;
+    if (n_ch) {
+        if ((rc = get_scratch(c, "gm_chunks", hch.size() * sizeof(GmChunk), &v))) return rc;
+        d_ch = (GmChunk *)v;
+        HIPCHK(c, hipMemcpyAsync(d_ch, hch.data(), hch.size() * sizeof(GmChunk), hipMemcpyHostToDevice, c->stream));
+    }
+
+    // host-resident sparse input goes up once: CSC the entries of [col_lb, col_ub), CSR every row
+    const void *data = in.data, *indices = in.indices, *indptr = in.indptr;
+    long long kshift = 0, ptr_col0 = 0; // entry k at data[k - kshift]; the window's first column is indptr[col - ptr_col0]
+    if (in.sparse && !in.on_dev) {
+        const int64_t a = in.is_csr ? 0 : col_lb, b = in.is_csr ? N : col_ub;
+        const int64_t k0 = gm_idx_at(in.indptr, in.idx_dtype, a), k1 = gm_idx_at(in.indptr, in.idx_dtype, b);
+        if (k0 < 0 || k1 < k0) return fail(c, ILLICO_ERR_ARG, "indptr is not non-decreasing");
+        const size_t nnz = (size_t)(k1 - k0), nptr = (size_t)(b - a + 1);
+        if ((rc = get_scratch(c, "gm_upload", std::max<size_t>(nnz, 1) * (esz + isz) + nptr * isz + 64, &v))) return rc;
+        unsigned char *u = (unsigned char *)v;
+        void *dd = u, *di = u + ((nnz * esz + 15) & ~(size_t)15), *dp = (unsigned char *)di + ((nnz * isz + 15) & ~(size_t)15);
+        HIPCHK(c, hipMemcpyAsync(dd, (const unsigned char *)in.data + (size_t)k0 * esz, nnz * esz, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(di, (const unsigned char *)in.indices + (size_t)k0 * isz, nnz * isz, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dp, (const unsigned char *)in.indptr + (size_t)a * isz, nptr * isz, hipMemcpyHostToDevice, c->stream));
+        c->h2d_input_bytes += (int64_t)(nnz * (esz + isz) + nptr * isz);
+        data = dd; indices = di; indptr = dp;
+        kshift = k0;
+        ptr_col0 = a;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (the chunk list and the staged arrays came from pageable host memory)
+
+    // column windows: the six [G][wn] planes (+ staged host outputs, + the staged rows of a host dense matrix) fit the scratch cap
+    double *const outs[4] = {o.sum, o.sumsq, o.sum_rest, o.sumsq_rest};
+    int n_out = 0;
+    for (double *p : outs) n_out += p ? 1 : 0;
+    const size_t per_col = (size_t)G * 48 + 64 + (out_dev ? 0 : (size_t)G * 8 * n_out) + ((!in.sparse && !in.on_dev) ? (size_t)N * esz : 0);
+    const int64_t WW = std::max<int64_t>(1, std::min<int64_t>({W, (int64_t)((size_t)std::max<int64_t>(c->scratch_bytes, 1) / per_col), (int64_t)1 << 24}));
+    const int n_part = (int)std::min<int64_t>(G, 32);
+    if ((rc = get_scratch(c, "gm_planes", (size_t)WW * per_col + (size_t)n_part * WW * sizeof(GmTotal) + 256, &v))) return rc;
+    unsigned char *base = (unsigned char *)v;
+    const size_t GW = (size_t)G * WW;
+    GmPlanes P;
+    P.L0 = (long long *)base;
+    P.L1 = P.L0 + GW;
+    P.Q0 = P.L1 + GW;
+    P.Q1 = P.Q0 + GW;
+    P.cat = (u64 *)(P.Q1 + GW);
+    P.ovf = P.cat + GW;
+    P.vmax = P.ovf + GW;
+    P.vmaxq = P.vmax + WW;
+    P.nonfin = (int *)(P.vmaxq + WW);
+    GmTotal *part = (GmTotal *)(((uintptr_t)(P.nonfin + WW) + 255) & ~(uintptr_t)255);
+    unsigned char *stage = (unsigned char *)(part + (size_t)n_part * WW);
+    double *st[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (!out_dev)
+        for (int k = 0; k < 4; ++k)
+            if (outs[k]) { st[k] = (double *)stage; stage += GW * 8; }
+    void *xwin = stage; // host dense: the window's rows, [N][wn] in the matrix's own type
+
+    for (int64_t w0 = col_lb; w0 < col_ub; w0 += WW) {
+        const int wn = (int)std::min<int64_t>(WW, col_ub - w0);
+        P.W = wn;
+        // the six planes, the two magnitude rows and the flags lie back to back: one clear (a narrower last window clears a little more than it uses)
+        HIPCHK(c, hipMemsetAsync(P.L0, 0, GW * 48 + (size_t)WW * 20, c->stream));
+        if (!in.sparse) {
+            const unsigned char *X = (const unsigned char *)in.X + (size_t)w0 * esz;
+            int64_t ld = in.ld;
+            if (!in.on_dev) {
+                HIPCHK(c, hipMemcpy2DAsync(xwin, (size_t)wn * esz, X, (size_t)in.ld * esz, (size_t)wn * esz, (size_t)N, hipMemcpyHostToDevice, c->stream));
+                c->h2d_input_bytes += (int64_t)((size_t)N * wn * esz);
+                X = (const unsigned char *)xwin;
+                ld = wn;
+            }
+            switch (dt) {
+            case ILLICO_F32: rc = gm_dense_window<float>(c, (const float *)X, ld, N, wn, d_ch, n_ch, P); break;
+            case ILLICO_F64: rc = gm_dense_window<double>(c, (const double *)X, ld, N, wn, d_ch, n_ch, P); break;
+            case ILLICO_I32: rc = gm_dense_window<int32_t>(c, (const int32_t *)X, ld, N, wn, d_ch, n_ch, P); break;
+            default: rc = gm_dense_window<int64_t>(c, (const int64_t *)X, ld, N, wn, d_ch, n_ch, P); break;
+            }
+        } else {
+            const long long col0 = w0 - ptr_col0;
+            switch (dt) {
+            case ILLICO_F32: rc = gm_sparse_any_idx<float>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, d_ch, n_ch, P); break;
+            case ILLICO_F64: rc = gm_sparse_any_idx<double>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, d_ch, n_ch, P); break;
+            case ILLICO_I32: rc = gm_sparse_any_idx<int32_t>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, d_ch, n_ch, P); break;
+            default: rc = gm_sparse_any_idx<int64_t>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, d_ch, n_ch, P); break;
+            }
+        }
+        if (rc) return rc;
+        const int gx = (wn + GM_NT - 1) / GM_NT;
+        {
+            ProfScope ps(c, KID_GM_TOTALS);
+            hipLaunchKernelGGL(k_gm_totals, dim3(gx, n_part), dim3(GM_NT), 0, c->stream, P, (int)G, wn, part);
+            HIPCHK(c, hipGetLastError());
+        }
+        GmOut O;
+        const int64_t off = w0 - col_lb;
+        if (out_dev) {
+            O.sum = o.sum ? o.sum + off : nullptr;
+            O.sumsq = o.sumsq ? o.sumsq + off : nullptr;
+            O.sum_rest = o.sum_rest ? o.sum_rest + off : nullptr;
+            O.sumsq_rest = o.sumsq_rest ? o.sumsq_rest + off : nullptr;
+            O.ld = o.ld;
+        } else {
+            O.sum = st[0]; O.sumsq = st[1]; O.sum_rest = st[2]; O.sumsq_rest = st[3];
+            O.ld = wn;
+        }
+        {
+            ProfScope ps(c, KID_GM_FINALIZE);
+            const int gy = (int)std::max<int64_t>(1, std::min<int64_t>(G, (8192 + gx - 1) / gx));
+            hipLaunchKernelGGL(k_gm_finalize, dim3(gx, gy), dim3(GM_NT), 0, c->stream, P, (int)G, wn, part, n_part, O);
+            HIPCHK(c, hipGetLastError());
+        }
+        if (!out_dev) {
+            for (int k = 0; k < 4; ++k)
+                if (outs[k])
+                    HIPCHK(c, hipMemcpy2DAsync((unsigned char *)outs[k] + (size_t)off * 8, (size_t)o.ld * 8, st[k], (size_t)wn * 8, (size_t)wn * 8, (size_t)G,
+                                               hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+    }
+    return ILLICO_OK;
+}
+
+int group_moments_sparse(illico_ctx *c, bool is_csr, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
+                         int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, double *out_sum, double *out_sumsq, double *out_sum_rest,
+                         double *out_sumsq_rest, int64_t out_ld) {
+    if (!c) return ILLICO_ERR_ARG;
+    CTX_LOCK(c);
+    GmInput in;
+    in.sparse = true; in.is_csr = is_csr; in.data = data; in.indices = indices; in.indptr = indptr; in.idx_dtype = idx_dtype; in.dtype = dtype;
+    in.n_rows = n_rows; in.n_cols = n_cols; in.on_dev = flags & ILLICO_FLAG_INPUT_DEVICE;
+    const GmOutputs o{out_sum, out_sumsq, out_sum_rest, out_sumsq_rest, out_ld};
+    int rc = gm_check(c, in, col_lb, col_ub, flags, o);
+    if (rc) return rc;
+    if (!data || !indices || !indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
+    return gm_run(c, in, col_lb, col_ub, flags, o);
+}
+
+// ---- the t-test from moment planes -------------------------------------------------------------------------------------------------
+int tt_alt_ok(illico_ctx *c, int alternative) {
+    if (alternative != ILLICO_ALT_TWO_SIDED && alternative != ILLICO_ALT_LESS && alternative != ILLICO_ALT_GREATER)
+        return fail(c, ILLICO_ERR_ALTERNATIVE, "Unsupported alternative hypothesis code: %d", alternative);
+    return ILLICO_OK;
+}
+
+} // namespace
+
+extern "C" int illico_group_moments_dense(illico_ctx *c, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t col_lb, int64_t col_ub,
+                                          int flags, double *out_sum, double *out_sumsq, double *out_sum_rest, double *out_sumsq_rest, int64_t out_ld) {
+    if (!c) return ILLICO_ERR_ARG;
+    CTX_LOCK(c);
+    GmInput in;
+    in.X = X; in.dtype = dtype; in.n_rows = n_rows; in.n_cols = n_cols; in.ld = ld; in.on_dev = flags & ILLICO_FLAG_INPUT_DEVICE;
+    const GmOutputs o{out_sum, out_sumsq, out_sum_rest, out_sumsq_rest, out_ld};
+    int rc = gm_check(c, in, col_lb, col_ub, flags, o);
+    if (rc) return rc;
+    if (!X) return fail(c, ILLICO_ERR_ARG, "null X");
+    if (ld < n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
+    return gm_run(c, in, col_lb, col_ub, flags, o);
+}
+extern "C" int illico_group_moments_csc(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
+                                        int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, double *out_sum, double *out_sumsq, double *out_sum_rest,
+                                        double *out_sumsq_rest, int64_t out_ld) {
+    return group_moments_sparse(c, false, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, out_sum, out_sumsq, out_sum_rest,
+                                out_sumsq_rest, out_ld);
+}
+extern "C" int illico_group_moments_csr(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
+                                        int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, double *out_sum, double *out_sumsq, double *out_sum_rest,
+                                        double *out_sumsq_rest, int64_t out_ld) {
+    return group_moments_sparse(c, true, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, out_sum, out_sumsq, out_sum_rest,
+                                out_sumsq_rest, out_ld);
+}
+extern "C" int illico_group_moments_bound(illico_ctx *c, const illico_matrix *m, int64_t col_lb, int64_t col_ub, int flags, double *out_sum, double *out_sumsq,
+                                          double *out_sum_rest, double *out_sumsq_rest, int64_t out_ld) {
+    if (!c || !m) return ILLICO_ERR_ARG;
+    CTX_LOCK(c); // (held for the whole call: illico_matrix_release on another thread cannot free the arrays under it)
+    if (m->owner != c || std::find(c->bound.begin(), c->bound.end(), m) == c->bound.end())
+        return fail(c, ILLICO_ERR_ARG, "the matrix handle does not belong to this context (or was released)");
+    return group_moments_sparse(c, m->is_csr, m->d_data, m->dtype, m->d_indices, m->d_indptr, m->idx_dtype, m->n_rows, m->n_cols, col_lb, col_ub,
+                                (flags & (ILLICO_FLAG_LOG1P | ILLICO_FLAG_OUTPUT_DEVICE)) | ILLICO_FLAG_INPUT_DEVICE, out_sum, out_sumsq, out_sum_rest,
+                                out_sumsq_rest, out_ld);
+}
+
+extern "C" int illico_ttest_from_moments(illico_ctx *c, const double *sum, const double *sumsq, const double *sum_rest, const double *sumsq_rest, int64_t n_cols,
+                                         int64_t in_ld, int variant, int alternative, int flags, double *out_p, double *out_t, double *out_df, double *out_mean,
+                                         double *out_var, double *out_mean_ref, double *out_var_ref, int64_t out_ld) {
+    if (!c) return ILLICO_ERR_ARG;
+    CTX_LOCK(c);
+    if (!c->has_groups) return fail(c, ILLICO_ERR_NO_GROUPS, "illico_set_groups has not been called");
+    if (variant != ILLICO_TT_WELCH && variant != ILLICO_TT_OVERESTIM_VAR) return fail(c, ILLICO_ERR_ARG, "unknown t-test variant code %d", variant);
+    int rc = tt_alt_ok(c, alternative);
+    if (rc) return rc;
+    const bool ovr = c->ref < 0;
+    if (!sum || !sumsq) return fail(c, ILLICO_ERR_ARG, "null sum / sumsq plane");
+    if (ovr && (!sum_rest || !sumsq_rest)) return fail(c, ILLICO_ERR_ARG, "one-versus-rest needs the sum_rest and sumsq_rest planes");
+    double *const outs[TT_N_OUT] = {out_p, out_t, out_df, out_mean, out_var, out_mean_ref, out_var_ref};
+    int n_out = 0;
+    for (double *p : outs) n_out += p ? 1 : 0;
+    if (!n_out) return fail(c, ILLICO_ERR_ARG, "all output planes are null: nothing to compute");
+    if (n_cols < 0 || in_ld < n_cols || out_ld < n_cols) return fail(c, ILLICO_ERR_ARG, "a pitch is smaller than the width (or the width is negative)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = resolve_pending(c))) return rc;
+    const int64_t G = c->n_groups, W = n_cols;
+    if (W == 0 || G == 0) return ILLICO_OK;
+    const bool in_dev = flags & ILLICO_FLAG_INPUT_DEVICE, out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
+    const double *const ins[4] = {sum, sumsq, ovr ? sum_rest : nullptr, ovr ? sumsq_rest : nullptr};
+    const int n_in = ovr ? 4 : 2;
+    // column windows under the scratch cap (host planes are staged)
+    const size_t per_col = (in_dev ? 0 : (size_t)G * 8 * n_in) + (out_dev ? 0 : (size_t)G * 8 * n_out);
+    const int64_t WW = per_col ? std::max<int64_t>(1, std::min<int64_t>(W, (int64_t)((size_t)std::max<int64_t>(c->scratch_bytes, 1) / per_col))) : W;
+    unsigned char *stage = nullptr;
+    if (per_col) {
+        void *v = nullptr;
+        if ((rc = get_scratch(c, "tt_stage", (size_t)WW * per_col + 64, &v))) return rc;
+        stage = (unsigned char *)v;
+    }
+    for (int64_t w0 = 0; w0 < W; w0 += WW) {
+        const int wn = (int)std::min<int64_t>(WW, W - w0);
+        TtParams T;
+        T.G = (int)G; T.W = wn; T.ref = (int)c->ref; T.n_cells = (long long)c->n_cells; T.counts = c->d_counts;
+        T.variant = variant; T.alternative = alternative;
+        unsigned char *s = stage;
+        const double *din[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int k = 0; k < 4; ++k) {
+            if (!ins[k]) continue;
+            if (in_dev) din[k] = ins[k] + w0;
+            else {
+                HIPCHK(c, hipMemcpy2DAsync(s, (size_t)wn * 8, ins[k] + w0, (size_t)in_ld * 8, (size_t)wn * 8, (size_t)G, hipMemcpyHostToDevice, c->stream));
+                din[k] = (const double *)s;
+                s += (size_t)G * wn * 8;
+            }
+        }
+        T.S = din[0]; T.Q = din[1]; T.SR = din[2]; T.QR = din[3];
+        T.in_ld = in_dev ? in_ld : wn;
+        double *st[TT_N_OUT];
+        for (int k = 0; k < TT_N_OUT; ++k) {
+            st[k] = nullptr;
+            if (!outs[k]) { T.out[k] = nullptr; continue; }
+            if (out_dev) T.out[k] = outs[k] + w0;
+            else { st[k] = (double *)s; T.out[k] = st[k]; s += (size_t)G * wn * 8; }
+        }
+        T.out_ld = out_dev ? out_ld : wn;
+        {
+            ProfScope ps(c, KID_TTEST);
+            const int gx = (wn + TT_NT - 1) / TT_NT;
+            hipLaunchKernelGGL(k_ttest_from_moments, dim3(gx, (unsigned)std::min<int64_t>(G, 65535)), dim3(TT_NT), 0, c->stream, T);
+            HIPCHK(c, hipGetLastError());
+        }
+        if (!out_dev) {
+            for (int k = 0; k < TT_N_OUT; ++k)
+                if (outs[k])
+                    HIPCHK(c, hipMemcpy2DAsync(outs[k] + w0, (size_t)out_ld * 8, st[k], (size_t)wn * 8, (size_t)wn * 8, (size_t)G, hipMemcpyDeviceToHost, c->stream));
+        }
+        if (!in_dev || !out_dev) HIPCHK(c, hipStreamSynchronize(c->stream)); // (the staging area is reused by the next window; host planes complete on return)
+    }
+    return ILLICO_OK;
+}
+
+extern "C" int illico_student_t_pvalues(illico_ctx *c, const double *t, const double *df, int64_t n, int alternative, int flags, double *out_p) {
+    if (!c) return ILLICO_ERR_ARG;
+    CTX_LOCK(c);
+    int rc = tt_alt_ok(c, alternative);
+    if (rc) return rc;
+    if (n < 0 || (n && (!t || !df || !out_p))) return fail(c, ILLICO_ERR_ARG, "null array or negative length");
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = resolve_pending(c))) return rc;
+    if (n == 0) return ILLICO_OK;
+    const bool in_dev = flags & ILLICO_FLAG_INPUT_DEVICE, out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
+    const int64_t chunk = (int64_t)1 << 24;
+    double *dt_ = nullptr, *ddf = nullptr, *dp = nullptr;
+    if (!in_dev || !out_dev) {
+        void *v = nullptr;
+        if ((rc = get_scratch(c, "tt_stage", (size_t)std::min(n, chunk) * 24 + 64, &v))) return rc;
+        dt_ = (double *)v; ddf = dt_ + std::min(n, chunk); dp = ddf + std::min(n, chunk);
+    }
+    for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+        const int64_t m = std::min(chunk, n - i0);
+        const double *kt = t + i0, *kd = df + i0;
+        double *kp = out_p + i0;
+        if (!in_dev) {
+            HIPCHK(c, hipMemcpyAsync(dt_, t + i0, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(ddf, df + i0, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+            kt = dt_; kd = ddf;
+        }
+        if (!out_dev) kp = dp;
+        {
+            ProfScope ps(c, KID_TTEST);
+            hipLaunchKernelGGL(k_student_t_pvalues, dim3((unsigned)((m + TT_NT - 1) / TT_NT)), dim3(TT_NT), 0, c->stream, kt, kd, (long long)m, alternative, kp);
+            HIPCHK(c, hipGetLastError());
+        }
+        if (!out_dev) HIPCHK(c, hipMemcpyAsync(out_p + i0, dp, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
+        if (!in_dev || !out_dev) HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return ILLICO_OK;
+}

@@ -289,6 +289,67 @@ int illico_group_stats_csr(illico_ctx *ctx, const void *data, int dtype, const v
 int illico_group_stats_bound(illico_ctx *ctx, const illico_matrix *matrix, int64_t col_lb, int64_t col_ub, int flags,
                              int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest, double *out_sum_rest, int64_t out_ld);
 
+/* ---- per-group first and second moments, Welch's t-test ---------------------------------------
+ * illico_group_moments_*: for each group g of illico_set_groups and each column j of [col_lb, col_ub) (plane column j - col_lb), float64:
+ *   out_sum[g][j]         the sum of g's values x (taken as double);
+ *   out_sumsq[g][j]       the sum of fl(x * x);
+ *   out_sum_rest[g][j], out_sumsq_rest[g][j]: the same over every cell NOT in g.
+ * Arguments, windowing under "scratch_bytes", host / device input and output, bound matrices and the completion of a deferred call are
+ * those of illico_group_stats_*.  The pass always works on the values as given: ILLICO_FLAG_LOG1P is ILLICO_ERR_ARG (the t-test is a
+ * test on the log values).  It reads the input as often as illico_group_stats_* does.
+ * Both sums are exact-limb sums (kernels_group_moments.h): 128-bit totals, rest = total - own in integers, each sum rounded to float64
+ * once -- byte-identical across dense / CSC / CSR / bound, host / device input, and from run to run.  The 84 limb bits hold a value
+ * exactly while it is within 2^-30 (float32 values: 2^-59) of the column's largest finite magnitude, and the 48-bit square of a float32
+ * value while it is within 2^-35 of the column's largest square; smaller ones are truncated toward zero at 2^-83 of the largest.  The
+ * squares' scale is fl(v * v), v the column's largest |x| whose square is finite.
+ * Non-finite: sum is NaN / +inf / -inf as numpy's would be.  A square that is not finite (NaN, +-inf, |x| beyond about 1.3e154) is kept
+ * out of the limbs: sumsq is NaN with a NaN among the values, else +inf with such a square.
+ * Any of the four pointers may be null; at least one must be given.  Errors: as illico_group_stats_* (the 2097151-cell group limit is
+ * ILLICO_ERR_UNSUPPORTED), plus ILLICO_ERR_ARG for ILLICO_FLAG_LOG1P. */
+int illico_group_moments_dense(illico_ctx *ctx, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld,
+                               int64_t col_lb, int64_t col_ub, int flags,
+                               double *out_sum, double *out_sumsq, double *out_sum_rest, double *out_sumsq_rest, int64_t out_ld);
+int illico_group_moments_csc(illico_ctx *ctx, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype,
+                             int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags,
+                             double *out_sum, double *out_sumsq, double *out_sum_rest, double *out_sumsq_rest, int64_t out_ld);
+int illico_group_moments_csr(illico_ctx *ctx, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype,
+                             int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags,
+                             double *out_sum, double *out_sumsq, double *out_sum_rest, double *out_sumsq_rest, int64_t out_ld);
+/* a matrix bound with illico_csr_bind / illico_csc_bind; flags: ILLICO_FLAG_OUTPUT_DEVICE */
+int illico_group_moments_bound(illico_ctx *ctx, const illico_matrix *matrix, int64_t col_lb, int64_t col_ub, int flags,
+                               double *out_sum, double *out_sumsq, double *out_sum_rest, double *out_sumsq_rest, int64_t out_ld);
+
+/* Welch's unequal-variance t-test of every (group, column) from moment planes (float64 [G][in_ld >= n_cols], all on the host, or all on
+ * the device with ILLICO_FLAG_INPUT_DEVICE).  The context's groups give the sizes and the test: with a reference group the reference is
+ * that group's row of sum / sumsq (the rest planes are not read), otherwise it is the rest planes, which are then required
+ * (ILLICO_ERR_ARG).  With n1, S1, Q1 the group's and n2, S2, Q2 the reference's size, sum and sum of squares, every step is one IEEE
+ * float64 operation, in this order:
+ *     m1 = S1 / n1                  m2 = S2 / n2
+ *     q1 = Q1 - S1 * m1             q2 = Q2 - S2 * m2        (q < 0 -> 0; NaN stays NaN)
+ *     v1 = q1 / (n1 - 1)            v2 = q2 / (n2 - 1)        (n = 1: 0 / 0 -> NaN)
+ *     n2' = n1 for ILLICO_TT_OVERESTIM_VAR (scanpy's "t-test_overestim_var"), else n2
+ *     a = v1 / n1                   b = v2 / n2'
+ *     t  = (m1 - m2) / sqrt(a + b)
+ *     df = ((a + b) * (a + b)) / (a * a / (n1 - 1) + b * b / (n2' - 1));   NaN -> 1   (as scipy)
+ * (scanpy's float64 form: the variance carries a relative error of about 2^-52 (1 + mean^2 / var); no exact integer form is offered.)
+ * p: two-sided 2 sf(|t|, df), ILLICO_ALT_GREATER sf(t, df), ILLICO_ALT_LESS sf(-t, df), sf Student's t tail in float64 -- what
+ * scipy.stats.ttest_ind_from_stats(..., equal_var=False, alternative=...) gives with the group first; p stays a normal number down to
+ * 1e-300.  A NaN t (0 / 0, n = 1, NaN input) gives (t, p) = (0, 1); t = +-inf (no variance on either side, different means) is kept and p
+ * follows from it; the reference row of a one-versus-reference call gets (0, 1).
+ * Outputs: float64 [G][out_ld >= n_cols], each may be null (at least one given): p, t, df, the group's mean m1 and variance v1, the
+ * reference's m2 and v2; on the device with ILLICO_FLAG_OUTPUT_DEVICE (ordered on the context's stream), else complete on return.
+ * Errors: ILLICO_ERR_NO_GROUPS, ILLICO_ERR_ALTERNATIVE, ILLICO_ERR_ARG (unknown variant, null sum / sumsq, missing rest planes, all
+ * outputs null, a pitch below the width). */
+enum { ILLICO_TT_WELCH = 0, ILLICO_TT_OVERESTIM_VAR = 1 };
+int illico_ttest_from_moments(illico_ctx *ctx, const double *sum, const double *sumsq, const double *sum_rest, const double *sumsq_rest,
+                              int64_t n_cols, int64_t in_ld, int variant, int alternative, int flags,
+                              double *out_p, double *out_t, double *out_df, double *out_mean, double *out_var,
+                              double *out_mean_ref, double *out_var_ref, int64_t out_ld);
+/* The same tail, elementwise: out_p[i] from (t[i], df[i]), df > 0 and finite (1 .. about 4e6 is what the test forms), i < n.  NaN for a
+ * NaN t, and for an evaluation whose continued fraction did not converge within its step limit.  flags: ILLICO_FLAG_INPUT_DEVICE (t and
+ * df), ILLICO_FLAG_OUTPUT_DEVICE (out_p). */
+int illico_student_t_pvalues(illico_ctx *ctx, const double *t, const double *df, int64_t n, int alternative, int flags, double *out_p);
+
 /* ---- measurement hooks (bench.py roofline leg) ------------------------------------------- */
 int illico_profile_num_kernels(void);
 const char *illico_profile_kernel_name(int kernel_id);
