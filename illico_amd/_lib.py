@@ -46,6 +46,7 @@ SYMBOLS = [
     "illico_run_dense_ex", "illico_run_csc_ex", "illico_run_csr_ex", "illico_run_bound_ex", "illico_top_by_score",
     "illico_group_moments_dense", "illico_group_moments_csc", "illico_group_moments_csr", "illico_group_moments_bound",
     "illico_ttest_from_moments", "illico_student_t_pvalues",
+    "illico_group_value_hists_dense", "illico_group_value_hists_csc", "illico_group_value_hists_csr", "illico_pairwise_from_hists",
 ]
 
 _lib = None
@@ -106,6 +107,10 @@ def load() -> ctypes.CDLL:
         lib.illico_group_moments_bound.argtypes = [vp, vp, i64, i64, ci, vp, vp, vp, vp, i64]
         lib.illico_ttest_from_moments.argtypes = [vp, vp, vp, vp, vp, i64, i64, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, i64]
         lib.illico_student_t_pvalues.argtypes = [vp, vp, vp, i64, ci, ci, vp]
+        lib.illico_group_value_hists_dense.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, vp, vp]
+        for f in (lib.illico_group_value_hists_csc, lib.illico_group_value_hists_csr):
+            f.argtypes = [vp, vp, ci, vp, vp, ci, i64, i64, i64, i64, ci, vp, vp]
+        lib.illico_pairwise_from_hists.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, i64, ci, ci, vp, vp, vp, vp, i64]
         for name in SYMBOLS:  # fail at load time, not at first use, if the library and the header have drifted
             getattr(lib, name)
         _lib = lib
@@ -754,6 +759,184 @@ class Engine:
             self._bind_torch_stream(t, df, p)
             self._check(self.lib.illico_student_t_pvalues(self.h, ptr(t), ptr(df), n, alt, flags, ptr(p)))
         return p
+
+    # ---- all-pairs Wilcoxon tests from value histograms (include/illico_hip.h: illico_group_value_hists_*, illico_pairwise_from_hists) ----
+    #: values a histogram holds (0 .. HIST_VALUES - 1)
+    HIST_VALUES = 256
+
+    def _hist_outputs(self, out, G, W, want_device):
+        """(H, flags, pointers, output flag): ``out`` None (allocate uint32 ``[G, W, 256]`` and ``[W]`` where the input lives) or a pair
+        of contiguous uint32 arrays of those shapes, both numpy or both CUDA tensors (torch has no uint32 kernels: int32 tensors)."""
+        if out is None:
+            if want_device:
+                import torch
+                dev = f"cuda:{self.device}"
+                H, fl = torch.empty((G, W, self.HIST_VALUES), dtype=torch.int32, device=dev), torch.empty((W,), dtype=torch.int32, device=dev)
+            else:
+                H, fl = np.empty((G, W, self.HIST_VALUES), dtype=np.uint32), np.empty((W,), dtype=np.uint32)
+        else:
+            H, fl = out
+        ptrs, side = [], None
+        for name, a, shape in (("H", H, (G, W, self.HIST_VALUES)), ("flags", fl, (W,))):
+            if _is_torch_tensor(a):
+                import torch
+                if not a.is_cuda or a.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(a.shape) != shape or not a.is_contiguous():
+                    raise ValueError(f"{name} must be a contiguous CUDA int32 tensor of shape {shape}")
+                dev, ptr = True, a.data_ptr()
+            else:
+                if not isinstance(a, np.ndarray) or a.dtype != np.uint32 or a.shape != shape or not a.flags.c_contiguous or not a.flags.writeable:
+                    raise ValueError(f"{name} must be a writeable contiguous uint32 array of shape {shape}")
+                dev, ptr = False, a.ctypes.data
+            if side is None:
+                side = dev
+            elif side != dev:
+                raise ValueError("H and flags must live on the same side (host or device)")
+            ptrs.append(ptr)
+        return H, fl, ptrs, FLAG_OUTPUT_DEVICE if side else 0
+
+    def group_value_hists(self, X, col_lb, col_ub, out=None):
+        """Per-(group, gene) histograms of the values 0 .. 255 over the dense columns [col_lb, col_ub) (illico_group_value_hists_dense),
+        for the engine's current groups (their reference / one-versus-rest mode plays no part).
+
+        ``X``: a row-major numpy array or a CUDA tensor.  Returns ``(H, flags)``: ``H[g, j, c]`` the cells of group g whose value in
+        column ``col_lb + j`` is c, ``flags[j]`` non-zero when the column holds a value that is no integer in [0, 255] (``H`` of such a
+        column is unspecified).  uint32 numpy arrays for host input, int32 CUDA tensors for device input, unless ``out`` (a pair of
+        either) says otherwise."""
+        if _is_torch_tensor(X):
+            if X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1):
+                raise ValueError("X must be row-major 2-D")
+            ptr, on_dev, keep = X.data_ptr(), X.is_cuda, X
+            n_rows, n_cols = int(X.shape[0]), int(X.shape[1])
+            ld = int(X.stride(0)) if n_rows > 1 else n_cols
+            dt = dtype_code(str(X.dtype).replace("torch.", ""))
+        else:
+            X = normalize_values(np.asarray(X))
+            if X.ndim != 2:
+                raise ValueError(f"X must be 2-D, got {X.ndim} dimensions")
+            if (X.shape[1] > 1 and X.strides[1] != X.itemsize) or X.strides[0] % X.itemsize or X.strides[0] < 0:
+                X = np.ascontiguousarray(X)
+            ptr, on_dev, keep = X.ctypes.data, False, X
+            n_rows, n_cols = X.shape
+            ld = X.strides[0] // X.itemsize if n_rows > 1 else n_cols
+            dt = dtype_code(X.dtype)
+        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
+            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        G, W = self.n_groups, col_ub - col_lb
+        H, fl, ptrs, oflag = self._hist_outputs(out, G, W, on_dev)
+        if W == 0:
+            return H, fl
+        self._bind_torch_stream(keep, H, fl)
+        self._check(self.lib.illico_group_value_hists_dense(self.h, ptr, dt, n_rows, n_cols, max(ld, n_cols), col_lb, col_ub,
+                                                            (FLAG_INPUT_DEVICE if on_dev else 0) | oflag, *ptrs))
+        del keep
+        return H, fl
+
+    def group_value_hists_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, out=None):
+        """``group_value_hists`` of a CSC (``fmt="csc"``) or CSR (``"csr"``) matrix given as its three arrays (numpy or CUDA tensors):
+        the dense answer -- a stored zero counts in bin 0, and so do the cells that are not stored.  CSR rows need not be sorted."""
+        if fmt not in ("csc", "csr"):
+            raise ValueError(f"fmt must be 'csc' or 'csr', got {fmt!r}")
+        n_rows, n_cols = int(shape[0]), int(shape[1])
+        if _is_torch_tensor(data):
+            d, i, p = _Buf(data), _Buf(indices), _Buf(indptr)
+        else:
+            d = _Buf(normalize_values(np.asarray(data)))
+            idt = np.int32 if (np.asarray(indices).dtype == np.int32 and np.asarray(indptr).dtype == np.int32) else np.int64
+            i, p = _Buf(indices, idt), _Buf(indptr, idt)
+        if i.np_dtype != p.np_dtype or i.np_dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+            raise KeyError(f"Support for index dtypes {i.np_dtype}/{p.np_dtype} is not implemented.")
+        if not (d.on_device == i.on_device == p.on_device):
+            raise ValueError("data, indices and indptr must live on the same side (host or device)")
+        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
+            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        G, W = self.n_groups, col_ub - col_lb
+        H, fl, ptrs, oflag = self._hist_outputs(out, G, W, d.on_device)
+        if W == 0:
+            return H, fl
+        fn = self.lib.illico_group_value_hists_csc if fmt == "csc" else self.lib.illico_group_value_hists_csr
+        self._bind_torch_stream(d.keep, i.keep, p.keep, H, fl)
+        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, IDX_I32 if i.np_dtype == np.int32 else IDX_I64,
+                       n_rows, n_cols, col_lb, col_ub, (FLAG_INPUT_DEVICE if d.on_device else 0) | oflag, *ptrs))
+        return H, fl
+
+    def pairwise_from_hists(self, H, flags, *, counts=None, sel=None, sums=None, is_log1p=False, use_continuity=True, tie_correct=True,
+                            alternative="two-sided", scores=False, out=None):
+        """The Wilcoxon rank-sum test of every ordered pair of groups from the histograms of ``group_value_hists``
+        (illico_pairwise_from_hists).
+
+        ``H`` ``[G, W, 256]`` and ``flags`` ``[W]``: as ``group_value_hists`` returns them (numpy, or CUDA tensors).  ``sel``: the K group
+        ids to compare (default: all G, in order).  ``counts``: the G group sizes (default: those of the engine's current groups).
+        ``sums``: an optional float64 ``[G, W]`` plane of per-group value sums for the fold change, on the side of ``H`` (under
+        ``is_log1p`` pass the ``expm1`` sums of ``group_stats(..., is_log1p=True)``: ``is_log1p`` itself changes nothing here); without
+        it the sums are those of the histograms.  Returns float64 planes ``(p, U, fold_change)`` -- and ``z`` with ``scores=True`` --
+        of shape ``[K, K, W]`` indexed ``[r, g, j]``: group ``sel[g]`` against reference ``sel[r]``, so that ``plane[r]`` is the
+        ``[K, W]`` plane of a one-versus-reference call with that reference.  Diagonal: p = 1, U = n^2 / 2, z = 0.  The columns of
+        flagged genes are left as they are in ``out`` (a tuple of 3 or 4 contiguous planes on the side of ``H``; uninitialised when
+        the planes are allocated here)."""
+        alt = self._alt(alternative)
+        if not isinstance(scores, (bool, np.bool_)):
+            raise ValueError(f"scores must be a bool, got {scores!r}")
+        on_dev = _is_torch_tensor(H)
+        if on_dev != _is_torch_tensor(flags) or (sums is not None and on_dev != _is_torch_tensor(sums)):
+            raise ValueError("H, flags and sums must live on the same side (host or device)")
+        if on_dev:
+            import torch
+            if not (H.is_cuda and flags.is_cuda and H.is_contiguous() and flags.is_contiguous()) or H.dim() != 3 or H.element_size() != 4 \
+                    or flags.element_size() != 4 or H.dtype.is_floating_point or flags.dtype.is_floating_point:
+                raise ValueError("H and flags must be contiguous 32-bit integer CUDA tensors [G, W, 256] and [W]")
+        else:
+            H, flags = np.ascontiguousarray(H, dtype=np.uint32), np.ascontiguousarray(flags, dtype=np.uint32)
+            if H.ndim != 3:
+                raise ValueError("H must be [G, W, 256]")
+        G, W, R = (int(x) for x in H.shape)
+        if R != self.HIST_VALUES or tuple(flags.shape) != (W,):
+            raise ValueError(f"H must be [G, W, {self.HIST_VALUES}] and flags [W], got {tuple(H.shape)} and {tuple(flags.shape)}")
+        if counts is None:
+            if self._groups_keep is None:
+                raise ValueError("counts is needed: no groups have been set on this engine")
+            counts = self._groups_keep.counts
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        if counts.shape != (G,):
+            raise ValueError(f"H holds {G} groups but counts has shape {counts.shape}")
+        if sel is None:
+            K, sel_arr, sel_ptr = G, None, None
+        else:
+            sel_arr = np.ascontiguousarray(sel, dtype=np.int64).reshape(-1)
+            K, sel_ptr = int(sel_arr.size), sel_arr.ctypes.data
+        sums_ptr, sums_ld = None, 0
+        if sums is not None:
+            sums, sg, sw, sums_ld, _ = _adjust_plane(sums, "sums", copy_ok=True)
+            if (sg, sw) != (G, W):
+                raise ValueError(f"sums must be a float64 [{G}, {W}] plane")
+            sums_ptr = sums.data_ptr() if on_dev else sums.ctypes.data
+        n = 4 if scores else 3
+        if out is None:
+            if on_dev:
+                import torch
+                planes = tuple(torch.empty((K, K, W), dtype=torch.float64, device=H.device) for _ in range(n))
+            else:
+                planes = tuple(np.empty((K, K, W), dtype=np.float64) for _ in range(n))
+        else:
+            planes = tuple(out)
+            if len(planes) != n:
+                raise ValueError(f"out must hold {n} planes (p, U, fold change{', z' if scores else ''})")
+        ptrs = []
+        for q in planes:
+            if on_dev:
+                import torch
+                ok = _is_torch_tensor(q) and q.is_cuda and q.dtype == torch.float64 and tuple(q.shape) == (K, K, W) and q.is_contiguous()
+            else:
+                ok = isinstance(q, np.ndarray) and q.dtype == np.float64 and q.shape == (K, K, W) and q.flags.c_contiguous and q.flags.writeable
+            if not ok:
+                raise ValueError(f"output planes must be contiguous float64 [{K}, {K}, {W}] on the side of H")
+            ptrs.append(q.data_ptr() if on_dev else q.ctypes.data)
+        ptrs += [None] * (4 - len(ptrs))
+        fl = self._flags(is_log1p, use_continuity, tie_correct) | ((FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0)
+        ptr = (lambda a: a.data_ptr()) if on_dev else (lambda a: a.ctypes.data)
+        self._bind_torch_stream(H, flags, sums, *planes)
+        self._check(self.lib.illico_pairwise_from_hists(self.h, ptr(H), ptr(flags), counts.ctypes.data, G, W, sel_ptr, K, sums_ptr, sums_ld, fl, alt,
+                                                        *ptrs, max(W, 1)))
+        return planes
 
     def csr_indices_sorted(self, indices, indptr, n_rows) -> bool:
         i, p = _Buf(indices), _Buf(indptr)

@@ -8,7 +8,8 @@ const char *const kKernelNames[KID_COUNT] = {"k_transpose_permute", "k_ovo_rank"
                                               "k_adj_validate", "k_adj_sort_lds", "k_adj_merge", "k_adj_scan", "k_adj_bonferroni",
                                               "k_gs_vmax", "k_gs_dense", "k_gs_csc", "k_gs_csr", "k_gs_totals", "k_gs_finalize",
                                               "k_finalize_z", "k_top_validate", "k_top_sort", "k_top_merge", "k_top_scan",
-                                              "k_gm_vmax", "k_gm_dense", "k_gm_csc", "k_gm_csr", "k_gm_totals", "k_gm_finalize", "k_ttest"};
+                                              "k_gm_vmax", "k_gm_dense", "k_gm_csc", "k_gm_csr", "k_gm_totals", "k_gm_finalize", "k_ttest",
+                                              "k_pw_hists_dense", "k_pw_hists_csc", "k_pw_hists_csr", "k_pw_hists_finish", "k_pw_pairs"};
 
 // The message of a failed call is kept per calling thread (and in the context, for single-threaded callers): a second
 // thread's failure must not replace the text the first is about to read through illico_last_error.

@@ -84,6 +84,11 @@ enum {
     KID_GM_TOTALS,
     KID_GM_FINALIZE,
     KID_TTEST, // illico_ttest_from_moments / illico_student_t_pvalues (kernels_ttest.h)
+    KID_PW_HIST_DENSE, // illico_group_value_hists_* (kernels_pairwise.h)
+    KID_PW_HIST_CSC,
+    KID_PW_HIST_CSR,
+    KID_PW_HIST_FINISH,
+    KID_PW_PAIRS, // illico_pairwise_from_hists
     KID_COUNT
 };
 extern const char *const kKernelNames[KID_COUNT];

@@ -1,0 +1,319 @@
+// illico_group_value_hists_{dense,csc,csr}: per-(group, gene) histograms of the values 0 .. 255 from one pass over the matrix;
+// illico_pairwise_from_hists: the Wilcoxon rank-sum test of every ordered pair of groups from those histograms (kernels_pairwise.h).
+// A translation unit of its own: siblings of the one-versus-reference routes, which it does not touch.
+#include "engine.h"
+#include "kernels_pairwise.h"
+
+namespace {
+
+struct PwInput {
+    bool sparse = false, is_csr = false, on_dev = false;
+    const void *X = nullptr; // dense
+    int64_t ld = 0;
+    const void *data = nullptr, *indices = nullptr, *indptr = nullptr; // sparse
+    int idx_dtype = 0;
+    int dtype = 0;
+    int64_t n_rows = 0, n_cols = 0;
+};
+
+int pw_check(illico_ctx *c, const PwInput &in, int64_t col_lb, int64_t col_ub, const uint32_t *H, const uint32_t *fl) {
+    if (!c->has_groups) return fail(c, ILLICO_ERR_NO_GROUPS, "illico_set_groups has not been called");
+    if (in.n_rows != c->n_cells)
+        return fail(c, ILLICO_ERR_NO_GROUPS, "X has %lld rows but the groups describe %lld cells", (long long)in.n_rows, (long long)c->n_cells);
+    if (col_lb < 0 || col_ub > in.n_cols || col_lb > col_ub)
+        return fail(c, ILLICO_ERR_BOUNDS, "Invalid chunk bounds: (%lld, %lld) for data with %lld columns.", (long long)col_lb, (long long)col_ub, (long long)in.n_cols);
+    if (in.dtype < 0 || in.dtype > 3) return fail(c, ILLICO_ERR_DTYPE, "unsupported dtype code %d", in.dtype);
+    if (in.sparse && in.idx_dtype != ILLICO_IDX_I32 && in.idx_dtype != ILLICO_IDX_I64)
+        return fail(c, ILLICO_ERR_DTYPE, "unsupported index dtype code %d", in.idx_dtype);
+    if (col_ub > col_lb && (!H || !fl)) return fail(c, ILLICO_ERR_ARG, "null out_H / out_flags");
+    return ILLICO_OK;
+}
+
+template <typename InT>
+int pw_dense(illico_ctx *c, const void *X, int64_t ld, int64_t col0, int wn, int tiles, u32 *T, u32 *d_flags) {
+    FusedParams P{};
+    P.X = X; P.ld = ld; P.col0 = col0; P.ncols = wn;
+    P.perm = c->d_perm; P.pos_ptr = c->d_posptr; P.counts = c->d_counts;
+    P.G = (int)c->n_groups; P.ref = -1; P.n_cells = c->n_cells;
+    P.gene_flags = d_flags;
+    constexpr int NWH = GH_NT / 64;
+    // positions per wavefront: ~2048 workgroups, at most 4096 positions (16-bit cells in LDS)
+    const int wave_rows = (int)std::min<int64_t>(4096, std::max<int64_t>(256, (c->n_cells * tiles / (2048 * NWH) + 31) & ~31ll));
+    const int64_t chunks = (c->n_cells + (int64_t)NWH * wave_rows - 1) / ((int64_t)NWH * wave_rows);
+    if (chunks > 65535) return fail(c, ILLICO_ERR_UNSUPPORTED, "%lld cells are more row stretches than one launch holds", (long long)c->n_cells);
+    ProfScope ps(c, KID_PW_HIST_DENSE);
+    hipLaunchKernelGGL((k_group_value_hists<InT, PW_RT>), dim3(tiles, (unsigned)chunks), dim3(GH_NT), 0, c->stream, P, T, wave_rows);
+    HIPCHK(c, hipGetLastError());
+    return ILLICO_OK;
+}
+
+template <typename InT, typename IdxT>
+int pw_sparse(illico_ctx *c, bool is_csr, const void *data, const void *indices, const void *indptr, long long kshift, long long col0, int wn, u32 *H,
+              u32 *d_flags) {
+    const int G = (int)c->n_groups;
+    const long long N = c->n_cells;
+    if (!is_csr) {
+        const int gw = std::min(G, 128);
+        const size_t lds = (size_t)gw * PW_RT * 4;
+        HIPCHK(c, hipFuncSetAttribute((const void *)k_pw_hists_csc<InT, IdxT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ProfScope ps(c, KID_PW_HIST_CSC);
+        hipLaunchKernelGGL((k_pw_hists_csc<InT, IdxT>), dim3((unsigned)std::min(wn, 1 << 20)), dim3(PW_NT), lds, c->stream, (const InT *)data,
+                           (const IdxT *)indices, (const IdxT *)indptr, kshift, col0, c->d_codes, c->d_counts, N, G, wn, gw, H, d_flags);
+        HIPCHK(c, hipGetLastError());
+        return ILLICO_OK;
+    }
+    HIPCHK(c, hipMemsetAsync(H, 0, (size_t)G * wn * PW_RT * 4, c->stream));
+    {
+        ProfScope ps(c, KID_PW_HIST_CSR);
+        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((N + 3) / 4, 1 << 16));
+        hipLaunchKernelGGL((k_pw_hists_csr<InT, IdxT>), dim3(gx), dim3(PW_NT), 0, c->stream, (const InT *)data, (const IdxT *)indices, (const IdxT *)indptr,
+                           kshift, col0, c->d_codes, N, G, wn, H, d_flags);
+        HIPCHK(c, hipGetLastError());
+    }
+    {
+        ProfScope ps(c, KID_PW_HIST_FINISH);
+        const long long rows = (long long)G * wn;
+        hipLaunchKernelGGL(k_pw_hists_bin0, dim3((unsigned)std::max<long long>(1, std::min<long long>((rows + 3) / 4, 1 << 16))), dim3(PW_NT), 0, c->stream, H,
+                           c->d_counts, rows, wn);
+        HIPCHK(c, hipGetLastError());
+    }
+    return ILLICO_OK;
+}
+
+template <typename InT>
+int pw_sparse_any_idx(illico_ctx *c, bool is_csr, int idx_dtype, const void *data, const void *indices, const void *indptr, long long kshift, long long col0,
+                      int wn, u32 *H, u32 *d_flags) {
+    if (idx_dtype == ILLICO_IDX_I32) return pw_sparse<InT, int32_t>(c, is_csr, data, indices, indptr, kshift, col0, wn, H, d_flags);
+    return pw_sparse<InT, int64_t>(c, is_csr, data, indices, indptr, kshift, col0, wn, H, d_flags);
+}
+
+int64_t pw_idx_at(const void *p, int idx_dtype, int64_t i) { return idx_dtype == ILLICO_IDX_I32 ? (int64_t)((const int32_t *)p)[i] : ((const int64_t *)p)[i]; }
+
+int pw_budget(illico_ctx *c, size_t need, const char *what) {
+    if (need > (size_t)std::max<int64_t>(c->scratch_bytes, 1))
+        return fail(c, ILLICO_ERR_OOM, "%s needs %zu bytes of device scratch, the budget (\"scratch_bytes\") is %lld: pass a narrower gene window", what, need,
+                    (long long)c->scratch_bytes);
+    return ILLICO_OK;
+}
+
+int pw_hists_run(illico_ctx *c, const PwInput &in, int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags) {
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = resolve_pending(c);
+    if (rc) return rc;
+    const int64_t W = col_ub - col_lb, G = c->n_groups, N = in.n_rows;
+    if (W == 0) return ILLICO_OK;
+    if (W > (int64_t)1 << 21) return fail(c, ILLICO_ERR_OOM, "a window of %lld genes: pass narrower gene windows", (long long)W);
+    if (G > 65535) return fail(c, ILLICO_ERR_UNSUPPORTED, "%lld groups: the histogram passes take up to 65535", (long long)G);
+    const bool out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
+    const int dt = in.dtype, wn = (int)W, tiles = (wn + 63) / 64;
+    const size_t esz = dtype_size(dt), isz = in.idx_dtype == ILLICO_IDX_I32 ? 4 : 8;
+    const size_t h_bytes = (size_t)G * W * PW_RT * 4, t_bytes = in.sparse ? 0 : (size_t)G * tiles * PW_TILE_WORDS * 4;
+    const size_t x_bytes = (!in.sparse && !in.on_dev) ? (size_t)N * W * esz : 0;
+    if ((rc = pw_budget(c, (out_dev ? 0 : h_bytes + (size_t)W * 4) + t_bytes + x_bytes, "illico_group_value_hists"))) return rc;
+    if (!in.sparse && (uint64_t)in.ld * esz > 0xFFFFFFFFull) return fail(c, ILLICO_ERR_UNSUPPORTED, "a row pitch of 4 GiB or more");
+    void *v = nullptr;
+    u32 *d_H = out_H, *d_flags = out_flags;
+    if (!out_dev) {
+        if ((rc = get_scratch(c, "pw_hist_out", h_bytes + (size_t)W * 4, &v))) return rc;
+        d_H = (u32 *)v;
+        d_flags = d_H + (size_t)G * W * PW_RT;
+    }
+    HIPCHK(c, hipMemsetAsync(d_flags, 0, (size_t)W * 4, c->stream));
+    if (!in.sparse) {
+        if ((rc = get_scratch(c, "pw_tiled", t_bytes, &v))) return rc;
+        u32 *T = (u32 *)v;
+        HIPCHK(c, hipMemsetAsync(T, 0, t_bytes, c->stream));
+        const void *X = in.X;
+        int64_t ld = in.ld, col0 = col_lb;
+        if (!in.on_dev) {
+            if ((rc = get_scratch(c, "pw_xwin", x_bytes, &v))) return rc;
+            HIPCHK(c, hipMemcpy2DAsync(v, (size_t)W * esz, (const unsigned char *)in.X + (size_t)col_lb * esz, (size_t)in.ld * esz, (size_t)W * esz, (size_t)N,
+                                       hipMemcpyHostToDevice, c->stream));
+            c->h2d_input_bytes += (int64_t)x_bytes;
+            X = v; ld = W; col0 = 0;
+        }
+        switch (dt) {
+        case ILLICO_F32: rc = pw_dense<float>(c, X, ld, col0, wn, tiles, T, d_flags); break;
+        case ILLICO_F64: rc = pw_dense<double>(c, X, ld, col0, wn, tiles, T, d_flags); break;
+        case ILLICO_I32: rc = pw_dense<int32_t>(c, X, ld, col0, wn, tiles, T, d_flags); break;
+        default: rc = pw_dense<int64_t>(c, X, ld, col0, wn, tiles, T, d_flags); break;
+        }
+        if (rc) return rc;
+        ProfScope ps(c, KID_PW_HIST_FINISH);
+        hipLaunchKernelGGL(k_pw_transpose<true>, dim3(tiles, (unsigned)G), dim3(PW_NT), 0, c->stream, d_H, T, (const int *)nullptr, wn, tiles);
+        HIPCHK(c, hipGetLastError());
+    } else {
+        // host-resident sparse input goes up once: CSC the entries of [col_lb, col_ub), CSR every row
+        const void *data = in.data, *indices = in.indices, *indptr = in.indptr;
+        long long kshift = 0, ptr_col0 = 0; // entry k at data[k - kshift]; the window's first column is indptr[col - ptr_col0]
+        if (!in.on_dev) {
+            const int64_t a = in.is_csr ? 0 : col_lb, b = in.is_csr ? N : col_ub;
+            const int64_t k0 = pw_idx_at(in.indptr, in.idx_dtype, a), k1 = pw_idx_at(in.indptr, in.idx_dtype, b);
+            if (k0 < 0 || k1 < k0) return fail(c, ILLICO_ERR_ARG, "indptr is not non-decreasing");
+            const size_t nnz = (size_t)(k1 - k0), nptr = (size_t)(b - a + 1);
+            if ((rc = get_scratch(c, "pw_upload", std::max<size_t>(nnz, 1) * (esz + isz) + nptr * isz + 64, &v))) return rc;
+            unsigned char *u = (unsigned char *)v;
+            void *dd = u, *di = u + ((nnz * esz + 15) & ~(size_t)15), *dp = (unsigned char *)di + ((nnz * isz + 15) & ~(size_t)15);
+            HIPCHK(c, hipMemcpyAsync(dd, (const unsigned char *)in.data + (size_t)k0 * esz, nnz * esz, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(di, (const unsigned char *)in.indices + (size_t)k0 * isz, nnz * isz, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(dp, (const unsigned char *)in.indptr + (size_t)a * isz, nptr * isz, hipMemcpyHostToDevice, c->stream));
+            c->h2d_input_bytes += (int64_t)(nnz * (esz + isz) + nptr * isz);
+            HIPCHK(c, hipStreamSynchronize(c->stream)); // (the arrays came from pageable host memory)
+            data = dd; indices = di; indptr = dp;
+            kshift = k0;
+            ptr_col0 = a;
+        }
+        // CSC: indptr is indexed by column (shifted by what was uploaded); CSR: by row, and col0 is the window's first column
+        const long long col0 = in.is_csr ? col_lb : col_lb - ptr_col0;
+        switch (dt) {
+        case ILLICO_F32: rc = pw_sparse_any_idx<float>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, wn, d_H, d_flags); break;
+        case ILLICO_F64: rc = pw_sparse_any_idx<double>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, wn, d_H, d_flags); break;
+        case ILLICO_I32: rc = pw_sparse_any_idx<int32_t>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, wn, d_H, d_flags); break;
+        default: rc = pw_sparse_any_idx<int64_t>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, wn, d_H, d_flags); break;
+        }
+        if (rc) return rc;
+    }
+    if (!out_dev) {
+        HIPCHK(c, hipMemcpyAsync(out_H, d_H, h_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out_flags, d_flags, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return ILLICO_OK;
+}
+
+int pw_hists_sparse(illico_ctx *c, bool is_csr, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
+                    int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags) {
+    if (!c) return ILLICO_ERR_ARG;
+    CTX_LOCK(c);
+    PwInput in;
+    in.sparse = true; in.is_csr = is_csr; in.data = data; in.indices = indices; in.indptr = indptr; in.idx_dtype = idx_dtype; in.dtype = dtype;
+    in.n_rows = n_rows; in.n_cols = n_cols; in.on_dev = flags & ILLICO_FLAG_INPUT_DEVICE;
+    int rc = pw_check(c, in, col_lb, col_ub, out_H, out_flags);
+    if (rc) return rc;
+    if (!data || !indices || !indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
+    return pw_hists_run(c, in, col_lb, col_ub, flags, out_H, out_flags);
+}
+
+} // namespace
+
+extern "C" int illico_group_value_hists_dense(illico_ctx *c, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t col_lb,
+                                              int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags) {
+    if (!c) return ILLICO_ERR_ARG;
+    CTX_LOCK(c);
+    PwInput in;
+    in.X = X; in.dtype = dtype; in.n_rows = n_rows; in.n_cols = n_cols; in.ld = ld; in.on_dev = flags & ILLICO_FLAG_INPUT_DEVICE;
+    int rc = pw_check(c, in, col_lb, col_ub, out_H, out_flags);
+    if (rc) return rc;
+    if (!X) return fail(c, ILLICO_ERR_ARG, "null X");
+    if (ld < n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
+    return pw_hists_run(c, in, col_lb, col_ub, flags, out_H, out_flags);
+}
+extern "C" int illico_group_value_hists_csc(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
+                                            int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags) {
+    return pw_hists_sparse(c, false, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, out_H, out_flags);
+}
+extern "C" int illico_group_value_hists_csr(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
+                                            int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags) {
+    return pw_hists_sparse(c, true, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, out_H, out_flags);
+}
+
+extern "C" int illico_pairwise_from_hists(illico_ctx *c, const uint32_t *H, const uint32_t *gene_flags, const int64_t *counts, int64_t n_groups, int64_t n_cols,
+                                          const int64_t *sel, int64_t n_sel, const double *sums, int64_t sums_ld, int flags, int alternative, double *out_p,
+                                          double *out_u, double *out_fc, double *out_z, int64_t out_ld) {
+    if (!c) return ILLICO_ERR_ARG;
+    CTX_LOCK(c);
+    if (alternative != ILLICO_ALT_TWO_SIDED && alternative != ILLICO_ALT_LESS && alternative != ILLICO_ALT_GREATER)
+        return fail(c, ILLICO_ERR_ALTERNATIVE, "Unsupported alternative hypothesis code: %d", alternative);
+    if (!counts || n_groups <= 0 || n_groups > 0x7FFFFFFF) return fail(c, ILLICO_ERR_ARG, "null counts or bad n_groups");
+    const int64_t G = n_groups, W = n_cols, K = sel ? n_sel : G;
+    if (K < 2) return fail(c, ILLICO_ERR_ARG, "%lld groups selected: a pair needs two", (long long)K);
+    if (K > 46340) return fail(c, ILLICO_ERR_ARG, "%lld groups selected: more pairs than a launch holds", (long long)K);
+    std::vector<int> h_sel((size_t)K);
+    std::vector<long long> h_n((size_t)K);
+    {
+        std::vector<char> seen((size_t)G, 0);
+        for (int64_t k = 0; k < K; ++k) {
+            const int64_t g = sel ? sel[k] : k;
+            if (g < 0 || g >= G) return fail(c, ILLICO_ERR_ARG, "sel[%lld] = %lld is no group id (0 .. %lld)", (long long)k, (long long)g, (long long)G - 1);
+            if (seen[g]) return fail(c, ILLICO_ERR_ARG, "group %lld is selected twice", (long long)g);
+            seen[g] = 1;
+            if (counts[g] < 0) return fail(c, ILLICO_ERR_ARG, "counts[%lld] is negative", (long long)g);
+            h_sel[k] = (int)g;
+            h_n[k] = counts[g];
+        }
+    }
+    {   // the two largest selected groups: their pair is the largest test
+        long long a = 0, b = 0;
+        for (long long n : h_n) { if (n > a) { b = a; a = n; } else if (n > b) b = n; }
+        if (a + b >= 2097152ll)
+            return fail(c, ILLICO_ERR_UNSUPPORTED, "%lld cells in one pair: the integer rank and tie sums hold below 2097152 cells per test", a + b);
+    }
+    if (W < 0 || out_ld < W) return fail(c, ILLICO_ERR_ARG, "out_ld smaller than n_cols (or n_cols negative)");
+    if (sums && sums_ld < W) return fail(c, ILLICO_ERR_ARG, "sums_ld smaller than n_cols");
+    if (W == 0) return ILLICO_OK;
+    if (!H || !gene_flags || !out_p || !out_u || !out_fc) return fail(c, ILLICO_ERR_ARG, "null H, gene_flags or output plane");
+    if (W > (int64_t)1 << 21) return fail(c, ILLICO_ERR_OOM, "a window of %lld genes: pass narrower gene windows", (long long)W);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = resolve_pending(c);
+    if (rc) return rc;
+    const bool in_dev = flags & ILLICO_FLAG_INPUT_DEVICE, out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
+    const int wn = (int)W, tiles = (wn + 63) / 64, n_out = out_z ? 4 : 3;
+    const size_t t_bytes = (size_t)K * tiles * PW_TILE_WORDS * 4, h_bytes = (size_t)G * W * PW_RT * 4, s_bytes = sums ? (size_t)G * W * 8 : 0;
+    const size_t plane = (size_t)K * K * W * 8;
+    if ((rc = pw_budget(c, t_bytes + (in_dev ? 0 : h_bytes + (size_t)W * 4 + s_bytes) + (out_dev ? 0 : plane * n_out), "illico_pairwise_from_hists"))) return rc;
+    void *v = nullptr;
+    if ((rc = get_scratch(c, "pw_pairs", t_bytes + (size_t)K * 16 + 64, &v))) return rc;
+    u32 *T = (u32 *)v;
+    long long *d_n = (long long *)((unsigned char *)v + t_bytes);
+    int *d_sel = (int *)(d_n + K);
+    HIPCHK(c, hipMemcpyAsync(d_n, h_n.data(), (size_t)K * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_sel, h_sel.data(), (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+    const u32 *d_H = H, *d_flags = gene_flags;
+    const double *d_sums = sums;
+    int64_t d_sums_ld = sums_ld;
+    if (!in_dev) {
+        if ((rc = get_scratch(c, "pw_stage_in", h_bytes + (size_t)W * 4 + s_bytes + 64, &v))) return rc;
+        unsigned char *u = (unsigned char *)v;
+        if (sums) {
+            HIPCHK(c, hipMemcpy2DAsync(u, (size_t)W * 8, sums, (size_t)sums_ld * 8, (size_t)W * 8, (size_t)G, hipMemcpyHostToDevice, c->stream));
+            d_sums = (const double *)u; d_sums_ld = W;
+            u += s_bytes;
+        }
+        HIPCHK(c, hipMemcpyAsync(u, H, h_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(u + h_bytes, gene_flags, (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
+        d_H = (const u32 *)u; d_flags = (const u32 *)(u + h_bytes);
+    }
+    double *outs[4] = {out_p, out_u, out_fc, out_z}, *d_out[4] = {out_p, out_u, out_fc, out_z};
+    int64_t d_out_ld = out_ld;
+    if (!out_dev) { // the caller's planes go up first: the columns of flagged genes come back as they were
+        if ((rc = get_scratch(c, "pw_stage_out", plane * n_out + 64, &v))) return rc;
+        for (int k = 0; k < n_out; ++k) {
+            d_out[k] = (double *)v + (size_t)k * K * K * W;
+            HIPCHK(c, hipMemcpy2DAsync(d_out[k], (size_t)W * 8, outs[k], (size_t)out_ld * 8, (size_t)W * 8, (size_t)(K * K), hipMemcpyHostToDevice, c->stream));
+        }
+        d_out_ld = W;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (h_n / h_sel and the staged arrays came from pageable host memory)
+    PwParams P;
+    P.T = T; P.gene_flags = d_flags; P.n = d_n; P.sel = d_sel; P.sums = d_sums; P.sums_ld = d_sums_ld;
+    P.K = (int)K; P.W = wn; P.tiles = tiles; P.nrb = ((int)K + PW_RB - 1) / PW_RB;
+    P.use_continuity = (flags & ILLICO_FLAG_CONTINUITY) ? 1 : 0;
+    P.tie_correct = (flags & ILLICO_FLAG_TIE_CORRECT) ? 1 : 0;
+    P.alternative = alternative;
+    P.out_p = d_out[0]; P.out_u = d_out[1]; P.out_fc = d_out[2]; P.out_z = d_out[3]; P.out_ld = d_out_ld;
+    {
+        ProfScope ps(c, KID_PW_PAIRS);
+        hipLaunchKernelGGL(k_pw_transpose<false>, dim3(tiles, (unsigned)K), dim3(PW_NT), 0, c->stream, const_cast<u32 *>(d_H), T, (const int *)d_sel, wn, tiles);
+        HIPCHK(c, hipGetLastError());
+        const dim3 grid((unsigned)((K * P.nrb + PW_NT / 64 - 1) / (PW_NT / 64)), (unsigned)tiles);
+        if (out_z) hipLaunchKernelGGL(k_pw_pairs<true>, grid, dim3(PW_NT), 0, c->stream, P);
+        else hipLaunchKernelGGL(k_pw_pairs<false>, grid, dim3(PW_NT), 0, c->stream, P);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (!out_dev) {
+        for (int k = 0; k < n_out; ++k)
+            HIPCHK(c, hipMemcpy2DAsync(outs[k], (size_t)out_ld * 8, d_out[k], (size_t)W * 8, (size_t)W * 8, (size_t)(K * K), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return ILLICO_OK;
+}

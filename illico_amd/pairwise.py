@@ -1,0 +1,238 @@
+"""All-pairs Wilcoxon rank-sum tests: every group against every other group, from one pass over the matrix.
+
+``pairwise_wilcoxon`` answers the marker-gene question of a clustering ("which genes separate cluster A from B, from C, ...") and of a
+perturbation screen that compares perturbations with each other.  Row ``(g, r, gene)`` of its frame is row ``(g, gene)`` of
+``asymptotic_wilcoxon(..., reference=r)``.
+
+For count-valued genes (integers 0 .. 255) the statistics of a test are functions of the two groups' value histograms alone: the
+histograms of all groups are formed on the device in one read of the matrix (include/illico_hip.h: illico_group_value_hists_*), and
+every ordered pair follows from them (illico_pairwise_from_hists).  Genes with other values (continuous, negative, beyond 255) are
+gathered once and completed by one one-versus-reference engine call per reference: a log-normalised matrix takes that path whole and
+costs K such calls.
+"""
+from __future__ import annotations
+
+import numpy as np
+import pandas as pd
+
+from illico_amd.utils.groups import encode_and_count_groups
+
+__all__ = ["pairwise_wilcoxon"]
+
+ALTERNATIVES = ("two-sided", "less", "greater")
+#: device bytes one gene window of the pair route may take (histograms in both layouts and the result planes); a window the engine's
+#: scratch budget refuses is halved
+PAIR_WINDOW_BYTES = 2 << 30
+
+
+def _check_arguments(is_log1p, alternative, use_continuity, tie_correct, scores, corr_method, max_result_bytes):
+    if not isinstance(is_log1p, (bool, np.bool_)):
+        raise ValueError(f"is_log1p must be a bool, got {is_log1p!r}")
+    if not isinstance(alternative, str) or alternative not in ALTERNATIVES:
+        raise ValueError(f"Unsupported alternative hypothesis: {alternative}")
+    for name, v in (("use_continuity", use_continuity), ("tie_correct", tie_correct), ("scores", scores)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be a bool, got {v!r}")
+    if isinstance(max_result_bytes, bool) or not isinstance(max_result_bytes, (int, np.integer)) or max_result_bytes < 0:
+        raise ValueError(f"max_result_bytes must be a non-negative integer, got {max_result_bytes!r}")
+    if corr_method is None:
+        return None
+    from illico_amd.adjust import _method
+    return _method(corr_method)
+
+
+def _select(unique_groups: np.ndarray, groups) -> np.ndarray:
+    """The selected group ids, ascending: all of them, or those of the labels in ``groups``."""
+    G = int(len(unique_groups))
+    if groups is None:
+        sel = np.arange(G, dtype=np.int64)
+    else:
+        if isinstance(groups, (str, bytes)):
+            raise ValueError(f"groups must be a sequence of labels, got the single label {groups!r}")
+        labels = [str(x) for x in groups]
+        known = {str(x): k for k, x in enumerate(unique_groups)}
+        unknown = [x for x in labels if x not in known]
+        if unknown:
+            raise ValueError(f"groups names labels that are not present: {unknown}")
+        if len(set(labels)) != len(labels):
+            raise ValueError(f"groups names a label twice: {labels}")
+        sel = np.array(sorted(known[x] for x in labels), dtype=np.int64)
+    if sel.size < 2:
+        raise ValueError(f"pairwise tests need at least two groups, got {sel.size}")
+    return sel
+
+
+def _pair_index(labels: np.ndarray, features: np.ndarray, r_idx: np.ndarray, g_idx: np.ndarray) -> pd.MultiIndex:
+    """(pert, reference, feature) for the pairs (g_idx[k], r_idx[k]) in order, each over all features."""
+    names = ["pert", "reference", "feature"]
+    li, fi = pd.Index(pd.Series(labels, dtype=str)), pd.Index(pd.Series(features, dtype=str))
+    M, P = len(fi), len(r_idx)
+    if li.is_unique and fi.is_unique and not li.hasnans and not fi.hasnans and M:
+        ll, lf = li.sort_values(), fi.sort_values()
+        lcode, fcode = ll.get_indexer(li), lf.get_indexer(fi)
+        return pd.MultiIndex(levels=[ll, ll, lf], codes=[np.repeat(lcode[g_idx], M), np.repeat(lcode[r_idx], M), np.tile(fcode, P)],
+                             names=names, verify_integrity=False)
+    return pd.MultiIndex.from_arrays([np.repeat(np.asarray(li)[g_idx], M), np.repeat(np.asarray(li)[r_idx], M), np.tile(np.asarray(fi), P)],
+                                     names=names)
+
+
+def _gather_columns(src, cols: np.ndarray):
+    """The columns ``cols`` of one fetched container, in a form the one-versus-reference engine calls take: a dense matrix stays dense
+    (numpy, or a CUDA tensor), a sparse one becomes a scipy CSC matrix."""
+    from illico_amd._lib import _is_torch_tensor
+    if _is_torch_tensor(src):
+        import torch
+        return src[:, torch.as_tensor(cols, device=src.device)].contiguous()
+    if hasattr(src, "indptr"):
+        from scipy import sparse
+        return sparse.csc_matrix(src[:, cols])
+    return np.ascontiguousarray(np.asarray(src)[:, cols])
+
+
+def _hstack(parts):
+    from illico_amd._lib import _is_torch_tensor
+    if len(parts) == 1:
+        return parts[0]
+    if _is_torch_tensor(parts[0]):
+        import torch
+        return torch.cat(parts, dim=1)
+    if hasattr(parts[0], "indptr"):
+        from scipy import sparse
+        return sparse.hstack(parts, format="csc")
+    return np.ascontiguousarray(np.concatenate(parts, axis=1))
+
+
+def _windows(lb: int, ub: int, w: int):
+    return [(a, min(ub, a + w)) for a in range(lb, ub, w)]
+
+
+def pairwise_planes(X, handler, group_container, sel: np.ndarray, is_log1p: bool, alternative: str, use_continuity: bool, tie_correct: bool,
+                    scores: bool):
+    """(planes float64 [3 or 4, K, K, n_genes] indexed [plane, r, g, gene], number of flagged genes) for the groups ``sel``."""
+    import torch
+    from illico_amd import _lib
+    from illico_amd.group_stats import _chunks
+    from illico_amd.ttest import device_handler
+    eng = _lib.get_engine()
+    dev = torch.device("cuda", eng.device)
+    src_handler = handler
+    handler = device_handler(X, handler)  # an in-RAM CSR matrix goes up once
+    counts = np.asarray(group_container.counts, dtype=np.int64)
+    G, M, K = int(counts.size), int(X.shape[1]), int(sel.size)
+    n_planes = 4 if scores else 3
+    ovr_groups = group_container._replace(encoded_ref_group=-1)  # the histogram pass uses codes, counts and order only
+    eng.set_groups(ovr_groups)
+    planes = np.empty((n_planes, K, K, M), dtype=np.float64)
+    per_gene = 2 * G * 1024 + K * 1024 + n_planes * K * K * 8 + (G * 8 if is_log1p else 0) + 4
+    width = max(64, (PAIR_WINDOW_BYTES // per_gene) // 64 * 64)
+    flagged_cols, flagged_parts = [], []
+    for lb, ub in _chunks(X, handler):
+        fetched, (a, b) = handler.fetch(lb, ub)
+        Xc = handler.to_nb(fetched)
+        sparse_in = hasattr(Xc, "indptr")
+        fmt = ("csr" if handler.fmt.name == "CSR" else "csc") if sparse_in else None
+        todo = _windows(0, ub - lb, width)
+        chunk_flagged = []
+        while todo:
+            o0, o1 = todo.pop(0)
+            w = o1 - o0
+            try:
+                H = torch.empty((G, w, eng.HIST_VALUES), dtype=torch.int32, device=dev)
+                fl = torch.empty((w,), dtype=torch.int32, device=dev)
+                sums = torch.empty((G, w), dtype=torch.float64, device=dev) if is_log1p else None
+                if sparse_in:
+                    eng.group_value_hists_sparse(fmt, Xc.data, Xc.indices, Xc.indptr, Xc.shape, a + o0, a + o1, out=(H, fl))
+                    if is_log1p:
+                        eng.group_stats_sparse(fmt, Xc.data, Xc.indices, Xc.indptr, Xc.shape, a + o0, a + o1, is_log1p=True, out=(None, sums))
+                else:
+                    eng.group_value_hists(Xc, a + o0, a + o1, out=(H, fl))
+                    if is_log1p:
+                        eng.group_stats(Xc, a + o0, a + o1, is_log1p=True, out=(None, sums))
+                got = eng.pairwise_from_hists(H, fl, counts=counts, sel=sel, sums=sums, is_log1p=is_log1p, use_continuity=use_continuity,
+                                              tie_correct=tie_correct, alternative=alternative, scores=scores)
+            except (MemoryError, torch.cuda.OutOfMemoryError):
+                if w <= 64:
+                    raise
+                half = max(64, (w // 2 + 63) // 64 * 64)
+                todo = _windows(o0, o1, half) + todo
+                H = fl = sums = None
+                continue
+            for k in range(n_planes):
+                planes[k][:, :, lb + o0:lb + o1] = got[k].cpu().numpy()
+            chunk_flagged.append(o0 + np.flatnonzero(fl.cpu().numpy()))
+        chunk_flagged = np.concatenate(chunk_flagged) if chunk_flagged else np.empty(0, dtype=np.int64)
+        if chunk_flagged.size:
+            # gathered from the container as the caller gave it (the device copy of an in-RAM CSR matrix is not sliced by columns)
+            src, off = (fetched, a) if getattr(handler, "streams", False) else (src_handler.data, lb)
+            flagged_parts.append(_gather_columns(src, off + chunk_flagged))
+            flagged_cols.append(lb + chunk_flagged)
+    n_flagged = int(sum(c.size for c in flagged_cols))
+    if n_flagged:
+        # what a user does by hand today: one one-versus-reference call per reference, here on the flagged genes alone
+        cols = np.concatenate(flagged_cols)
+        Xf = _hstack(flagged_parts)
+        sparse_f = hasattr(Xf, "indptr")
+        for ri, r in enumerate(sel):
+            eng.set_groups(group_container._replace(encoded_ref_group=int(r)))
+            kw = dict(is_log1p=is_log1p, use_continuity=use_continuity, tie_correct=tie_correct, alternative=alternative, scores=scores)
+            if sparse_f:
+                got = eng.run_sparse("csc", Xf.data, Xf.indices, Xf.indptr, Xf.shape, 0, n_flagged, **kw)
+            else:
+                got = eng.run_dense(Xf, 0, n_flagged, **kw)
+            for k in range(n_planes):
+                q = got[k].cpu().numpy() if hasattr(got[k], "cpu") else got[k]
+                planes[k][ri][:, cols] = q[sel]
+    return planes, n_flagged
+
+
+def pairwise_wilcoxon(adata, is_log1p: bool, group_keys: str, *, groups=None, alternative: str = "two-sided", use_continuity: bool = True,
+                      tie_correct: bool = True, layer: str | None = None, scores: bool = False, corr_method: str | None = None,
+                      max_result_bytes: int = 8 << 30) -> pd.DataFrame:
+    """Asymptotic Wilcoxon rank-sum tests of every group against every other group, on one MI355X.
+
+    ``adata``, ``is_log1p``, ``group_keys``, ``alternative``, ``use_continuity``, ``tie_correct`` and ``layer`` as in
+    ``asymptotic_wilcoxon``; every container it accepts is accepted, backed containers are streamed chunk by chunk, an in-RAM CSR
+    matrix is uploaded once.  ``groups``: a sequence of labels that restricts both sides of the comparison (default: all groups);
+    whatever its order, groups appear in the order ``asymptotic_wilcoxon`` gives them.
+
+    Returns a DataFrame with MultiIndex ``(pert, reference, feature)`` -- reference-major, then pert, then gene; a group is not
+    compared with itself -- and float64 columns ``p_value``, ``statistic`` and ``fold_change``; ``z_score`` with ``scores=True``;
+    ``p_value_adj`` with ``corr_method`` (``"benjamini-hochberg"`` / ``"bh"``, ``"benjamini-yekutieli"`` / ``"by"``,
+    ``"bonferroni"``): each (pert, reference) pair adjusted across its genes.  Row ``(g, r, gene)`` is row ``(g, gene)`` of
+    ``asymptotic_wilcoxon(..., reference=r)``.  ``df.attrs["n_flagged_genes"]``: the genes that hold a value which is no integer in
+    [0, 255] -- they are completed by one one-versus-reference engine call per reference.
+
+    ``ValueError``: a label of ``groups`` that is not present or named twice, fewer than two groups, a bad ``alternative``, a
+    non-bool ``is_log1p``, and a result of more than ``max_result_bytes`` bytes (K (K - 1) x genes x 8 bytes x columns), raised before
+    any device work.  ``NotImplementedError``: two selected groups of 2097152 cells or more together."""
+    code = _check_arguments(is_log1p, alternative, use_continuity, tie_correct, scores, corr_method, max_result_bytes)
+    from illico_amd.group_stats import _input
+    X = _input(adata, layer)
+    unique_raw_groups, group_container = encode_and_count_groups(groups=adata.obs[group_keys], ref_group=None)
+    sel = _select(np.asarray(unique_raw_groups), groups)
+    K, M = int(sel.size), int(X.shape[1])
+    n_cols = 3 + int(bool(scores)) + int(code is not None)
+    need = K * (K - 1) * M * 8 * n_cols
+    if need > max_result_bytes:
+        raise ValueError(f"the result of {K} x {K - 1} pairs over {M} genes with {n_cols} columns takes {need} bytes, more than "
+                         f"max_result_bytes = {int(max_result_bytes)}: restrict `groups`, or raise max_result_bytes")
+    from illico_amd.utils.registry import data_handler_registry
+    handler = data_handler_registry.get(X)
+    planes, n_flagged = pairwise_planes(X, handler, group_container, sel, bool(is_log1p), alternative, bool(use_continuity),
+                                        bool(tie_correct), bool(scores))
+    r_idx, g_idx = np.divmod(np.arange(K * K), K)
+    off = r_idx != g_idx
+    rows = np.flatnonzero(off)
+    cols = {"p_value": planes[0].reshape(K * K, M)[rows].reshape(-1), "statistic": planes[1].reshape(K * K, M)[rows].reshape(-1),
+            "fold_change": planes[2].reshape(K * K, M)[rows].reshape(-1)}
+    if scores:
+        cols["z_score"] = planes[3].reshape(K * K, M)[rows].reshape(-1)
+    if code is not None:
+        from illico_amd import _lib
+        adj = _lib.get_engine().adjust_pvalues(np.ascontiguousarray(planes[0].reshape(K * K, M)[rows]), code)
+        cols["p_value_adj"] = np.asarray(adj).reshape(-1)
+    labels = np.asarray(unique_raw_groups)[sel]
+    index = _pair_index(labels, np.asarray(adata.var_names), r_idx[rows], g_idx[rows])
+    df = pd.DataFrame(cols, index=index, copy=False)
+    df.attrs["n_flagged_genes"] = n_flagged
+    return df

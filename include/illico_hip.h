@@ -350,6 +350,44 @@ int illico_ttest_from_moments(illico_ctx *ctx, const double *sum, const double *
  * df), ILLICO_FLAG_OUTPUT_DEVICE (out_p). */
 int illico_student_t_pvalues(illico_ctx *ctx, const double *t, const double *df, int64_t n, int alternative, int flags, double *out_p);
 
+/* ---- all-pairs Wilcoxon rank-sum tests from value histograms ----------------------------------
+ * Stage 1, illico_group_value_hists_*: for each group g of illico_set_groups (codes, counts and the group-contiguous order are used;
+ * the reference / one-versus-rest mode is ignored) and each column j of [col_lb, col_ub), W = col_ub - col_lb:
+ *   out_H[(g * W + (j - col_lb)) * 256 + c]   uint32: the cells of g whose value in column j is the integer c, c in 0 .. 255;
+ *   out_flags[j - col_lb]                     uint32: non-zero when column j holds a value that is not an integer in [0, 255] (negative,
+ *                                             fractional, larger, NaN); out_H of such a column is unspecified.
+ * Sparse input gives the dense answer: a stored zero counts in bin 0, the cells that are not stored too (counts[g] minus the stored
+ * entries of g); CSR rows need not be sorted.  Input: as illico_group_stats_* (f32 / f64 / i32 / i64 values, i32 / i64 indices, host
+ * arrays or, with ILLICO_FLAG_INPUT_DEVICE, device arrays).  Output: host arrays, complete on return, or device arrays with
+ * ILLICO_FLAG_OUTPUT_DEVICE (ordered on the context's stream).  The whole window is held in device scratch (G * W KB, twice for dense
+ * input): a window beyond "scratch_bytes" is ILLICO_ERR_OOM before any work -- pass narrower windows.  A pending deferred call is
+ * completed first.  Errors: ILLICO_ERR_NO_GROUPS, ILLICO_ERR_BOUNDS, ILLICO_ERR_DTYPE, ILLICO_ERR_ARG, ILLICO_ERR_OOM, and
+ * ILLICO_ERR_UNSUPPORTED for a dense row pitch of 4 GiB or more. */
+int illico_group_value_hists_dense(illico_ctx *ctx, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld,
+                                   int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags);
+int illico_group_value_hists_csc(illico_ctx *ctx, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype,
+                                 int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags);
+int illico_group_value_hists_csr(illico_ctx *ctx, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype,
+                                 int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags);
+/* Stage 2: every ordered pair of the K = n_sel groups sel[0 .. K) (sel null: all n_groups, in order) from H [n_groups][n_cols][256] and
+ * gene_flags [n_cols] as stage 1 writes them (both on the host, or both on the device with ILLICO_FLAG_INPUT_DEVICE; sums goes with
+ * them).  counts [n_groups] and sel are HOST arrays; the context's groups are not used.  With h_g, h_r the histograms of group sel[g]
+ * and of the reference sel[r], n_g, n_r their sizes, cum_r[c] = sum_{c' < c} h_r[c']:
+ *     S2  = sum_c h_g[c] (cum_r[c] + cum_r[c + 1])           U = 0.5 (double)(2 n_r n_g - S2)
+ *     tie = (double) sum_c (t^3 - t), t = h_g[c] + h_r[c]    (0.0 without ILLICO_FLAG_TIE_CORRECT)
+ * p and z follow as in illico_run_*_ex from U, tie and the sizes (n = n_g + n_r): the same integers and functions as a one-versus-
+ * reference call, so plane slab r is that call's [K, n_cols] plane set with reference sel[r].  fold change: (S_g / n_g) / (S_r / n_r),
+ * +inf where the reference's mean is 0, S = sums[sel[.]][j] (float64 [n_groups][sums_ld]) or, sums null, sum_c c h[c] (exact).
+ * Outputs: float64 [K][K][out_ld >= n_cols] indexed [r][g][j]; out_z may be null.  Diagonal: p = 1, U = n^2 / 2, z = 0.  Columns with a
+ * non-zero flag are left untouched in every plane.  flags: ILLICO_FLAG_CONTINUITY, ILLICO_FLAG_TIE_CORRECT, ILLICO_FLAG_INPUT_DEVICE,
+ * ILLICO_FLAG_OUTPUT_DEVICE (ILLICO_FLAG_LOG1P is accepted and has no effect: pass the expm1 sums as sums).
+ * Refused before anything is written: K < 2, ids of sel outside [0, n_groups) or repeated (ILLICO_ERR_ARG); two selected groups with
+ * n_g + n_r >= 2^21 (ILLICO_ERR_UNSUPPORTED: the integer sums hold below that); ILLICO_ERR_ALTERNATIVE; a working set beyond
+ * "scratch_bytes" (ILLICO_ERR_OOM). */
+int illico_pairwise_from_hists(illico_ctx *ctx, const uint32_t *H, const uint32_t *gene_flags, const int64_t *counts, int64_t n_groups,
+                               int64_t n_cols, const int64_t *sel, int64_t n_sel, const double *sums, int64_t sums_ld, int flags,
+                               int alternative, double *out_p, double *out_u, double *out_fc, double *out_z, int64_t out_ld);
+
 /* ---- measurement hooks (bench.py roofline leg) ------------------------------------------- */
 int illico_profile_num_kernels(void);
 const char *illico_profile_kernel_name(int kernel_id);
