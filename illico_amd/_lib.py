@@ -177,6 +177,48 @@ def normalize_values(a: np.ndarray) -> np.ndarray:
     raise KeyError(f"Support for element dtype {dt} is not implemented.")
 
 
+def _dense_input(X):
+    """``(pointer, on the device, keepalive, n_rows, n_cols, row pitch in elements, dtype code)`` of the dense matrix of a group pass:
+    a row-major CUDA tensor as it is; a host array widened as ``normalize_values`` says, and copied only if its strides are not
+    ones the C side can walk (a view of some columns of a wider matrix is passed as it is)."""
+    if _is_torch_tensor(X):
+        if X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1):
+            raise ValueError("X must be row-major 2-D")
+        n_rows, n_cols = int(X.shape[0]), int(X.shape[1])
+        ld = int(X.stride(0)) if n_rows > 1 else n_cols
+        return X.data_ptr(), X.is_cuda, X, n_rows, n_cols, ld, dtype_code(str(X.dtype).replace("torch.", ""))
+    X = normalize_values(np.asarray(X))
+    if X.ndim != 2:
+        raise ValueError(f"X must be 2-D, got {X.ndim} dimensions")
+    if (X.shape[1] > 1 and X.strides[1] != X.itemsize) or X.strides[0] % X.itemsize or X.strides[0] < 0:
+        X = np.ascontiguousarray(X)
+    n_rows, n_cols = X.shape
+    ld = X.strides[0] // X.itemsize if n_rows > 1 else n_cols
+    return X.ctypes.data, False, X, n_rows, n_cols, ld, dtype_code(X.dtype)
+
+
+def _sparse_input(data, indices, indptr, shape):
+    """``(data, indices, indptr as _Buf, index dtype code, n_rows, n_cols)`` of a CSC / CSR matrix given as its three arrays: CUDA
+    tensors as they are; host values widened as ``normalize_values`` says, host indices int32 if both arrays are, else int64."""
+    n_rows, n_cols = int(shape[0]), int(shape[1])
+    if _is_torch_tensor(data):
+        d, i, p = _Buf(data), _Buf(indices), _Buf(indptr)
+    else:
+        d = _Buf(normalize_values(np.asarray(data)))
+        idt = np.int32 if (np.asarray(indices).dtype == np.int32 and np.asarray(indptr).dtype == np.int32) else np.int64
+        i, p = _Buf(indices, idt), _Buf(indptr, idt)
+    if i.np_dtype != p.np_dtype or i.np_dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise KeyError(f"Support for index dtypes {i.np_dtype}/{p.np_dtype} is not implemented.")
+    if not (d.on_device == i.on_device == p.on_device):
+        raise ValueError("data, indices and indptr must live on the same side (host or device)")
+    return d, i, p, IDX_I32 if i.np_dtype == np.int32 else IDX_I64, n_rows, n_cols
+
+
+def _check_chunk_bounds(col_lb, col_ub, n_cols):
+    if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
+        raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+
+
 class Engine:
     """One illico_ctx: one device, one stream, device scratch, the current GroupContainer."""
 
@@ -342,19 +384,8 @@ class Engine:
         pass is enqueued; the planes are complete after ``synchronize()`` or the next call on this engine.  ``scores``: as in
         ``run_dense``."""
         alt = self._alt(alternative)
-        n_rows, n_cols = int(shape[0]), int(shape[1])
-        if _is_torch_tensor(data):
-            d, i, p = _Buf(data), _Buf(indices), _Buf(indptr)
-        else:
-            d = _Buf(normalize_values(np.asarray(data)))
-            idt = np.int32 if (np.asarray(indices).dtype == np.int32 and np.asarray(indptr).dtype == np.int32) else np.int64
-            i, p = _Buf(indices, idt), _Buf(indptr, idt)
-        if i.np_dtype != p.np_dtype or i.np_dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
-            raise KeyError(f"Support for index dtypes {i.np_dtype}/{p.np_dtype} is not implemented.")
-        if not (d.on_device == i.on_device == p.on_device):
-            raise ValueError("data, indices and indptr must live on the same side (host or device)")
-        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
-            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        d, i, p, idx, n_rows, n_cols = _sparse_input(data, indices, indptr, shape)
+        _check_chunk_bounds(col_lb, col_ub, n_cols)
         G, W = self.n_groups, col_ub - col_lb
         planes, ptrs, oflag, out_ld = self._outputs(out, G, W, device_out, scores)
         if ptrs is None:
@@ -366,29 +397,19 @@ class Engine:
         else:
             fn = self.lib.illico_run_csc if fmt == "csc" else self.lib.illico_run_csr
         self._bind_torch_stream(d.keep, i.keep, p.keep, *planes)
-        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, IDX_I32 if i.np_dtype == np.int32 else IDX_I64,
-                       n_rows, n_cols, col_lb, col_ub, flags, alt, *ptrs, out_ld))
+        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols,
+                       col_lb, col_ub, flags, alt, *ptrs, out_ld))
         return planes
 
     def bind_sparse(self, fmt, data, indices, indptr, shape):
         """Upload a host CSR / CSC matrix once (or adopt device tensors) -- illico_csr_bind / illico_csc_bind; returns a
         ``BoundMatrix`` whose ``run(col_lb, col_ub, ...)`` computes chunks without moving the matrix again."""
-        n_rows, n_cols = int(shape[0]), int(shape[1])
-        if _is_torch_tensor(data):
-            d, i, p = _Buf(data), _Buf(indices), _Buf(indptr)
-        else:
-            d = _Buf(normalize_values(np.asarray(data)))
-            idt = np.int32 if (np.asarray(indices).dtype == np.int32 and np.asarray(indptr).dtype == np.int32) else np.int64
-            i, p = _Buf(indices, idt), _Buf(indptr, idt)
-        if i.np_dtype != p.np_dtype or i.np_dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
-            raise KeyError(f"Support for index dtypes {i.np_dtype}/{p.np_dtype} is not implemented.")
-        if not (d.on_device == i.on_device == p.on_device):
-            raise ValueError("data, indices and indptr must live on the same side (host or device)")
+        d, i, p, idx, n_rows, n_cols = _sparse_input(data, indices, indptr, shape)
         h = ctypes.c_void_p()
         fn = self.lib.illico_csc_bind if fmt == "csc" else self.lib.illico_csr_bind
         self._bind_torch_stream(d.keep, i.keep, p.keep)
-        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, IDX_I32 if i.np_dtype == np.int32 else IDX_I64,
-                       n_rows, n_cols, FLAG_INPUT_DEVICE if d.on_device else 0, ctypes.byref(h)))
+        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols,
+                       FLAG_INPUT_DEVICE if d.on_device else 0, ctypes.byref(h)))
         return BoundMatrix(self, h, (n_rows, n_cols), (d.keep, i.keep, p.keep) if d.on_device else None)
 
     def input_bytes(self) -> int:
@@ -539,68 +560,45 @@ class Engine:
         ptrs += [None] * (4 - len(ptrs))
         return planes, ptrs, FLAG_OUTPUT_DEVICE if side else 0, int(max(ld or 1, W, 1))
 
+    def _group_planes_dense(self, family, X, col_lb, col_ub, flags, rest, out, *planes_spec):
+        """illico_<family>_dense on X; ``planes_spec``: the ``kinds`` and ``names`` of ``_gs_outputs`` where they are not its defaults."""
+        ptr, on_dev, keep, n_rows, n_cols, ld, dt = _dense_input(X)
+        _check_chunk_bounds(col_lb, col_ub, n_cols)
+        G, W = self.n_groups, col_ub - col_lb
+        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, on_dev, *planes_spec)
+        if W == 0:
+            return planes
+        self._bind_torch_stream(keep, *[p for p in planes if p is not None])
+        self._check(getattr(self.lib, f"illico_{family}_dense")(self.h, ptr, dt, n_rows, n_cols, max(ld, n_cols), col_lb, col_ub,
+                                                                 flags | (FLAG_INPUT_DEVICE if on_dev else 0) | oflag, *ptrs, out_ld))
+        return planes
+
+    def _group_planes_sparse(self, family, fmt, data, indices, indptr, shape, col_lb, col_ub, flags, rest, out, *planes_spec):
+        """illico_<family>_csc / _csr on the three arrays; ``planes_spec`` as in ``_group_planes_dense``."""
+        if fmt not in ("csc", "csr"):
+            raise ValueError(f"fmt must be 'csc' or 'csr', got {fmt!r}")
+        d, i, p, idx, n_rows, n_cols = _sparse_input(data, indices, indptr, shape)
+        _check_chunk_bounds(col_lb, col_ub, n_cols)
+        G, W = self.n_groups, col_ub - col_lb
+        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, d.on_device, *planes_spec)
+        if W == 0:
+            return planes
+        self._bind_torch_stream(d.keep, i.keep, p.keep, *[q for q in planes if q is not None])
+        self._check(getattr(self.lib, f"illico_{family}_{fmt}")(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols, col_lb, col_ub,
+                                                                flags | (FLAG_INPUT_DEVICE if d.on_device else 0) | oflag, *ptrs, out_ld))
+        return planes
+
     def group_stats(self, X, col_lb, col_ub, *, is_log1p=False, rest=False, out=None):
         """Per-group non-zero counts and value sums of the dense columns [col_lb, col_ub) (illico_group_stats_dense).
 
         ``X``: a row-major numpy array or a CUDA tensor.  Returns ``(nnz, sum)`` -- int64 / float64 ``[G, W]`` -- or, with
         ``rest=True``, ``(nnz, sum, nnz_rest, sum_rest)``, living where ``X`` lives unless ``out`` (see ``_gs_outputs``) says otherwise."""
-        if _is_torch_tensor(X):
-            if X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1):
-                raise ValueError("X must be row-major 2-D")
-            ptr, on_dev, keep = X.data_ptr(), X.is_cuda, X
-            n_rows, n_cols = int(X.shape[0]), int(X.shape[1])
-            ld = int(X.stride(0)) if n_rows > 1 else n_cols
-            dt = dtype_code(str(X.dtype).replace("torch.", ""))
-        else:
-            X = normalize_values(np.asarray(X))
-            if X.ndim != 2:
-                raise ValueError(f"X must be 2-D, got {X.ndim} dimensions")
-            if (X.shape[1] > 1 and X.strides[1] != X.itemsize) or X.strides[0] % X.itemsize or X.strides[0] < 0:
-                X = np.ascontiguousarray(X)
-            ptr, on_dev, keep = X.ctypes.data, False, X
-            n_rows, n_cols = X.shape
-            ld = X.strides[0] // X.itemsize if n_rows > 1 else n_cols
-            dt = dtype_code(X.dtype)
-        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
-            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
-        G, W = self.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, on_dev)
-        if W == 0:
-            return planes
-        flags = (FLAG_LOG1P if is_log1p else 0) | (FLAG_INPUT_DEVICE if on_dev else 0) | oflag
-        self._bind_torch_stream(keep, *[p for p in planes if p is not None])
-        self._check(self.lib.illico_group_stats_dense(self.h, ptr, dt, n_rows, n_cols, max(ld, n_cols), col_lb, col_ub, flags, *ptrs, out_ld))
-        del keep
-        return planes
+        return self._group_planes_dense("group_stats", X, col_lb, col_ub, FLAG_LOG1P if is_log1p else 0, rest, out)
 
     def group_stats_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, *, is_log1p=False, rest=False, out=None):
         """``group_stats`` of a CSC (``fmt="csc"``) or CSR (``"csr"``) matrix given as its three arrays (numpy or CUDA tensors);
         CSR rows need not be sorted.  Duplicate entries count once per stored entry."""
-        if fmt not in ("csc", "csr"):
-            raise ValueError(f"fmt must be 'csc' or 'csr', got {fmt!r}")
-        n_rows, n_cols = int(shape[0]), int(shape[1])
-        if _is_torch_tensor(data):
-            d, i, p = _Buf(data), _Buf(indices), _Buf(indptr)
-        else:
-            d = _Buf(normalize_values(np.asarray(data)))
-            idt = np.int32 if (np.asarray(indices).dtype == np.int32 and np.asarray(indptr).dtype == np.int32) else np.int64
-            i, p = _Buf(indices, idt), _Buf(indptr, idt)
-        if i.np_dtype != p.np_dtype or i.np_dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
-            raise KeyError(f"Support for index dtypes {i.np_dtype}/{p.np_dtype} is not implemented.")
-        if not (d.on_device == i.on_device == p.on_device):
-            raise ValueError("data, indices and indptr must live on the same side (host or device)")
-        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
-            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
-        G, W = self.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, d.on_device)
-        if W == 0:
-            return planes
-        flags = (FLAG_LOG1P if is_log1p else 0) | (FLAG_INPUT_DEVICE if d.on_device else 0) | oflag
-        fn = self.lib.illico_group_stats_csc if fmt == "csc" else self.lib.illico_group_stats_csr
-        self._bind_torch_stream(d.keep, i.keep, p.keep, *[q for q in planes if q is not None])
-        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, IDX_I32 if i.np_dtype == np.int32 else IDX_I64,
-                       n_rows, n_cols, col_lb, col_ub, flags, *ptrs, out_ld))
-        return planes
+        return self._group_planes_sparse("group_stats", fmt, data, indices, indptr, shape, col_lb, col_ub, FLAG_LOG1P if is_log1p else 0, rest, out)
 
     # ---- per-group moments and Welch's t-test (include/illico_hip.h: illico_group_moments_*, illico_ttest_from_moments) ----
     _GM_KINDS = (np.float64, np.float64, np.float64, np.float64)
@@ -612,63 +610,12 @@ class Engine:
         ``X``: a row-major numpy array or a CUDA tensor.  Returns ``(sum, sumsq)`` -- float64 ``[G, W]`` -- or, with ``rest=True``,
         ``(sum, sumsq, sum_rest, sumsq_rest)``, living where ``X`` lives unless ``out`` (2 or 4 planes in that order, each a host
         ndarray, a CUDA tensor or None) says otherwise.  The values are taken as given: there is no ``is_log1p``."""
-        if _is_torch_tensor(X):
-            if X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1):
-                raise ValueError("X must be row-major 2-D")
-            ptr, on_dev, keep = X.data_ptr(), X.is_cuda, X
-            n_rows, n_cols = int(X.shape[0]), int(X.shape[1])
-            ld = int(X.stride(0)) if n_rows > 1 else n_cols
-            dt = dtype_code(str(X.dtype).replace("torch.", ""))
-        else:
-            X = normalize_values(np.asarray(X))
-            if X.ndim != 2:
-                raise ValueError(f"X must be 2-D, got {X.ndim} dimensions")
-            if (X.shape[1] > 1 and X.strides[1] != X.itemsize) or X.strides[0] % X.itemsize or X.strides[0] < 0:
-                X = np.ascontiguousarray(X)
-            ptr, on_dev, keep = X.ctypes.data, False, X
-            n_rows, n_cols = X.shape
-            ld = X.strides[0] // X.itemsize if n_rows > 1 else n_cols
-            dt = dtype_code(X.dtype)
-        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
-            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
-        G, W = self.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, on_dev, self._GM_KINDS, self._GM_NAMES)
-        if W == 0:
-            return planes
-        flags = (FLAG_INPUT_DEVICE if on_dev else 0) | oflag
-        self._bind_torch_stream(keep, *[p for p in planes if p is not None])
-        self._check(self.lib.illico_group_moments_dense(self.h, ptr, dt, n_rows, n_cols, max(ld, n_cols), col_lb, col_ub, flags, *ptrs, out_ld))
-        del keep
-        return planes
+        return self._group_planes_dense("group_moments", X, col_lb, col_ub, 0, rest, out, self._GM_KINDS, self._GM_NAMES)
 
     def group_moments_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, *, rest=False, out=None):
         """``group_moments`` of a CSC (``fmt="csc"``) or CSR (``"csr"``) matrix given as its three arrays (numpy or CUDA tensors);
         CSR rows need not be sorted.  Duplicate entries count as separate values."""
-        if fmt not in ("csc", "csr"):
-            raise ValueError(f"fmt must be 'csc' or 'csr', got {fmt!r}")
-        n_rows, n_cols = int(shape[0]), int(shape[1])
-        if _is_torch_tensor(data):
-            d, i, p = _Buf(data), _Buf(indices), _Buf(indptr)
-        else:
-            d = _Buf(normalize_values(np.asarray(data)))
-            idt = np.int32 if (np.asarray(indices).dtype == np.int32 and np.asarray(indptr).dtype == np.int32) else np.int64
-            i, p = _Buf(indices, idt), _Buf(indptr, idt)
-        if i.np_dtype != p.np_dtype or i.np_dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
-            raise KeyError(f"Support for index dtypes {i.np_dtype}/{p.np_dtype} is not implemented.")
-        if not (d.on_device == i.on_device == p.on_device):
-            raise ValueError("data, indices and indptr must live on the same side (host or device)")
-        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
-            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
-        G, W = self.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, d.on_device, self._GM_KINDS, self._GM_NAMES)
-        if W == 0:
-            return planes
-        flags = (FLAG_INPUT_DEVICE if d.on_device else 0) | oflag
-        fn = self.lib.illico_group_moments_csc if fmt == "csc" else self.lib.illico_group_moments_csr
-        self._bind_torch_stream(d.keep, i.keep, p.keep, *[q for q in planes if q is not None])
-        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, IDX_I32 if i.np_dtype == np.int32 else IDX_I64,
-                       n_rows, n_cols, col_lb, col_ub, flags, *ptrs, out_ld))
-        return planes
+        return self._group_planes_sparse("group_moments", fmt, data, indices, indptr, shape, col_lb, col_ub, 0, rest, out, self._GM_KINDS, self._GM_NAMES)
 
     def ttest_from_moments(self, sum, sumsq, sum_rest=None, sumsq_rest=None, *, variant="welch", alternative="two-sided",
                            want=("p", "t"), out=None):
@@ -802,25 +749,8 @@ class Engine:
         column ``col_lb + j`` is c, ``flags[j]`` non-zero when the column holds a value that is no integer in [0, 255] (``H`` of such a
         column is unspecified).  uint32 numpy arrays for host input, int32 CUDA tensors for device input, unless ``out`` (a pair of
         either) says otherwise."""
-        if _is_torch_tensor(X):
-            if X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1):
-                raise ValueError("X must be row-major 2-D")
-            ptr, on_dev, keep = X.data_ptr(), X.is_cuda, X
-            n_rows, n_cols = int(X.shape[0]), int(X.shape[1])
-            ld = int(X.stride(0)) if n_rows > 1 else n_cols
-            dt = dtype_code(str(X.dtype).replace("torch.", ""))
-        else:
-            X = normalize_values(np.asarray(X))
-            if X.ndim != 2:
-                raise ValueError(f"X must be 2-D, got {X.ndim} dimensions")
-            if (X.shape[1] > 1 and X.strides[1] != X.itemsize) or X.strides[0] % X.itemsize or X.strides[0] < 0:
-                X = np.ascontiguousarray(X)
-            ptr, on_dev, keep = X.ctypes.data, False, X
-            n_rows, n_cols = X.shape
-            ld = X.strides[0] // X.itemsize if n_rows > 1 else n_cols
-            dt = dtype_code(X.dtype)
-        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
-            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        ptr, on_dev, keep, n_rows, n_cols, ld, dt = _dense_input(X)
+        _check_chunk_bounds(col_lb, col_ub, n_cols)
         G, W = self.n_groups, col_ub - col_lb
         H, fl, ptrs, oflag = self._hist_outputs(out, G, W, on_dev)
         if W == 0:
@@ -828,7 +758,6 @@ class Engine:
         self._bind_torch_stream(keep, H, fl)
         self._check(self.lib.illico_group_value_hists_dense(self.h, ptr, dt, n_rows, n_cols, max(ld, n_cols), col_lb, col_ub,
                                                             (FLAG_INPUT_DEVICE if on_dev else 0) | oflag, *ptrs))
-        del keep
         return H, fl
 
     def group_value_hists_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, out=None):
@@ -836,27 +765,16 @@ class Engine:
         the dense answer -- a stored zero counts in bin 0, and so do the cells that are not stored.  CSR rows need not be sorted."""
         if fmt not in ("csc", "csr"):
             raise ValueError(f"fmt must be 'csc' or 'csr', got {fmt!r}")
-        n_rows, n_cols = int(shape[0]), int(shape[1])
-        if _is_torch_tensor(data):
-            d, i, p = _Buf(data), _Buf(indices), _Buf(indptr)
-        else:
-            d = _Buf(normalize_values(np.asarray(data)))
-            idt = np.int32 if (np.asarray(indices).dtype == np.int32 and np.asarray(indptr).dtype == np.int32) else np.int64
-            i, p = _Buf(indices, idt), _Buf(indptr, idt)
-        if i.np_dtype != p.np_dtype or i.np_dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
-            raise KeyError(f"Support for index dtypes {i.np_dtype}/{p.np_dtype} is not implemented.")
-        if not (d.on_device == i.on_device == p.on_device):
-            raise ValueError("data, indices and indptr must live on the same side (host or device)")
-        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
-            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        d, i, p, idx, n_rows, n_cols = _sparse_input(data, indices, indptr, shape)
+        _check_chunk_bounds(col_lb, col_ub, n_cols)
         G, W = self.n_groups, col_ub - col_lb
         H, fl, ptrs, oflag = self._hist_outputs(out, G, W, d.on_device)
         if W == 0:
             return H, fl
         fn = self.lib.illico_group_value_hists_csc if fmt == "csc" else self.lib.illico_group_value_hists_csr
         self._bind_torch_stream(d.keep, i.keep, p.keep, H, fl)
-        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, IDX_I32 if i.np_dtype == np.int32 else IDX_I64,
-                       n_rows, n_cols, col_lb, col_ub, (FLAG_INPUT_DEVICE if d.on_device else 0) | oflag, *ptrs))
+        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols,
+                       col_lb, col_ub, (FLAG_INPUT_DEVICE if d.on_device else 0) | oflag, *ptrs))
         return H, fl
 
     def pairwise_from_hists(self, H, flags, *, counts=None, sel=None, sums=None, is_log1p=False, use_continuity=True, tie_correct=True,
@@ -987,8 +905,7 @@ class BoundMatrix:
         eng = self.engine
         alt = eng._alt(alternative)
         n_cols = self.shape[1]
-        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
-            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        _check_chunk_bounds(col_lb, col_ub, n_cols)
         G, W = eng.n_groups, col_ub - col_lb
         planes, ptrs, oflag, out_ld = eng._outputs(out, G, W, device_out, scores)
         if ptrs is None:
@@ -1001,33 +918,25 @@ class BoundMatrix:
             eng._check(eng.lib.illico_run_bound(eng.h, self.h, col_lb, col_ub, flags, alt, ptrs[0], ptrs[1], ptrs[2], out_ld))
         return planes
 
-    def group_stats(self, col_lb, col_ub, *, is_log1p=False, rest=False, out=None, device_out=False):
-        """``Engine.group_stats`` of the bound matrix (illico_group_stats_bound); host planes unless ``device_out`` or ``out``."""
+    def _group_planes(self, family, col_lb, col_ub, flags, rest, out, device_out, *planes_spec):
+        """illico_<family>_bound on this matrix; ``planes_spec`` as in ``Engine._group_planes_dense``."""
         eng = self.engine
-        n_cols = self.shape[1]
-        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
-            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
+        _check_chunk_bounds(col_lb, col_ub, self.shape[1])
         G, W = eng.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = eng._gs_outputs(out, G, W, rest, device_out)
+        planes, ptrs, oflag, out_ld = eng._gs_outputs(out, G, W, rest, device_out, *planes_spec)
         if W == 0:
             return planes
         eng._bind_torch_stream(*[p for p in planes if p is not None])
-        eng._check(eng.lib.illico_group_stats_bound(eng.h, self.h, col_lb, col_ub, (FLAG_LOG1P if is_log1p else 0) | oflag, *ptrs, out_ld))
+        eng._check(getattr(eng.lib, f"illico_{family}_bound")(eng.h, self.h, col_lb, col_ub, flags | oflag, *ptrs, out_ld))
         return planes
+
+    def group_stats(self, col_lb, col_ub, *, is_log1p=False, rest=False, out=None, device_out=False):
+        """``Engine.group_stats`` of the bound matrix (illico_group_stats_bound); host planes unless ``device_out`` or ``out``."""
+        return self._group_planes("group_stats", col_lb, col_ub, FLAG_LOG1P if is_log1p else 0, rest, out, device_out)
 
     def group_moments(self, col_lb, col_ub, *, rest=False, out=None, device_out=False):
         """``Engine.group_moments`` of the bound matrix (illico_group_moments_bound); host planes unless ``device_out`` or ``out``."""
-        eng = self.engine
-        n_cols = self.shape[1]
-        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
-            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
-        G, W = eng.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = eng._gs_outputs(out, G, W, rest, device_out, eng._GM_KINDS, eng._GM_NAMES)
-        if W == 0:
-            return planes
-        eng._bind_torch_stream(*[p for p in planes if p is not None])
-        eng._check(eng.lib.illico_group_moments_bound(eng.h, self.h, col_lb, col_ub, oflag, *ptrs, out_ld))
-        return planes
+        return self._group_planes("group_moments", col_lb, col_ub, 0, rest, out, device_out, self.engine._GM_KINDS, self.engine._GM_NAMES)
 
     def touch(self):
         """Adopted device arrays were rewritten in place: forget what the context remembers about them (include/illico_hip.h)."""

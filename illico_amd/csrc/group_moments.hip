@@ -1,35 +1,21 @@
 // illico_group_moments_{dense,csc,csr,bound}: per-(group, gene) exact sums of the values and of their squares, and the same over
 // every other cell (kernels_group_moments.h); illico_ttest_from_moments / illico_student_t_pvalues: Welch's t-test from those
-// planes (kernels_ttest.h).  A translation unit of its own: the kernels depend on nothing the other routes use.
-#include "engine.h"
+// planes (kernels_ttest.h).  A translation unit of its own: the kernels depend on nothing the other routes use; the host scaffolding
+// (input description, common checks, sparse upload, type dispatch) is shared with the other group passes (group_pass.h).
+#include "group_pass.h"
 #include "kernels_group_moments.h"
 #include "kernels_ttest.h"
 
 namespace {
 
-struct GmInput {
-    bool sparse = false, is_csr = false, on_dev = false;
-    const void *X = nullptr; // dense
-    int64_t ld = 0;
-    const void *data = nullptr, *indices = nullptr, *indptr = nullptr; // sparse
-    int idx_dtype = 0;
-    int dtype = 0;
-    int64_t n_rows = 0, n_cols = 0;
-};
 struct GmOutputs {
     double *sum, *sumsq, *sum_rest, *sumsq_rest;
     int64_t ld;
 };
 
-int gm_check(illico_ctx *c, const GmInput &in, int64_t col_lb, int64_t col_ub, int flags, const GmOutputs &o) {
-    if (!c->has_groups) return fail(c, ILLICO_ERR_NO_GROUPS, "illico_set_groups has not been called");
-    if (in.n_rows != c->n_cells)
-        return fail(c, ILLICO_ERR_NO_GROUPS, "X has %lld rows but the groups describe %lld cells", (long long)in.n_rows, (long long)c->n_cells);
-    if (col_lb < 0 || col_ub > in.n_cols || col_lb > col_ub)
-        return fail(c, ILLICO_ERR_BOUNDS, "Invalid chunk bounds: (%lld, %lld) for data with %lld columns.", (long long)col_lb, (long long)col_ub, (long long)in.n_cols);
-    if (in.dtype < 0 || in.dtype > 3) return fail(c, ILLICO_ERR_DTYPE, "unsupported dtype code %d", in.dtype);
-    if (in.sparse && in.idx_dtype != ILLICO_IDX_I32 && in.idx_dtype != ILLICO_IDX_I64)
-        return fail(c, ILLICO_ERR_DTYPE, "unsupported index dtype code %d", in.idx_dtype);
+int gm_check(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub, int flags, const GmOutputs &o) {
+    int rc = check_matrix_input(c, in, col_lb, col_ub);
+    if (rc) return rc;
     if (flags & ILLICO_FLAG_LOG1P)
         return fail(c, ILLICO_ERR_ARG, "ILLICO_FLAG_LOG1P: the moments are those of the values as given (the t-test is a test on the log values)");
     if (!o.sum && !o.sumsq && !o.sum_rest && !o.sumsq_rest) return fail(c, ILLICO_ERR_ARG, "all four output planes are null: nothing to compute");
@@ -38,17 +24,6 @@ int gm_check(illico_ctx *c, const GmInput &in, int64_t col_lb, int64_t col_ub, i
         if (c->h_counts[g] > 2097151)
             return fail(c, ILLICO_ERR_UNSUPPORTED, "group %lld holds %d cells: the exact per-group sums hold up to 2097151", (long long)g, c->h_counts[g]);
     return ILLICO_OK;
-}
-
-// the groups' positions in chunks of at most GM_CHUNK (a group of 100 000 cells is spread over ~100 workgroups)
-void gm_chunks(const illico_ctx *c, std::vector<GmChunk> &ch) {
-    ch.clear();
-    int pos = 0;
-    for (int64_t g = 0; g < c->n_groups; ++g) {
-        const int n = c->h_counts[g];
-        for (int p = 0; p < n; p += GM_CHUNK) ch.push_back({(int)g, pos + p, pos + std::min(n, p + GM_CHUNK), n <= GM_CHUNK ? 1 : 0});
-        pos += n;
-    }
 }
 
 template <typename InT>
@@ -103,16 +78,7 @@ int gm_sparse_window(illico_ctx *c, bool is_csr, const void *data, const void *i
     return ILLICO_OK;
 }
 
-template <typename InT>
-int gm_sparse_any_idx(illico_ctx *c, bool is_csr, int idx_dtype, const void *data, const void *indices, const void *indptr, long long kshift, long long col0,
-                      int64_t N, int wn, int dt, const GmChunk *d_ch, int n_ch, const GmPlanes &P) {
-    if (idx_dtype == ILLICO_IDX_I32) return gm_sparse_window<InT, int32_t>(c, is_csr, data, indices, indptr, kshift, col0, N, wn, dt, d_ch, n_ch, P);
-    return gm_sparse_window<InT, int64_t>(c, is_csr, data, indices, indptr, kshift, col0, N, wn, dt, d_ch, n_ch, P);
-}
-
-int64_t gm_idx_at(const void *p, int idx_dtype, int64_t i) { return idx_dtype == ILLICO_IDX_I32 ? (int64_t)((const int32_t *)p)[i] : ((const int64_t *)p)[i]; }
-
-int gm_run(illico_ctx *c, const GmInput &in, int64_t col_lb, int64_t col_ub, int flags, const GmOutputs &o) {
+int gm_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub, int flags, const GmOutputs &o) {
     HIPCHK(c, hipSetDevice(c->device));
     int rc = resolve_pending(c); // a plane written under ILLICO_FLAG_DEFER is complete only after its leftover genes
     if (rc) return rc;
@@ -120,12 +86,12 @@ int gm_run(illico_ctx *c, const GmInput &in, int64_t col_lb, int64_t col_ub, int
     if (W == 0) return ILLICO_OK;
     const bool out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
     const int dt = in.dtype;
-    const size_t esz = dtype_size(dt), isz = in.idx_dtype == ILLICO_IDX_I32 ? 4 : 8;
+    const size_t esz = dtype_size(dt);
     void *v = nullptr;
 
     // chunks of the groups' positions (dense, CSR)
     std::vector<GmChunk> hch;
-    gm_chunks(c, hch);
+    group_chunks(c, GM_CHUNK, hch);
     const int n_ch = (int)hch.size();
     GmChunk *d_ch = nullptr;
     if (n_ch) {
@@ -134,25 +100,8 @@ int gm_run(illico_ctx *c, const GmInput &in, int64_t col_lb, int64_t col_ub, int
         HIPCHK(c, hipMemcpyAsync(d_ch, hch.data(), hch.size() * sizeof(GmChunk), hipMemcpyHostToDevice, c->stream));
     }
 
-    // host-resident sparse input goes up once: CSC the entries of [col_lb, col_ub), CSR every row
-    const void *data = in.data, *indices = in.indices, *indptr = in.indptr;
-    long long kshift = 0, ptr_col0 = 0; // entry k at data[k - kshift]; the window's first column is indptr[col - ptr_col0]
-    if (in.sparse && !in.on_dev) {
-        const int64_t a = in.is_csr ? 0 : col_lb, b = in.is_csr ? N : col_ub;
-        const int64_t k0 = gm_idx_at(in.indptr, in.idx_dtype, a), k1 = gm_idx_at(in.indptr, in.idx_dtype, b);
-        if (k0 < 0 || k1 < k0) return fail(c, ILLICO_ERR_ARG, "indptr is not non-decreasing");
-        const size_t nnz = (size_t)(k1 - k0), nptr = (size_t)(b - a + 1);
-        if ((rc = get_scratch(c, "gm_upload", std::max<size_t>(nnz, 1) * (esz + isz) + nptr * isz + 64, &v))) return rc;
-        unsigned char *u = (unsigned char *)v;
-        void *dd = u, *di = u + ((nnz * esz + 15) & ~(size_t)15), *dp = (unsigned char *)di + ((nnz * isz + 15) & ~(size_t)15);
-        HIPCHK(c, hipMemcpyAsync(dd, (const unsigned char *)in.data + (size_t)k0 * esz, nnz * esz, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(di, (const unsigned char *)in.indices + (size_t)k0 * isz, nnz * isz, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dp, (const unsigned char *)in.indptr + (size_t)a * isz, nptr * isz, hipMemcpyHostToDevice, c->stream));
-        c->h2d_input_bytes += (int64_t)(nnz * (esz + isz) + nptr * isz);
-        data = dd; indices = di; indptr = dp;
-        kshift = k0;
-        ptr_col0 = a;
-    }
+    SparseOnDevice sp{}; // host-resident sparse input goes up once: CSC the entries of [col_lb, col_ub), CSR every row
+    if (in.sparse && (rc = stage_sparse_input(c, in, col_lb, col_ub, "gm_upload", &sp))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the chunk list and the staged arrays came from pageable host memory)
 
     // column windows: the six [G][wn] planes (+ staged host outputs, + the staged rows of a host dense matrix) fit the scratch cap
@@ -197,20 +146,16 @@ int gm_run(illico_ctx *c, const GmInput &in, int64_t col_lb, int64_t col_ub, int
                 X = (const unsigned char *)xwin;
                 ld = wn;
             }
-            switch (dt) {
-            case ILLICO_F32: rc = gm_dense_window<float>(c, (const float *)X, ld, N, wn, d_ch, n_ch, P); break;
-            case ILLICO_F64: rc = gm_dense_window<double>(c, (const double *)X, ld, N, wn, d_ch, n_ch, P); break;
-            case ILLICO_I32: rc = gm_dense_window<int32_t>(c, (const int32_t *)X, ld, N, wn, d_ch, n_ch, P); break;
-            default: rc = gm_dense_window<int64_t>(c, (const int64_t *)X, ld, N, wn, d_ch, n_ch, P); break;
-            }
+            rc = dispatch_value_type(dt, [&](auto t) {
+                using InT = typename decltype(t)::type;
+                return gm_dense_window<InT>(c, (const InT *)X, ld, N, wn, d_ch, n_ch, P);
+            });
         } else {
-            const long long col0 = w0 - ptr_col0;
-            switch (dt) {
-            case ILLICO_F32: rc = gm_sparse_any_idx<float>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, d_ch, n_ch, P); break;
-            case ILLICO_F64: rc = gm_sparse_any_idx<double>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, d_ch, n_ch, P); break;
-            case ILLICO_I32: rc = gm_sparse_any_idx<int32_t>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, d_ch, n_ch, P); break;
-            default: rc = gm_sparse_any_idx<int64_t>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, d_ch, n_ch, P); break;
-            }
+            const long long col0 = w0 - sp.ptr_col0;
+            rc = dispatch_value_index_type(dt, in.idx_dtype, [&](auto t, auto i) {
+                return gm_sparse_window<typename decltype(t)::type, typename decltype(i)::type>(c, in.is_csr, sp.data, sp.indices, sp.indptr, sp.kshift, col0, N, wn,
+                                                                                                 dt, d_ch, n_ch, P);
+            });
         }
         if (rc) return rc;
         const int gx = (wn + GM_NT - 1) / GM_NT;
@@ -248,18 +193,17 @@ int gm_run(illico_ctx *c, const GmInput &in, int64_t col_lb, int64_t col_ub, int
     return ILLICO_OK;
 }
 
-int group_moments_sparse(illico_ctx *c, bool is_csr, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
-                         int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, double *out_sum, double *out_sumsq, double *out_sum_rest,
-                         double *out_sumsq_rest, int64_t out_ld) {
+int gm_entry(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub, int flags, const GmOutputs &o) {
     if (!c) return ILLICO_ERR_ARG;
     CTX_LOCK(c);
-    GmInput in;
-    in.sparse = true; in.is_csr = is_csr; in.data = data; in.indices = indices; in.indptr = indptr; in.idx_dtype = idx_dtype; in.dtype = dtype;
-    in.n_rows = n_rows; in.n_cols = n_cols; in.on_dev = flags & ILLICO_FLAG_INPUT_DEVICE;
-    const GmOutputs o{out_sum, out_sumsq, out_sum_rest, out_sumsq_rest, out_ld};
     int rc = gm_check(c, in, col_lb, col_ub, flags, o);
     if (rc) return rc;
-    if (!data || !indices || !indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
+    if (in.sparse) {
+        if (!in.data || !in.indices || !in.indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
+    } else {
+        if (!in.X) return fail(c, ILLICO_ERR_ARG, "null X");
+        if (in.ld < in.n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
+    }
     return gm_run(c, in, col_lb, col_ub, flags, o);
 }
 
@@ -274,38 +218,29 @@ int tt_alt_ok(illico_ctx *c, int alternative) {
 
 extern "C" int illico_group_moments_dense(illico_ctx *c, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t col_lb, int64_t col_ub,
                                           int flags, double *out_sum, double *out_sumsq, double *out_sum_rest, double *out_sumsq_rest, int64_t out_ld) {
-    if (!c) return ILLICO_ERR_ARG;
-    CTX_LOCK(c);
-    GmInput in;
-    in.X = X; in.dtype = dtype; in.n_rows = n_rows; in.n_cols = n_cols; in.ld = ld; in.on_dev = flags & ILLICO_FLAG_INPUT_DEVICE;
-    const GmOutputs o{out_sum, out_sumsq, out_sum_rest, out_sumsq_rest, out_ld};
-    int rc = gm_check(c, in, col_lb, col_ub, flags, o);
-    if (rc) return rc;
-    if (!X) return fail(c, ILLICO_ERR_ARG, "null X");
-    if (ld < n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
-    return gm_run(c, in, col_lb, col_ub, flags, o);
+    return gm_entry(c, dense_input(X, dtype, n_rows, n_cols, ld, flags), col_lb, col_ub, flags, {out_sum, out_sumsq, out_sum_rest, out_sumsq_rest, out_ld});
 }
 extern "C" int illico_group_moments_csc(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
                                         int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, double *out_sum, double *out_sumsq, double *out_sum_rest,
                                         double *out_sumsq_rest, int64_t out_ld) {
-    return group_moments_sparse(c, false, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, out_sum, out_sumsq, out_sum_rest,
-                                out_sumsq_rest, out_ld);
+    return gm_entry(c, sparse_input(false, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, flags), col_lb, col_ub, flags,
+                    {out_sum, out_sumsq, out_sum_rest, out_sumsq_rest, out_ld});
 }
 extern "C" int illico_group_moments_csr(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
                                         int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, double *out_sum, double *out_sumsq, double *out_sum_rest,
                                         double *out_sumsq_rest, int64_t out_ld) {
-    return group_moments_sparse(c, true, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, out_sum, out_sumsq, out_sum_rest,
-                                out_sumsq_rest, out_ld);
+    return gm_entry(c, sparse_input(true, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, flags), col_lb, col_ub, flags,
+                    {out_sum, out_sumsq, out_sum_rest, out_sumsq_rest, out_ld});
 }
 extern "C" int illico_group_moments_bound(illico_ctx *c, const illico_matrix *m, int64_t col_lb, int64_t col_ub, int flags, double *out_sum, double *out_sumsq,
                                           double *out_sum_rest, double *out_sumsq_rest, int64_t out_ld) {
     if (!c || !m) return ILLICO_ERR_ARG;
-    CTX_LOCK(c); // (held for the whole call: illico_matrix_release on another thread cannot free the arrays under it)
-    if (m->owner != c || std::find(c->bound.begin(), c->bound.end(), m) == c->bound.end())
-        return fail(c, ILLICO_ERR_ARG, "the matrix handle does not belong to this context (or was released)");
-    return group_moments_sparse(c, m->is_csr, m->d_data, m->dtype, m->d_indices, m->d_indptr, m->idx_dtype, m->n_rows, m->n_cols, col_lb, col_ub,
-                                (flags & (ILLICO_FLAG_LOG1P | ILLICO_FLAG_OUTPUT_DEVICE)) | ILLICO_FLAG_INPUT_DEVICE, out_sum, out_sumsq, out_sum_rest,
-                                out_sumsq_rest, out_ld);
+    CTX_LOCK(c);
+    int rc = check_bound_matrix(c, m);
+    if (rc) return rc;
+    flags = bound_matrix_flags(flags);
+    return gm_entry(c, sparse_input(m->is_csr, m->d_data, m->dtype, m->d_indices, m->d_indptr, m->idx_dtype, m->n_rows, m->n_cols, flags), col_lb, col_ub, flags,
+                    {out_sum, out_sumsq, out_sum_rest, out_sumsq_rest, out_ld});
 }
 
 extern "C" int illico_ttest_from_moments(illico_ctx *c, const double *sum, const double *sumsq, const double *sum_rest, const double *sumsq_rest, int64_t n_cols,

@@ -1,51 +1,26 @@
 // illico_group_stats_{dense,csc,csr,bound}: per-(group, gene) non-zero counts and exact value sums, and the same over every other
-// cell (kernels_group_stats.h).  A translation unit of its own: the kernels depend on nothing the Wilcoxon routes use.
-#include "engine.h"
+// cell (kernels_group_stats.h).  A translation unit of its own: the kernels depend on nothing the Wilcoxon routes use; the host
+// scaffolding (input description, common checks, sparse upload, type dispatch) is shared with the other group passes (group_pass.h).
+#include "group_pass.h"
 #include "kernels_group_stats.h"
 
 namespace {
 
-struct GsInput {
-    bool sparse = false, is_csr = false, on_dev = false;
-    const void *X = nullptr; // dense
-    int64_t ld = 0;
-    const void *data = nullptr, *indices = nullptr, *indptr = nullptr; // sparse
-    int idx_dtype = 0;
-    int dtype = 0;
-    int64_t n_rows = 0, n_cols = 0;
-};
 struct GsOutputs {
     int64_t *nnz, *nnz_rest;
     double *sum, *sum_rest;
     int64_t ld;
 };
 
-int gs_check(illico_ctx *c, const GsInput &in, int64_t col_lb, int64_t col_ub, const GsOutputs &o) {
-    if (!c->has_groups) return fail(c, ILLICO_ERR_NO_GROUPS, "illico_set_groups has not been called");
-    if (in.n_rows != c->n_cells)
-        return fail(c, ILLICO_ERR_NO_GROUPS, "X has %lld rows but the groups describe %lld cells", (long long)in.n_rows, (long long)c->n_cells);
-    if (col_lb < 0 || col_ub > in.n_cols || col_lb > col_ub)
-        return fail(c, ILLICO_ERR_BOUNDS, "Invalid chunk bounds: (%lld, %lld) for data with %lld columns.", (long long)col_lb, (long long)col_ub, (long long)in.n_cols);
-    if (in.dtype < 0 || in.dtype > 3) return fail(c, ILLICO_ERR_DTYPE, "unsupported dtype code %d", in.dtype);
-    if (in.sparse && in.idx_dtype != ILLICO_IDX_I32 && in.idx_dtype != ILLICO_IDX_I64)
-        return fail(c, ILLICO_ERR_DTYPE, "unsupported index dtype code %d", in.idx_dtype);
+int gs_check(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub, const GsOutputs &o) {
+    int rc = check_matrix_input(c, in, col_lb, col_ub);
+    if (rc) return rc;
     if (!o.nnz && !o.sum && !o.nnz_rest && !o.sum_rest) return fail(c, ILLICO_ERR_ARG, "all four output planes are null: nothing to compute");
     if (o.ld < col_ub - col_lb) return fail(c, ILLICO_ERR_ARG, "out_ld smaller than the chunk width");
     for (int64_t g = 0; g < c->n_groups; ++g)
         if (c->h_counts[g] > 2097151)
             return fail(c, ILLICO_ERR_UNSUPPORTED, "group %lld holds %d cells: the exact per-group sums hold up to 2097151", (long long)g, c->h_counts[g]);
     return ILLICO_OK;
-}
-
-// the groups' positions in chunks of at most GS_CHUNK (a group of 100 000 cells is spread over ~100 workgroups)
-void gs_chunks(const illico_ctx *c, std::vector<GsChunk> &ch) {
-    ch.clear();
-    int pos = 0;
-    for (int64_t g = 0; g < c->n_groups; ++g) {
-        const int n = c->h_counts[g];
-        for (int p = 0; p < n; p += GS_CHUNK) ch.push_back({(int)g, pos + p, pos + std::min(n, p + GS_CHUNK), n <= GS_CHUNK ? 1 : 0});
-        pos += n;
-    }
 }
 
 template <typename InT>
@@ -100,16 +75,7 @@ int gs_sparse_window(illico_ctx *c, bool is_csr, const void *data, const void *i
     return ILLICO_OK;
 }
 
-template <typename InT>
-int gs_sparse_any_idx(illico_ctx *c, bool is_csr, int idx_dtype, const void *data, const void *indices, const void *indptr, long long kshift, long long col0,
-                      int64_t N, int wn, int dt, int log1p, const GsChunk *d_ch, int n_ch, const GsPlanes &P) {
-    if (idx_dtype == ILLICO_IDX_I32) return gs_sparse_window<InT, int32_t>(c, is_csr, data, indices, indptr, kshift, col0, N, wn, dt, log1p, d_ch, n_ch, P);
-    return gs_sparse_window<InT, int64_t>(c, is_csr, data, indices, indptr, kshift, col0, N, wn, dt, log1p, d_ch, n_ch, P);
-}
-
-int64_t idx_at(const void *p, int idx_dtype, int64_t i) { return idx_dtype == ILLICO_IDX_I32 ? (int64_t)((const int32_t *)p)[i] : ((const int64_t *)p)[i]; }
-
-int gs_run(illico_ctx *c, const GsInput &in, int64_t col_lb, int64_t col_ub, int flags, const GsOutputs &o) {
+int gs_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub, int flags, const GsOutputs &o) {
     HIPCHK(c, hipSetDevice(c->device));
     int rc = resolve_pending(c); // a plane written under ILLICO_FLAG_DEFER is complete only after its leftover genes
     if (rc) return rc;
@@ -117,12 +83,12 @@ int gs_run(illico_ctx *c, const GsInput &in, int64_t col_lb, int64_t col_ub, int
     if (W == 0) return ILLICO_OK;
     const bool out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
     const int log1p = (flags & ILLICO_FLAG_LOG1P) ? 1 : 0, dt = in.dtype;
-    const size_t esz = dtype_size(dt), isz = in.idx_dtype == ILLICO_IDX_I32 ? 4 : 8;
+    const size_t esz = dtype_size(dt);
     void *v = nullptr;
 
     // chunks of the groups' positions (dense, CSR)
     std::vector<GsChunk> hch;
-    gs_chunks(c, hch);
+    group_chunks(c, GS_CHUNK, hch);
     const int n_ch = (int)hch.size();
     GsChunk *d_ch = nullptr;
     if (n_ch) {
@@ -131,25 +97,8 @@ int gs_run(illico_ctx *c, const GsInput &in, int64_t col_lb, int64_t col_ub, int
         HIPCHK(c, hipMemcpyAsync(d_ch, hch.data(), hch.size() * sizeof(GsChunk), hipMemcpyHostToDevice, c->stream));
     }
 
-    // host-resident sparse input goes up once: CSC the entries of [col_lb, col_ub), CSR every row
-    const void *data = in.data, *indices = in.indices, *indptr = in.indptr;
-    long long kshift = 0, ptr_col0 = 0; // entry k at data[k - kshift]; the window's first column is indptr[col - ptr_col0]
-    if (in.sparse && !in.on_dev) {
-        const int64_t a = in.is_csr ? 0 : col_lb, b = in.is_csr ? N : col_ub;
-        const int64_t k0 = idx_at(in.indptr, in.idx_dtype, a), k1 = idx_at(in.indptr, in.idx_dtype, b);
-        if (k0 < 0 || k1 < k0) return fail(c, ILLICO_ERR_ARG, "indptr is not non-decreasing");
-        const size_t nnz = (size_t)(k1 - k0), nptr = (size_t)(b - a + 1);
-        if ((rc = get_scratch(c, "gs_upload", std::max<size_t>(nnz, 1) * (esz + isz) + nptr * isz + 64, &v))) return rc;
-        unsigned char *u = (unsigned char *)v;
-        void *dd = u, *di = u + ((nnz * esz + 15) & ~(size_t)15), *dp = (unsigned char *)di + ((nnz * isz + 15) & ~(size_t)15);
-        HIPCHK(c, hipMemcpyAsync(dd, (const unsigned char *)in.data + (size_t)k0 * esz, nnz * esz, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(di, (const unsigned char *)in.indices + (size_t)k0 * isz, nnz * isz, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dp, (const unsigned char *)in.indptr + (size_t)a * isz, nptr * isz, hipMemcpyHostToDevice, c->stream));
-        c->h2d_input_bytes += (int64_t)(nnz * (esz + isz) + nptr * isz);
-        data = dd; indices = di; indptr = dp;
-        kshift = k0;
-        ptr_col0 = a;
-    }
+    SparseOnDevice sp{}; // host-resident sparse input goes up once: CSC the entries of [col_lb, col_ub), CSR every row
+    if (in.sparse && (rc = stage_sparse_input(c, in, col_lb, col_ub, "gs_upload", &sp))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the chunk list and the staged arrays came from pageable host memory)
 
     // column windows: the [G][wn] planes (+ staged host outputs, + the staged rows of a host dense matrix) fit the scratch cap
@@ -199,20 +148,16 @@ int gs_run(illico_ctx *c, const GsInput &in, int64_t col_lb, int64_t col_ub, int
                 X = (const unsigned char *)xwin;
                 ld = wn;
             }
-            switch (dt) {
-            case ILLICO_F32: rc = gs_dense_window<float>(c, (const float *)X, ld, N, wn, dt, log1p, d_ch, n_ch, P); break;
-            case ILLICO_F64: rc = gs_dense_window<double>(c, (const double *)X, ld, N, wn, dt, log1p, d_ch, n_ch, P); break;
-            case ILLICO_I32: rc = gs_dense_window<int32_t>(c, (const int32_t *)X, ld, N, wn, dt, log1p, d_ch, n_ch, P); break;
-            default: rc = gs_dense_window<int64_t>(c, (const int64_t *)X, ld, N, wn, dt, log1p, d_ch, n_ch, P); break;
-            }
+            rc = dispatch_value_type(dt, [&](auto t) {
+                using InT = typename decltype(t)::type;
+                return gs_dense_window<InT>(c, (const InT *)X, ld, N, wn, dt, log1p, d_ch, n_ch, P);
+            });
         } else {
-            const long long col0 = w0 - ptr_col0;
-            switch (dt) {
-            case ILLICO_F32: rc = gs_sparse_any_idx<float>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, log1p, d_ch, n_ch, P); break;
-            case ILLICO_F64: rc = gs_sparse_any_idx<double>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, log1p, d_ch, n_ch, P); break;
-            case ILLICO_I32: rc = gs_sparse_any_idx<int32_t>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, log1p, d_ch, n_ch, P); break;
-            default: rc = gs_sparse_any_idx<int64_t>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, N, wn, dt, log1p, d_ch, n_ch, P); break;
-            }
+            const long long col0 = w0 - sp.ptr_col0;
+            rc = dispatch_value_index_type(dt, in.idx_dtype, [&](auto t, auto i) {
+                return gs_sparse_window<typename decltype(t)::type, typename decltype(i)::type>(c, in.is_csr, sp.data, sp.indices, sp.indptr, sp.kshift, col0, N, wn,
+                                                                                                 dt, log1p, d_ch, n_ch, P);
+            });
         }
         if (rc) return rc;
         const int gx = (wn + GS_NT - 1) / GS_NT;
@@ -254,56 +199,45 @@ int gs_run(illico_ctx *c, const GsInput &in, int64_t col_lb, int64_t col_ub, int
     return ILLICO_OK;
 }
 
+int gs_entry(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub, int flags, const GsOutputs &o) {
+    if (!c) return ILLICO_ERR_ARG;
+    CTX_LOCK(c);
+    int rc = gs_check(c, in, col_lb, col_ub, o);
+    if (rc) return rc;
+    if (in.sparse) {
+        if (!in.data || !in.indices || !in.indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
+    } else {
+        if (!in.X) return fail(c, ILLICO_ERR_ARG, "null X");
+        if (in.ld < in.n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
+    }
+    return gs_run(c, in, col_lb, col_ub, flags, o);
+}
+
 } // namespace
 
 extern "C" int illico_group_stats_dense(illico_ctx *c, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t col_lb, int64_t col_ub,
                                         int flags, int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest, double *out_sum_rest, int64_t out_ld) {
-    if (!c) return ILLICO_ERR_ARG;
-    CTX_LOCK(c);
-    GsInput in;
-    in.X = X; in.dtype = dtype; in.n_rows = n_rows; in.n_cols = n_cols; in.ld = ld; in.on_dev = flags & ILLICO_FLAG_INPUT_DEVICE;
-    const GsOutputs o{out_nnz, out_nnz_rest, out_sum, out_sum_rest, out_ld};
-    int rc = gs_check(c, in, col_lb, col_ub, o);
-    if (rc) return rc;
-    if (!X) return fail(c, ILLICO_ERR_ARG, "null X");
-    if (ld < n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
-    return gs_run(c, in, col_lb, col_ub, flags, o);
+    return gs_entry(c, dense_input(X, dtype, n_rows, n_cols, ld, flags), col_lb, col_ub, flags, {out_nnz, out_nnz_rest, out_sum, out_sum_rest, out_ld});
 }
-
-static int group_stats_sparse(illico_ctx *c, bool is_csr, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
-                              int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest,
-                              double *out_sum_rest, int64_t out_ld) {
-    if (!c) return ILLICO_ERR_ARG;
-    CTX_LOCK(c);
-    GsInput in;
-    in.sparse = true; in.is_csr = is_csr; in.data = data; in.indices = indices; in.indptr = indptr; in.idx_dtype = idx_dtype; in.dtype = dtype;
-    in.n_rows = n_rows; in.n_cols = n_cols; in.on_dev = flags & ILLICO_FLAG_INPUT_DEVICE;
-    const GsOutputs o{out_nnz, out_nnz_rest, out_sum, out_sum_rest, out_ld};
-    int rc = gs_check(c, in, col_lb, col_ub, o);
-    if (rc) return rc;
-    if (!data || !indices || !indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
-    return gs_run(c, in, col_lb, col_ub, flags, o);
-}
-
 extern "C" int illico_group_stats_csc(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
                                       int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest,
                                       double *out_sum_rest, int64_t out_ld) {
-    return group_stats_sparse(c, false, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, out_nnz, out_sum, out_nnz_rest,
-                              out_sum_rest, out_ld);
+    return gs_entry(c, sparse_input(false, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, flags), col_lb, col_ub, flags,
+                    {out_nnz, out_nnz_rest, out_sum, out_sum_rest, out_ld});
 }
 extern "C" int illico_group_stats_csr(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
                                       int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, int64_t *out_nnz, double *out_sum, int64_t *out_nnz_rest,
                                       double *out_sum_rest, int64_t out_ld) {
-    return group_stats_sparse(c, true, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, out_nnz, out_sum, out_nnz_rest,
-                              out_sum_rest, out_ld);
+    return gs_entry(c, sparse_input(true, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, flags), col_lb, col_ub, flags,
+                    {out_nnz, out_nnz_rest, out_sum, out_sum_rest, out_ld});
 }
 extern "C" int illico_group_stats_bound(illico_ctx *c, const illico_matrix *m, int64_t col_lb, int64_t col_ub, int flags, int64_t *out_nnz, double *out_sum,
                                         int64_t *out_nnz_rest, double *out_sum_rest, int64_t out_ld) {
     if (!c || !m) return ILLICO_ERR_ARG;
-    CTX_LOCK(c); // (held for the whole call: illico_matrix_release on another thread cannot free the arrays under it)
-    if (m->owner != c || std::find(c->bound.begin(), c->bound.end(), m) == c->bound.end())
-        return fail(c, ILLICO_ERR_ARG, "the matrix handle does not belong to this context (or was released)");
-    return group_stats_sparse(c, m->is_csr, m->d_data, m->dtype, m->d_indices, m->d_indptr, m->idx_dtype, m->n_rows, m->n_cols, col_lb, col_ub,
-                              (flags & (ILLICO_FLAG_LOG1P | ILLICO_FLAG_OUTPUT_DEVICE)) | ILLICO_FLAG_INPUT_DEVICE, out_nnz, out_sum, out_nnz_rest, out_sum_rest,
-                              out_ld);
+    CTX_LOCK(c);
+    int rc = check_bound_matrix(c, m);
+    if (rc) return rc;
+    flags = bound_matrix_flags(flags);
+    return gs_entry(c, sparse_input(m->is_csr, m->d_data, m->dtype, m->d_indices, m->d_indptr, m->idx_dtype, m->n_rows, m->n_cols, flags), col_lb, col_ub, flags,
+                    {out_nnz, out_nnz_rest, out_sum, out_sum_rest, out_ld});
 }

@@ -28,10 +28,6 @@
 #define GM_CSR_CW 2048       // CSR: columns per workgroup: 4 limb planes of 8 bytes = 64 KB of LDS, two workgroups per CU
 #define GM_CSC_LDS_G 2048    // CSC: groups held in LDS (32 bytes each, 64 KB: two workgroups per CU); more go through global atomics
 #define GM_VMAX_CW 4096      // CSR max pass: columns per LDS window
-#define GM_NAN 1ull
-#define GM_PINF (1ull << 21)
-#define GM_NINF (1ull << 42)
-#define GM_M21 ((1ull << 21) - 1ull)
 
 struct GmPlanes {
     long long *L0, *L1, *Q0, *Q1;
@@ -44,9 +40,6 @@ struct GmPlanes {
 // a chunk of one group's positions: [p0, p1) of d_perm, all of group g; single = the group's only chunk
 struct GmChunk { int g, p0, p1, single; };
 
-__device__ __forceinline__ bool gm_finite(double x) { return fabs(x) < __longlong_as_double(0x7FF0000000000000ll); }
-__device__ __forceinline__ u64 gm_cat_of(double x) { return x != x ? GM_NAN : (x > 0 ? GM_PINF : GM_NINF); }
-__device__ __forceinline__ u64 gm_absbits(double x) { return (u64)__double_as_longlong(x) & 0x7FFFFFFFFFFFFFFFull; }
 __device__ __forceinline__ double gm_from_bits(u64 b) { return __longlong_as_double((long long)b); }
 // the two scales of a gene from its vmax / vmaxq words
 __device__ __forceinline__ ExsScale gm_scale_x(u64 vb) { return exs_scale(vb ? gm_from_bits(vb) : 1.0); }
@@ -56,10 +49,10 @@ __device__ __forceinline__ ExsScale gm_scale_q(u64 vqb) {
 }
 // a value's part in the two magnitudes
 __device__ __forceinline__ void gm_track(double x, u64 &m, u64 &mq, bool &nf) {
-    if (gm_finite(x)) {
-        const u64 b = gm_absbits(x);
+    if (exs_finite(x)) {
+        const u64 b = exs_absbits(x);
         m = umax_t(m, b);
-        if (gm_finite(x * x)) mq = umax_t(mq, b); else nf = true;
+        if (exs_finite(x * x)) mq = umax_t(mq, b); else nf = true;
     } else nf = true;
 }
 
@@ -69,16 +62,16 @@ __device__ __forceinline__ void gm_add(InT v, const ExsScale &S, const ExsScale 
                                        u64 *ovfp) {
     if (!(v != (InT)0)) return;
     const double x = (double)v;
-    if (gm_finite(x)) {
+    if (exs_finite(x)) {
         long long l0, l1;
         exs_split(x, S, l0, l1);
         a0 += l0; a1 += l1;
         const double q = x * x;
-        if (gm_finite(q)) {
+        if (exs_finite(q)) {
             exs_split(q, SQ, l0, l1);
             b0 += l0; b1 += l1;
         } else atomicAdd(ovfp, 1ull);
-    } else atomicAdd(catp, gm_cat_of(x));
+    } else atomicAdd(catp, exs_cat_of(x));
 }
 
 // ---- dense: the genes' magnitudes ------------------------------------------------------------------------------------------------
@@ -223,12 +216,12 @@ __global__ __launch_bounds__(GM_NT) void k_gm_csc(GmCscParams C, GmPlanes P) {
             const size_t o = (size_t)g * P.W + gene;
             const double x = (double)v;
             long long l0 = 0, l1 = 0, q0 = 0, q1 = 0;
-            if (gm_finite(x)) {
+            if (exs_finite(x)) {
                 exs_split(x, S, l0, l1);
                 const double q = x * x;
-                if (gm_finite(q)) exs_split(q, SQ, q0, q1);
+                if (exs_finite(q)) exs_split(q, SQ, q0, q1);
                 else atomicAdd(&P.ovf[o], 1ull);
-            } else atomicAdd(&P.cat[o], gm_cat_of(x));
+            } else atomicAdd(&P.cat[o], exs_cat_of(x));
             if constexpr (LDSG) {
                 if (l0) atomicAdd((u64 *)&L0[g], (u64)l0);
                 if (l1) atomicAdd((u64 *)&L1[g], (u64)l1);
@@ -279,9 +272,9 @@ __global__ __launch_bounds__(GM_NT) void k_gm_csr_vmax(const InT *__restrict__ d
             if (!(v != (InT)0)) continue;
             const double x = (double)v;
             bool nf = true;
-            if (gm_finite(x)) {
-                const u64 b = gm_absbits(x);
-                nf = !gm_finite(x * x);
+            if (exs_finite(x)) {
+                const u64 b = exs_absbits(x);
+                nf = !exs_finite(x * x);
                 if (nf) atomicMax(&vmax[wo + c], b);
                 else if (b) atomicMax(&sm[c], b);
             }
@@ -320,18 +313,18 @@ __global__ __launch_bounds__(GM_NT) void k_gm_csr(const InT *__restrict__ data, 
             if (!(v != (InT)0)) continue;
             const double x = (double)v;
             const size_t o = (size_t)ch.g * P.W + w0 + c;
-            if (gm_finite(x)) {
+            if (exs_finite(x)) {
                 long long l0, l1;
                 exs_split(x, gm_scale_x(P.vmax[w0 + c]), l0, l1);
                 if (l0) atomicAdd((u64 *)&L[0][c], (u64)l0);
                 if (l1) atomicAdd((u64 *)&L[1][c], (u64)l1);
                 const double q = x * x;
-                if (gm_finite(q)) {
+                if (exs_finite(q)) {
                     exs_split(q, gm_scale_q(P.vmaxq[w0 + c]), l0, l1);
                     if (l0) atomicAdd((u64 *)&L[2][c], (u64)l0);
                     if (l1) atomicAdd((u64 *)&L[3][c], (u64)l1);
                 } else atomicAdd(&P.ovf[o], 1ull);
-            } else atomicAdd(&P.cat[o], gm_cat_of(x));
+            } else atomicAdd(&P.cat[o], exs_cat_of(x));
         }
     }
     __syncthreads();
@@ -366,39 +359,17 @@ static __global__ __launch_bounds__(GM_NT) void k_gm_totals(GmPlanes P, int G, i
         t.TQ += gm_pair(P.Q0[o], P.Q1[o]);
         if (nf) {
             const u64 c = P.cat[o];
-            t.nan += (long long)(c & GM_M21); t.pinf += (long long)((c >> 21) & GM_M21); t.ninf += (long long)(c >> 42);
+            t.nan += (long long)(c & EXS_M21); t.pinf += (long long)((c >> 21) & EXS_M21); t.ninf += (long long)(c >> 42);
             t.ovf += (long long)P.ovf[o];
         }
     }
     part[(size_t)blockIdx.y * W + j] = t;
 }
 
-// T / 2^k rounded to float64 once (exs_combine for a 128-bit total)
-__device__ __forceinline__ double gm_combine128(__int128 T, const ExsScale &S) {
-    const bool neg = T < 0;
-    const unsigned __int128 a = neg ? (unsigned __int128)(-T) : (unsigned __int128)T;
-    const u64 hi = (u64)(a >> 64), lo = (u64)a;
-    double r;
-    if (hi == 0) r = (double)lo;
-    else {
-        const int s = 64 - __clzll((long long)hi);
-        u64 top = (hi << (64 - s)) | (lo >> s);
-        if ((lo << (64 - s)) != 0ull) top |= 1ull;
-        r = (double)top * exs_pow2(s);
-    }
-    r = r * S.u1 * S.u2;
-    return neg ? -r : r;
-}
-__device__ __forceinline__ double gm_sum_value(__int128 T, long long nan, long long pinf, long long ninf, const ExsScale &S) {
-    if (nan || (pinf && ninf)) return __longlong_as_double(0x7FF8000000000000ll);
-    if (pinf) return __longlong_as_double(0x7FF0000000000000ll);
-    if (ninf) return -__longlong_as_double(0x7FF0000000000000ll);
-    return gm_combine128(T, S);
-}
 __device__ __forceinline__ double gm_sumsq_value(__int128 TQ, long long nan, long long inf, const ExsScale &SQ) {
     if (nan) return __longlong_as_double(0x7FF8000000000000ll);
     if (inf) return __longlong_as_double(0x7FF0000000000000ll);
-    return gm_combine128(TQ, SQ);
+    return exs_combine128(TQ, SQ);
 }
 
 struct GmOut {
@@ -422,13 +393,13 @@ static __global__ __launch_bounds__(GM_NT) void k_gm_finalize(GmPlanes P, int G,
         long long a = 0, b = 0, c = 0, v = 0;
         if (nf) {
             const u64 w = P.cat[o];
-            a = (long long)(w & GM_M21); b = (long long)((w >> 21) & GM_M21); c = (long long)(w >> 42);
+            a = (long long)(w & EXS_M21); b = (long long)((w >> 21) & EXS_M21); c = (long long)(w >> 42);
             v = (long long)P.ovf[o];
         }
         if (O.sum || O.sum_rest) {
             const __int128 own = gm_pair(P.L0[o], P.L1[o]);
-            if (O.sum) O.sum[q] = gm_sum_value(own, a, b, c, S);
-            if (O.sum_rest) O.sum_rest[q] = gm_sum_value(t.T - own, t.nan - a, t.pinf - b, t.ninf - c, S);
+            if (O.sum) O.sum[q] = exs_sum_value(own, a, b, c, S);
+            if (O.sum_rest) O.sum_rest[q] = exs_sum_value(t.T - own, t.nan - a, t.pinf - b, t.ninf - c, S);
         }
         if (O.sumsq || O.sumsq_rest) {
             const __int128 own = gm_pair(P.Q0[o], P.Q1[o]);

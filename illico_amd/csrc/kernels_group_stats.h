@@ -11,7 +11,7 @@
 // gene's largest magnitude are truncated there, see kernels_sums.h).
 //
 // Non-finite values (NaN, +inf, -inf, or an expm1 that overflows) are kept out of the limbs and counted per (group, gene) in one
-// packed word (GS_NAN / GS_PINF / GS_NINF, 21 bits each); a sum that meets one is NaN, +inf or -inf as numpy's would be.
+// packed word (EXS_NAN / EXS_PINF / EXS_NINF, 21 bits each); a sum that meets one is NaN, +inf or -inf as numpy's would be.
 //
 // Planes (device scratch, row-major [G][W], W = the window's width): L0 / L1 limb sums, cnt non-zero counts, cat non-finite
 // counts; vmax[W] the bits of each gene's largest finite |x| (u64 atomicMax: non-negative doubles order as their bit patterns),
@@ -26,10 +26,6 @@
 #define GS_CSR_CW 2048       // CSR: columns per workgroup (LDS counters + limbs)
 #define GS_CSC_LDS_G 4096    // CSC: groups held in LDS; more go through global atomics on the planes
 #define GS_VMAX_CW 8192      // CSR max pass: columns per LDS window
-#define GS_NAN 1ull
-#define GS_PINF (1ull << 21)
-#define GS_NINF (1ull << 42)
-#define GS_M21 ((1ull << 21) - 1ull)
 
 struct GsPlanes {
     long long *L0, *L1, *cnt;
@@ -42,9 +38,6 @@ struct GsPlanes {
 // a chunk of one group's positions: [p0, p1) of d_perm, all of group g; single = the group's only chunk
 struct GsChunk { int g, p0, p1, single; };
 
-__device__ __forceinline__ bool gs_finite(double x) { return fabs(x) < __longlong_as_double(0x7FF0000000000000ll); }
-__device__ __forceinline__ u64 gs_cat_of(double x) { return x != x ? GS_NAN : (x > 0 ? GS_PINF : GS_NINF); }
-__device__ __forceinline__ u64 gs_absbits(double x) { return (u64)__double_as_longlong(x) & 0x7FFFFFFFFFFFFFFFull; }
 
 // one value into a lane's (l0, l1, n) accumulators; a non-finite x goes straight to the packed counter word of its (group, gene)
 template <typename InT>
@@ -52,11 +45,11 @@ __device__ __forceinline__ void gs_add(InT v, int dt, int is_log1p, const ExsSca
     if (!(v != (InT)0)) return;
     ++n;
     const double x = sums_value(v, dt, is_log1p);
-    if (gs_finite(x)) {
+    if (exs_finite(x)) {
         long long l0, l1;
         exs_split(x, S, l0, l1);
         a0 += l0; a1 += l1;
-    } else atomicAdd(catp, gs_cat_of(x));
+    } else atomicAdd(catp, exs_cat_of(x));
 }
 
 // ---- dense: the genes' largest finite magnitudes -------------------------------------------------------------------------------
@@ -78,14 +71,14 @@ __global__ __launch_bounds__(GS_NT) void k_gs_dense_vmax(const InT *__restrict__
         for (int u = 0; u < 4; ++u)
             if (v[u] != (InT)0) {
                 const double x = sums_value(v[u], dt, is_log1p);
-                if (gs_finite(x)) m = umax_t(m, gs_absbits(x)); else nf = true;
+                if (exs_finite(x)) m = umax_t(m, exs_absbits(x)); else nf = true;
             }
     }
     for (; r < r1; ++r) {
         const InT v = X[(size_t)r * ld + j];
         if (v != (InT)0) {
             const double x = sums_value(v, dt, is_log1p);
-            if (gs_finite(x)) m = umax_t(m, gs_absbits(x)); else nf = true;
+            if (exs_finite(x)) m = umax_t(m, exs_absbits(x)); else nf = true;
         }
     }
     if (m) atomicMax(&vmax[j], m);
@@ -185,7 +178,7 @@ __global__ __launch_bounds__(GS_NT) void k_gs_csc(GsCscParams C, GsPlanes P) {
             const InT v = data[k];
             if (v != (InT)0) {
                 const double x = sums_value(v, C.dt, C.is_log1p);
-                if (gs_finite(x)) m = umax_t(m, gs_absbits(x)); else nf = true;
+                if (exs_finite(x)) m = umax_t(m, exs_absbits(x)); else nf = true;
             }
         }
 #pragma unroll
@@ -207,9 +200,9 @@ __global__ __launch_bounds__(GS_NT) void k_gs_csc(GsCscParams C, GsPlanes P) {
             const size_t o = (size_t)g * P.W + gene;
             const double x = sums_value(v, C.dt, C.is_log1p);
             long long l0 = 0, l1 = 0;
-            const bool fin = gs_finite(x);
+            const bool fin = exs_finite(x);
             if (fin) exs_split(x, S, l0, l1);
-            else atomicAdd(&P.cat[o], gs_cat_of(x));
+            else atomicAdd(&P.cat[o], exs_cat_of(x));
             if constexpr (LDSG) {
                 atomicAdd(&CN[g], 1);
                 if (l0) atomicAdd((u64 *)&L0[g], (u64)l0);
@@ -255,7 +248,7 @@ __global__ __launch_bounds__(GS_NT) void k_gs_csr_vmax(const InT *__restrict__ d
             const InT v = data[k];
             if (!(v != (InT)0)) continue;
             const double x = sums_value(v, dt, is_log1p);
-            if (gs_finite(x)) { const u64 b = gs_absbits(x); if (b) atomicMax(&sm[c], b); }
+            if (exs_finite(x)) { const u64 b = exs_absbits(x); if (b) atomicMax(&sm[c], b); }
             else atomicOr(&snf[c >> 5], 1 << (c & 31));
         }
     }
@@ -293,14 +286,14 @@ __global__ __launch_bounds__(GS_NT) void k_gs_csr(const InT *__restrict__ data, 
             if (!(v != (InT)0)) continue;
             atomicAdd(&CN[c], 1);
             const double x = sums_value(v, dt, is_log1p);
-            if (gs_finite(x)) {
+            if (exs_finite(x)) {
                 const u64 vb = P.vmax[w0 + c];
                 const ExsScale S = exs_scale(vb ? __longlong_as_double((long long)vb) : 1.0);
                 long long l0, l1;
                 exs_split(x, S, l0, l1);
                 if (l0) atomicAdd((u64 *)&L0[c], (u64)l0);
                 if (l1) atomicAdd((u64 *)&L1[c], (u64)l1);
-            } else atomicAdd(&P.cat[(size_t)ch.g * P.W + w0 + c], gs_cat_of(x));
+            } else atomicAdd(&P.cat[(size_t)ch.g * P.W + w0 + c], exs_cat_of(x));
         }
     }
     __syncthreads();
@@ -332,33 +325,11 @@ __global__ __launch_bounds__(GS_NT) void k_gs_totals(GsPlanes P, int G, int W, G
         const size_t o = (size_t)g * P.W + j;
         t.T += (__int128)P.L1[o] * ((__int128)1 << EXS_LIMB) + (__int128)P.L0[o];
         t.n += P.cnt[o];
-        if (nf) { const u64 c = P.cat[o]; t.nan += (long long)(c & GS_M21); t.pinf += (long long)((c >> 21) & GS_M21); t.ninf += (long long)(c >> 42); }
+        if (nf) { const u64 c = P.cat[o]; t.nan += (long long)(c & EXS_M21); t.pinf += (long long)((c >> 21) & EXS_M21); t.ninf += (long long)(c >> 42); }
     }
     part[(size_t)blockIdx.y * W + j] = t;
 }
 
-// T / 2^k rounded to float64 once (exs_combine for a 128-bit total)
-__device__ __forceinline__ double gs_combine128(__int128 T, const ExsScale &S) {
-    const bool neg = T < 0;
-    const unsigned __int128 a = neg ? (unsigned __int128)(-T) : (unsigned __int128)T;
-    const u64 hi = (u64)(a >> 64), lo = (u64)a;
-    double r;
-    if (hi == 0) r = (double)lo;
-    else {
-        const int s = 64 - __clzll((long long)hi);
-        u64 top = (hi << (64 - s)) | (lo >> s);
-        if ((lo << (64 - s)) != 0ull) top |= 1ull;
-        r = (double)top * exs_pow2(s);
-    }
-    r = r * S.u1 * S.u2;
-    return neg ? -r : r;
-}
-__device__ __forceinline__ double gs_sum_value(__int128 T, long long nan, long long pinf, long long ninf, const ExsScale &S) {
-    if (nan || (pinf && ninf)) return __longlong_as_double(0x7FF8000000000000ll);
-    if (pinf) return __longlong_as_double(0x7FF0000000000000ll);
-    if (ninf) return -__longlong_as_double(0x7FF0000000000000ll);
-    return gs_combine128(T, S);
-}
 
 struct GsOut {
     long long *nnz, *nnz_rest;
@@ -386,9 +357,9 @@ __global__ __launch_bounds__(GS_NT) void k_gs_finalize(GsPlanes P, int G, int W,
         if (O.sum || O.sum_rest) {
             const __int128 own = (__int128)P.L1[o] * ((__int128)1 << EXS_LIMB) + (__int128)P.L0[o];
             long long a = 0, b = 0, c = 0;
-            if (nf) { const u64 w = P.cat[o]; a = (long long)(w & GS_M21); b = (long long)((w >> 21) & GS_M21); c = (long long)(w >> 42); }
-            if (O.sum) O.sum[q] = gs_sum_value(own, a, b, c, S);
-            if (O.sum_rest) O.sum_rest[q] = gs_sum_value(t.T - own, t.nan - a, t.pinf - b, t.ninf - c, S);
+            if (nf) { const u64 w = P.cat[o]; a = (long long)(w & EXS_M21); b = (long long)((w >> 21) & EXS_M21); c = (long long)(w >> 42); }
+            if (O.sum) O.sum[q] = exs_sum_value(own, a, b, c, S);
+            if (O.sum_rest) O.sum_rest[q] = exs_sum_value(t.T - own, t.nan - a, t.pinf - b, t.ninf - c, S);
         }
     }
 }

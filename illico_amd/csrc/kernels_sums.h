@@ -76,6 +76,39 @@ __device__ __forceinline__ double exs_combine(long long L0, long long L1, const 
     return neg ? -r : r;
 }
 
+// ---- shared by the exact per-group passes (kernels_group_stats.h, kernels_group_moments.h) --------------------------------------
+// Non-finite values stay out of the limbs: they are counted per (group, gene) in one packed word, 21 bits per kind
+#define EXS_NAN 1ull
+#define EXS_PINF (1ull << 21)
+#define EXS_NINF (1ull << 42)
+#define EXS_M21 ((1ull << 21) - 1ull)
+__device__ __forceinline__ bool exs_finite(double x) { return fabs(x) < __longlong_as_double(0x7FF0000000000000ll); }
+__device__ __forceinline__ u64 exs_cat_of(double x) { return x != x ? EXS_NAN : (x > 0 ? EXS_PINF : EXS_NINF); }
+__device__ __forceinline__ u64 exs_absbits(double x) { return (u64)__double_as_longlong(x) & 0x7FFFFFFFFFFFFFFFull; }
+// T / 2^k rounded to float64 once (exs_combine for a 128-bit total)
+__device__ __forceinline__ double exs_combine128(__int128 T, const ExsScale &S) {
+    const bool neg = T < 0;
+    const unsigned __int128 a = neg ? (unsigned __int128)(-T) : (unsigned __int128)T;
+    const u64 hi = (u64)(a >> 64), lo = (u64)a;
+    double r;
+    if (hi == 0) r = (double)lo;
+    else {
+        const int s = 64 - __clzll((long long)hi);
+        u64 top = (hi << (64 - s)) | (lo >> s);
+        if ((lo << (64 - s)) != 0ull) top |= 1ull;
+        r = (double)top * exs_pow2(s);
+    }
+    r = r * S.u1 * S.u2;
+    return neg ? -r : r;
+}
+// a sum from its 128-bit total and the counts of the non-finite values it met: NaN, +inf or -inf as numpy's would be
+__device__ __forceinline__ double exs_sum_value(__int128 T, long long nan, long long pinf, long long ninf, const ExsScale &S) {
+    if (nan || (pinf && ninf)) return __longlong_as_double(0x7FF8000000000000ll);
+    if (pinf) return __longlong_as_double(0x7FF0000000000000ll);
+    if (ninf) return -__longlong_as_double(0x7FF0000000000000ll);
+    return exs_combine128(T, S);
+}
+
 template <typename InT> __device__ __forceinline__ double sums_value(InT v, int dt, int is_log1p) {
     return is_log1p ? key_to_expm1(key_of(v), dt) : (double)v;
 }

@@ -1,30 +1,15 @@
 // illico_group_value_hists_{dense,csc,csr}: per-(group, gene) histograms of the values 0 .. 255 from one pass over the matrix;
 // illico_pairwise_from_hists: the Wilcoxon rank-sum test of every ordered pair of groups from those histograms (kernels_pairwise.h).
-// A translation unit of its own: siblings of the one-versus-reference routes, which it does not touch.
-#include "engine.h"
+// A translation unit of its own: siblings of the one-versus-reference routes, which it does not touch; the host scaffolding of the
+// histogram pass (input description, common checks, sparse upload, type dispatch) is shared with the other group passes (group_pass.h).
+#include "group_pass.h"
 #include "kernels_pairwise.h"
 
 namespace {
 
-struct PwInput {
-    bool sparse = false, is_csr = false, on_dev = false;
-    const void *X = nullptr; // dense
-    int64_t ld = 0;
-    const void *data = nullptr, *indices = nullptr, *indptr = nullptr; // sparse
-    int idx_dtype = 0;
-    int dtype = 0;
-    int64_t n_rows = 0, n_cols = 0;
-};
-
-int pw_check(illico_ctx *c, const PwInput &in, int64_t col_lb, int64_t col_ub, const uint32_t *H, const uint32_t *fl) {
-    if (!c->has_groups) return fail(c, ILLICO_ERR_NO_GROUPS, "illico_set_groups has not been called");
-    if (in.n_rows != c->n_cells)
-        return fail(c, ILLICO_ERR_NO_GROUPS, "X has %lld rows but the groups describe %lld cells", (long long)in.n_rows, (long long)c->n_cells);
-    if (col_lb < 0 || col_ub > in.n_cols || col_lb > col_ub)
-        return fail(c, ILLICO_ERR_BOUNDS, "Invalid chunk bounds: (%lld, %lld) for data with %lld columns.", (long long)col_lb, (long long)col_ub, (long long)in.n_cols);
-    if (in.dtype < 0 || in.dtype > 3) return fail(c, ILLICO_ERR_DTYPE, "unsupported dtype code %d", in.dtype);
-    if (in.sparse && in.idx_dtype != ILLICO_IDX_I32 && in.idx_dtype != ILLICO_IDX_I64)
-        return fail(c, ILLICO_ERR_DTYPE, "unsupported index dtype code %d", in.idx_dtype);
+int pw_check(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub, const uint32_t *H, const uint32_t *fl) {
+    int rc = check_matrix_input(c, in, col_lb, col_ub);
+    if (rc) return rc;
     if (col_ub > col_lb && (!H || !fl)) return fail(c, ILLICO_ERR_ARG, "null out_H / out_flags");
     return ILLICO_OK;
 }
@@ -80,15 +65,6 @@ int pw_sparse(illico_ctx *c, bool is_csr, const void *data, const void *indices,
     return ILLICO_OK;
 }
 
-template <typename InT>
-int pw_sparse_any_idx(illico_ctx *c, bool is_csr, int idx_dtype, const void *data, const void *indices, const void *indptr, long long kshift, long long col0,
-                      int wn, u32 *H, u32 *d_flags) {
-    if (idx_dtype == ILLICO_IDX_I32) return pw_sparse<InT, int32_t>(c, is_csr, data, indices, indptr, kshift, col0, wn, H, d_flags);
-    return pw_sparse<InT, int64_t>(c, is_csr, data, indices, indptr, kshift, col0, wn, H, d_flags);
-}
-
-int64_t pw_idx_at(const void *p, int idx_dtype, int64_t i) { return idx_dtype == ILLICO_IDX_I32 ? (int64_t)((const int32_t *)p)[i] : ((const int64_t *)p)[i]; }
-
 int pw_budget(illico_ctx *c, size_t need, const char *what) {
     if (need > (size_t)std::max<int64_t>(c->scratch_bytes, 1))
         return fail(c, ILLICO_ERR_OOM, "%s needs %zu bytes of device scratch, the budget (\"scratch_bytes\") is %lld: pass a narrower gene window", what, need,
@@ -96,7 +72,7 @@ int pw_budget(illico_ctx *c, size_t need, const char *what) {
     return ILLICO_OK;
 }
 
-int pw_hists_run(illico_ctx *c, const PwInput &in, int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags) {
+int pw_hists_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags) {
     HIPCHK(c, hipSetDevice(c->device));
     int rc = resolve_pending(c);
     if (rc) return rc;
@@ -106,7 +82,7 @@ int pw_hists_run(illico_ctx *c, const PwInput &in, int64_t col_lb, int64_t col_u
     if (G > 65535) return fail(c, ILLICO_ERR_UNSUPPORTED, "%lld groups: the histogram passes take up to 65535", (long long)G);
     const bool out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
     const int dt = in.dtype, wn = (int)W, tiles = (wn + 63) / 64;
-    const size_t esz = dtype_size(dt), isz = in.idx_dtype == ILLICO_IDX_I32 ? 4 : 8;
+    const size_t esz = dtype_size(dt);
     const size_t h_bytes = (size_t)G * W * PW_RT * 4, t_bytes = in.sparse ? 0 : (size_t)G * tiles * PW_TILE_WORDS * 4;
     const size_t x_bytes = (!in.sparse && !in.on_dev) ? (size_t)N * W * esz : 0;
     if ((rc = pw_budget(c, (out_dev ? 0 : h_bytes + (size_t)W * 4) + t_bytes + x_bytes, "illico_group_value_hists"))) return rc;
@@ -132,45 +108,20 @@ int pw_hists_run(illico_ctx *c, const PwInput &in, int64_t col_lb, int64_t col_u
             c->h2d_input_bytes += (int64_t)x_bytes;
             X = v; ld = W; col0 = 0;
         }
-        switch (dt) {
-        case ILLICO_F32: rc = pw_dense<float>(c, X, ld, col0, wn, tiles, T, d_flags); break;
-        case ILLICO_F64: rc = pw_dense<double>(c, X, ld, col0, wn, tiles, T, d_flags); break;
-        case ILLICO_I32: rc = pw_dense<int32_t>(c, X, ld, col0, wn, tiles, T, d_flags); break;
-        default: rc = pw_dense<int64_t>(c, X, ld, col0, wn, tiles, T, d_flags); break;
-        }
+        rc = dispatch_value_type(dt, [&](auto t) { return pw_dense<typename decltype(t)::type>(c, X, ld, col0, wn, tiles, T, d_flags); });
         if (rc) return rc;
         ProfScope ps(c, KID_PW_HIST_FINISH);
         hipLaunchKernelGGL(k_pw_transpose<true>, dim3(tiles, (unsigned)G), dim3(PW_NT), 0, c->stream, d_H, T, (const int *)nullptr, wn, tiles);
         HIPCHK(c, hipGetLastError());
     } else {
-        // host-resident sparse input goes up once: CSC the entries of [col_lb, col_ub), CSR every row
-        const void *data = in.data, *indices = in.indices, *indptr = in.indptr;
-        long long kshift = 0, ptr_col0 = 0; // entry k at data[k - kshift]; the window's first column is indptr[col - ptr_col0]
-        if (!in.on_dev) {
-            const int64_t a = in.is_csr ? 0 : col_lb, b = in.is_csr ? N : col_ub;
-            const int64_t k0 = pw_idx_at(in.indptr, in.idx_dtype, a), k1 = pw_idx_at(in.indptr, in.idx_dtype, b);
-            if (k0 < 0 || k1 < k0) return fail(c, ILLICO_ERR_ARG, "indptr is not non-decreasing");
-            const size_t nnz = (size_t)(k1 - k0), nptr = (size_t)(b - a + 1);
-            if ((rc = get_scratch(c, "pw_upload", std::max<size_t>(nnz, 1) * (esz + isz) + nptr * isz + 64, &v))) return rc;
-            unsigned char *u = (unsigned char *)v;
-            void *dd = u, *di = u + ((nnz * esz + 15) & ~(size_t)15), *dp = (unsigned char *)di + ((nnz * isz + 15) & ~(size_t)15);
-            HIPCHK(c, hipMemcpyAsync(dd, (const unsigned char *)in.data + (size_t)k0 * esz, nnz * esz, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(di, (const unsigned char *)in.indices + (size_t)k0 * isz, nnz * isz, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(dp, (const unsigned char *)in.indptr + (size_t)a * isz, nptr * isz, hipMemcpyHostToDevice, c->stream));
-            c->h2d_input_bytes += (int64_t)(nnz * (esz + isz) + nptr * isz);
-            HIPCHK(c, hipStreamSynchronize(c->stream)); // (the arrays came from pageable host memory)
-            data = dd; indices = di; indptr = dp;
-            kshift = k0;
-            ptr_col0 = a;
-        }
+        SparseOnDevice sp; // host-resident sparse input goes up once: CSC the entries of [col_lb, col_ub), CSR every row
+        if ((rc = stage_sparse_input(c, in, col_lb, col_ub, "pw_upload", &sp))) return rc;
+        if (!in.on_dev) HIPCHK(c, hipStreamSynchronize(c->stream)); // (the arrays came from pageable host memory)
         // CSC: indptr is indexed by column (shifted by what was uploaded); CSR: by row, and col0 is the window's first column
-        const long long col0 = in.is_csr ? col_lb : col_lb - ptr_col0;
-        switch (dt) {
-        case ILLICO_F32: rc = pw_sparse_any_idx<float>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, wn, d_H, d_flags); break;
-        case ILLICO_F64: rc = pw_sparse_any_idx<double>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, wn, d_H, d_flags); break;
-        case ILLICO_I32: rc = pw_sparse_any_idx<int32_t>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, wn, d_H, d_flags); break;
-        default: rc = pw_sparse_any_idx<int64_t>(c, in.is_csr, in.idx_dtype, data, indices, indptr, kshift, col0, wn, d_H, d_flags); break;
-        }
+        const long long col0 = in.is_csr ? col_lb : col_lb - sp.ptr_col0;
+        rc = dispatch_value_index_type(dt, in.idx_dtype, [&](auto t, auto i) {
+            return pw_sparse<typename decltype(t)::type, typename decltype(i)::type>(c, in.is_csr, sp.data, sp.indices, sp.indptr, sp.kshift, col0, wn, d_H, d_flags);
+        });
         if (rc) return rc;
     }
     if (!out_dev) {
@@ -181,16 +132,17 @@ int pw_hists_run(illico_ctx *c, const PwInput &in, int64_t col_lb, int64_t col_u
     return ILLICO_OK;
 }
 
-int pw_hists_sparse(illico_ctx *c, bool is_csr, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
-                    int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags) {
+int pw_hists_entry(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags) {
     if (!c) return ILLICO_ERR_ARG;
     CTX_LOCK(c);
-    PwInput in;
-    in.sparse = true; in.is_csr = is_csr; in.data = data; in.indices = indices; in.indptr = indptr; in.idx_dtype = idx_dtype; in.dtype = dtype;
-    in.n_rows = n_rows; in.n_cols = n_cols; in.on_dev = flags & ILLICO_FLAG_INPUT_DEVICE;
     int rc = pw_check(c, in, col_lb, col_ub, out_H, out_flags);
     if (rc) return rc;
-    if (!data || !indices || !indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
+    if (in.sparse) {
+        if (!in.data || !in.indices || !in.indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
+    } else {
+        if (!in.X) return fail(c, ILLICO_ERR_ARG, "null X");
+        if (in.ld < in.n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
+    }
     return pw_hists_run(c, in, col_lb, col_ub, flags, out_H, out_flags);
 }
 
@@ -198,23 +150,15 @@ int pw_hists_sparse(illico_ctx *c, bool is_csr, const void *data, int dtype, con
 
 extern "C" int illico_group_value_hists_dense(illico_ctx *c, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t col_lb,
                                               int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags) {
-    if (!c) return ILLICO_ERR_ARG;
-    CTX_LOCK(c);
-    PwInput in;
-    in.X = X; in.dtype = dtype; in.n_rows = n_rows; in.n_cols = n_cols; in.ld = ld; in.on_dev = flags & ILLICO_FLAG_INPUT_DEVICE;
-    int rc = pw_check(c, in, col_lb, col_ub, out_H, out_flags);
-    if (rc) return rc;
-    if (!X) return fail(c, ILLICO_ERR_ARG, "null X");
-    if (ld < n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
-    return pw_hists_run(c, in, col_lb, col_ub, flags, out_H, out_flags);
+    return pw_hists_entry(c, dense_input(X, dtype, n_rows, n_cols, ld, flags), col_lb, col_ub, flags, out_H, out_flags);
 }
 extern "C" int illico_group_value_hists_csc(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
                                             int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags) {
-    return pw_hists_sparse(c, false, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, out_H, out_flags);
+    return pw_hists_entry(c, sparse_input(false, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, flags), col_lb, col_ub, flags, out_H, out_flags);
 }
 extern "C" int illico_group_value_hists_csr(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
                                             int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, uint32_t *out_H, uint32_t *out_flags) {
-    return pw_hists_sparse(c, true, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, out_H, out_flags);
+    return pw_hists_entry(c, sparse_input(true, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, flags), col_lb, col_ub, flags, out_H, out_flags);
 }
 
 extern "C" int illico_pairwise_from_hists(illico_ctx *c, const uint32_t *H, const uint32_t *gene_flags, const int64_t *counts, int64_t n_groups, int64_t n_cols,
