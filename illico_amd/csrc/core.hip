@@ -1,6 +1,7 @@
 // libillico_hip: MI355X (gfx950) engine behind include/illico_hip.h.
-// This translation unit: context, device scratch, groups, output staging, the C-ABI entry points and the dispatch on value / index
-// types.  The kernels live in the per-type translation units (dense_*.hip, sparse_*.hip, keyed_*.hip).
+// This translation unit: context, device scratch, groups, output staging, the deferred-call protocol (run_with_outputs,
+// reserve_deferred_slot / post_deferred_call, resolve_pending) and the C-ABI entry points of the Wilcoxon routes.  The kernels live in
+// the per-type translation units (dense_*.hip, sparse_*.hip, keyed_*.hip); the dispatch on the value / index types is engine.h's.
 #include "engine.h"
 
 const char *const kKernelNames[KID_COUNT] = {"k_transpose_permute", "k_ovo_rank", "k_ovo_counts", "k_ovo_fused", "k_ovr_fused",
@@ -298,19 +299,20 @@ int illico_profile_reset(illico_ctx *c) {
 }
 
 // ---- groups ---------------------------------------------------------------------------------
-int illico_set_groups(illico_ctx *c, const int64_t *encoded_groups, const int64_t *counts, const int64_t *indices,
-                      const int64_t *indptr, int64_t n_cells, int64_t n_groups, int64_t ref) {
-    if (!c) return ILLICO_ERR_ARG;
-    CTX_LOCK(c);
-    if (!encoded_groups || !counts || !indices || !indptr) return fail(c, ILLICO_ERR_ARG, "null group array");
-    if (n_cells <= 0 || n_groups <= 0 || n_cells > 0x7FFFFFF0ll) return fail(c, ILLICO_ERR_ARG, "bad n_cells/n_groups");
-    if (ref < -1 || ref >= n_groups) return fail(c, ILLICO_ERR_ARG, "encoded_ref_group out of range");
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc0 = resolve_pending(c); if (rc0) return rc0; } // (its leftover genes need the groups it was made with)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_groups(c);
+} // extern "C"
+// a host vector as a fresh device array
+template <typename T> static int to_device(illico_ctx *c, const std::vector<T> &h, T **d) {
+    HIPCHK(c, hipMalloc((void **)d, h.size() * sizeof(T)));
+    HIPCHK(c, hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    return ILLICO_OK;
+}
+
+// the cells' positions and codes -- [N] code of each cell (and as 16-bit values), [N] cell and code at each group-contiguous position,
+// [G+1] first position, [G] counts -- after the checks of the four group arrays against each other
+static int lay_out_positions(illico_ctx *c, const int64_t *encoded_groups, const int64_t *counts, const int64_t *indices, const int64_t *indptr,
+                             int64_t n_cells, int64_t n_groups, int64_t ref, std::vector<int> &cnt, int64_t *max_nonref_out) {
     // perm is padded with valid indices: tail chunks of k_ovo_fused read (and discard) up to 8 entries past a group's end
-    std::vector<int> codes(n_cells), perm(n_cells + 64, 0), cbp(n_cells), posptr(n_groups + 1), cnt(n_groups);
+    std::vector<int> codes(n_cells), perm(n_cells + 64, 0), cbp(n_cells), posptr(n_groups + 1);
     int64_t tot = 0, max_nonref = 0;
     for (int64_t g = 0; g < n_groups; ++g) {
         if (counts[g] < 0 || indptr[g] != tot) return fail(c, ILLICO_ERR_ARG, "indptr/counts inconsistent at group %lld", (long long)g);
@@ -343,141 +345,137 @@ int illico_set_groups(illico_ctx *c, const int64_t *encoded_groups, const int64_
             perm[p] = (int)cell;
             cbp[p] = (int)g;
         }
-    auto up = [&](int **d, const std::vector<int> &h) -> int {
-        HIPCHK(c, hipMalloc((void **)d, h.size() * sizeof(int)));
-        HIPCHK(c, hipMemcpy(*d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
-        return ILLICO_OK;
-    };
+    *max_nonref_out = max_nonref;
     int rc;
-    if ((rc = up(&c->d_codes, codes)) || (rc = up(&c->d_perm, perm)) || (rc = up(&c->d_posptr, posptr)) ||
-        (rc = up(&c->d_counts, cnt)) || (rc = up(&c->d_code_by_pos, cbp)))
+    if ((rc = to_device(c, codes, &c->d_codes)) || (rc = to_device(c, perm, &c->d_perm)) || (rc = to_device(c, posptr, &c->d_posptr)) ||
+        (rc = to_device(c, cnt, &c->d_counts)) || (rc = to_device(c, cbp, &c->d_code_by_pos)))
         return rc;
-    {
-        std::vector<GroupConst> gc(n_groups);
-        for (int64_t g = 0; g < n_groups; ++g) {
-            const long long n_tgt = cnt[g], n_ref = ref >= 0 ? (long long)cnt[ref] : (long long)n_cells - n_tgt;
-            gc[g] = group_const(n_ref, n_tgt, ref >= 0 ? n_ref + n_tgt : (long long)n_cells);
-        }
-        HIPCHK(c, hipMalloc((void **)&c->d_gconst, gc.size() * sizeof(GroupConst)));
-        HIPCHK(c, hipMemcpy(c->d_gconst, gc.data(), gc.size() * sizeof(GroupConst), hipMemcpyHostToDevice));
+    if (n_groups > 65535) return ILLICO_OK;
+    return to_device(c, std::vector<u16>(codes.begin(), codes.end()), &c->d_codes16);
+}
+
+// blocks of the packed / padded dense layouts -- consecutive groups (never the reference) of >= GCMP_BLOCK_ROWS rows together: [g0, g1)
+// and first key slot `out` of each -- with their order, long and big lists
+static int lay_out_packed_blocks(illico_ctx *c, const int64_t *counts, int64_t n_groups, int64_t ref, std::vector<int> &g0, std::vector<int> &g1,
+                                 std::vector<int> &out) {
+    std::vector<int64_t> rows_b; // rows of each block
+    int64_t pos = 0, rows = 0;
+    bool open = false;
+    auto close = [&](int64_t end) { g1.push_back((int)end); rows_b.push_back(rows); pos += (rows + 63) & ~63ll; open = false; };
+    for (int64_t g = 0; g < n_groups; ++g) {
+        if (g == ref) { if (open) close(g); continue; }
+        if (!open) { g0.push_back((int)g); out.push_back((int)pos); rows = 0; open = true; }
+        rows += counts[g];
+        if (rows >= GCMP_BLOCK_ROWS) close(g + 1);
     }
-    {
-        std::vector<u32> ho(n_groups + 1, 0u);
-        for (int64_t g = 0; g < n_groups; ++g) ho[g + 1] = ho[g] + (counts[g] <= 255 ? 16u : 32u);
-        HIPCHK(c, hipMalloc((void **)&c->d_hist_off, ho.size() * sizeof(u32)));
-        HIPCHK(c, hipMemcpy(c->d_hist_off, ho.data(), ho.size() * sizeof(u32), hipMemcpyHostToDevice));
-        c->hist_words = ho[n_groups];
+    if (open) close(n_groups);
+    std::vector<int> packed;
+    packed.insert(packed.end(), g0.begin(), g0.end());
+    packed.insert(packed.end(), g1.begin(), g1.end());
+    packed.insert(packed.end(), out.begin(), out.end());
+    if (packed.empty()) packed.push_back(0);
+    c->pk_nblk = (int)g0.size();
+    int rc;
+    int64_t tot = 0;
+    c->pk_max_block_rows = 0;
+    for (int64_t r : rows_b) { tot += r; c->pk_max_block_rows = std::max(c->pk_max_block_rows, r); }
+    // blocks of very different lengths (clusters from fifty to tens of thousands of cells): k_group_compact numbers its workgroups
+    // block-major, longest block first, so that a long block's chain of chunks starts with the launch instead of ending it
+    if (g0.size() >= 2 && c->pk_max_block_rows * (int64_t)g0.size() >= 4 * tot) {
+        std::vector<int> ord(g0.size());
+        for (size_t b = 0; b < ord.size(); ++b) ord[b] = (int)b;
+        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return rows_b[a] > rows_b[b]; });
+        if ((rc = to_device(c, ord, &c->d_pk_order))) return rc;
     }
-    c->pk_nblk = 0;
-    { // blocks of the packed / padded dense layouts: consecutive groups (never the reference) of >= GCMP_BLOCK_ROWS rows together
-        std::vector<int> g0, g1, out;
-        int64_t pos = 0, rows = 0;
-        bool open = false;
-        c->pk_max_block_rows = 0;
-        auto close = [&](int64_t end) { g1.push_back((int)end); pos += (rows + 63) & ~63ll; open = false; c->pk_max_block_rows = std::max(c->pk_max_block_rows, rows); };
-        for (int64_t g = 0; g < n_groups; ++g) {
-            if (g == ref) { if (open) close(g); continue; }
-            if (!open) { g0.push_back((int)g); out.push_back((int)pos); rows = 0; open = true; }
-            rows += counts[g];
-            if (rows >= GCMP_BLOCK_ROWS) close(g + 1);
-        }
-        if (open) close(n_groups);
-        std::vector<int> packed;
-        packed.insert(packed.end(), g0.begin(), g0.end());
-        packed.insert(packed.end(), g1.begin(), g1.end());
-        packed.insert(packed.end(), out.begin(), out.end());
-        if (packed.empty()) packed.push_back(0);
-        c->pk_nblk = (int)g0.size();
-        { // blocks of very different lengths (clusters from fifty to tens of thousands of cells): k_group_compact numbers its workgroups
-            // block-major, longest block first, so that a long block's chain of chunks starts with the launch instead of ending it
-            std::vector<int64_t> rows_b(g0.size(), 0);
-            int64_t tot = 0, mx = 0;
-            for (size_t b = 0; b < g0.size(); ++b) {
-                for (int g = g0[b]; g < g1[b]; ++g) rows_b[b] += counts[g];
-                tot += rows_b[b]; mx = std::max(mx, rows_b[b]);
-            }
-            if (g0.size() >= 2 && mx * (int64_t)g0.size() >= 4 * tot) {
-                std::vector<int> ord(g0.size());
-                for (size_t b = 0; b < ord.size(); ++b) ord[b] = (int)b;
-                std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return rows_b[a] > rows_b[b]; });
-                HIPCHK(c, hipMalloc((void **)&c->d_pk_order, ord.size() * sizeof(int)));
-                HIPCHK(c, hipMemcpy(c->d_pk_order, ord.data(), ord.size() * sizeof(int), hipMemcpyHostToDevice));
-            }
-        }
-        { // long blocks (a cluster of thousands of cells, the control group of a screen): see k_ovr_partition_packed<COOP>
-            std::vector<int> lng;
-            std::vector<unsigned char> is_long(g0.size() + 1, 0);
-            for (size_t b = 0; b < g0.size(); ++b) {
-                int64_t rows_b = 0;
-                for (int g = g0[b]; g < g1[b]; ++g) rows_b += counts[g];
-                if (rows_b > 4096 /* OVRP_LONG_ROWS */ && g1[b] - g0[b] <= 64) { lng.push_back((int)b); is_long[b] = 1; }
-            }
-            c->pk_nlong = (int)lng.size();
-            if (lng.empty()) lng.push_back(0);
-            HIPCHK(c, hipMalloc((void **)&c->d_pk_long, lng.size() * sizeof(int)));
-            HIPCHK(c, hipMemcpy(c->d_pk_long, lng.data(), lng.size() * sizeof(int), hipMemcpyHostToDevice));
-            HIPCHK(c, hipMalloc((void **)&c->d_pk_islong, is_long.size()));
-            HIPCHK(c, hipMemcpy(c->d_pk_islong, is_long.data(), is_long.size(), hipMemcpyHostToDevice));
-        }
-        c->pk_ref_out = (int)pos;
-        c->pk_len = pos;
-        c->pk_stride = pos + (ref >= 0 ? ((counts[ref] + 63) & ~63ll) : 0) + 64;
-        HIPCHK(c, hipMalloc((void **)&c->d_pk_blk, packed.size() * sizeof(int)));
-        HIPCHK(c, hipMemcpy(c->d_pk_blk, packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice));
-        { // groups whose packed runs can exceed the 256 keys the packed rank kernel looks up at a time
-            std::vector<int> big;
-            for (int64_t g = 0; g < n_groups; ++g)
-                if (g != ref && counts[g] > 256) big.push_back((int)g);
-            c->pk_nbig = (int)big.size();
-            if (!big.empty()) {
-                std::vector<int> both(big);
-                both.resize(big.size() + (size_t)n_groups, -1);
-                for (size_t k = 0; k < big.size(); ++k) both[big.size() + (size_t)big[k]] = (int)k;
-                HIPCHK(c, hipMalloc((void **)&c->d_pk_big, both.size() * sizeof(int)));
-                HIPCHK(c, hipMemcpy(c->d_pk_big, both.data(), both.size() * sizeof(int), hipMemcpyHostToDevice));
-            }
-        }
-        if (ref < 0) { // dense OVR walks the padded rows: group code per key slot
-            std::vector<int> pc((size_t)c->pk_stride, 0);
-            for (size_t b = 0; b < g0.size(); ++b) {
-                int64_t o = out[b];
-                for (int g = g0[b]; g < g1[b]; ++g)
-                    for (int64_t k = 0; k < counts[g]; ++k) pc[(size_t)o++] = g;
-            }
-            HIPCHK(c, hipMalloc((void **)&c->d_pk_code, pc.size() * sizeof(int)));
-            HIPCHK(c, hipMemcpy(c->d_pk_code, pc.data(), pc.size() * sizeof(int), hipMemcpyHostToDevice));
-        }
+    { // long blocks (a cluster of thousands of cells, the control group of a screen): see k_ovr_partition_packed<COOP>
+        std::vector<int> lng;
+        std::vector<unsigned char> is_long(g0.size() + 1, 0);
+        for (size_t b = 0; b < g0.size(); ++b)
+            if (rows_b[b] > 4096 /* OVRP_LONG_ROWS */ && g1[b] - g0[b] <= 64) { lng.push_back((int)b); is_long[b] = 1; }
+        c->pk_nlong = (int)lng.size();
+        if (lng.empty()) lng.push_back(0);
+        if ((rc = to_device(c, lng, &c->d_pk_long)) || (rc = to_device(c, is_long, &c->d_pk_islong))) return rc;
     }
-    if (n_groups <= 65535) {
-        std::vector<u16> c16(codes.begin(), codes.end());
-        HIPCHK(c, hipMalloc((void **)&c->d_codes16, c16.size() * sizeof(u16)));
-        HIPCHK(c, hipMemcpy(c->d_codes16, c16.data(), c16.size() * sizeof(u16), hipMemcpyHostToDevice));
+    c->pk_ref_out = (int)pos;
+    c->pk_len = pos;
+    c->pk_stride = pos + (ref >= 0 ? ((counts[ref] + 63) & ~63ll) : 0) + 64;
+    if ((rc = to_device(c, packed, &c->d_pk_blk))) return rc;
+    // groups whose packed runs can exceed the 256 keys the packed rank kernel looks up at a time
+    std::vector<int> big;
+    for (int64_t g = 0; g < n_groups; ++g)
+        if (g != ref && counts[g] > 256) big.push_back((int)g);
+    c->pk_nbig = (int)big.size();
+    if (big.empty()) return ILLICO_OK;
+    std::vector<int> both(big);
+    both.resize(big.size() + (size_t)n_groups, -1);
+    for (size_t k = 0; k < big.size(); ++k) both[big.size() + (size_t)big[k]] = (int)k;
+    return to_device(c, both, &c->d_pk_big);
+}
+
+// dense OVR walks the padded rows: group code per key slot
+static int lay_out_padded_codes(illico_ctx *c, const int64_t *counts, const std::vector<int> &g0, const std::vector<int> &g1, const std::vector<int> &out) {
+    std::vector<int> pc((size_t)c->pk_stride, 0);
+    for (size_t b = 0; b < g0.size(); ++b) {
+        int64_t o = out[b];
+        for (int g = g0[b]; g < g1[b]; ++g)
+            for (int64_t k = 0; k < counts[g]; ++k) pc[(size_t)o++] = g;
     }
-    { // row chunks of the group-major CSR pass (kernels_csr_counts.h)
-        std::vector<int> p0, nr, slab, big;
-        auto chunks = [&](int64_t first, int64_t rows, int s, bool natural) {
-            for (int64_t r = 0; r < rows; r += CSRH_ROWS) {
-                p0.push_back(natural ? (int)(-1 - (first + r)) : (int)(first + r));
-                nr.push_back((int)std::min<int64_t>(CSRH_ROWS, rows - r));
-                slab.push_back(s);
-            }
-        };
-        if (ref >= 0) chunks(indptr[ref], counts[ref], 0, false); // (OVR: the column histograms come out of the count pass itself)
-        for (int64_t g = 0; g < n_groups; ++g)
-            if (g != ref && counts[g] > 255) big.push_back((int)g);
-        c->csr_n_big = (int)big.size();
-        if (big.size() > CSRC_MAX_BIG) { c->csr_n_big = -1; big.clear(); }
-        for (size_t k = 0; k < big.size(); ++k) chunks(indptr[big[k]], counts[big[k]], 1 + (int)k, false);
-        c->csr_n_chunks = (int)p0.size();
-        std::vector<int> all;
-        all.insert(all.end(), p0.begin(), p0.end());
-        all.insert(all.end(), nr.begin(), nr.end());
-        all.insert(all.end(), slab.begin(), slab.end());
-        all.insert(all.end(), big.begin(), big.end());
-        if (all.empty()) all.push_back(0);
-        HIPCHK(c, hipMalloc((void **)&c->d_csr_chunks, all.size() * sizeof(int)));
-        HIPCHK(c, hipMemcpy(c->d_csr_chunks, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
+    return to_device(c, pc, &c->d_pk_code);
+}
+
+// row chunks of the group-major CSR pass (kernels_csr_counts.h)
+static int lay_out_csr_chunks(illico_ctx *c, const int64_t *counts, const int64_t *indptr, int64_t n_groups, int64_t ref) {
+    std::vector<int> p0, nr, slab, big;
+    auto chunks = [&](int64_t first, int64_t rows, int s, bool natural) {
+        for (int64_t r = 0; r < rows; r += CSRH_ROWS) {
+            p0.push_back(natural ? (int)(-1 - (first + r)) : (int)(first + r));
+            nr.push_back((int)std::min<int64_t>(CSRH_ROWS, rows - r));
+            slab.push_back(s);
+        }
+    };
+    if (ref >= 0) chunks(indptr[ref], counts[ref], 0, false); // (OVR: the column histograms come out of the count pass itself)
+    for (int64_t g = 0; g < n_groups; ++g)
+        if (g != ref && counts[g] > 255) big.push_back((int)g);
+    c->csr_n_big = (int)big.size();
+    if (big.size() > CSRC_MAX_BIG) { c->csr_n_big = -1; big.clear(); }
+    for (size_t k = 0; k < big.size(); ++k) chunks(indptr[big[k]], counts[big[k]], 1 + (int)k, false);
+    c->csr_n_chunks = (int)p0.size();
+    std::vector<int> all;
+    all.insert(all.end(), p0.begin(), p0.end());
+    all.insert(all.end(), nr.begin(), nr.end());
+    all.insert(all.end(), slab.begin(), slab.end());
+    all.insert(all.end(), big.begin(), big.end());
+    if (all.empty()) all.push_back(0);
+    return to_device(c, all, &c->d_csr_chunks);
+}
+
+extern "C" int illico_set_groups(illico_ctx *c, const int64_t *encoded_groups, const int64_t *counts, const int64_t *indices,
+                                 const int64_t *indptr, int64_t n_cells, int64_t n_groups, int64_t ref) {
+    if (!c) return ILLICO_ERR_ARG;
+    CTX_LOCK(c);
+    if (!encoded_groups || !counts || !indices || !indptr) return fail(c, ILLICO_ERR_ARG, "null group array");
+    if (n_cells <= 0 || n_groups <= 0 || n_cells > 0x7FFFFFF0ll) return fail(c, ILLICO_ERR_ARG, "bad n_cells/n_groups");
+    if (ref < -1 || ref >= n_groups) return fail(c, ILLICO_ERR_ARG, "encoded_ref_group out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = resolve_pending(c); // (its leftover genes need the groups it was made with)
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_groups(c);
+    std::vector<int> cnt(n_groups), g0, g1, out;
+    int64_t max_nonref = 0;
+    if ((rc = lay_out_positions(c, encoded_groups, counts, indices, indptr, n_cells, n_groups, ref, cnt, &max_nonref))) return rc;
+    std::vector<GroupConst> gc(n_groups);
+    for (int64_t g = 0; g < n_groups; ++g) {
+        const long long n_tgt = cnt[g], n_ref = ref >= 0 ? (long long)cnt[ref] : (long long)n_cells - n_tgt;
+        gc[g] = group_const(n_ref, n_tgt, ref >= 0 ? n_ref + n_tgt : (long long)n_cells);
     }
+    std::vector<u32> ho(n_groups + 1, 0u);
+    for (int64_t g = 0; g < n_groups; ++g) ho[g + 1] = ho[g] + (counts[g] <= 255 ? 16u : 32u);
+    c->hist_words = ho[n_groups];
+    if ((rc = to_device(c, gc, &c->d_gconst)) || (rc = to_device(c, ho, &c->d_hist_off)) ||
+        (rc = lay_out_packed_blocks(c, counts, n_groups, ref, g0, g1, out)) || (ref < 0 && (rc = lay_out_padded_codes(c, counts, g0, g1, out))) ||
+        (rc = lay_out_csr_chunks(c, counts, indptr, n_groups, ref)))
+        return rc;
     c->h_counts = cnt;
     c->n_cells = n_cells;
     c->n_groups = n_groups;
@@ -488,7 +486,6 @@ int illico_set_groups(illico_ctx *c, const int64_t *encoded_groups, const int64_
     return ILLICO_OK;
 }
 
-} // extern "C"
 int launch_gene_totals(illico_ctx *c, const double *ssum, int G, int nb, double *gtot) {
     ProfScope ps(c, KID_GENE_TOTALS);
     hipLaunchKernelGGL(k_gene_totals, dim3((nb + 63) / 64), dim3(256), 0, c->stream, ssum, G, nb, gtot);
@@ -587,8 +584,8 @@ static int end_outputs(illico_ctx *c, const OutPlanes &o, int64_t W, double *out
                        double *out_z = nullptr) {
     if (!o.staged) return ILLICO_OK;
     const size_t G = (size_t)c->n_groups, row = (size_t)W * 8, NP = out_z ? 4 : 3;
-    const size_t total = NP * G * row;
-    if (total < ((size_t)8 << 20)) { // small results: three (four) strided copies
+    const size_t total = NP * G * row, buf = (size_t)32 << 20;
+    if (total < ((size_t)8 << 20) || row > buf) { // small results, or a window too wide for the buffers: three (four) strided copies
         HIPCHK(c, hipMemcpy2DAsync(out_p, out_ld * 8, o.p, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpy2DAsync(out_u, out_ld * 8, o.u, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpy2DAsync(out_fc, out_ld * 8, o.fc, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
@@ -596,7 +593,6 @@ static int end_outputs(illico_ctx *c, const OutPlanes &o, int64_t W, double *out
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return ILLICO_OK;
     }
-    const size_t buf = (size_t)32 << 20;
     if (c->out_pin_bytes < buf) {
         for (int k = 0; k < 2; ++k) { if (c->out_pin[k]) hipHostFree(c->out_pin[k]); c->out_pin[k] = nullptr; }
         c->out_pin_bytes = 0;
@@ -605,14 +601,6 @@ static int end_outputs(illico_ctx *c, const OutPlanes &o, int64_t W, double *out
         c->out_pin_bytes = buf;
     }
     const size_t rows_per = std::max<size_t>(1, buf / row), n_rows = NP * G; // rows of the three (four) planes, one after the other
-    if (row > buf) { // (a window too wide for the buffers: the plain copies)
-        HIPCHK(c, hipMemcpy2DAsync(out_p, out_ld * 8, o.p, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpy2DAsync(out_u, out_ld * 8, o.u, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpy2DAsync(out_fc, out_ld * 8, o.fc, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
-        if (out_z) HIPCHK(c, hipMemcpy2DAsync(out_z, out_ld * 8, o.z, W * 8, W * 8, G, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return ILLICO_OK;
-    }
     const double *src[4] = {o.p, o.u, o.fc, o.z};
     double *dst[4] = {out_p, out_u, out_fc, out_z};
     auto scatter = [&](int k, size_t r0, size_t r1) { // rows [r0, r1) of the concatenated planes, from pinned buffer k
@@ -696,10 +684,10 @@ void free_host_stage(illico_ctx *c) {
     delete hs;
     c->host_stage = nullptr;
 }
-// Completes a deferred dense call: waits for its route flags and sends the genes the fused pass could not take through the
-// two-pass routes.  Every entry point that takes the context runs this first (illico_run_dense may enqueue its own fused pass
-// before it, see there), so results are complete after illico_ctx_synchronize or any later call.
-static int resolve_pending_csc(illico_ctx *c, const PendingDense &q); // sparse_driver.h
+// Completes a deferred call: waits for its route flags and sends the genes its single pass could not take through the ordinary
+// routes.  Every entry point that takes the context runs this first (a run entry point may enqueue its own pass before it, see
+// run_with_outputs), so results are complete after illico_ctx_synchronize or any later call.
+static int resolve_pending_csc(illico_ctx *c, const PendingDense &q);
 static int resolve_pending(illico_ctx *c, PendingDense q) {
     if (!q.on) return ILLICO_OK;
     HIPCHK(c, hipSetDevice(c->device));
@@ -707,17 +695,10 @@ static int resolve_pending(illico_ctx *c, PendingDense q) {
     if (q.kind == 1) return resolve_pending_csc(c, q);
     const u32 *hf = (const u32 *)c->pend_pinned[q.slot];
     const bool skipped = hf[q.col_ub - q.col_lb] != 0u; // the 256-value stage was left to run_leftovers (k_wide_decide)
-    const OutPlanes o{q.p, q.u, q.fc, q.out_ld, false, q.z};
-    switch (q.dtype) {
-    case ILLICO_F32: return run_leftovers<float, u32>(c, q.X, q.dtype, q.N, q.ld, q.col_lb, q.col_ub, q.flags, q.alternative, o, hf, skipped);
-#ifndef ILLICO_DEV_F32_ONLY
-    case ILLICO_F64: return run_leftovers<double, u64>(c, q.X, q.dtype, q.N, q.ld, q.col_lb, q.col_ub, q.flags, q.alternative, o, hf, skipped);
-    case ILLICO_I32: return run_leftovers<int32_t, u32>(c, q.X, q.dtype, q.N, q.ld, q.col_lb, q.col_ub, q.flags, q.alternative, o, hf, skipped);
-    default: return run_leftovers<int64_t, u64>(c, q.X, q.dtype, q.N, q.ld, q.col_lb, q.col_ub, q.flags, q.alternative, o, hf, skipped);
-#else
-    default: return fail(c, ILLICO_ERR_DTYPE, "this development build holds the float32 kernels only");
-#endif
-    }
+    return dispatch_driver_types(c, q.dtype, [&](auto v, auto k) {
+        return run_leftovers<typename decltype(v)::type, typename decltype(k)::type>(c, q.X, q.dtype, q.N, q.ld, q.col_lb, q.col_ub, q.flags, q.alternative,
+                                                                                    q.planes(), hf, skipped);
+    });
 }
 int resolve_pending(illico_ctx *c) {
     const PendingDense q = c->pend;
@@ -725,18 +706,77 @@ int resolve_pending(illico_ctx *c) {
     return resolve_pending(c, q);
 }
 
+// A route that defers posts its call in two steps, its own device-to-host copies of the route flags in between (engine.h).
+int reserve_deferred_slot(illico_ctx *c, size_t bytes, int *slot, void **pin) {
+    const int k = c->pend_next; // (two slots: the next call may be enqueued before this one is completed)
+    if (c->pend_pinned_bytes[k] < bytes) {
+        if (c->pend_pinned[k]) hipHostFree(c->pend_pinned[k]);
+        c->pend_pinned[k] = nullptr;
+        c->pend_pinned_bytes[k] = 0;
+        HIPCHK(c, hipHostMalloc(&c->pend_pinned[k], bytes + 4096, hipHostMallocDefault));
+        c->pend_pinned_bytes[k] = bytes + 4096;
+    }
+    if (!c->pend_event[k]) HIPCHK(c, hipEventCreateWithFlags(&c->pend_event[k], hipEventDisableTiming));
+    *slot = k;
+    *pin = c->pend_pinned[k];
+    return ILLICO_OK;
+}
+int post_deferred_call(illico_ctx *c, int slot, int kind, int dtype, int flags, int alternative, int64_t N, int64_t col_lb, int64_t col_ub,
+                       const OutPlanes &o) {
+    HIPCHK(c, hipEventRecord(c->pend_event[slot], c->stream));
+    c->pend_next ^= 1;
+    PendingDense &q = c->pend;
+    q = PendingDense();
+    q.on = true; q.kind = kind; q.dtype = dtype; q.flags = flags & ~ILLICO_FLAG_DEFER; q.alternative = alternative; q.slot = slot;
+    q.N = N; q.col_lb = col_lb; q.col_ub = col_ub; q.out_ld = o.ld; q.p = o.p; q.u = o.u; q.fc = o.fc; q.z = o.z;
+    return ILLICO_OK;
+}
+
+// The protocol of the run entry points, after their argument checks: the deferred call in flight, the output planes, `run(o)`.
+// A deferred call still in flight: when this call is deferred too and writes other planes, its pass is enqueued FIRST (the GPU goes
+// from one pass to the next without waiting for the host) and the earlier call is completed after; otherwise the earlier call is
+// completed before anything else happens.
+template <typename Run>
+static int run_with_outputs(illico_ctx *c, int flags, int64_t W, double *out_p, double *out_u, double *out_fc, double *out_z, int64_t out_ld,
+                            Run &&run) {
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    const PendingDense prev = c->pend;
+    c->pend.on = false;
+    bool later = false;
+    if (prev.on && (flags & ILLICO_FLAG_DEFER) && (flags & ILLICO_FLAG_OUTPUT_DEVICE) && (flags & ILLICO_FLAG_INPUT_DEVICE) && W > 0) {
+        const size_t span = (size_t)(c->n_groups - 1) * (size_t)out_ld + (size_t)W, pspan = (size_t)(c->n_groups - 1) * (size_t)prev.out_ld + (size_t)(prev.col_ub - prev.col_lb);
+        auto apart = [](const double *a, size_t na, const double *b, size_t nb) { return a + na <= b || b + nb <= a; };
+        later = true;
+        for (const double *a : {out_p, out_u, out_fc, out_z})
+            for (const double *b : {prev.p, prev.u, prev.fc, prev.z}) later = later && (!a || !b || apart(a, span, b, pspan));
+    }
+    if (!later && (rc = resolve_pending(c, prev))) return rc;
+    if (W == 0) return ILLICO_OK; // (never `later`)
+    auto complete_later = [&]() -> int { // (the earlier call's leftovers run on the ordinary routes; this call's own pending state must survive them)
+        if (!later) return ILLICO_OK;
+        const PendingDense mine = c->pend;
+        c->pend.on = false;
+        const int rc2 = resolve_pending(c, prev);
+        c->pend = mine;
+        return rc2;
+    };
+    OutPlanes o;
+    if ((rc = begin_outputs(c, flags, W, out_p, out_u, out_fc, out_ld, &o, out_z))) { complete_later(); return rc; }
+    PlaneTouch touch; // (joined before the first result is scattered, and on every way out)
+    if (o.staged) { double *const dst[4] = {out_p, out_u, out_fc, out_z}; touch.start(dst, (size_t)c->n_groups, (size_t)W * 8, (size_t)out_ld * 8); }
+    rc = run(o);
+    if (const int rc2 = complete_later(); !rc) rc = rc2;
+    if (rc) return rc;
+    touch.join();
+    return end_outputs(c, o, W, out_p, out_u, out_fc, out_ld, out_z);
+}
+
 static int run_dense_any(illico_ctx *c, const void *X, int dtype, int64_t n_rows, int64_t ld, int64_t col_lb, int64_t col_ub, int flags,
                          int alternative, const OutPlanes &o) {
-    switch (dtype) {
-    case ILLICO_F32: return run_dense_t<float, u32>(c, X, dtype, n_rows, ld, col_lb, col_ub, flags, alternative, o);
-#ifndef ILLICO_DEV_F32_ONLY // development builds (ILLICO_DEV_F32_ONLY=1 python build.py) compile the float32 kernels only: 4x faster to build
-    case ILLICO_F64: return run_dense_t<double, u64>(c, X, dtype, n_rows, ld, col_lb, col_ub, flags, alternative, o);
-    case ILLICO_I32: return run_dense_t<int32_t, u32>(c, X, dtype, n_rows, ld, col_lb, col_ub, flags, alternative, o);
-    default: return run_dense_t<int64_t, u64>(c, X, dtype, n_rows, ld, col_lb, col_ub, flags, alternative, o);
-#else
-    default: return fail(c, ILLICO_ERR_DTYPE, "this development build holds the float32 kernels only");
-#endif
-    }
+    return dispatch_driver_types(c, dtype, [&](auto v, auto k) {
+        return run_dense_t<typename decltype(v)::type, typename decltype(k)::type>(c, X, dtype, n_rows, ld, col_lb, col_ub, flags, alternative, o);
+    });
 }
 
 extern "C" int illico_run_dense_ex(illico_ctx *c, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld,
@@ -750,32 +790,9 @@ extern "C" int illico_run_dense_ex(illico_ctx *c, const void *X, int dtype, int6
     if (ld < n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
     if (dtype < 0 || dtype > 3) return fail(c, ILLICO_ERR_DTYPE, "unsupported dtype code %d", dtype);
     if (c->big_n) return fail(c, ILLICO_ERR_UNSUPPORTED, "%lld cells in one test: the dense routes' 64-bit tie sums hold up to 2097151 cells (the reference's int64 arithmetic wraps there, utils/math.py:95); sparse input is taken", (long long)c->n_cells);
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t W = col_ub - col_lb;
-    // A deferred call still in flight: when this call is deferred too and writes other planes, its fused pass is enqueued
-    // FIRST (the GPU goes from one pass to the next without waiting for the host) and the earlier call is completed after;
-    // otherwise the earlier call is completed before anything else happens.
-    PendingDense prev = c->pend;
-    c->pend.on = false;
-    bool later = false;
-    if (prev.on && (flags & ILLICO_FLAG_DEFER) && (flags & ILLICO_FLAG_OUTPUT_DEVICE) && (flags & ILLICO_FLAG_INPUT_DEVICE) && W > 0) {
-        const size_t span = (size_t)(c->n_groups - 1) * (size_t)out_ld + (size_t)W, pspan = (size_t)(c->n_groups - 1) * (size_t)prev.out_ld + (size_t)(prev.col_ub - prev.col_lb);
-        auto apart = [](const double *a, size_t na, const double *b, size_t nb) { return a + na <= b || b + nb <= a; };
-        later = true;
-        for (const double *a : {out_p, out_u, out_fc, out_z})
-            for (const double *b : {prev.p, prev.u, prev.fc, prev.z}) later = later && (!a || !b || apart(a, span, b, pspan));
-    }
-    if (!later && (rc = resolve_pending(c, prev))) return rc;
-    if (W == 0) return later ? resolve_pending(c, prev) : ILLICO_OK;
-    OutPlanes o;
-    if ((rc = begin_outputs(c, flags, W, out_p, out_u, out_fc, out_ld, &o, out_z))) { if (later) resolve_pending(c, prev); return rc; }
-    PlaneTouch touch; // (joined before the first result is scattered, and on every way out)
-    if (o.staged) { double *const dst[4] = {out_p, out_u, out_fc, out_z}; touch.start(dst, (size_t)c->n_groups, (size_t)W * 8, (size_t)out_ld * 8); }
-    rc = run_dense_any(c, X, dtype, n_rows, ld, col_lb, col_ub, flags, alternative, o);
-    if (later) { const int rc2 = resolve_pending(c, prev); if (!rc) rc = rc2; }
-    if (rc) return rc;
-    touch.join();
-    return end_outputs(c, o, W, out_p, out_u, out_fc, out_ld, out_z);
+    return run_with_outputs(c, flags, col_ub - col_lb, out_p, out_u, out_fc, out_z, out_ld, [&](const OutPlanes &o) {
+        return run_dense_any(c, X, dtype, n_rows, ld, col_lb, col_ub, flags, alternative, o);
+    });
 }
 
 extern "C" int illico_run_dense(illico_ctx *c, const void *X, int dtype, int64_t n_rows, int64_t n_cols, int64_t ld,
@@ -825,25 +842,10 @@ extern "C" int illico_rank_statistics(illico_ctx *c, const void *X, int dtype, i
 int run_sparse_inner(illico_ctx *c, bool is_csr, const void *data, int dtype, const void *indices, const void *indptr,
                             int idx_dtype, int64_t n_rows, int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, int alternative,
                             const OutPlanes &o) {
-    int rc;
-#ifndef ILLICO_DEV_F32_ONLY
-#define SP_CALL(InT, KeyT)                                                                                                 \
-    (idx_dtype == ILLICO_IDX_I32                                                                                           \
-         ? run_sparse_t<InT, int32_t, KeyT>(c, is_csr, data, indices, indptr, dtype, n_rows, n_cols, col_lb, col_ub, flags, alternative, o) \
-         : run_sparse_t<InT, int64_t, KeyT>(c, is_csr, data, indices, indptr, dtype, n_rows, n_cols, col_lb, col_ub, flags, alternative, o))
-    switch (dtype) {
-    case ILLICO_F32: rc = SP_CALL(float, u32); break;
-    case ILLICO_F64: rc = SP_CALL(double, u64); break;
-    case ILLICO_I32: rc = SP_CALL(int32_t, u32); break;
-    default: rc = SP_CALL(int64_t, u64); break;
-    }
-#undef SP_CALL
-#else // development build: float32 values, int32 indices only
-    if (dtype == ILLICO_F32 && idx_dtype == ILLICO_IDX_I32)
-        rc = run_sparse_t<float, int32_t, u32>(c, is_csr, data, indices, indptr, dtype, n_rows, n_cols, col_lb, col_ub, flags, alternative, o);
-    else rc = fail(c, ILLICO_ERR_DTYPE, "this development build holds the float32 / int32-index kernels only");
-#endif
-    return rc;
+    return dispatch_driver_types(c, dtype, idx_dtype, [&](auto v, auto i, auto k) {
+        return run_sparse_t<typename decltype(v)::type, typename decltype(i)::type, typename decltype(k)::type>(c, is_csr, data, indices, indptr, dtype, n_rows, n_cols,
+                                                                                                                col_lb, col_ub, flags, alternative, o);
+    });
 }
 
 // the columns a deferred count-valued CSC / CSR pass could not take, through the ordinary routes
@@ -860,14 +862,13 @@ static int resolve_pending_csc(illico_ctx *c, const PendingDense &q) {
         int64_t n_flagged = 0;
         for (int64_t j = 0; j < W; ++j) n_flagged += hf[j] ? 1 : 0;
         if ((double)vd[0] > 0.02 * (double)vd[2] || (double)vd[1] > 0.005 * (double)vd[2] || vd[3] != 0u || n_flagged * 16 > W) { // not a matrix for the route (or many genes left it): all of it
-            const OutPlanes o{q.p, q.u, q.fc, q.out_ld, false, q.z};
-            return run_sparse_inner(c, true, q.sp_data, q.dtype, q.sp_indices, q.sp_indptr, q.idx_dtype, q.N, q.n_cols, q.col_lb, q.col_ub, q.flags, q.alternative, o);
+            return run_sparse_inner(c, true, q.sp_data, q.dtype, q.sp_indices, q.sp_indptr, q.idx_dtype, q.N, q.n_cols, q.col_lb, q.col_ub, q.flags, q.alternative, q.planes());
         }
         for (int64_t j = 0; j < W;) { // runs of flagged genes (closer than 32 genes: one run)
             if (!hf[j]) { ++j; continue; }
             int64_t last = j;
             for (int64_t e = j + 1; e < W && e - last <= 32; ++e) if (hf[e]) last = e;
-            const OutPlanes o = OutPlanes{q.p, q.u, q.fc, q.out_ld, false, q.z}.shifted(j);
+            const OutPlanes o = q.planes().shifted(j);
             const int rc = run_sparse_inner(c, true, q.sp_data, q.dtype, q.sp_indices, q.sp_indptr, q.idx_dtype, q.N, q.n_cols, q.col_lb + j, q.col_lb + last + 1,
                                             q.flags, q.alternative, o);
             if (rc) return rc;
@@ -883,7 +884,7 @@ static int resolve_pending_csc(illico_ctx *c, const PendingDense &q) {
         for (int64_t j = 0; j < W; ++j)
             if (hf[j]) { if (j == 0 || !hf[j - 1]) ++runs; if (first < 0) first = j; last = j; }
         if (runs > 8) {
-            const OutPlanes o = OutPlanes{q.p, q.u, q.fc, q.out_ld, false, q.z}.shifted(first);
+            const OutPlanes o = q.planes().shifted(first);
             return run_sparse_inner(c, false, q.sp_data, q.dtype, q.sp_indices, q.sp_indptr, q.idx_dtype, q.N, q.n_cols, q.col_lb + first,
                                     q.col_lb + last + 1, q.flags, q.alternative, o);
         }
@@ -892,7 +893,7 @@ static int resolve_pending_csc(illico_ctx *c, const PendingDense &q) {
         if (!hf[j]) { ++j; continue; }
         int64_t e = j;
         while (e < W && hf[e]) ++e;
-        const OutPlanes o = OutPlanes{q.p, q.u, q.fc, q.out_ld, false, q.z}.shifted(j);
+        const OutPlanes o = q.planes().shifted(j);
         const int rc = run_sparse_inner(c, false, q.sp_data, q.dtype, q.sp_indices, q.sp_indptr, q.idx_dtype, q.N, q.n_cols, q.col_lb + j,
                                         q.col_lb + e, q.flags, q.alternative, o);
         if (rc) return rc;
@@ -911,38 +912,9 @@ static int run_sparse(illico_ctx *c, bool is_csr, const void *data, int dtype, c
     if (!data || !indices || !indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
     if (dtype < 0 || dtype > 3) return fail(c, ILLICO_ERR_DTYPE, "unsupported dtype code %d", dtype);
     if (idx_dtype != ILLICO_IDX_I32 && idx_dtype != ILLICO_IDX_I64) return fail(c, ILLICO_ERR_DTYPE, "unsupported index dtype code %d", idx_dtype);
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t W = col_ub - col_lb;
-    // A deferred call still in flight: as in illico_run_dense, a deferred call that writes OTHER planes is enqueued first and
-    // the earlier one completed after (the GPU goes from one pass to the next without waiting for the host); otherwise the
-    // earlier call is completed before anything else happens.
-    PendingDense prev = c->pend;
-    c->pend.on = false;
-    bool later = false;
-    if (prev.on && (flags & ILLICO_FLAG_DEFER) && (flags & ILLICO_FLAG_OUTPUT_DEVICE) && (flags & ILLICO_FLAG_INPUT_DEVICE) && W > 0) {
-        const size_t span = (size_t)(c->n_groups - 1) * (size_t)out_ld + (size_t)W, pspan = (size_t)(c->n_groups - 1) * (size_t)prev.out_ld + (size_t)(prev.col_ub - prev.col_lb);
-        auto apart = [](const double *a, size_t na, const double *b, size_t nb) { return a + na <= b || b + nb <= a; };
-        later = true;
-        for (const double *a : {out_p, out_u, out_fc, out_z})
-            for (const double *b : {prev.p, prev.u, prev.fc, prev.z}) later = later && (!a || !b || apart(a, span, b, pspan));
-    }
-    if (!later && (rc = resolve_pending(c, prev))) return rc;
-    if (W == 0) return later ? resolve_pending(c, prev) : ILLICO_OK;
-    OutPlanes o;
-    if ((rc = begin_outputs(c, flags, W, out_p, out_u, out_fc, out_ld, &o, out_z))) { if (later) resolve_pending(c, prev); return rc; }
-    PlaneTouch touch;
-    if (o.staged) { double *const dst[4] = {out_p, out_u, out_fc, out_z}; touch.start(dst, (size_t)c->n_groups, (size_t)W * 8, (size_t)out_ld * 8); }
-    rc = run_sparse_inner(c, is_csr, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, alternative, o);
-    if (later) { // (the earlier call's leftovers run on the ordinary routes; this call's own pending state must survive them)
-        const PendingDense mine = c->pend;
-        c->pend.on = false;
-        const int rc2 = resolve_pending(c, prev);
-        c->pend = mine;
-        if (!rc) rc = rc2;
-    }
-    if (rc) return rc;
-    touch.join();
-    return end_outputs(c, o, W, out_p, out_u, out_fc, out_ld, out_z);
+    return run_with_outputs(c, flags, col_ub - col_lb, out_p, out_u, out_fc, out_z, out_ld, [&](const OutPlanes &o) {
+        return run_sparse_inner(c, is_csr, data, dtype, indices, indptr, idx_dtype, n_rows, n_cols, col_lb, col_ub, flags, alternative, o);
+    });
 }
 
 extern "C" int illico_run_csc_ex(illico_ctx *c, const void *data, int dtype, const void *indices, const void *indptr,
@@ -971,22 +943,34 @@ extern "C" int illico_run_csr(illico_ctx *c, const void *data, int dtype, const 
 }
 
 // ---- bound matrices -------------------------------------------------------------------------
-// the rows' order of a bound CSR matrix, looked at once: the group-major CSR pass of every later call relies on it
+int check_bound_matrix(illico_ctx *c, const illico_matrix *m) {
+    if (std::find(c->bound.begin(), c->bound.end(), m) == c->bound.end() || m->owner != c)
+        return fail(c, ILLICO_ERR_ARG, "the matrix handle does not belong to this context (or was released)");
+    return ILLICO_OK;
+}
+// do every row's column indices ascend?  Device arrays, on the context's stream; *sorted is written on success only.
+static int csr_rows_sorted_on_device(illico_ctx *c, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows, int *sorted) {
+    void *v;
+    int rc = get_scratch(c, "flag", 16, &v);
+    if (rc) return rc;
+    int *d_bad = (int *)v;
+    HIPCHK(c, hipMemsetAsync(d_bad, 0, 4, c->stream));
+    const int grid = (int)std::min<int64_t>((n_rows + 3) / 4 + 1, 8192);
+    if (idx_dtype == ILLICO_IDX_I32)
+        hipLaunchKernelGGL((k_csr_sorted_check<int32_t>), dim3(grid), dim3(256), 0, c->stream, (const int32_t *)indices, (const int32_t *)indptr, (int)n_rows, d_bad);
+    else
+        hipLaunchKernelGGL((k_csr_sorted_check<int64_t>), dim3(grid), dim3(256), 0, c->stream, (const int64_t *)indices, (const int64_t *)indptr, (int)n_rows, d_bad);
+    HIPCHK(c, hipGetLastError());
+    int bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *sorted = bad ? 0 : 1;
+    return ILLICO_OK;
+}
+// the rows' order of a bound CSR matrix, looked at once: the group-major CSR pass of every later call relies on it (any failure: not looked at)
 static void look_at_row_order(illico_ctx *c, illico_matrix *m) {
     m->sorted = -1;
-    if (!m->is_csr || m->n_rows >= (1ll << 31)) return;
-    void *v;
-    int bad = 0;
-    if (get_scratch(c, "flag", 16, &v) == ILLICO_OK && hipMemsetAsync(v, 0, 4, c->stream) == hipSuccess) {
-        const unsigned grid = (unsigned)std::min<int64_t>((m->n_rows + 3) / 4 + 1, 8192);
-        if (m->idx_dtype == ILLICO_IDX_I32)
-            hipLaunchKernelGGL((k_csr_sorted_check<int32_t>), dim3(grid), dim3(256), 0, c->stream, (const int32_t *)m->d_indices, (const int32_t *)m->d_indptr, (int)m->n_rows, (int *)v);
-        else
-            hipLaunchKernelGGL((k_csr_sorted_check<int64_t>), dim3(grid), dim3(256), 0, c->stream, (const int64_t *)m->d_indices, (const int64_t *)m->d_indptr, (int)m->n_rows, (int *)v);
-        if (hipGetLastError() == hipSuccess && hipMemcpyAsync(&bad, v, 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
-            hipStreamSynchronize(c->stream) == hipSuccess)
-            m->sorted = bad ? 0 : 1;
-    }
+    if (m->is_csr && m->n_rows < (1ll << 31)) csr_rows_sorted_on_device(c, m->d_indices, m->d_indptr, m->idx_dtype, m->n_rows, &m->sorted);
 }
 
 static int sparse_bind(illico_ctx *c, bool is_csr, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype,
@@ -1090,9 +1074,7 @@ static int run_bound_ahead(illico_ctx *c, const illico_matrix *m, int64_t col_lb
             return rc;
         w->m = m; w->gen = c->groups_gen; w->flags = kflags; w->alternative = alternative; w->lb = lb; w->ub = ub;
     } else { // (a deferred call of another kind may still be in flight: completed first, as every entry point does)
-        PendingDense prev = c->pend;
-        c->pend.on = false;
-        if ((rc = resolve_pending(c, prev))) return rc;
+        if ((rc = resolve_pending(c))) return rc;
     }
     w->stamp = ++c->ahead_clock;
     OutPlanes o;
@@ -1115,15 +1097,14 @@ extern "C" int illico_run_bound_ex(illico_ctx *c, const illico_matrix *m, int64_
                                    double *out_p, double *out_u, double *out_fc, double *out_z, int64_t out_ld) {
     if (!c || !m) return ILLICO_ERR_ARG;
     CTX_LOCK(c); // (recursive: held for the whole call, so that illico_matrix_release on another thread cannot free the arrays under it)
-    if (m->owner != c || std::find(c->bound.begin(), c->bound.end(), m) == c->bound.end())
-        return fail(c, ILLICO_ERR_ARG, "the matrix handle does not belong to this context (or was released)");
+    int rc = check_bound_matrix(c, m);
+    if (rc) return rc;
     const int keep = ILLICO_FLAG_LOG1P | ILLICO_FLAG_CONTINUITY | ILLICO_FLAG_TIE_CORRECT | ILLICO_FLAG_OUTPUT_DEVICE | ILLICO_FLAG_DEFER;
     // what was learnt about the rows' order when the matrix was bound: in order -- the group-major CSR pass need not ask again; not --
     // it is not for that pass
     const bool hold0 = c->hold_csr_counts;
     c->cur_sorted_known = m->is_csr && m->sorted == 1;
     if (m->is_csr && m->sorted == 0) c->hold_csr_counts = true;
-    int rc;
     const int64_t A = c->bound_ahead_genes;
     if (A > 0 && m->is_csr && !c->tap && c->has_groups && col_lb >= 0 && col_lb < col_ub && col_ub <= m->n_cols && col_ub - col_lb < A && col_ub - col_lb < m->n_cols &&
         out_p && out_u && out_fc && !out_z && out_ld >= col_ub - col_lb) // (a call with z computes its chunk directly: the windows hold three planes)
@@ -1142,12 +1123,12 @@ extern "C" int illico_run_bound(illico_ctx *c, const illico_matrix *m, int64_t c
 extern "C" int illico_matrix_release(illico_ctx *c, illico_matrix *m) {
     if (!c || !m) return ILLICO_ERR_ARG;
     CTX_LOCK(c);
-    auto it = std::find(c->bound.begin(), c->bound.end(), m);
-    if (it == c->bound.end() || m->owner != c) return fail(c, ILLICO_ERR_ARG, "the matrix handle does not belong to this context (or was released)");
+    int rc = check_bound_matrix(c, m);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = resolve_pending(c); // a deferred call may still read the arrays
+    rc = resolve_pending(c); // a deferred call may still read the arrays
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->bound.erase(it);
+    c->bound.erase(std::find(c->bound.begin(), c->bound.end(), m));
     for (auto &a : c->ahead) if (a.m == m) a.m = nullptr;
     if (m->owns) { hipFree(m->d_data); hipFree(m->d_indices); hipFree(m->d_indptr); }
     delete m;
@@ -1157,10 +1138,10 @@ extern "C" int illico_matrix_release(illico_ctx *c, illico_matrix *m) {
 extern "C" int illico_matrix_touch(illico_ctx *c, illico_matrix *m) {
     if (!c || !m) return ILLICO_ERR_ARG;
     CTX_LOCK(c);
-    if (m->owner != c || std::find(c->bound.begin(), c->bound.end(), m) == c->bound.end())
-        return fail(c, ILLICO_ERR_ARG, "the matrix handle does not belong to this context (or was released)");
+    int rc = check_bound_matrix(c, m);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    const int rc = resolve_pending(c); // (a deferred call on the arrays as they were completes first)
+    rc = resolve_pending(c); // (a deferred call on the arrays as they were completes first)
     for (auto &a : c->ahead) if (a.m == m) a.m = nullptr;
     look_at_row_order(c, m);
     return rc;
@@ -1185,20 +1166,5 @@ extern "C" int illico_csr_indices_sorted(illico_ctx *c, const void *indices, con
         return ILLICO_OK;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    void *v;
-    int rc = get_scratch(c, "flag", 16, &v);
-    if (rc) return rc;
-    int *d_bad = (int *)v;
-    HIPCHK(c, hipMemsetAsync(d_bad, 0, 4, c->stream));
-    const int grid = (int)std::min<int64_t>((n_rows + 3) / 4 + 1, 8192);
-    if (idx_dtype == ILLICO_IDX_I32)
-        hipLaunchKernelGGL((k_csr_sorted_check<int32_t>), dim3(grid), dim3(256), 0, c->stream, (const int32_t *)indices, (const int32_t *)indptr, (int)n_rows, d_bad);
-    else
-        hipLaunchKernelGGL((k_csr_sorted_check<int64_t>), dim3(grid), dim3(256), 0, c->stream, (const int64_t *)indices, (const int64_t *)indptr, (int)n_rows, d_bad);
-    HIPCHK(c, hipGetLastError());
-    int bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *out_sorted = bad ? 0 : 1;
-    return ILLICO_OK;
+    return csr_rows_sorted_on_device(c, indices, indptr, idx_dtype, n_rows, out_sorted);
 }

@@ -428,19 +428,11 @@ int run_fused_ovo(illico_ctx *c, const void *X, int64_t ld, int64_t b0, int nb, 
         HIPCHK(c, hipGetLastError());
     }
     // route flags back through a pinned staging buffer (a pageable destination makes the copy a blocking, staged one)
-    if (defer_slot >= 0) { // deferred: the copy is enqueued, an event marks it, nobody waits here (resolve_pending does)
-        void *&pin = c->pend_pinned[defer_slot];
-        if (c->pend_pinned_bytes[defer_slot] < (size_t)nb * 4 + 4) {
-            if (pin) hipHostFree(pin);
-            pin = nullptr;
-            c->pend_pinned_bytes[defer_slot] = 0;
-            HIPCHK(c, hipHostMalloc(&pin, (size_t)nb * 4 + 4096, hipHostMallocDefault));
-            c->pend_pinned_bytes[defer_slot] = (size_t)nb * 4 + 4096;
-        }
-        if (!c->pend_event[defer_slot]) HIPCHK(c, hipEventCreateWithFlags(&c->pend_event[defer_slot], hipEventDisableTiming));
+    if (defer_slot >= 0) { // deferred: the copy is enqueued, the caller's event marks it, nobody waits here (resolve_pending does)
+        void *pin;
+        if ((rc = reserve_deferred_slot(c, (size_t)nb * 4 + 4, &defer_slot, &pin))) return rc; // (the slot the caller named, which posts the call)
         HIPCHK(c, hipMemcpyAsync(pin, P.gene_flags, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync((u32 *)pin + nb, skipw, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipEventRecord(c->pend_event[defer_slot], c->stream));
         return ILLICO_OK;
     }
     if ((rc = ensure_pinned(c, (size_t)nb * 4 + 4))) return rc;
@@ -884,10 +876,8 @@ int run_dense_t(illico_ctx *c, const void *X, int dtype, int64_t N, int64_t ld, 
         if (defer) {
             const int slot = c->pend_next;
             if ((rc = run_fused_ovo<InT>(c, X, ld, col_lb, (int)W, flags, alternative, o, 0, hf, slot, ovr, max_gather))) return rc;
-            c->pend_next ^= 1;
-            PendingDense &q = c->pend;
-            q.on = true; q.kind = 0; q.X = X; q.dtype = dtype; q.flags = flags & ~ILLICO_FLAG_DEFER; q.alternative = alternative; q.slot = slot;
-            q.N = N; q.ld = ld; q.col_lb = col_lb; q.col_ub = col_ub; q.out_ld = o.ld; q.p = o.p; q.u = o.u; q.fc = o.fc; q.z = o.z;
+            if ((rc = post_deferred_call(c, slot, 0, dtype, flags, alternative, N, col_lb, col_ub, o))) return rc;
+            c->pend.X = X; c->pend.ld = ld;
             return ILLICO_OK;
         }
         if ((rc = run_fused_ovo<InT>(c, X, ld, col_lb, (int)W, flags, alternative, o, 0, hf, -1, ovr, max_gather))) return rc;

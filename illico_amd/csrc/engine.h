@@ -1,6 +1,7 @@
-// Host-side shared definitions of libillico_hip: the context, its helpers, and the declarations that tie the translation
-// units together.  core.hip holds the context / C-ABI / dispatch; keyed_*.hip the launchers that depend on the key type only;
-// dense_*.hip / sparse_*.hip one value type each (explicit instantiations of dense_driver.h / sparse_driver.h).
+// Host-side shared definitions of libillico_hip: the context, its helpers, the dispatch on the value / index types, and the
+// declarations that tie the translation units together.  core.hip holds the context / C-ABI / deferred-call protocol; keyed_*.hip
+// the launchers that depend on the key type only; dense_*.hip / sparse_*.hip one value type each (explicit instantiations of
+// dense_driver.h / sparse_driver.h); group_stats / group_moments / pairwise.hip the per-group passes (group_pass.h).
 #pragma once
 #include <cstring>
 #include <hip/hip_runtime.h>
@@ -93,8 +94,16 @@ enum {
 };
 extern const char *const kKernelNames[KID_COUNT];
 
-// A dense call made with ILLICO_FLAG_DEFER whose fused pass is in flight: which genes it could not take is known only once
-// its route flags have reached the host; they are then recomputed by the two-pass routes (resolve_pending).
+struct OutPlanes {
+    double *p, *u, *fc; // device
+    int64_t ld;
+    bool staged;
+    double *z = nullptr; // device z-score plane (the *_ex entry points), null = none
+    OutPlanes shifted(int64_t j) const { return {p + j, u + j, fc + j, ld, staged, z ? z + j : nullptr}; } // column j on
+};
+
+// A call made with ILLICO_FLAG_DEFER whose single pass is in flight: which genes it could not take is known only once
+// its route flags have reached the host; they are then recomputed by the ordinary routes (resolve_pending).
 struct PendingDense {
     bool on = false;
     int kind = 0;                 // 0: dense (X, ld), 1: CSC (sp_*: the count-valued CSC pass, sparse_driver.h)
@@ -108,6 +117,7 @@ struct PendingDense {
     int64_t N = 0, ld = 0, col_lb = 0, col_ub = 0, out_ld = 0;
     double *p = nullptr, *u = nullptr, *fc = nullptr;
     double *z = nullptr;          // the call's z-score plane (null: none): complete exactly when p is
+    OutPlanes planes() const { return {p, u, fc, out_ld, false, z}; }
 };
 
 // a sparse matrix bound to a context (illico_csr_bind / illico_csc_bind): device arrays, owned or adopted
@@ -306,21 +316,23 @@ struct ProfScope {
 };
 
 void drain_events(illico_ctx *c);
-int resolve_pending(illico_ctx *c); // completes a deferred call (core.hip)
+// ---- deferred calls (core.hip) ----
+int resolve_pending(illico_ctx *c); // completes the deferred call in flight, if any
+// A route that defers: reserve_deferred_slot (pinned room for `bytes` of route flags, the slot's event), then its own device-to-host
+// copies into `pin` on the context's stream, then post_deferred_call (records the event, installs c->pend from the common fields);
+// what is the route's own -- X / ld, or sp_* / idx_dtype / n_cols / is_csr / sorted_known -- it sets in c->pend afterwards.
+int reserve_deferred_slot(illico_ctx *c, size_t bytes, int *slot, void **pin);
+int post_deferred_call(illico_ctx *c, int slot, int kind, int dtype, int flags, int alternative, int64_t N, int64_t col_lb, int64_t col_ub,
+                       const OutPlanes &o);
+// a handle of illico_csr_bind / illico_csc_bind, under the context's lock (held by the caller for the whole call: illico_matrix_release on
+// another thread cannot free the arrays under it).  The list is searched first: a released handle is not read.
+int check_bound_matrix(illico_ctx *c, const illico_matrix *m);
 
 #define FUSED_RT 64 // table size of the fused single-pass routes (values 0 .. 63)
 static const size_t kMaxLds = 160 * 1024;
 static const int kOvoThreads = 512;
 
 static inline size_t dtype_size(int dt) { return (dt == ILLICO_F32 || dt == ILLICO_I32) ? 4 : 8; }
-
-struct OutPlanes {
-    double *p, *u, *fc; // device
-    int64_t ld;
-    bool staged;
-    double *z = nullptr; // device z-score plane (the *_ex entry points), null = none
-    OutPlanes shifted(int64_t j) const { return {p + j, u + j, fc + j, ld, staged, z ? z + j : nullptr}; } // column j on
-};
 
 // pinned slots / copy stream of the host-window pipeline (dense_driver.h: host_windows_pipeline); one per context, freed with it
 #define HS_SLOTS 3
@@ -336,6 +348,37 @@ struct HostStage {
 };
 HostStage *host_stage_of(illico_ctx *c);
 void free_host_stage(illico_ctx *c);
+
+// ---- dispatch on the value / index types ----
+// f(Tag<value type>{}) for a checked dtype code: every build instantiates f for all four value types (the per-group passes)
+template <typename T> struct Tag { using type = T; };
+template <typename F> int dispatch_value_type(int dt, F &&f) {
+    switch (dt) {
+    case ILLICO_F32: return f(Tag<float>{});
+    case ILLICO_F64: return f(Tag<double>{});
+    case ILLICO_I32: return f(Tag<int32_t>{});
+    default: return f(Tag<int64_t>{});
+    }
+}
+// The Wilcoxon drivers: f(Tag<InT>{}, Tag<KeyT>{}), or with an index dtype code f(Tag<InT>{}, Tag<IdxT>{}, Tag<KeyT>{}) -- for the
+// types the build holds.  A development build (ILLICO_DEV_F32_ONLY=1 python build.py: 4x faster) compiles the float32 / int32-index
+// drivers only, and f is instantiated for nothing else.
+#ifndef ILLICO_DEV_F32_ONLY
+template <typename F> int dispatch_driver_types(illico_ctx *, int dt, F &&f) {
+    return dispatch_value_type(dt, [&](auto v) { return f(v, Tag<std::conditional_t<sizeof(typename decltype(v)::type) == 4, u32, u64>>{}); });
+}
+template <typename F> int dispatch_driver_types(illico_ctx *c, int dt, int idx_dtype, F &&f) {
+    return dispatch_driver_types(c, dt, [&](auto v, auto k) { return idx_dtype == ILLICO_IDX_I32 ? f(v, Tag<int32_t>{}, k) : f(v, Tag<int64_t>{}, k); });
+}
+#else
+template <typename F> int dispatch_driver_types(illico_ctx *c, int dt, F &&f) {
+    return dt == ILLICO_F32 ? f(Tag<float>{}, Tag<u32>{}) : fail(c, ILLICO_ERR_DTYPE, "this development build holds the float32 kernels only");
+}
+template <typename F> int dispatch_driver_types(illico_ctx *c, int dt, int idx_dtype, F &&f) {
+    return dt == ILLICO_F32 && idx_dtype == ILLICO_IDX_I32 ? f(Tag<float>{}, Tag<int32_t>{}, Tag<u32>{})
+                                                            : fail(c, ILLICO_ERR_DTYPE, "this development build holds the float32 / int32-index kernels only");
+}
+#endif
 
 // ---- non-template host helpers (core.hip) ----
 int ovo_counts_limit(const illico_ctx *c);           // table size of the two-pass histogram route (k_ovo_counts)

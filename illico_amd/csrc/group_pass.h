@@ -1,6 +1,6 @@
 // Host scaffolding of the passes that read the matrix once per group family -- group_stats.hip, group_moments.hip, pairwise.hip,
 // and nothing else: the description of the input, the checks every entry point makes first, the upload of host-resident sparse
-// arrays, the dispatch on the value and index types, and the groups' positions in chunks.  Everything is local to the including
+// arrays, the dispatch on the index type, and the groups' positions in chunks.  Everything is local to the including
 // unit (the three are linked into one library).  The kernels, the planes, the column windows and the outputs are each family's own.
 #pragma once
 #include "engine.h"
@@ -42,13 +42,6 @@ inline int check_matrix_input(illico_ctx *c, const MatrixInput &in, int64_t col_
     return ILLICO_OK;
 }
 
-// a handle of illico_csr_bind / illico_csc_bind, under the context's lock (held by the caller for the whole call: illico_matrix_release on
-// another thread cannot free the arrays under it).  The list is searched first: a released handle is not read.
-inline int check_bound_matrix(illico_ctx *c, const illico_matrix *m) {
-    if (std::find(c->bound.begin(), c->bound.end(), m) == c->bound.end() || m->owner != c)
-        return fail(c, ILLICO_ERR_ARG, "the matrix handle does not belong to this context (or was released)");
-    return ILLICO_OK;
-}
 // the flags a bound matrix passes on: its arrays are on the device whatever the caller says
 inline int bound_matrix_flags(int flags) { return (flags & (ILLICO_FLAG_LOG1P | ILLICO_FLAG_OUTPUT_DEVICE)) | ILLICO_FLAG_INPUT_DEVICE; }
 
@@ -83,17 +76,8 @@ inline int stage_sparse_input(illico_ctx *c, const MatrixInput &in, int64_t col_
     return ILLICO_OK;
 }
 
-// f(Tag<value type>{}) / f(Tag<value type>{}, Tag<index type>{}) for a checked dtype code (and index dtype code): every build
-// instantiates f for all four value types and both index types
-template <typename T> struct Tag { using type = T; };
-template <typename F> int dispatch_value_type(int dt, F &&f) {
-    switch (dt) {
-    case ILLICO_F32: return f(Tag<float>{});
-    case ILLICO_F64: return f(Tag<double>{});
-    case ILLICO_I32: return f(Tag<int32_t>{});
-    default: return f(Tag<int64_t>{});
-    }
-}
+// f(Tag<value type>{}, Tag<index type>{}) for checked dtype codes: as dispatch_value_type (engine.h), every build instantiates f for
+// all four value types and both index types
 template <typename F> int dispatch_value_index_type(int dt, int idx_dtype, F &&f) {
     return dispatch_value_type(dt, [&](auto v) {
         if (idx_dtype == ILLICO_IDX_I32) return f(v, Tag<int32_t>{});

@@ -294,24 +294,12 @@ static int run_csc_counts_deferred(illico_ctx *c, const void *data, const void *
         }
         if ((rc = launch_finalize(c, s2u, stie, ssum, ovr ? gtot : nullptr, nb, flags, alternative, o, b0, nullptr, pack16, ovr))) return rc;
     }
-    const int slot = c->pend_next;
-    void *&pin = c->pend_pinned[slot];
-    if (c->pend_pinned_bytes[slot] < (size_t)W * 4) {
-        if (pin) hipHostFree(pin);
-        pin = nullptr;
-        c->pend_pinned_bytes[slot] = 0;
-        HIPCHK(c, hipHostMalloc(&pin, (size_t)W * 4 + 4096, hipHostMallocDefault));
-        c->pend_pinned_bytes[slot] = (size_t)W * 4 + 4096;
-    }
-    if (!c->pend_event[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->pend_event[slot], hipEventDisableTiming));
-    HIPCHK(c, hipMemcpyAsync(pin, fb, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->pend_event[slot], c->stream));
-    c->pend_next ^= 1;
+    int slot;
+    if ((rc = reserve_deferred_slot(c, (size_t)W * 4, &slot, &v))) return rc;
+    HIPCHK(c, hipMemcpyAsync(v, fb, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = post_deferred_call(c, slot, 1, dtype, flags, alternative, n_rows, col_lb, col_ub, o))) return rc;
     PendingDense &q = c->pend;
-    q = PendingDense();
-    q.on = true; q.kind = 1; q.sp_data = data; q.sp_indices = indices; q.sp_indptr = indptr; q.idx_dtype = idx_dtype; q.n_cols = n_cols;
-    q.dtype = dtype; q.flags = flags & ~ILLICO_FLAG_DEFER; q.alternative = alternative; q.slot = slot; q.N = n_rows;
-    q.col_lb = col_lb; q.col_ub = col_ub; q.out_ld = o.ld; q.p = o.p; q.u = o.u; q.fc = o.fc; q.z = o.z;
+    q.sp_data = data; q.sp_indices = indices; q.sp_indptr = indptr; q.idx_dtype = idx_dtype; q.n_cols = n_cols;
     return ILLICO_OK;
 }
 
@@ -738,26 +726,13 @@ int run_sparse_t(illico_ctx *c, bool is_csr, const void *data, const void *indic
         u32 *d_flags = (u32 *)v;
         if ((rc = launch_csr_counts_route<InT, IdxT>(c, (const InT *)data, (const IdxT *)indices, (const IdxT *)indptr, n_rows, n_cols, col_lb, col_ub, flags,
                                                      alternative, o, d_flags))) return rc;
-        const int slot = c->pend_next;
-        void *&pin = c->pend_pinned[slot];
-        if (c->pend_pinned_bytes[slot] < (size_t)(W + 4) * 4) {
-            if (pin) hipHostFree(pin);
-            pin = nullptr;
-            c->pend_pinned_bytes[slot] = 0;
-            HIPCHK(c, hipHostMalloc(&pin, (size_t)(W + 4) * 4 + 4096, hipHostMallocDefault));
-            c->pend_pinned_bytes[slot] = (size_t)(W + 4) * 4 + 4096;
-        }
-        if (!c->pend_event[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->pend_event[slot], hipEventDisableTiming));
-        HIPCHK(c, hipMemcpyAsync(pin, d_flags, (size_t)(W + 4) * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipEventRecord(c->pend_event[slot], c->stream));
-        c->pend_next ^= 1;
+        int slot;
+        if ((rc = reserve_deferred_slot(c, (size_t)(W + 4) * 4, &slot, &v))) return rc;
+        HIPCHK(c, hipMemcpyAsync(v, d_flags, (size_t)(W + 4) * 4, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = post_deferred_call(c, slot, 1, dtype, flags, alternative, n_rows, col_lb, col_ub, o))) return rc;
         PendingDense &q = c->pend;
-        q = PendingDense();
-        q.on = true; q.kind = 1; q.is_csr = true; q.sp_data = data; q.sp_indices = indices; q.sp_indptr = indptr;
-        q.sorted_known = c->cur_sorted_known;
+        q.is_csr = true; q.sp_data = data; q.sp_indices = indices; q.sp_indptr = indptr; q.sorted_known = c->cur_sorted_known;
         q.idx_dtype = (int)(sizeof(IdxT) == 4 ? ILLICO_IDX_I32 : ILLICO_IDX_I64); q.n_cols = n_cols;
-        q.dtype = dtype; q.flags = flags & ~ILLICO_FLAG_DEFER; q.alternative = alternative; q.slot = slot; q.N = n_rows;
-        q.col_lb = col_lb; q.col_ub = col_ub; q.out_ld = o.ld; q.p = o.p; q.u = o.u; q.fc = o.fc; q.z = o.z;
         return ILLICO_OK;
     }
 

@@ -187,6 +187,20 @@ def test_bound_handle_used_after_release(env):
         _refused(env.call(fam, "bound", handle=h), _lib.ERR_ARG, "the matrix handle does not belong to this context (or was released)")
 
 
+def test_bound_handle_used_after_release_by_the_wilcoxon_entry_points(env):
+    """illico_run_bound, illico_run_bound_ex and illico_matrix_touch look the handle up in the context's list before they read it."""
+    h = env.bind("csr", "host")
+    p, u, fc, z = (np.zeros((G, M)) for _ in range(4))
+    planes = [a.ctypes.data for a in (p, u, fc)]
+    assert env.lib.illico_run_bound(env.ctx, h, 0, M, 0, 0, *planes, M) == 0
+    assert env.lib.illico_matrix_release(env.ctx, h) == 0
+    for rc in (lambda: env.lib.illico_run_bound(env.ctx, h, 0, M, 0, 0, *planes, M),
+               lambda: env.lib.illico_run_bound_ex(env.ctx, h, 0, M, 0, 0, *planes, z.ctypes.data, M),
+               lambda: env.lib.illico_matrix_touch(env.ctx, h),
+               lambda: env.lib.illico_matrix_release(env.ctx, h)):
+        _refused((rc(), env.err(), None), _lib.ERR_ARG, "the matrix handle does not belong to this context (or was released)")
+
+
 @pytest.mark.parametrize("side", SIDES)
 @pytest.mark.parametrize("fam,shape", ENTRIES)
 def test_good_call_on_an_inner_window(env, fam, shape, side):
