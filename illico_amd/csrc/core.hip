@@ -10,7 +10,7 @@ const char *const kKernelNames[KID_COUNT] = {"k_transpose_permute", "k_ovo_rank"
                                               "k_gs_vmax", "k_gs_dense", "k_gs_csc", "k_gs_csr", "k_gs_totals", "k_gs_finalize",
                                               "k_finalize_z", "k_top_validate", "k_top_sort", "k_top_merge", "k_top_scan",
                                               "k_gm_vmax", "k_gm_dense", "k_gm_csc", "k_gm_csr", "k_gm_totals", "k_gm_finalize", "k_ttest",
-                                              "k_pw_hists_dense", "k_pw_hists_csc", "k_pw_hists_csr", "k_pw_hists_finish", "k_pw_pairs"};
+                                              "k_pw_hists_dense", "k_pw_hists_csc", "k_pw_hists_csr", "k_pw_hists_finish", "k_pw_pairs", "k_ovo_fused_st16"};
 
 // The message of a failed call is kept per calling thread (and in the context, for single-threaded callers): a second
 // thread's failure must not replace the text the first is about to read through illico_last_error.
@@ -253,6 +253,10 @@ int illico_ctx_set_option(illico_ctx *c, const char *key, int64_t value) {
     else if (!strcmp(key, "no_dense_window_path")) c->no_dense_window_path = value != 0;
     else if (!strcmp(key, "ovr_hist_groups_per_wg")) c->ovr_hist_groups_per_wg = (int)std::max<int64_t>(0, value);
     else if (!strcmp(key, "fused_groups_per_wg")) c->fused_groups_per_wg = (int)std::max<int64_t>(0, value);
+    else if (!strcmp(key, "fused_mem_policy")) {
+        if (value < 0 || value > 15 || (value & 3) == 3) return fail(c, ILLICO_ERR_ARG, "fused_mem_policy: loads 0 / 1 / 2 plus stores 0 / 4 / 8 / 12, not %lld", (long long)value);
+        c->fused_mem_policy = (int)value;
+    }
     else return fail(c, ILLICO_ERR_ARG, "unknown option '%s'", key);
     return ILLICO_OK;
 }

@@ -174,6 +174,25 @@ static int ensure_pinned(illico_ctx *c, size_t bytes) {
     c->pinned_bytes = bytes + 4096;
     return ILLICO_OK;
 }
+// The first-pass OVO kernel for a cell width, with or without the z plane, under a memory policy (FUSED_MP_* bits, kernels_ovo_fused.h).
+// What "fused_mem_policy" = 0 stands for: non-temporal loads and 8-byte stores, i.e. 6 (same-process A/B at C2, profiles/NOTES_r06.md:
+// 1.815 -> 1.711 ms; the 16-byte write-through stores on top of it, 14, are worth 0.3 % more and did not clear the round's rule).
+#define FUSED_DEFAULT_NT_LOADS 1
+#define FUSED_DEFAULT_STORES 4
+typedef void (*fused_main_fn)(FusedParams);
+template <typename InT, int RT, int CB, bool Z> static fused_main_fn fused_ovo_main_z(int mp) {
+    switch (mp) {
+    case FUSED_MP_NT: return k_ovo_fused<InT, RT, false, CB, FUSED_U, false, Z, FUSED_MP_NT>;
+    case FUSED_MP_ST16: return k_ovo_fused<InT, RT, false, CB, FUSED_U, false, Z, FUSED_MP_ST16>;
+    case FUSED_MP_ST16 | FUSED_MP_NT: return k_ovo_fused<InT, RT, false, CB, FUSED_U, false, Z, FUSED_MP_ST16 | FUSED_MP_NT>;
+    case FUSED_MP_ST16WT: return k_ovo_fused<InT, RT, false, CB, FUSED_U, false, Z, FUSED_MP_ST16WT>;
+    case FUSED_MP_ST16WT | FUSED_MP_NT: return k_ovo_fused<InT, RT, false, CB, FUSED_U, false, Z, FUSED_MP_ST16WT | FUSED_MP_NT>;
+    default: return k_ovo_fused<InT, RT, false, CB, FUSED_U, false, Z, 0>;
+    }
+}
+template <typename InT, int RT, int CB> static fused_main_fn fused_ovo_main(bool zp, int mp) {
+    return zp ? fused_ovo_main_z<InT, RT, CB, true>(mp) : fused_ovo_main_z<InT, RT, CB, false>(mp);
+}
 // Fused single-pass route over genes [b0, b0+nb): writes final planes for every gene it can take and sets
 // h_flags[j] != 0 for the others (1 / 3: left to the two-pass routes; 2: done by the 256-value stage).  h_flags[nb] (also word nb of
 // the deferred call's pinned flags) != 0: the 256-value stage was left to the host (k_wide_decide; only with max_gather > 0).
@@ -304,13 +323,22 @@ int run_fused_ovo(illico_ctx *c, const void *X, int64_t ld, int64_t b0, int nb, 
             HIPCHK(c, hipGetLastError());
         }
         if (!wide_only) {
-            ProfScope ps(c, KID_OVO_FUSED);
+            // memory policy of the pass ("fused_mem_policy"): 16-byte stores only where every pair of a plane in use is 16-byte aligned.
+            // Left to the engine, the loads are non-temporal where a wavefront's row segment is whole 128-byte lines (4- and 8-byte
+            // values); a byte window's 64-byte segments share each line between two tiles, so it is not read once (and not measured).
+            const int pol = c->fused_mem_policy;
+            int mp = ((pol & 3) == 2 || ((pol & 3) == 0 && FUSED_DEFAULT_NT_LOADS && sizeof(InT) >= 4)) ? FUSED_MP_NT : 0;
+            const int st = (pol & 12) ? (pol & 12) : FUSED_DEFAULT_STORES;
+            auto aligned16 = [](const double *q) { return ((uintptr_t)q & 15) == 0; };
+            if (st != 4 && (P.out_ld & 1) == 0 && aligned16(P.out_p) && aligned16(P.out_u) && aligned16(P.out_fc) && (!zp || aligned16(P.out_z)))
+                mp |= st == 12 ? FUSED_MP_ST16WT : FUSED_MP_ST16;
+            ProfScope ps(c, (mp & (FUSED_MP_ST16 | FUSED_MP_ST16WT)) ? KID_OVO_FUSED_ST16 : KID_OVO_FUSED); // (a name of its own: tests tell the forms apart)
             if (c->max_nonref <= 255) // 8-bit running multiplicities: 34 KB of LDS per workgroup instead of 50 KB
-                hipLaunchKernelGGL((zp ? k_ovo_fused<InT, RT, false, 8, FUSED_U, false, true> : k_ovo_fused<InT, RT, false, 8>), main_grid, dim3(FUSED_NT), lds8, c->stream, P);
+                hipLaunchKernelGGL((fused_ovo_main<InT, RT, 8>(zp, mp)), main_grid, dim3(FUSED_NT), lds8, c->stream, P);
             else if (c->max_nonref <= 65535)
-                hipLaunchKernelGGL((zp ? k_ovo_fused<InT, RT, false, 16, FUSED_U, false, true> : k_ovo_fused<InT, RT, false, 16>), main_grid, dim3(FUSED_NT), lds16, c->stream, P);
+                hipLaunchKernelGGL((fused_ovo_main<InT, RT, 16>(zp, mp)), main_grid, dim3(FUSED_NT), lds16, c->stream, P);
             else { // clusters of more than 65535 cells: 32-bit multiplicities (82 KB: one workgroup per CU)
-                auto kern = zp ? k_ovo_fused<InT, RT, false, 32, FUSED_U, false, true> : k_ovo_fused<InT, RT, false, 32>;
+                auto kern = fused_ovo_main<InT, RT, 32>(zp, mp);
                 const size_t lds32 = fused_main_lds_bytes<RT, false, 32>();
                 HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32));
                 hipLaunchKernelGGL(kern, main_grid, dim3(FUSED_NT), lds32, c->stream, P);

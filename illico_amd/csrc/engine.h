@@ -90,6 +90,7 @@ enum {
     KID_PW_HIST_CSR,
     KID_PW_HIST_FINISH,
     KID_PW_PAIRS, // illico_pairwise_from_hists
+    KID_OVO_FUSED_ST16, // k_ovo_fused's first pass in a 16-byte-store form ("fused_mem_policy" 8 / 12 where the planes allow it)
     KID_COUNT
 };
 extern const char *const kKernelNames[KID_COUNT];
@@ -239,6 +240,7 @@ struct illico_ctx {
     bool no_csr_counts_path = false;   // 1: count-valued CSR never takes the group-major single pass (k_csr_counts)
     bool no_dense_window_path = false; // 1: CSR never goes through dense float32 windows + the fused kernels
     int fused_groups_per_wg = 0; // 0 = auto
+    int fused_mem_policy = 0;    // first OVO pass of the fused route: loads 0 = default / 1 = plain / 2 = non-temporal, + stores 4 = 8 B / 8 = 16 B / 12 = 16 B write-through
     int ovr_hist_groups_per_wg = 0; // k_ovr_from_hists; 0 = auto
     bool profile = false;
     int profile_only = -1;        // >= 0: time this kernel id only (the others run without events around them)

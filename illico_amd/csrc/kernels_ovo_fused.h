@@ -108,7 +108,9 @@ template <> struct CntCell<32> { typedef unsigned int type; };   // groups above
 // UU rows of the wavefront's 64-gene tile, requested back to back: v[u] = X[row_u][gene0 + lane], row_u = perm[p + u].
 // p, p1 are wave-uniform.  PRED: positions at or past p1 (the group's end) re-read the group's last row -- a cache hit,
 // no HBM traffic -- and are masked out by the consumer.
-template <typename InT, int UU, bool PRED, int NV>
+// NTL: the row segments are requested with the non-temporal policy (the first OVO pass, "fused_mem_policy": X is read once, the tables,
+// perm and pos_ptr -- default policy -- are what should stay in L2).  The load keeps its scalar-base form: global_load_dword v, v, s[..] nt.
+template <typename InT, int UU, bool PRED, bool NTL = false, int NV = 0>
 __device__ __forceinline__ void gather_rows(const char *__restrict__ Xg, u32 row_bytes, const_int_p perm, int p, int p1, u32 col_bytes,
                                             InT (&v)[NV]) {
     static_assert(UU <= NV, "chunk larger than the value array");
@@ -131,7 +133,8 @@ __device__ __forceinline__ void gather_rows(const char *__restrict__ Xg, u32 row
         typedef const __attribute__((address_space(1))) char *gchar_p;
         typedef const __attribute__((address_space(1))) InT *gval_p;
         const gchar_p rp = (gchar_p)(((u64)bhi << 32) | blo); // uniform row base
-        v[u] = *(gval_p)(rp + coff);
+        if constexpr (NTL) v[u] = __builtin_nontemporal_load((gval_p)(rp + coff));
+        else v[u] = *(gval_p)(rp + coff);
     }
 }
 
@@ -508,9 +511,33 @@ template <int RT, bool OVR, int CB> static inline size_t fused_main_lds_bytes() 
     return (size_t)(RT + 1) * 64 * 4 + (size_t)(FUSED_NT / 64) * (OVR ? 1 : RT * CB / 32) * 64 * 4;
 }
 // Z: also the z-score plane (zscore_device_pre); Z = false has no z code (the calls without z).
-template <typename InT, int RT, bool OVR, int CB, int U = FUSED_U, bool WIDE = false, bool Z = false>
+// MP (first OVO pass only, option "fused_mem_policy"): FUSED_MP_NT = non-temporal loads of X; result stores FUSED_MP_ST16 = 16 bytes per
+// lane, FUSED_MP_ST16WT = the same, write-through (sc0 sc1: the line does not stay in L2).  A 16-byte store needs a neighbour's half:
+// lanes 2 k and 2 k + 1 exchange, the even lane writes (p[gene], p[gene + 1]) and the odd lane, in the same instruction, (U[gene - 1], U[gene]);
+// a second instruction writes the fold changes from the even lanes and z from the odd ones.  The host launches these forms only when every
+// plane's first column is 16-byte aligned and out_ld is even; the last gene of an odd ncols has no partner and writes its 8 bytes as before.
+#define FUSED_MP_NT 1
+#define FUSED_MP_ST16 2
+#define FUSED_MP_ST16WT 4
+typedef double fused_f64x2 __attribute__((ext_vector_type(2)));
+template <bool WT> __device__ __forceinline__ void fused_store_pair(double *p, double x, double y) {
+    fused_f64x2 v;
+    v.x = x; v.y = y;
+    // (the s_nop: the compiler does not know that the statement reads its data registers for two more cycles)
+    if constexpr (WT) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+    else *(fused_f64x2 *)p = v;
+}
+// the value of lane ^ 1 (DPP quad_perm [1, 0, 3, 2]); every lane of the wavefront must be active
+__device__ __forceinline__ double fused_lane_xor1(double x) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0xB1, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), 0xB1, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+template <typename InT, int RT, bool OVR, int CB, int U = FUSED_U, bool WIDE = false, bool Z = false, int MP = 0>
 __global__ __launch_bounds__(FUSED_NT, WIDE ? (OVR ? 2 : 1) : ((OVR || CB == 8) ? 4 : 3)) void k_ovo_fused(FusedParams P) {
     constexpr int NT = FUSED_NT, NW = NT / 64, CSTR = RT + 1, BW = OVR ? 1 : RT * CB / 32;
+    constexpr bool NTL = (MP & FUSED_MP_NT) != 0, ST16 = (MP & (FUSED_MP_ST16 | FUSED_MP_ST16WT)) != 0, STWT = (MP & FUSED_MP_ST16WT) != 0;
+    static_assert(MP == 0 || (!OVR && !WIDE), "memory policies: the first OVO pass only");
     // Both tables are laid out [value][lane]: the LDS bank of a lookup is set by the lane alone, whatever the values
     // (32-bit cells: conflict-free; 8- / 16-bit cells: four / two neighbouring lanes share a bank).  With [lane][value]
     // rows and an odd lane stride the data-dependent lookups collided at random (4.8 extra LDS cycles per instruction,
@@ -564,7 +591,7 @@ __global__ __launch_bounds__(FUSED_NT, WIDE ? (OVR ? 2 : 1) : ((OVR || CB == 8) 
 
     // ---- this lane's (group, gene) result from the group's integer statistics ----
     auto emit = [&](int g, long long n_tgt, u64 S2, u64 TT, u32 vsum) {
-        if (!act) return;
+        if constexpr (!ST16) { if (!act) return; } // (ST16: every lane stays for the exchange; an inactive lane's values go nowhere)
         double pv, Ustat, fc, tie;
         const GroupConst gc = P.gconst[g]; // (uniform address: one scalar load per group)
         if (OVR) { // dense_ovr.py:57-75: the "reference" of group g is every other cell
@@ -584,10 +611,27 @@ __global__ __launch_bounds__(FUSED_NT, WIDE ? (OVR ? 2 : 1) : ((OVR || CB == 8) 
             fc = (mu_ref_ovo == 0.0) ? __longlong_as_double(0x7FF0000000000000ll) : ((double)vsum / gc.d_tgt) / mu_ref_ovo;
         }
         const size_t o = (size_t)g * P.out_ld + gene;
-        P.out_p[o] = pv;
-        P.out_u[o] = Ustat;
-        P.out_fc[o] = fc;
-        if constexpr (Z) P.out_z[o] = zscore_device_pre(gc.nnn, gc.var0, tie, Ustat, gc.mu);
+        if constexpr (!ST16) {
+            P.out_p[o] = pv;
+            P.out_u[o] = Ustat;
+            P.out_fc[o] = fc;
+            if constexpr (Z) P.out_z[o] = zscore_device_pre(gc.nnn, gc.var0, tie, Ustat, gc.mu);
+        } else {
+            double zs = 0.0;
+            if constexpr (Z) zs = zscore_device_pre(gc.nnn, gc.var0, tie, Ustat, gc.mu);
+            const bool odd = (lane & 1) != 0;
+            const bool paired = (gene | 1) < P.ncols; // both lanes of the pair hold a gene of the window
+            const double r1 = fused_lane_xor1(odd ? pv : Ustat), r2 = fused_lane_xor1((Z && !odd) ? zs : fc);
+            if (paired) { // even lane: (p, p'), (fc, fc'); odd lane: (U', U), (z', z) -- one element back
+                fused_store_pair<STWT>(odd ? P.out_u + o - 1 : P.out_p + o, odd ? r1 : pv, odd ? Ustat : r1);
+                if (Z || !odd) fused_store_pair<STWT>(odd ? P.out_z + o - 1 : P.out_fc + o, odd ? r2 : fc, odd ? zs : r2);
+            } else if (act) {
+                P.out_p[o] = pv;
+                P.out_u[o] = Ustat;
+                P.out_fc[o] = fc;
+                if constexpr (Z) P.out_z[o] = zs;
+            }
+        }
     };
 
     // Scalar row addressing and read/write counters (gather_rows / consume_rmw).  The p-values are evaluated here:
@@ -604,7 +648,7 @@ __global__ __launch_bounds__(FUSED_NT, WIDE ? (OVR ? 2 : 1) : ((OVR || CB == 8) 
         auto chunk = [&](auto uu, auto pred) {
             constexpr int UU = decltype(uu)::value;
             constexpr bool PRED = decltype(pred)::value;
-            gather_rows<InT, UU, PRED>(Xb, row_bytes, permc, p, p1, col_bytes, v);
+            gather_rows<InT, UU, PRED, NTL>(Xb, row_bytes, permc, p, p1, col_bytes, v);
             if (OVR) consume_ovr<InT, RT, UU, PRED, LS>(v, p, p1, ca, S2, vsum);
             else consume_rmw<InT, RT, UU, PRED, CB, LS>(v, p, p1, ca, cb, S2, TT, vsum, bad);
             p += UU;

@@ -113,7 +113,8 @@ int illico_ctx_set_stream(illico_ctx *ctx, void *hip_stream);
  * float64 kernels).
  * Not route switches: "host_narrow" (-1 automatic / 1 / 0: host-resident count matrices go up as bytes), "bound_ahead_genes" (0 = off:
  * a call for fewer genes of a bound CSR matrix computes the aligned window of that many genes around them once and later calls inside
- * the window are slices of it -- for bindings that keep the reference's 256-gene chunk loop).
+ * the window are slices of it -- for bindings that keep the reference's 256-gene chunk loop),
+ * "fused_mem_policy" (cache policy of the fused dense OVO pass, same bits whatever the value: 0 = the engine's choice -- non-temporal loads for 4- and 8-byte values, default loads for byte windows, 8-byte stores; loads of X 1 = default policy, 2 = non-temporal; plus result stores 4 = 8 bytes per lane, 8 = 16 bytes per lane, 12 = 16 bytes write-through).
  * Unknown keys return ILLICO_ERR_ARG. */
 int illico_ctx_set_option(illico_ctx *ctx, const char *key, int64_t value);
 const char *illico_last_error(const illico_ctx *ctx);
