@@ -848,7 +848,7 @@ int run_sparse_inner(illico_ctx *c, bool is_csr, const void *data, int dtype, co
                             const OutPlanes &o) {
     return dispatch_driver_types(c, dtype, idx_dtype, [&](auto v, auto i, auto k) {
         return run_sparse_t<typename decltype(v)::type, typename decltype(i)::type, typename decltype(k)::type>(c, is_csr, data, indices, indptr, dtype, n_rows, n_cols,
-                                                                                                                col_lb, col_ub, flags, alternative, o);
+                                                                                                                col_lb, col_ub, flags, alternative, o, SparseAllow::everything());
     });
 }
 
@@ -954,20 +954,15 @@ int check_bound_matrix(illico_ctx *c, const illico_matrix *m) {
 }
 // do every row's column indices ascend?  Device arrays, on the context's stream; *sorted is written on success only.
 static int csr_rows_sorted_on_device(illico_ctx *c, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows, int *sorted) {
-    void *v;
-    int rc = get_scratch(c, "flag", 16, &v);
-    if (rc) return rc;
-    int *d_bad = (int *)v;
-    HIPCHK(c, hipMemsetAsync(d_bad, 0, 4, c->stream));
     const int grid = (int)std::min<int64_t>((n_rows + 3) / 4 + 1, 8192);
-    if (idx_dtype == ILLICO_IDX_I32)
-        hipLaunchKernelGGL((k_csr_sorted_check<int32_t>), dim3(grid), dim3(256), 0, c->stream, (const int32_t *)indices, (const int32_t *)indptr, (int)n_rows, d_bad);
-    else
-        hipLaunchKernelGGL((k_csr_sorted_check<int64_t>), dim3(grid), dim3(256), 0, c->stream, (const int64_t *)indices, (const int64_t *)indptr, (int)n_rows, d_bad);
-    HIPCHK(c, hipGetLastError());
-    int bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    u32 bad = 0;
+    const int rc = device_probe(c, &bad, 1, [&](u32 *d_bad) {
+        if (idx_dtype == ILLICO_IDX_I32)
+            hipLaunchKernelGGL((k_csr_sorted_check<int32_t>), dim3(grid), dim3(256), 0, c->stream, (const int32_t *)indices, (const int32_t *)indptr, (int)n_rows, (int *)d_bad);
+        else
+            hipLaunchKernelGGL((k_csr_sorted_check<int64_t>), dim3(grid), dim3(256), 0, c->stream, (const int64_t *)indices, (const int64_t *)indptr, (int)n_rows, (int *)d_bad);
+    });
+    if (rc) return rc;
     *sorted = bad ? 0 : 1;
     return ILLICO_OK;
 }

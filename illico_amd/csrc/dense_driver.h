@@ -83,37 +83,10 @@ static int run_ovo_packed(illico_ctx *c, const void *X, int64_t ld, int64_t col0
     }
     {
         OvoCompactParams C;
-        C.Xs = Xt; C.gene_stride = stride; C.counts = c->d_counts; C.nnz = nnz; C.gofs = gofs; C.ref_out = c->pk_ref_out; C.seg_nnz = seg_nnz; C.seg_sum = seg_sum;
-        C.out_sum = ssum; C.G = G; C.ref = ref; C.n_genes = nb; C.nseg = nseg;
-        packed_ref_sizing<KeyT>(n_ref, &C.ref_cap, &C.nbk_lg);
-        if (c->packed_ref_cap > 0) C.ref_cap = std::min(C.ref_cap, std::max(c->packed_ref_cap, 1024));
-        C.out_2u = s2u; C.out_tie = stie; C.route = route; C.big_sorted = c->pk_nbig > 0 ? 1 : 0;
-        C.ref_by_gofs = 0; C.gene_flags = nullptr; C.big_fn = big_fn; C.big_tmp = big_tmp; C.run_cuts = run_cuts; C.run_n = run_n; C.cand_of = c->pk_nbig > 0 ? c->d_pk_big + c->pk_nbig : nullptr; C.n_cand = c->pk_nbig;
-        // small problems per gene (a reference of at most 2048 cells, fewer than 128 groups, none above 256 cells): workgroups of 256 threads,
-        // several per CU
-        const bool eq0 = c->packed_eq_buckets >= 0 ? c->packed_eq_buckets != 0 : n_ref > 16384;
-        const bool small_wg = n_ref <= 2048 && G < 128 && c->pk_nbig == 0 && !c->no_packed_small_wg && C.nbk_lg <= 16 && !eq0; // (such a reference never needs parts)
-        const size_t lds = ocr_lds_bytes(C.ref_cap, C.nbk_lg, sizeof(KeyT), small_wg ? 256 : OCR_NT);
-        // large references: the bucket function follows the reference's distribution (a crowded stretch of values would otherwise
-        // fill buckets beyond three keys and send whole table words to key-by-key walks); "packed_eq_buckets" = 0 / 1 forces
-        const bool eq = c->packed_eq_buckets >= 0 ? c->packed_eq_buckets != 0 : n_ref > 16384;
-        // a reference with more cells than the kernel has key slots: its genes may need value-range parts (kernels_ovo_compact.h: PARTS)
-        C.n_parts = packed_ref_parts<KeyT>(c, n_ref, C.ref_cap, C.nbk_lg);
-        parts = C.n_parts > 1;
-        C.needs_parts = nullptr;
-        if (parts) { // every part adds its share: the statistics start from zero (the plain kernel, first, stores those of the genes that need no parts)
-            if ((rc = get_scratch(c, "packed_needs_parts", (size_t)nb * 4, &v))) return rc;
-            C.needs_parts = (u32 *)v;
-            HIPCHK(c, hipMemsetAsync(C.needs_parts, 0, (size_t)nb * 4, c->stream));
-            HIPCHK(c, hipMemsetAsync(s2u, 0, (size_t)nb * G * sizeof(long long), c->stream));
-            HIPCHK(c, hipMemsetAsync(stie, 0, (size_t)nb * G * sizeof(u64), c->stream));
-        }
-        auto kern = small_wg ? k_ovo_rank_compact<KeyT, false, false, 256> : eq ? k_ovo_rank_compact<KeyT, true> : k_ovo_rank_compact<KeyT, false>;
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ProfScope ps(c, KID_OVO_RANK_COMPACT);
-        hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(small_wg ? 256 : OCR_NT), lds, c->stream, C);
-        HIPCHK(c, hipGetLastError());
-        if (parts && (rc = launch_rank_parts<KeyT>(c, C, nb, lds))) return rc;
+        C.Xs = Xt; C.gene_stride = stride; C.nnz = nnz; C.gofs = gofs; C.ref_out = c->pk_ref_out; C.seg_nnz = seg_nnz; C.seg_sum = seg_sum;
+        C.out_sum = ssum; C.nseg = nseg; C.route = route; C.ref_by_gofs = 0; C.gene_flags = nullptr; C.big_fn = big_fn; C.big_tmp = big_tmp;
+        C.run_cuts = run_cuts; C.run_n = run_n;
+        if ((rc = launch_packed_rank<KeyT, true>(c, C, nb, n_ref, s2u, stie, &parts))) return rc;
     }
     // What the packed kernels left.  The plain kernel's genes (route word 1: a tie-heavy reference column, the reference's segments moved
     // together) go to k_ovo_rank over the packed layout when its LDS holds the reference and the groups (<= 1024 keys); everything else --
@@ -165,15 +138,6 @@ static int launch_transpose(illico_ctx *c, const void *X, int64_t ld, int64_t co
 }
 
 
-static int ensure_pinned(illico_ctx *c, size_t bytes) {
-    if (c->pinned_bytes >= bytes) return ILLICO_OK;
-    if (c->pinned) hipHostFree(c->pinned);
-    c->pinned = nullptr;
-    c->pinned_bytes = 0;
-    HIPCHK(c, hipHostMalloc(&c->pinned, bytes + 4096, hipHostMallocDefault));
-    c->pinned_bytes = bytes + 4096;
-    return ILLICO_OK;
-}
 // The first-pass OVO kernel for a cell width, with or without the z plane, under a memory policy (FUSED_MP_* bits, kernels_ovo_fused.h).
 // What "fused_mem_policy" = 0 stands for: non-temporal loads and 8-byte stores, i.e. 6 (same-process A/B at C2, profiles/NOTES_r06.md:
 // 1.815 -> 1.711 ms; the 16-byte write-through stores on top of it, 14, are worth 0.3 % more and did not clear the round's rule).
@@ -979,11 +943,11 @@ static int run_dense_twopass(illico_ctx *c, const void *X, int dtype, int64_t N,
 
     if ((rc = get_scratch(c, "xt", (size_t)nb_max * stride * sizeof(KeyT), &v))) return rc;
     KeyT *Xt = (KeyT *)v;
-    if ((rc = get_scratch(c, "stats", (size_t)nb_max * G * 24 + (size_t)nb_max * 8, &v))) return rc;
-    long long *s2u = (long long *)v;
-    u64 *stie = (u64 *)(s2u + (size_t)nb_max * G);
-    double *ssum = (double *)(stie + (size_t)nb_max * G);
-    double *gtot = ssum + (size_t)nb_max * G;
+    StatsPlanes st;
+    if ((rc = carve_stats(c, nb_max, G, false, &st))) return rc;
+    long long *const s2u = st.s2u;
+    u64 *const stie = st.stie;
+    double *const ssum = st.ssum, *const gtot = st.gtot;
     u32 *gflags = nullptr;
     if ((counts_path_allowed(c, flags) && !packed && !ovr) || ovr_counts) {
         if ((rc = get_scratch(c, "gene_flags", (size_t)nb_max * 4, &v))) return rc;

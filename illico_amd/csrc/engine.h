@@ -317,6 +317,71 @@ struct ProfScope {
     }
 };
 
+// ---- small host idioms shared by the drivers ----
+// Ask the device up to four words.  clear_flag_words: the "flag" scratch, zeroed, on the context's stream.  device_probe: that, then
+// `launch(words)` (the caller's kernel launches), the first `n` words copied to `out` -- and the wait for them, unless `wait` is false
+// (the caller then waits itself, with further copies behind the same wait).  The scratch is shared by name: a probe's words are
+// read before the next probe is enqueued.
+static inline int clear_flag_words(illico_ctx *c, u32 **words) {
+    void *v;
+    int rc = get_scratch(c, "flag", 16, &v);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(v, 0, 16, c->stream));
+    *words = (u32 *)v;
+    return ILLICO_OK;
+}
+template <typename Launch> static int device_probe(illico_ctx *c, u32 *out, int n, Launch &&launch, bool wait = true) {
+    u32 *words;
+    int rc = clear_flag_words(c, &words);
+    if (rc) return rc;
+    launch(words);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, words, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (wait) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ILLICO_OK;
+}
+// the context's pinned staging for small device -> host results, grown to `bytes`
+static inline int ensure_pinned(illico_ctx *c, size_t bytes) {
+    if (c->pinned_bytes >= bytes) return ILLICO_OK;
+    if (c->pinned) hipHostFree(c->pinned);
+    c->pinned = nullptr;
+    c->pinned_bytes = 0;
+    HIPCHK(c, hipHostMalloc(&c->pinned, bytes + 4096, hipHostMallocDefault));
+    c->pinned_bytes = bytes + 4096;
+    return ILLICO_OK;
+}
+// the per-gene words a kernel left for `nb` genes, on the host (the context's pinned staging): one wait
+static inline int read_gene_flags(illico_ctx *c, const u32 *d_flags, int nb, const u32 **h_flags) {
+    int rc = ensure_pinned(c, (size_t)nb * 4);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->pinned, d_flags, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *h_flags = (const u32 *)c->pinned;
+    return ILLICO_OK;
+}
+// The "stats" scratch of the two-pass routes carved for `nb` genes: doubled rank sums, tie sums, value sums ([nb][G] each), gene
+// totals ([nb]); with_flags: the per-gene words of "gene_flags" too (else null).  stats_batch_genes: how many genes of `n` one carving
+// takes (4 GB of statistics at the most).
+struct StatsPlanes { long long *s2u; u64 *stie; double *ssum, *gtot; u32 *flags; };
+static inline int64_t stats_batch_genes(int64_t n, int G) {
+    return std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)((size_t)(4ll << 30) / ((size_t)G * 24 + 16))));
+}
+static inline int carve_stats(illico_ctx *c, int64_t nb, int G, bool with_flags, StatsPlanes *s) {
+    void *v;
+    int rc = get_scratch(c, "stats", (size_t)nb * G * 24 + (size_t)nb * 8, &v);
+    if (rc) return rc;
+    s->s2u = (long long *)v;
+    s->stie = (u64 *)(s->s2u + (size_t)nb * G);
+    s->ssum = (double *)(s->stie + (size_t)nb * G);
+    s->gtot = s->ssum + (size_t)nb * G;
+    s->flags = nullptr;
+    if (with_flags) {
+        if ((rc = get_scratch(c, "gene_flags", (size_t)nb * 4, &v))) return rc;
+        s->flags = (u32 *)v;
+    }
+    return ILLICO_OK;
+}
+
 void drain_events(illico_ctx *c);
 // ---- deferred calls (core.hip) ----
 int resolve_pending(illico_ctx *c); // completes the deferred call in flight, if any
@@ -401,10 +466,20 @@ int run_leftovers(illico_ctx *c, const void *X, int dtype, int64_t N, int64_t ld
 template <typename InT>
 int run_fused_ovo(illico_ctx *c, const void *X, int64_t ld, int64_t b0, int nb, int flags, int alternative, const OutPlanes &o, int64_t col_off,
                   std::vector<u32> &h_flags, int defer_slot = -1, bool probe = false, int64_t max_gather = 0, const u32 *init_flags = nullptr);
+// Which routes a (re-)entry of run_sparse_t may still take.  `indices_are_codes`: CSC whose `indices` hold the
+// group code of each stored entry's cell (what the device CSR -> CSC transposition writes: the per-entry lookup codes[row] is an
+// uncoalesced gather the CSC kernels then skip).
+struct SparseAllow {
+    bool dense_window, transpose, indices_are_codes, csr_counts;
+    static SparseAllow everything() { return {true, true, false, true}; }           // the entry from core.hip
+    static SparseAllow after_csr_counts() { return {true, true, false, false}; }    // the whole window again, without the group-major pass
+    static SparseAllow exact_window() { return {false, true, false, false}; }       // the exact sparse routes over a window of left-over genes
+    static SparseAllow transposed_codes() { return {false, false, true, false}; }   // the CSC the device transposition wrote
+    SparseAllow in_float32() const { return {dense_window, transpose, indices_are_codes, false}; } // the same call, values narrowed
+};
 template <typename InT, typename IdxT, typename KeyT>
 int run_sparse_t(illico_ctx *c, bool is_csr, const void *data, const void *indices, const void *indptr, int dtype, int64_t n_rows, int64_t n_cols,
-                 int64_t col_lb, int64_t col_ub, int flags, int alternative, const OutPlanes &o, bool allow_dense_window = true,
-                 bool allow_transpose = true, bool indices_are_codes = false, bool allow_csr_counts = true);
+                 int64_t col_lb, int64_t col_ub, int flags, int alternative, const OutPlanes &o, SparseAllow allow);
 // the run_sparse_t of a type given by its codes (core.hip; what a deferred CSC pass's leftovers and the drivers' own re-entries call)
 int run_sparse_inner(illico_ctx *c, bool is_csr, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
                      int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, int alternative, const OutPlanes &o);

@@ -145,6 +145,52 @@ static int launch_rank_parts(illico_ctx *c, OvoCompactParams C, int nb, size_t l
     return ILLICO_OK;
 }
 
+// The packed rank kernel (k_ovo_rank_compact) over `nb` genes, with its PARTS launch where the reference needs one; *parts says whether.
+// The caller fills what describes its own layout in C (Xs / gene_stride, nnz / gofs, the reference's segments, out_sum, route,
+// ref_by_gofs, gene_flags, the big runs' buffers); here: the fields every caller sets alike, the LDS sizing for a reference of at most
+// `n_ref` keys per gene, the bucket function, the clears the parts need, the kernel choice.  SMALL_WG: the dense layout's 256-thread
+// form may be chosen (the sparse units do not hold it).
+template <typename KeyT, bool SMALL_WG>
+static int launch_packed_rank(illico_ctx *c, OvoCompactParams &C, int nb, int64_t n_ref, long long *s2u, u64 *stie, bool *parts) {
+    const int G = (int)c->n_groups;
+    int rc;
+    void *v;
+    C.counts = c->d_counts; C.G = G; C.ref = (int)c->ref; C.n_genes = nb;
+    packed_ref_sizing<KeyT>(n_ref, &C.ref_cap, &C.nbk_lg);
+    if (c->packed_ref_cap > 0) C.ref_cap = std::min(C.ref_cap, std::max(c->packed_ref_cap, 1024));
+    C.out_2u = s2u; C.out_tie = stie; C.big_sorted = c->pk_nbig > 0 ? 1 : 0;
+    C.cand_of = c->pk_nbig > 0 ? c->d_pk_big + c->pk_nbig : nullptr; C.n_cand = c->pk_nbig;
+    // large references: the bucket function follows the reference's distribution (a crowded stretch of values would otherwise
+    // fill buckets beyond three keys and send whole table words to key-by-key walks); "packed_eq_buckets" = 0 / 1 forces
+    // (`eq` and `small_wg` go by the reference GROUP's cells, c->h_counts[c->ref]; the sizing and the parts by `n_ref`, the keys a gene can hold of
+    //  it -- the sparse caller's is smaller --: two sizes on purpose)
+    const bool eq = c->packed_eq_buckets >= 0 ? c->packed_eq_buckets != 0 : c->h_counts[c->ref] > 16384;
+    // small problems per gene (a reference of at most 2048 cells, fewer than 128 groups, none above 256 cells): workgroups of 256 threads,
+    // several per CU (such a reference never needs parts)
+    const bool small_wg = SMALL_WG && c->h_counts[c->ref] <= 2048 && G < 128 && c->pk_nbig == 0 && !c->no_packed_small_wg && C.nbk_lg <= 16 && !eq;
+    const size_t lds = ocr_lds_bytes(C.ref_cap, C.nbk_lg, sizeof(KeyT), small_wg ? 256 : OCR_NT);
+    // a reference with more keys than the kernel has slots: its genes may need value-range parts (kernels_ovo_compact.h: PARTS).  Every
+    // part adds its share: the statistics start from zero (the plain kernel, first, stores those of the genes that need no parts)
+    C.n_parts = packed_ref_parts<KeyT>(c, n_ref, C.ref_cap, C.nbk_lg);
+    *parts = C.n_parts > 1;
+    C.needs_parts = nullptr;
+    if (*parts) {
+        if ((rc = get_scratch(c, "packed_needs_parts", (size_t)nb * 4, &v))) return rc;
+        C.needs_parts = (u32 *)v;
+        HIPCHK(c, hipMemsetAsync(C.needs_parts, 0, (size_t)nb * 4, c->stream));
+        HIPCHK(c, hipMemsetAsync(s2u, 0, (size_t)nb * G * sizeof(long long), c->stream));
+        HIPCHK(c, hipMemsetAsync(stie, 0, (size_t)nb * G * sizeof(u64), c->stream));
+    }
+    auto kern = eq ? k_ovo_rank_compact<KeyT, true> : k_ovo_rank_compact<KeyT, false>;
+    if constexpr (SMALL_WG) { if (small_wg) kern = k_ovo_rank_compact<KeyT, false, false, 256>; }
+    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ProfScope ps(c, KID_OVO_RANK_COMPACT);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(small_wg ? 256 : OCR_NT), lds, c->stream, C);
+    HIPCHK(c, hipGetLastError());
+    if (*parts && (rc = launch_rank_parts<KeyT>(c, C, nb, lds))) return rc;
+    return ILLICO_OK;
+}
+
 constexpr int kOvrThreads = 256; // several small workgroups per CU overlap each other's barriers (1024 measured the same)
 
 struct OvrPackedInput {
