@@ -2,4 +2,4 @@
 // narrow uploads)
 #define ILLICO_DENSE_U8_UNIT
 #include "dense_driver.h"
-template int run_fused_ovo<uint8_t>(illico_ctx *, const void *, int64_t, int64_t, int, int, int, const OutPlanes &, int64_t, std::vector<u32> &, int, bool, int64_t, const u32 *);
+template int run_fused_ovo<uint8_t>(illico_ctx *, const FusedCall &, std::vector<u32> &);

@@ -463,9 +463,19 @@ int run_dense_t(illico_ctx *c, const void *X, int dtype, int64_t N, int64_t ld, 
 template <typename InT, typename KeyT>
 int run_leftovers(illico_ctx *c, const void *X, int dtype, int64_t N, int64_t ld, int64_t col_lb, int64_t col_ub, int flags, int alternative,
                   const OutPlanes &o, const u32 *hf, bool wide_skipped = false, const int *outer = nullptr);
-template <typename InT>
-int run_fused_ovo(illico_ctx *c, const void *X, int64_t ld, int64_t b0, int nb, int flags, int alternative, const OutPlanes &o, int64_t col_off,
-                  std::vector<u32> &h_flags, int defer_slot = -1, bool probe = false, int64_t max_gather = 0, const u32 *init_flags = nullptr);
+// One call of the fused single pass (run_fused_ovo, dense_driver.h): genes [b0, b0 + nb) of X, whose column j is
+// column col_off + j of the planes.  defer_slot >= 0: the route flags go to that deferred slot and nobody waits; probe: find the
+// count-valued genes on the device first (OVR); max_gather > 0: the device may leave the 256-value stage to the host when at most
+// that many genes are flagged; init_flags (host, [nb]): the 256-value stage alone, for the genes marked 1.
+struct FusedCall {
+    const void *X;
+    int64_t ld, b0;
+    int nb, flags, alternative;
+    OutPlanes o;
+    int64_t col_off;
+    int defer_slot = -1; bool probe = false; int64_t max_gather = 0; const u32 *init_flags = nullptr;
+};
+template <typename InT> int run_fused_ovo(illico_ctx *c, const FusedCall &q, std::vector<u32> &h_flags);
 // Which routes a (re-)entry of run_sparse_t may still take.  `indices_are_codes`: CSC whose `indices` hold the
 // group code of each stored entry's cell (what the device CSR -> CSC transposition writes: the per-entry lookup codes[row] is an
 // uncoalesced gather the CSC kernels then skip).

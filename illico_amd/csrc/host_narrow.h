@@ -1,7 +1,7 @@
 // Host side of the narrow uploads: a count matrix that lives in host memory travels to the device as BYTES (a quarter of the float32
 // bytes over a 50 GB/s link) -- cell = the value itself when it is an integer in [0, 255), else 255, the marker the fused kernels
 // already know from k_csr_densify's byte windows ("this gene is not for me").  The conversion runs on the threads that fill the pinned
-// staging slots (dense_driver.h: host_windows_pipeline_narrow); float32 rows go through AVX2 when the CPU has it (16 cells per step).
+// staging slots (dense_driver.h: host_windows_pipeline with ByteWindows); float32 rows go through AVX2 when the CPU has it (16 cells per step).
 #pragma once
 #include <cstdint>
 #include <cstdio>

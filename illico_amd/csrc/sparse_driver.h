@@ -928,9 +928,8 @@ static int route_csr_byte_windows(SparseCall<InT, IdxT> &S, bool *done) {
             HIPCHK(c, hipGetLastError());
         }
         c->fused_tie_sparse = true; // (the window holds CSR input: the reference ranks it by its sparse path)
-        int rcf;
-        if (bytes) rcf = run_fused_ovo<uint8_t>(c, v, ldD, 0, (int)wn, S.flags, S.alternative, S.o, w0 - S.col_lb, hf);
-        else rcf = run_fused_ovo<float>(c, v, ldD, 0, (int)wn, S.flags, S.alternative, S.o, w0 - S.col_lb, hf);
+        const FusedCall q{v, ldD, 0, (int)wn, S.flags, S.alternative, S.o, w0 - S.col_lb};
+        const int rcf = bytes ? run_fused_ovo<uint8_t>(c, q, hf) : run_fused_ovo<float>(c, q, hf);
         c->fused_tie_sparse = false;
         if (rcf) return rcf;
         for (int64_t j = 0; j < wn; ++j)

@@ -27,6 +27,7 @@ from scipy import sparse
 
 import oracle
 from conftest import assert_planes_match
+from route_trace import labels as _labels, trace
 
 pytestmark = pytest.mark.gpu
 
@@ -40,17 +41,6 @@ def engine():
 def _dev(M):
     import torch
     return tuple(torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (M.data, M.indices, M.indptr))
-
-
-def _groups(labels, test):
-    return oracle.encode_and_count_groups(labels, "non-targeting" if test == "ovo" else None)[1]
-
-
-def _labels(rng, sizes):
-    """Groups of the given sizes, the first one the reference, cells shuffled."""
-    codes = np.repeat(np.arange(len(sizes)), sizes)
-    rng.shuffle(codes)
-    return np.array(["non-targeting" if c == 0 else f"pert_{c:03d}" for c in codes])
 
 
 def _counts(seed, n=600, m=256, sizes=(100,) * 6):
@@ -190,24 +180,6 @@ TABLE = {
     "8-deferred-csr-ovo": {"k_csr_counts": 1, "k_fused_tables": 3, "k_ovo_fused": 1, "k_ovo_fused_wide": 1, "k_sparse_seg": 2},
     "8-deferred-csr-ovr": {"k_csr_counts": 1, "k_fused_tables": 4, "k_ovo_fused_wide": 1, "k_ovr_fused": 1, "k_ovr_gene": 1, "k_sparse_seg": 2},
 }
-
-
-def trace(engine, case):
-    """One run of the case under the profiler: (launches per family, planes)."""
-    g = _groups(case["labels"], case["test"])
-    engine.set_groups(g)
-    for k, v in case["opts"].items():
-        engine.set_option(k, v)
-    engine.profile(True)
-    engine.profile_reset()
-    try:
-        got = case["run"](engine, case["X"])
-        prof = engine.profile_get()
-    finally:
-        engine.profile(False)
-        for k in case["opts"]:
-            engine.set_option(k, 0)
-    return {k: v["launches"] for k, v in prof.items()}, got, g
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
