@@ -6,8 +6,10 @@ calls below raise -- nothing here imports the CPU oracle.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 import threading
+from collections import namedtuple
 from pathlib import Path
 
 import numpy as np
@@ -35,19 +37,64 @@ TT_OUTPUTS = ("p", "t", "df", "mean", "var", "mean_ref", "var_ref")
 
 _DTYPES = {np.dtype(np.float32): F32, np.dtype(np.float64): F64, np.dtype(np.int32): I32, np.dtype(np.int64): I64}
 
-# every symbol include/illico_hip.h declares
-SYMBOLS = [
-    "illico_ctx_create", "illico_ctx_destroy", "illico_ctx_set_stream", "illico_ctx_set_option",
-    "illico_last_error", "illico_ctx_synchronize", "illico_set_groups", "illico_run_dense", "illico_run_csc",
-    "illico_run_csr", "illico_csr_indices_sorted", "illico_rank_statistics", "illico_profile_num_kernels", "illico_profile_kernel_name",
-    "illico_profile_get", "illico_profile_reset", "illico_version", "illico_csr_bind", "illico_csc_bind", "illico_run_bound",
-    "illico_matrix_release", "illico_matrix_touch", "illico_profile_input_bytes", "illico_planes_to_host",
-    "illico_adjust_pvalues", "illico_group_stats_dense", "illico_group_stats_csc", "illico_group_stats_csr", "illico_group_stats_bound",
-    "illico_run_dense_ex", "illico_run_csc_ex", "illico_run_csr_ex", "illico_run_bound_ex", "illico_top_by_score",
-    "illico_group_moments_dense", "illico_group_moments_csc", "illico_group_moments_csr", "illico_group_moments_bound",
-    "illico_ttest_from_moments", "illico_student_t_pvalues",
-    "illico_group_value_hists_dense", "illico_group_value_hists_csc", "illico_group_value_hists_csr", "illico_pairwise_from_hists",
-]
+_vp, _i64, _ci, _str = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_char_p
+# How a call names its matrix, after the context: dense (X, dtype, n_rows, n_cols, ld), CSC / CSR (data, dtype, indices, indptr,
+# index dtype, n_rows, n_cols), or a bound handle ...
+_DENSE, _SPARSE, _BOUND = [_vp, _vp, _ci, _i64, _i64, _i64], [_vp, _vp, _ci, _vp, _vp, _ci, _i64, _i64], [_vp, _vp]
+# ... and what follows it: (col_lb, col_ub, flags, ...) and the planes with their row pitch.
+_RUN = [_i64, _i64, _ci, _ci, _vp, _vp, _vp, _i64]          # alternative; p, U, fold change
+_RUN_EX = _RUN[:-1] + [_vp, _i64]                            # ... and z
+_GROUP = [_i64, _i64, _ci, _vp, _vp, _vp, _vp, _i64]        # four planes, any of them null
+_HISTS = [_i64, _i64, _ci, _vp, _vp]                         # H, flags
+
+#: every symbol include/illico_hip.h declares: name -> (argtypes, restype)
+SIGNATURES = {
+    "illico_ctx_create": ([_ci, ctypes.POINTER(_vp)], _ci),
+    "illico_ctx_destroy": ([_vp], _ci),
+    "illico_ctx_set_stream": ([_vp, _vp], _ci),
+    "illico_ctx_set_option": ([_vp, _str, _i64], _ci),
+    "illico_last_error": ([_vp], _str),
+    "illico_ctx_synchronize": ([_vp], _ci),
+    "illico_version": (None, _str),
+    "illico_set_groups": ([_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64], _ci),
+    "illico_run_dense": (_DENSE + _RUN, _ci),
+    "illico_run_csc": (_SPARSE + _RUN, _ci),
+    "illico_run_csr": (_SPARSE + _RUN, _ci),
+    "illico_run_bound": (_BOUND + _RUN, _ci),
+    "illico_run_dense_ex": (_DENSE + _RUN_EX, _ci),
+    "illico_run_csc_ex": (_SPARSE + _RUN_EX, _ci),
+    "illico_run_csr_ex": (_SPARSE + _RUN_EX, _ci),
+    "illico_run_bound_ex": (_BOUND + _RUN_EX, _ci),
+    "illico_csr_bind": (_SPARSE + [_ci, ctypes.POINTER(_vp)], _ci),
+    "illico_csc_bind": (_SPARSE + [_ci, ctypes.POINTER(_vp)], _ci),
+    "illico_matrix_release": ([_vp, _vp], _ci),
+    "illico_matrix_touch": ([_vp, _vp], _ci),
+    "illico_csr_indices_sorted": ([_vp, _vp, _vp, _ci, _i64, _ci, ctypes.POINTER(_ci)], _ci),
+    "illico_rank_statistics": (_DENSE + [_i64, _i64, _ci, _vp, _vp, _vp], _ci),
+    "illico_planes_to_host": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64], _ci),
+    "illico_adjust_pvalues": ([_vp, _vp, _i64, _i64, _i64, _ci, _ci, _vp, _i64, _i64, _vp, _i64], _ci),
+    "illico_top_by_score": ([_vp, _vp, _i64, _i64, _i64, _ci, _i64, _vp, _i64], _ci),
+    "illico_group_stats_dense": (_DENSE + _GROUP, _ci),
+    "illico_group_stats_csc": (_SPARSE + _GROUP, _ci),
+    "illico_group_stats_csr": (_SPARSE + _GROUP, _ci),
+    "illico_group_stats_bound": (_BOUND + _GROUP, _ci),
+    "illico_group_moments_dense": (_DENSE + _GROUP, _ci),
+    "illico_group_moments_csc": (_SPARSE + _GROUP, _ci),
+    "illico_group_moments_csr": (_SPARSE + _GROUP, _ci),
+    "illico_group_moments_bound": (_BOUND + _GROUP, _ci),
+    "illico_ttest_from_moments": ([_vp] * 5 + [_i64, _i64, _ci, _ci, _ci] + [_vp] * 7 + [_i64], _ci),
+    "illico_student_t_pvalues": ([_vp, _vp, _vp, _i64, _ci, _ci, _vp], _ci),
+    "illico_group_value_hists_dense": (_DENSE + _HISTS, _ci),
+    "illico_group_value_hists_csc": (_SPARSE + _HISTS, _ci),
+    "illico_group_value_hists_csr": (_SPARSE + _HISTS, _ci),
+    "illico_pairwise_from_hists": ([_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _i64], _ci),
+    "illico_profile_num_kernels": ([], _ci),
+    "illico_profile_kernel_name": ([_ci], _str),
+    "illico_profile_get": ([_vp, _ci, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64)], _ci),
+    "illico_profile_reset": ([_vp], _ci),
+    "illico_profile_input_bytes": ([_vp, ctypes.POINTER(_i64)], _ci),
+}
+SYMBOLS = list(SIGNATURES)
 
 _lib = None
 _lock = threading.Lock()
@@ -64,55 +111,9 @@ def load() -> ctypes.CDLL:
                 f"{_SO} is missing: the HIP engine has not been built. Run `python __graft_entry__.py` or "
                 "`python illico_amd/csrc/build.py`. There is no CPU fallback.")
         lib = ctypes.CDLL(str(_SO))
-        vp, i64, ci = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
-        lib.illico_ctx_create.argtypes = [ci, ctypes.POINTER(vp)]
-        lib.illico_ctx_destroy.argtypes = [vp]
-        lib.illico_ctx_set_stream.argtypes = [vp, vp]
-        lib.illico_ctx_set_option.argtypes = [vp, ctypes.c_char_p, i64]
-        lib.illico_last_error.argtypes = [vp]
-        lib.illico_last_error.restype = ctypes.c_char_p
-        lib.illico_ctx_synchronize.argtypes = [vp]
-        lib.illico_set_groups.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64]
-        lib.illico_run_dense.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, ci, vp, vp, vp, i64]
-        for f in (lib.illico_run_csc, lib.illico_run_csr):
-            f.argtypes = [vp, vp, ci, vp, vp, ci, i64, i64, i64, i64, ci, ci, vp, vp, vp, i64]
-        lib.illico_csr_indices_sorted.argtypes = [vp, vp, vp, ci, i64, ci, ctypes.POINTER(ci)]
-        lib.illico_rank_statistics.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, vp, vp, vp]
-        lib.illico_profile_num_kernels.argtypes = []
-        lib.illico_profile_kernel_name.argtypes = [ci]
-        lib.illico_profile_kernel_name.restype = ctypes.c_char_p
-        lib.illico_profile_get.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
-        lib.illico_profile_reset.argtypes = [vp]
-        lib.illico_version.restype = ctypes.c_char_p
-        for f in (lib.illico_csr_bind, lib.illico_csc_bind):
-            f.argtypes = [vp, vp, ci, vp, vp, ci, i64, i64, ci, ctypes.POINTER(vp)]
-        lib.illico_run_bound.argtypes = [vp, vp, i64, i64, ci, ci, vp, vp, vp, i64]
-        lib.illico_matrix_release.argtypes = [vp, vp]
-        lib.illico_matrix_touch.argtypes = [vp, vp]
-        lib.illico_profile_input_bytes.argtypes = [vp, ctypes.POINTER(i64)]
-        lib.illico_planes_to_host.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64]
-        lib.illico_adjust_pvalues.argtypes = [vp, vp, i64, i64, i64, ci, ci, vp, i64, i64, vp, i64]
-        lib.illico_group_stats_dense.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, vp, vp, vp, vp, i64]
-        for f in (lib.illico_group_stats_csc, lib.illico_group_stats_csr):
-            f.argtypes = [vp, vp, ci, vp, vp, ci, i64, i64, i64, i64, ci, vp, vp, vp, vp, i64]
-        lib.illico_group_stats_bound.argtypes = [vp, vp, i64, i64, ci, vp, vp, vp, vp, i64]
-        lib.illico_run_dense_ex.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, ci, vp, vp, vp, vp, i64]
-        for f in (lib.illico_run_csc_ex, lib.illico_run_csr_ex):
-            f.argtypes = [vp, vp, ci, vp, vp, ci, i64, i64, i64, i64, ci, ci, vp, vp, vp, vp, i64]
-        lib.illico_run_bound_ex.argtypes = [vp, vp, i64, i64, ci, ci, vp, vp, vp, vp, i64]
-        lib.illico_top_by_score.argtypes = [vp, vp, i64, i64, i64, ci, i64, vp, i64]
-        lib.illico_group_moments_dense.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, vp, vp, vp, vp, i64]
-        for f in (lib.illico_group_moments_csc, lib.illico_group_moments_csr):
-            f.argtypes = [vp, vp, ci, vp, vp, ci, i64, i64, i64, i64, ci, vp, vp, vp, vp, i64]
-        lib.illico_group_moments_bound.argtypes = [vp, vp, i64, i64, ci, vp, vp, vp, vp, i64]
-        lib.illico_ttest_from_moments.argtypes = [vp, vp, vp, vp, vp, i64, i64, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, i64]
-        lib.illico_student_t_pvalues.argtypes = [vp, vp, vp, i64, ci, ci, vp]
-        lib.illico_group_value_hists_dense.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, vp, vp]
-        for f in (lib.illico_group_value_hists_csc, lib.illico_group_value_hists_csr):
-            f.argtypes = [vp, vp, ci, vp, vp, ci, i64, i64, i64, i64, ci, vp, vp]
-        lib.illico_pairwise_from_hists.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, i64, ci, ci, vp, vp, vp, vp, i64]
-        for name in SYMBOLS:  # fail at load time, not at first use, if the library and the header have drifted
-            getattr(lib, name)
+        for name, (argtypes, restype) in SIGNATURES.items():  # a symbol the library lacks fails here, not at first use
+            f = getattr(lib, name)
+            f.argtypes, f.restype = argtypes, restype
         _lib = lib
         return lib
 
@@ -177,24 +178,125 @@ def normalize_values(a: np.ndarray) -> np.ndarray:
     raise KeyError(f"Support for element dtype {dt} is not implemented.")
 
 
+def _torch():
+    """torch, imported at first need: importing this module does not import it."""
+    import torch
+    return torch
+
+
+@functools.lru_cache(maxsize=None)
+def _name(dtype) -> str:
+    """The name of a dtype a caller here asks for ("float64" for np.float64), which torch gives it too.  (``np.dtype(...).name`` costs
+    microseconds; never for the dtype of an array that came in: names do not tell byte orders apart.)"""
+    return np.dtype(dtype).name
+
+
+def _dtype_name(t) -> str:
+    """The element type of a torch tensor as numpy names it ("float64")."""
+    return str(t.dtype).replace("torch.", "")
+
+
+def _has_dtype(x, *dtypes) -> bool:
+    """Whether the elements of ``x`` are exactly of one of the numpy ``dtypes``: a numpy array by its dtype itself, so that another
+    byte order is another type; a tensor by the name of its own."""
+    return x.dtype in dtypes if isinstance(x, np.ndarray) else _dtype_name(x) in [_name(d) for d in dtypes]
+
+
+def _ptr(x):
+    """The address of the first element of a numpy array or a torch tensor; None stays None."""
+    return None if x is None else x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr()
+
+
+def _empty(shape, dtype, device=None):
+    """An uninitialised numpy array, or with ``device`` (a torch device or its name) a tensor there."""
+    if device is None:
+        return np.empty(shape, dtype=dtype)
+    return _torch().empty(tuple(shape), dtype=getattr(_torch(), _name(dtype)), device=device)
+
+
+def _host_or_cuda(x, what) -> bool:
+    """Whether ``x`` is a CUDA tensor; ``ValueError`` unless it is that or a numpy array."""
+    if isinstance(x, np.ndarray):
+        return False
+    if not _is_torch_tensor(x):
+        raise ValueError(f"{what} must be a numpy array or a CUDA tensor, got {type(x).__name__}")
+    if not x.is_cuda:
+        raise ValueError(f"{what} must be a numpy array or a CUDA tensor (got a CPU tensor)")
+    return True
+
+
+def _row_pitch(x):
+    """The row pitch in elements of the 2-D array or tensor ``x`` if the C side can walk it -- unit column stride where it has more
+    than one column; where it has more than one row, a row stride of a whole number of elements, at least the columns, so that
+    rows do not overlap -- else None.  The pitch of a single row is its length."""
+    rows, cols = x.shape
+    (s0, s1), unit = (x.strides, x.itemsize) if isinstance(x, np.ndarray) else (x.stride(), 1)
+    if (cols > 1 and s1 != unit) or (rows > 1 and (s0 % unit or s0 < cols * unit)):
+        return None
+    return int(s0 // unit if rows > 1 else cols)
+
+
+_Plane = namedtuple("_Plane", "array ptr rows cols pitch on_device")
+
+
+def _plane(x, what, *, dtype=np.float64, shape=None, copy_ok=False, writeable=False):
+    """The ``_Plane`` of a [rows, cols] numpy array or CUDA tensor of exactly ``dtype`` (and ``shape``, if given) that ``_row_pitch``
+    can walk.  A host array it cannot walk is copied with ``copy_ok`` and refused without; a device tensor is never copied.
+    ``writeable``: refuse a read-only host array.  Every refusal is a ``ValueError``."""
+    on_dev = _host_or_cuda(x, what)
+    if not _has_dtype(x, dtype) or len(x.shape) != 2 or (shape is not None and tuple(x.shape) != tuple(shape)):
+        raise ValueError(f"{what} must be a {np.dtype(dtype).name} 2-D plane{'' if shape is None else f' of shape {tuple(shape)}'}, "
+                         f"got {x.dtype} of shape {tuple(x.shape)}")
+    pitch = _row_pitch(x)
+    if pitch is None:
+        if on_dev or not copy_ok:
+            raise ValueError(f"{what} must have unit column stride and rows that do not overlap")
+        x = np.ascontiguousarray(x)
+        pitch = x.shape[1]
+    if writeable and not on_dev and not x.flags.writeable:
+        raise ValueError(f"{what} must be writeable")
+    return _Plane(x, _ptr(x), int(x.shape[0]), int(x.shape[1]), pitch, on_dev)
+
+
+def _plane_set(planes, what):
+    """``(pointers, FLAG_OUTPUT_DEVICE or 0, row pitch)`` of ``_Plane`` records the C side takes with one pitch: all on one side, all
+    of one pitch.  A None entry gives a None pointer; the pitch of no planes at all is None."""
+    given = [q for q in planes if q is not None]
+    if len({q.on_device for q in given}) > 1:
+        raise ValueError(f"{what} must all live on the same side (host or device)")
+    if len({q.pitch for q in given}) > 1:
+        raise ValueError(f"{what} must share one row stride")
+    return ([None if q is None else q.ptr for q in planes], FLAG_OUTPUT_DEVICE if given and given[0].on_device else 0,
+            given[0].pitch if given else None)
+
+
+def _block(x, what, dtypes, shape, *, on_device=None, writeable=False):
+    """``(pointer, on the device)`` of a contiguous numpy array or CUDA tensor of exactly ``shape`` whose element type is one of
+    ``dtypes`` (numpy's).  ``on_device``: the side it must be on, if not None.  ``writeable``: refuse a read-only host array."""
+    on_dev = _host_or_cuda(x, what)
+    if not _has_dtype(x, *dtypes) or tuple(x.shape) != tuple(shape) or not (x.is_contiguous() if on_dev else x.flags.c_contiguous) \
+            or (on_device is not None and on_dev != on_device) or (writeable and not on_dev and not x.flags.writeable):
+        side = {None: "", True: "CUDA ", False: "host "}[on_device]
+        raise ValueError(f"{what} must be a {'writeable ' if writeable else ''}contiguous {side}{' / '.join(np.dtype(d).name for d in dtypes)} array of shape {tuple(shape)}")
+    return _ptr(x), on_dev
+
+
 def _dense_input(X):
-    """``(pointer, on the device, keepalive, n_rows, n_cols, row pitch in elements, dtype code)`` of the dense matrix of a group pass:
-    a row-major CUDA tensor as it is; a host array widened as ``normalize_values`` says, and copied only if its strides are not
-    ones the C side can walk (a view of some columns of a wider matrix is passed as it is)."""
-    if _is_torch_tensor(X):
-        if X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1):
-            raise ValueError("X must be row-major 2-D")
-        n_rows, n_cols = int(X.shape[0]), int(X.shape[1])
-        ld = int(X.stride(0)) if n_rows > 1 else n_cols
-        return X.data_ptr(), X.is_cuda, X, n_rows, n_cols, ld, dtype_code(str(X.dtype).replace("torch.", ""))
-    X = normalize_values(np.asarray(X))
-    if X.ndim != 2:
-        raise ValueError(f"X must be 2-D, got {X.ndim} dimensions")
-    if (X.shape[1] > 1 and X.strides[1] != X.itemsize) or X.strides[0] % X.itemsize or X.strides[0] < 0:
+    """``(pointer, on the device, keepalive, n_rows, n_cols, row pitch in elements, dtype code)`` of a dense matrix: a torch tensor as
+    it is (a CPU tensor is host memory); anything else as a host array widened as ``normalize_values`` says.  A view of some columns
+    of a wider matrix is passed as it is; a host array that ``_row_pitch`` cannot walk is copied, such a tensor is refused."""
+    is_tensor = _is_torch_tensor(X)
+    if not is_tensor:
+        X = normalize_values(np.asarray(X))
+    if len(X.shape) != 2:
+        raise ValueError(f"X must be 2-D, got {len(X.shape)} dimensions")
+    ld = _row_pitch(X)
+    if ld is None:
+        if is_tensor:
+            raise ValueError("a tensor X must be row-major with rows that do not overlap: tensors are not copied")
         X = np.ascontiguousarray(X)
-    n_rows, n_cols = X.shape
-    ld = X.strides[0] // X.itemsize if n_rows > 1 else n_cols
-    return X.ctypes.data, False, X, n_rows, n_cols, ld, dtype_code(X.dtype)
+        ld = X.shape[1]
+    return _ptr(X), is_tensor and X.is_cuda, X, int(X.shape[0]), int(X.shape[1]), ld, dtype_code(_dtype_name(X) if is_tensor else X.dtype)
 
 
 def _sparse_input(data, indices, indptr, shape):
@@ -269,8 +371,7 @@ class Engine:
         """
         if not any(_is_torch_tensor(t) and t.is_cuda for t in tensors):
             return
-        import torch
-        s = int(torch.cuda.current_stream(self.device).cuda_stream)
+        s = int(_torch().cuda.current_stream(self.device).cuda_stream)
         if s != self._stream:
             self.set_stream(s)
 
@@ -309,97 +410,50 @@ class Engine:
         if not isinstance(scores, (bool, np.bool_)):
             raise ValueError(f"scores must be a bool, got {scores!r}")
         if out is None:
-            n = 4 if scores else 3
-            if want_device:
-                import torch
-                planes = tuple(torch.empty((G, W), dtype=torch.float64, device=f"cuda:{self.device}") for _ in range(n))
-            else:
-                planes = tuple(np.empty((G, W), dtype=np.float64) for _ in range(n))
+            planes = tuple(_empty((G, W), np.float64, f"cuda:{self.device}" if want_device else None) for _ in range(4 if scores else 3))
         else:
             planes = tuple(out)
             if len(planes) not in (3, 4) or (scores and len(planes) != 4):
                 raise ValueError("out must hold 3 planes (p, U, fold change), or 4 with the z-score plane last (4 with scores=True)")
         if W == 0:  # empty chunk (lb == ub is legal, asymptotic_wilcoxon.py:49): nothing to compute
             return planes, None, 0, 1
-        ptrs, flag, ld = [], 0, None
-        for p in planes:
-            if _is_torch_tensor(p):
-                if p.dtype != __import__("torch").float64 or p.dim() != 2 or p.stride(1) != 1:
-                    raise ValueError("device output planes must be float64 [G, W] with unit column stride")
-                l = p.stride(0)
-                ptrs.append(p.data_ptr())
-                flag = FLAG_OUTPUT_DEVICE if p.is_cuda else 0
-            else:
-                if p.dtype != np.float64 or p.ndim != 2 or p.strides[1] != 8 or p.shape != (G, W):
-                    raise ValueError("output planes must be float64 [G, W] with unit column stride")
-                l = p.strides[0] // 8 if G > 1 else max(W, p.strides[0] // 8)
-                ptrs.append(p.ctypes.data)
-            if ld is None:
-                ld = l
-            elif ld != l:
-                raise ValueError("output planes must share one row stride")
-        return planes, ptrs, flag, int(ld if ld else max(W, 1))
+        ptrs, flag, ld = _plane_set([_plane(p, f"output plane {k}", shape=(G, W), writeable=True) for k, p in enumerate(planes)], "output planes")
+        return planes, ptrs, flag, ld
 
-    def run_dense(self, X, col_lb, col_ub, *, is_log1p=False, use_continuity=True, tie_correct=True,
-                  alternative="two-sided", out=None, device_out=False, defer=False, scores=False):
-        """``defer=True`` (device input and device planes only): return once the pass is enqueued; the planes are complete
+    def _rank_tests(self, fn, matrix, keep, on_dev, n_cols, col_lb, col_ub, is_log1p, use_continuity, tie_correct, alternative, out,
+                    device_out, defer, scores):
+        """What ``run_dense``, ``run_sparse`` and ``BoundMatrix.run`` share: ``fn``, one of illico_run_*_ex, on the columns
+        [col_lb, col_ub) of the matrix its arguments ``matrix`` name (``keep``: the arrays behind them, ``on_dev``: where), with the
+        keywords of those three.  Returns the planes of ``_outputs``; without a fourth one the library gets a null ``out_z``."""
+        alt = self._alt(alternative)
+        _check_chunk_bounds(col_lb, col_ub, n_cols)
+        planes, ptrs, oflag, out_ld = self._outputs(out, self.n_groups, col_ub - col_lb, device_out, scores)
+        if ptrs is None:
+            return planes
+        flags = self._flags(is_log1p, use_continuity, tie_correct) | (FLAG_INPUT_DEVICE if on_dev else 0) | oflag | (FLAG_DEFER if defer else 0)
+        self._bind_torch_stream(*keep, *planes)
+        self._check(fn(self.h, *matrix, col_lb, col_ub, flags, alt, *ptrs, *[None] * (4 - len(ptrs)), out_ld))
+        return planes
+
+    def run_dense(self, X, col_lb, col_ub, *, is_log1p=False, use_continuity=True, tie_correct=True, alternative="two-sided",
+                  out=None, device_out=False, defer=False, scores=False):
+        """The rank-sum tests of the dense columns [col_lb, col_ub) of ``X``.
+        ``defer=True`` (device input and device planes only): return once the pass is enqueued; the planes are complete
         after ``synchronize()`` or the next call on this engine (ILLICO_FLAG_DEFER, include/illico_hip.h).  ``scores=True``
         (or a 4-tuple ``out``): a fourth plane, the z-score of every test (include/illico_hip.h: illico_run_dense_ex)."""
-        alt = self._alt(alternative)
-        if _is_torch_tensor(X):
-            if X.dim() != 2 or X.stride(1) != 1:
-                raise ValueError("X must be row-major 2-D")
-            buf_ptr, on_dev, keep = X.data_ptr(), X.is_cuda, X
-            n_rows, n_cols, ld = X.shape[0], X.shape[1], X.stride(0)
-            dt = dtype_code(str(X.dtype).replace("torch.", ""))
-        else:
-            X = normalize_values(np.asarray(X))
-            if X.ndim != 2 or (X.shape[1] > 1 and X.strides[1] != X.itemsize):
-                X = np.ascontiguousarray(X)
-            buf_ptr, on_dev, keep = X.ctypes.data, False, X
-            n_rows, n_cols = X.shape
-            ld = X.strides[0] // X.itemsize if n_rows > 1 else n_cols
-            dt = dtype_code(X.dtype)
-        if col_lb < 0 or col_ub > n_cols or col_lb > col_ub:
-            raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
-        G, W = self.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = self._outputs(out, G, W, device_out, scores)
-        if ptrs is None:
-            return planes
-        flags = self._flags(is_log1p, use_continuity, tie_correct) | (FLAG_INPUT_DEVICE if on_dev else 0) | oflag | \
-            (FLAG_DEFER if defer else 0)
-        self._bind_torch_stream(keep, *planes)
-        if len(ptrs) == 4:
-            self._check(self.lib.illico_run_dense_ex(self.h, buf_ptr, dt, n_rows, n_cols, ld, col_lb, col_ub, flags, alt,
-                                                     ptrs[0], ptrs[1], ptrs[2], ptrs[3], out_ld))
-        else:
-            self._check(self.lib.illico_run_dense(self.h, buf_ptr, dt, n_rows, n_cols, ld, col_lb, col_ub, flags, alt,
-                                                  ptrs[0], ptrs[1], ptrs[2], out_ld))
-        del keep
-        return planes
+        ptr, on_dev, keep, n_rows, n_cols, ld, dt = _dense_input(X)
+        return self._rank_tests(self.lib.illico_run_dense_ex, (ptr, dt, n_rows, n_cols, ld), (keep,), on_dev, n_cols, col_lb, col_ub,
+                                is_log1p, use_continuity, tie_correct, alternative, out, device_out, defer, scores)
 
-    def run_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, *, is_log1p=False, use_continuity=True,
-                   tie_correct=True, alternative="two-sided", out=None, device_out=False, defer=False, scores=False):
-        """``defer=True`` (device-resident CSC arrays and device planes only; ignored elsewhere): return once the count-valued
-        pass is enqueued; the planes are complete after ``synchronize()`` or the next call on this engine.  ``scores``: as in
-        ``run_dense``."""
-        alt = self._alt(alternative)
+    def run_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, *, is_log1p=False, use_continuity=True, tie_correct=True,
+                   alternative="two-sided", out=None, device_out=False, defer=False, scores=False):
+        """``run_dense`` of a CSC (``fmt="csc"``) or CSR matrix given as its three arrays.  ``defer=True`` (device-resident CSC arrays
+        and device planes only; ignored elsewhere): return once the count-valued pass is enqueued; the planes are complete after
+        ``synchronize()`` or the next call on this engine."""
         d, i, p, idx, n_rows, n_cols = _sparse_input(data, indices, indptr, shape)
-        _check_chunk_bounds(col_lb, col_ub, n_cols)
-        G, W = self.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = self._outputs(out, G, W, device_out, scores)
-        if ptrs is None:
-            return planes
-        flags = self._flags(is_log1p, use_continuity, tie_correct) | (FLAG_INPUT_DEVICE if d.on_device else 0) | oflag | \
-            (FLAG_DEFER if defer else 0)
-        if len(ptrs) == 4:
-            fn = self.lib.illico_run_csc_ex if fmt == "csc" else self.lib.illico_run_csr_ex
-        else:
-            fn = self.lib.illico_run_csc if fmt == "csc" else self.lib.illico_run_csr
-        self._bind_torch_stream(d.keep, i.keep, p.keep, *planes)
-        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols,
-                       col_lb, col_ub, flags, alt, *ptrs, out_ld))
-        return planes
+        fn = self.lib.illico_run_csc_ex if fmt == "csc" else self.lib.illico_run_csr_ex
+        return self._rank_tests(fn, (d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols), (d.keep, i.keep, p.keep), d.on_device,
+                                n_cols, col_lb, col_ub, is_log1p, use_continuity, tie_correct, alternative, out, device_out, defer, scores)
 
     def bind_sparse(self, fmt, data, indices, indptr, shape):
         """Upload a host CSR / CSC matrix once (or adopt device tensors) -- illico_csr_bind / illico_csc_bind; returns a
@@ -422,46 +476,32 @@ class Engine:
         """A contiguous device tensor ``[3, n_groups, n_cols]`` of float64 planes -> a host ndarray of the same shape, through the
         context's pinned double buffer (include/illico_hip.h: illico_planes_to_host): what the gathering rank of a multi-GPU call does
         ONCE with everything it has received."""
-        if not (_is_torch_tensor(planes) and planes.is_cuda and planes.is_contiguous() and planes.dim() == 3 and planes.shape[0] == 3):
+        if not _is_torch_tensor(planes) or planes.dim() != 3 or planes.shape[0] != 3:
             raise ValueError("planes_to_host wants a contiguous CUDA tensor of shape [3, n_groups, n_cols]")
         _, G, W = (int(x) for x in planes.shape)
-        import torch
-        if planes.dtype != torch.float64:
-            raise ValueError(f"planes_to_host wants float64 planes, got {planes.dtype}")
+        base, _ = _block(planes, "planes", (np.float64,), (3, G, W), on_device=True)
         if G != getattr(self, "n_groups", -1):  # the library copies n_groups rows per plane: the groups last set on this engine
             raise ValueError(f"planes hold {G} groups, the engine's groups are {getattr(self, 'n_groups', None)} (set_groups first)")
         if out is None:
             out = np.empty((3, G, W), dtype=np.float64)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == (3, G, W) and out.strides[2] == 8
-                  and out.strides[1] % 8 == 0 and out.strides[1] >= 8 * W and out.flags.writeable):
+        elif not isinstance(out, np.ndarray) or out.shape != (3, G, W):
             raise ValueError("out must be a writeable float64 ndarray [3, n_groups, n_cols] whose rows are contiguous")
+        ptrs, _, out_ld = _plane_set([_plane(out[k], "a plane of out", shape=(G, W), writeable=True) for k in range(3)], "the planes of out")
         self._bind_torch_stream(planes)
-        esz = planes.element_size()
-        base = planes.data_ptr()
-        self._check(self.lib.illico_planes_to_host(self.h, base, base + G * W * esz, base + 2 * G * W * esz, W,
-                                                   out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, out.strides[1] // 8))
+        self._check(self.lib.illico_planes_to_host(self.h, base, base + G * W * 8, base + 2 * G * W * 8, W, *ptrs, out_ld))
         return out
 
     def rank_statistics(self, X, col_lb, col_ub, *, is_log1p=False):
         """The ranking primitives before finalisation (include/illico_hip.h: illico_rank_statistics):
         ``(two_u int64 [W, G], tie_sum uint64 [W, G], value_sum float64 [W, G])`` for the dense columns [col_lb, col_ub)."""
-        if _is_torch_tensor(X):
-            if X.dim() != 2 or X.stride(1) != 1:
-                raise ValueError("X must be row-major 2-D")
-            ptr, on_dev, keep = X.data_ptr(), X.is_cuda, X
-            n_rows, n_cols, ld = X.shape[0], X.shape[1], X.stride(0)
-            dt = dtype_code(str(X.dtype).replace("torch.", ""))
-        else:
-            X = np.ascontiguousarray(normalize_values(np.asarray(X)))
-            ptr, on_dev, keep = X.ctypes.data, False, X
-            (n_rows, n_cols), ld, dt = X.shape, X.shape[1], dtype_code(X.dtype)
+        ptr, on_dev, keep, n_rows, n_cols, ld, dt = _dense_input(X)
+        _check_chunk_bounds(col_lb, col_ub, n_cols)
         W, G = col_ub - col_lb, self.n_groups
         two_u, tie, vsum = np.zeros((W, G), np.int64), np.zeros((W, G), np.uint64), np.zeros((W, G), np.float64)
         self._bind_torch_stream(keep)
         flags = (FLAG_LOG1P if is_log1p else 0) | (FLAG_INPUT_DEVICE if on_dev else 0)
         self._check(self.lib.illico_rank_statistics(self.h, ptr, dt, n_rows, n_cols, ld, col_lb, col_ub, flags,
                                                     two_u.ctypes.data, tie.ctypes.data, vsum.ctypes.data))
-        del keep
         return two_u, tie, vsum
 
     def adjust_pvalues(self, p, method="bh", *, n_top=0, out=None):
@@ -472,43 +512,31 @@ class Engine:
         unit column stride; ``p`` itself adjusts in place) receives the adjusted values.  Returns ``adj``, or ``(adj, top)`` with
         ``top`` int64 ``[G, n_top]`` -- each row's first ``n_top`` columns by ascending p, ties by column -- when ``n_top > 0``."""
         code = _adjust_method(method)
-        p, G, M, ld, on_dev = _adjust_plane(p, "p", copy_ok=True)
+        p = _plane(p, "p", copy_ok=True)
+        G, M, device = p.rows, p.cols, p.array.device if p.on_device else None
         n_top = _adjust_n_top(n_top, M)
-        if on_dev:
-            import torch
-            adj = torch.empty((G, M), dtype=torch.float64, device=p.device) if out is None else out
-            top = torch.empty((G, n_top), dtype=torch.int64, device=p.device) if n_top else None
-        else:
-            adj = np.empty((G, M), dtype=np.float64) if out is None else out
-            top = np.empty((G, n_top), dtype=np.int64) if n_top else None
-        adj, oG, oM, out_ld, o_dev = _adjust_plane(adj, "out", copy_ok=False)
-        if (oG, oM) != (G, M) or o_dev != on_dev:
+        adj = _plane(_empty((G, M), np.float64, device) if out is None else out, "out", shape=(G, M), writeable=True)
+        if adj.on_device != p.on_device:
             raise ValueError(f"out must be a float64 [{G}, {M}] plane on the same side as p")
-        if not on_dev and not adj.flags.writeable:
-            raise ValueError("out must be writeable")
+        top = _empty((G, n_top), np.int64, device) if n_top else None
         if G and M:
-            self._bind_torch_stream(p, adj, top)
-            ptr = (lambda x: x.data_ptr()) if on_dev else (lambda x: x.ctypes.data)
-            self._check(self.lib.illico_adjust_pvalues(self.h, ptr(p), G, M, ld, code, (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0,
-                                                       ptr(adj), out_ld, n_top, ptr(top) if n_top else None, max(n_top, 1)))
-        return (adj, top) if n_top else adj
+            self._bind_torch_stream(p.array, adj.array, top)
+            self._check(self.lib.illico_adjust_pvalues(self.h, p.ptr, G, M, p.pitch, code, (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if p.on_device else 0,
+                                                       adj.ptr, adj.pitch, n_top, _ptr(top), max(n_top, 1)))
+        return (adj.array, top) if n_top else adj.array
 
     def top_by_score(self, x, n_top, *, out=None):
         """Each row's first ``n_top`` columns by DESCENDING score, ties by column (include/illico_hip.h: illico_top_by_score) --
         ``np.argsort(-(x + 0.0), axis=1, kind="stable")[:, :n_top]``.  ``x``: float64 ``[G, M]``, numpy or CUDA tensor with unit
         column stride (a z-score plane); the int64 ``[G, n_top]`` result lives where ``x`` lives.  ``ValueError`` for a NaN."""
-        x, G, M, ld, on_dev = _adjust_plane(x, "x", copy_ok=True)
+        x = _plane(x, "x", copy_ok=True)
+        G, M = x.rows, x.cols
         n_top = _adjust_n_top(n_top, M)
-        if on_dev:
-            import torch
-            top = torch.empty((G, n_top), dtype=torch.int64, device=x.device) if out is None else out
-        else:
-            top = np.empty((G, n_top), dtype=np.int64) if out is None else out
+        top = _empty((G, n_top), np.int64, x.array.device if x.on_device else None) if out is None else out
         if G and M and n_top:
-            self._bind_torch_stream(x, top)
-            ptr = (lambda a: a.data_ptr()) if on_dev else (lambda a: a.ctypes.data)
-            self._check(self.lib.illico_top_by_score(self.h, ptr(x), G, M, ld, (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0,
-                                                     n_top, ptr(top), n_top))
+            self._bind_torch_stream(x.array, top)
+            self._check(self.lib.illico_top_by_score(self.h, x.ptr, G, M, x.pitch, (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if x.on_device else 0,
+                                                     n_top, _ptr(top), n_top))
         return top
 
     # ---- per-group expression statistics (include/illico_hip.h: illico_group_stats_*) ----
@@ -519,46 +547,16 @@ class Engine:
         host ndarray or a CUDA tensor of the right dtype with unit column stride, or None (not computed).  ``kinds`` / ``names``: the
         four planes' dtypes and what the error message calls them (the moment planes are four float64 ones)."""
         if out is None:
-            n = 4 if rest else 2
-            if want_device:
-                import torch
-                tdt = {np.int64: torch.int64, np.float64: torch.float64}
-                planes = tuple(torch.empty((G, W), dtype=tdt[kinds[k]], device=f"cuda:{self.device}") for k in range(n))
-            else:
-                planes = tuple(np.empty((G, W), dtype=kinds[k]) for k in range(n))
+            planes = tuple(_empty((G, W), kinds[k], f"cuda:{self.device}" if want_device else None) for k in range(4 if rest else 2))
         else:
             planes = tuple(out)
             if len(planes) not in (2, 4):
                 raise ValueError(f"out must hold 2 planes {names}")
         if all(p is None for p in planes):
             raise ValueError("at least one output plane is needed")
-        ptrs, side, ld = [], None, None
-        for k, p in enumerate(planes):
-            if p is None:
-                ptrs.append(None)
-                continue
-            if _is_torch_tensor(p):
-                import torch
-                want = torch.int64 if kinds[k] is np.int64 else torch.float64
-                if not p.is_cuda or p.dtype != want or p.dim() != 2 or tuple(p.shape) != (G, W) or (W > 1 and p.stride(1) != 1):
-                    raise ValueError(f"device output plane {k} must be a CUDA {want} [{G}, {W}] tensor with unit column stride")
-                l, dev, ptr = (int(p.stride(0)) if G > 1 else W), True, p.data_ptr()
-            else:
-                if not isinstance(p, np.ndarray) or p.dtype != kinds[k] or p.ndim != 2 or p.shape != (G, W) or \
-                        (W > 1 and p.strides[1] != 8) or (G > 1 and p.strides[0] % 8) or not p.flags.writeable:
-                    raise ValueError(f"output plane {k} must be a writeable {np.dtype(kinds[k])} [{G}, {W}] array with unit column stride")
-                l, dev, ptr = (p.strides[0] // 8 if G > 1 else W), False, p.ctypes.data
-            if side is None:
-                side = dev
-            elif side != dev:
-                raise ValueError("output planes must all live on the same side (host or device)")
-            if ld is None:
-                ld = l
-            elif ld != l:
-                raise ValueError("output planes must share one row stride")
-            ptrs.append(ptr)
-        ptrs += [None] * (4 - len(ptrs))
-        return planes, ptrs, FLAG_OUTPUT_DEVICE if side else 0, int(max(ld or 1, W, 1))
+        ptrs, flag, ld = _plane_set([None if p is None else _plane(p, f"output plane {k}", dtype=kinds[k], shape=(G, W), writeable=True)
+                                     for k, p in enumerate(planes)], "output planes")
+        return planes, ptrs + [None] * (4 - len(ptrs)), flag, max(ld, 1)
 
     def _group_planes_dense(self, family, X, col_lb, col_ub, flags, rest, out, *planes_spec):
         """illico_<family>_dense on X; ``planes_spec``: the ``kinds`` and ``names`` of ``_gs_outputs`` where they are not its defaults."""
@@ -569,7 +567,7 @@ class Engine:
         if W == 0:
             return planes
         self._bind_torch_stream(keep, *[p for p in planes if p is not None])
-        self._check(getattr(self.lib, f"illico_{family}_dense")(self.h, ptr, dt, n_rows, n_cols, max(ld, n_cols), col_lb, col_ub,
+        self._check(getattr(self.lib, f"illico_{family}_dense")(self.h, ptr, dt, n_rows, n_cols, ld, col_lb, col_ub,
                                                                  flags | (FLAG_INPUT_DEVICE if on_dev else 0) | oflag, *ptrs, out_ld))
         return planes
 
@@ -633,53 +631,35 @@ class Engine:
         want = tuple(want)
         if not want or any(w not in TT_OUTPUTS for w in want) or len(set(want)) != len(want):
             raise ValueError(f"want must name distinct planes of {TT_OUTPUTS}, got {want!r}")
-        ins, lds, G, M, on_dev = [], set(), None, None, None
-        for name, x in (("sum", sum), ("sumsq", sumsq), ("sum_rest", sum_rest), ("sumsq_rest", sumsq_rest)):
-            if x is None:
-                if name in ("sum", "sumsq"):
-                    raise ValueError(f"{name} is required")
-                ins.append(None)
-                continue
-            x, g, m, l, dev = _adjust_plane(x, name, copy_ok=True)
-            if G is None:
-                G, M, on_dev = g, m, dev
-            elif (g, m, dev) != (G, M, on_dev):
-                raise ValueError("the moment planes must share one shape and live on the same side (host or device)")
-            lds.add(l)
-            ins.append(x)
-        if len(lds) > 1:
-            if on_dev:
-                raise ValueError("device moment planes must share one row stride")
-            ins, lds = [None if q is None else np.ascontiguousarray(q) for q in ins], {M}
-        ld = max(lds.pop(), M, 1)
+        ins = [None if x is None else _plane(x, name, copy_ok=True)
+               for name, x in (("sum", sum), ("sumsq", sumsq), ("sum_rest", sum_rest), ("sumsq_rest", sumsq_rest))]
+        if ins[0] is None or ins[1] is None:
+            raise ValueError("sum and sumsq are required")
+        given = [q for q in ins if q is not None]
+        G, M, on_dev = given[0].rows, given[0].cols, given[0].on_device
+        if any((q.rows, q.cols) != (G, M) for q in given):
+            raise ValueError("the moment planes must share one shape")
+        if not any(q.on_device for q in given) and len({q.pitch for q in given}) > 1:  # host planes of several pitches: made contiguous
+            ins = [None if q is None else _plane(np.ascontiguousarray(q.array), "a moment plane") for q in ins]
+        in_ptrs, _, ld = _plane_set(ins, "the moment planes")
         if G != getattr(self, "n_groups", None):
             raise ValueError(f"the moment planes have {G} rows but the engine's groups number {getattr(self, 'n_groups', None)}")
         if out is None:
-            if on_dev:
-                import torch
-                planes = tuple(torch.empty((G, M), dtype=torch.float64, device=ins[0].device) for _ in want)
-            else:
-                planes = tuple(np.empty((G, M), dtype=np.float64) for _ in want)
+            planes = tuple(_empty((G, M), np.float64, given[0].array.device if on_dev else None) for _ in want)
         else:
             planes = tuple(out)
             if len(planes) != len(want):
                 raise ValueError(f"out must hold {len(want)} planes, one per entry of want")
-        ptr = (lambda a: a.data_ptr()) if on_dev else (lambda a: a.ctypes.data)
-        optrs, out_ld = [None] * len(TT_OUTPUTS), None
+        outs = dict.fromkeys(TT_OUTPUTS)  # in the order of the library's output arguments
         for w, pl in zip(want, planes):
-            pl2, g, m, l, dev = _adjust_plane(pl, f"out[{w}]", copy_ok=False)
-            if (g, m, dev) != (G, M, on_dev) or (not dev and not pl.flags.writeable):
-                raise ValueError(f"out[{w}] must be a writeable float64 [{G}, {M}] plane on the same side as the moments")
-            if out_ld is None:
-                out_ld = l
-            elif out_ld != l:
-                raise ValueError("output planes must share one row stride")
-            optrs[TT_OUTPUTS.index(w)] = ptr(pl)
+            outs[w] = _plane(pl, f"out[{w}]", shape=(G, M), writeable=True)
+        out_ptrs, oflag, out_ld = _plane_set(list(outs.values()), "the output planes")
+        if bool(oflag) != on_dev:
+            raise ValueError("the output planes must live on the same side as the moments")
         if G and M:
-            self._bind_torch_stream(*[q for q in ins if q is not None], *planes)
-            flags = (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0
-            self._check(self.lib.illico_ttest_from_moments(self.h, *[None if q is None else ptr(q) for q in ins], M, ld, var, alt, flags,
-                                                           *optrs, out_ld))
+            self._bind_torch_stream(*[q.array for q in ins if q is not None], *planes)
+            self._check(self.lib.illico_ttest_from_moments(self.h, *in_ptrs, M, max(ld, 1), var, alt, (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0,
+                                                           *out_ptrs, out_ld))
         return planes
 
     def student_t_pvalues(self, t, df, alternative="two-sided"):
@@ -690,21 +670,18 @@ class Engine:
         if _is_torch_tensor(t) != _is_torch_tensor(df):
             raise ValueError("t and df must both be numpy arrays or both CUDA tensors")
         if _is_torch_tensor(t):
-            import torch
-            if not (t.is_cuda and df.is_cuda) or t.dtype != torch.float64 or df.dtype != torch.float64 or t.shape != df.shape:
+            if not (t.is_cuda and df.is_cuda) or _dtype_name(t) != "float64" or _dtype_name(df) != "float64" or t.shape != df.shape:
                 raise ValueError("t and df must be float64 CUDA tensors of one shape")
             t, df = t.contiguous(), df.contiguous()
-            p = torch.empty_like(t)
-            n, flags, ptr = t.numel(), FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE, (lambda a: a.data_ptr())
+            p, n, flags = _empty(t.shape, np.float64, t.device), t.numel(), FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE
         else:
             t, df = np.ascontiguousarray(t, dtype=np.float64), np.ascontiguousarray(df, dtype=np.float64)
             if t.shape != df.shape:
                 raise ValueError(f"t and df must have one shape, got {t.shape} and {df.shape}")
-            p = np.empty_like(t)
-            n, flags, ptr = t.size, 0, (lambda a: a.ctypes.data)
+            p, n, flags = np.empty_like(t), t.size, 0
         if n:
             self._bind_torch_stream(t, df, p)
-            self._check(self.lib.illico_student_t_pvalues(self.h, ptr(t), ptr(df), n, alt, flags, ptr(p)))
+            self._check(self.lib.illico_student_t_pvalues(self.h, _ptr(t), _ptr(df), n, alt, flags, _ptr(p)))
         return p
 
     # ---- all-pairs Wilcoxon tests from value histograms (include/illico_hip.h: illico_group_value_hists_*, illico_pairwise_from_hists) ----
@@ -715,31 +692,15 @@ class Engine:
         """(H, flags, pointers, output flag): ``out`` None (allocate uint32 ``[G, W, 256]`` and ``[W]`` where the input lives) or a pair
         of contiguous uint32 arrays of those shapes, both numpy or both CUDA tensors (torch has no uint32 kernels: int32 tensors)."""
         if out is None:
-            if want_device:
-                import torch
-                dev = f"cuda:{self.device}"
-                H, fl = torch.empty((G, W, self.HIST_VALUES), dtype=torch.int32, device=dev), torch.empty((W,), dtype=torch.int32, device=dev)
-            else:
-                H, fl = np.empty((G, W, self.HIST_VALUES), dtype=np.uint32), np.empty((W,), dtype=np.uint32)
+            dtype, dev = (np.int32, f"cuda:{self.device}") if want_device else (np.uint32, None)
+            H, fl = _empty((G, W, self.HIST_VALUES), dtype, dev), _empty((W,), dtype, dev)
         else:
             H, fl = out
-        ptrs, side = [], None
-        for name, a, shape in (("H", H, (G, W, self.HIST_VALUES)), ("flags", fl, (W,))):
-            if _is_torch_tensor(a):
-                import torch
-                if not a.is_cuda or a.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(a.shape) != shape or not a.is_contiguous():
-                    raise ValueError(f"{name} must be a contiguous CUDA int32 tensor of shape {shape}")
-                dev, ptr = True, a.data_ptr()
-            else:
-                if not isinstance(a, np.ndarray) or a.dtype != np.uint32 or a.shape != shape or not a.flags.c_contiguous or not a.flags.writeable:
-                    raise ValueError(f"{name} must be a writeable contiguous uint32 array of shape {shape}")
-                dev, ptr = False, a.ctypes.data
-            if side is None:
-                side = dev
-            elif side != dev:
-                raise ValueError("H and flags must live on the same side (host or device)")
-            ptrs.append(ptr)
-        return H, fl, ptrs, FLAG_OUTPUT_DEVICE if side else 0
+        (hp, h_dev), (fp, f_dev) = (_block(a, name, (np.int32, np.uint32) if _is_torch_tensor(a) else (np.uint32,), shape, writeable=True)
+                                    for name, a, shape in (("H", H, (G, W, self.HIST_VALUES)), ("flags", fl, (W,))))
+        if h_dev != f_dev:
+            raise ValueError("H and flags must live on the same side (host or device)")
+        return H, fl, [hp, fp], FLAG_OUTPUT_DEVICE if h_dev else 0
 
     def group_value_hists(self, X, col_lb, col_ub, out=None):
         """Per-(group, gene) histograms of the values 0 .. 255 over the dense columns [col_lb, col_ub) (illico_group_value_hists_dense),
@@ -756,7 +717,7 @@ class Engine:
         if W == 0:
             return H, fl
         self._bind_torch_stream(keep, H, fl)
-        self._check(self.lib.illico_group_value_hists_dense(self.h, ptr, dt, n_rows, n_cols, max(ld, n_cols), col_lb, col_ub,
+        self._check(self.lib.illico_group_value_hists_dense(self.h, ptr, dt, n_rows, n_cols, ld, col_lb, col_ub,
                                                             (FLAG_INPUT_DEVICE if on_dev else 0) | oflag, *ptrs))
         return H, fl
 
@@ -798,7 +759,6 @@ class Engine:
         if on_dev != _is_torch_tensor(flags) or (sums is not None and on_dev != _is_torch_tensor(sums)):
             raise ValueError("H, flags and sums must live on the same side (host or device)")
         if on_dev:
-            import torch
             if not (H.is_cuda and flags.is_cuda and H.is_contiguous() and flags.is_contiguous()) or H.dim() != 3 or H.element_size() != 4 \
                     or flags.element_size() != 4 or H.dtype.is_floating_point or flags.dtype.is_floating_point:
                 raise ValueError("H and flags must be contiguous 32-bit integer CUDA tensors [G, W, 256] and [W]")
@@ -821,39 +781,21 @@ class Engine:
         else:
             sel_arr = np.ascontiguousarray(sel, dtype=np.int64).reshape(-1)
             K, sel_ptr = int(sel_arr.size), sel_arr.ctypes.data
-        sums_ptr, sums_ld = None, 0
         if sums is not None:
-            sums, sg, sw, sums_ld, _ = _adjust_plane(sums, "sums", copy_ok=True)
-            if (sg, sw) != (G, W):
-                raise ValueError(f"sums must be a float64 [{G}, {W}] plane")
-            sums_ptr = sums.data_ptr() if on_dev else sums.ctypes.data
+            sums = _plane(sums, "sums", shape=(G, W), copy_ok=True)
         n = 4 if scores else 3
         if out is None:
-            if on_dev:
-                import torch
-                planes = tuple(torch.empty((K, K, W), dtype=torch.float64, device=H.device) for _ in range(n))
-            else:
-                planes = tuple(np.empty((K, K, W), dtype=np.float64) for _ in range(n))
+            planes = tuple(_empty((K, K, W), np.float64, H.device if on_dev else None) for _ in range(n))
         else:
             planes = tuple(out)
             if len(planes) != n:
                 raise ValueError(f"out must hold {n} planes (p, U, fold change{', z' if scores else ''})")
-        ptrs = []
-        for q in planes:
-            if on_dev:
-                import torch
-                ok = _is_torch_tensor(q) and q.is_cuda and q.dtype == torch.float64 and tuple(q.shape) == (K, K, W) and q.is_contiguous()
-            else:
-                ok = isinstance(q, np.ndarray) and q.dtype == np.float64 and q.shape == (K, K, W) and q.flags.c_contiguous and q.flags.writeable
-            if not ok:
-                raise ValueError(f"output planes must be contiguous float64 [{K}, {K}, {W}] on the side of H")
-            ptrs.append(q.data_ptr() if on_dev else q.ctypes.data)
-        ptrs += [None] * (4 - len(ptrs))
+        ptrs = [_block(q, "an output plane", (np.float64,), (K, K, W), on_device=on_dev, writeable=True)[0] for q in planes]
         fl = self._flags(is_log1p, use_continuity, tie_correct) | ((FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0)
-        ptr = (lambda a: a.data_ptr()) if on_dev else (lambda a: a.ctypes.data)
-        self._bind_torch_stream(H, flags, sums, *planes)
-        self._check(self.lib.illico_pairwise_from_hists(self.h, ptr(H), ptr(flags), counts.ctypes.data, G, W, sel_ptr, K, sums_ptr, sums_ld, fl, alt,
-                                                        *ptrs, max(W, 1)))
+        sums_array, sums_ptr, sums_ld = (None, None, 0) if sums is None else (sums.array, sums.ptr, sums.pitch)
+        self._bind_torch_stream(H, flags, sums_array, *planes)
+        self._check(self.lib.illico_pairwise_from_hists(self.h, _ptr(H), _ptr(flags), counts.ctypes.data, G, W, sel_ptr, K, sums_ptr, sums_ld,
+                                                        fl, alt, *ptrs, *[None] * (4 - n), max(W, 1)))
         return planes
 
     def csr_indices_sorted(self, indices, indptr, n_rows) -> bool:
@@ -898,25 +840,13 @@ class BoundMatrix:
     def __init__(self, engine, handle, shape, keep):
         self.engine, self.h, self.shape, self._keep = engine, handle, shape, keep
 
-    def run(self, col_lb, col_ub, *, is_log1p=False, use_continuity=True, tie_correct=True, alternative="two-sided", out=None,
-            device_out=False, defer=False, scores=False):
-        """``scores``: as in ``Engine.run_dense``.  A call with the z-score plane computes its chunk directly: the windows of
-        the option "bound_ahead_genes" are neither used nor replaced by it (include/illico_hip.h: illico_run_bound_ex)."""
+    def run(self, col_lb, col_ub, *, is_log1p=False, use_continuity=True, tie_correct=True, alternative="two-sided",
+            out=None, device_out=False, defer=False, scores=False):
+        """``Engine.run_dense`` of the bound matrix, with its keywords.  A call with the z-score plane computes its chunk directly: the
+        windows of the option "bound_ahead_genes" are neither used nor replaced by it (include/illico_hip.h: illico_run_bound_ex)."""
         eng = self.engine
-        alt = eng._alt(alternative)
-        n_cols = self.shape[1]
-        _check_chunk_bounds(col_lb, col_ub, n_cols)
-        G, W = eng.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = eng._outputs(out, G, W, device_out, scores)
-        if ptrs is None:
-            return planes
-        flags = eng._flags(is_log1p, use_continuity, tie_correct) | oflag | (FLAG_DEFER if defer else 0)
-        eng._bind_torch_stream(*planes)
-        if len(ptrs) == 4:
-            eng._check(eng.lib.illico_run_bound_ex(eng.h, self.h, col_lb, col_ub, flags, alt, *ptrs, out_ld))
-        else:
-            eng._check(eng.lib.illico_run_bound(eng.h, self.h, col_lb, col_ub, flags, alt, ptrs[0], ptrs[1], ptrs[2], out_ld))
-        return planes
+        return eng._rank_tests(eng.lib.illico_run_bound_ex, (self.h,), (), False, self.shape[1], col_lb, col_ub,
+                               is_log1p, use_continuity, tie_correct, alternative, out, device_out, defer, scores)
 
     def _group_planes(self, family, col_lb, col_ub, flags, rest, out, device_out, *planes_spec):
         """illico_<family>_bound on this matrix; ``planes_spec`` as in ``Engine._group_planes_dense``."""
@@ -969,36 +899,10 @@ def _adjust_n_top(n_top, M) -> int:
     return int(n_top)
 
 
-def _adjust_plane(x, what, copy_ok):
-    """(plane, rows, columns, row pitch in elements, on the device) of a float64 2-D plane whose rows the C side can walk: unit
-    column stride, rows evenly pitched and not overlapping.  copy_ok: a host plane that is not laid out so is copied."""
-    if _is_torch_tensor(x):
-        import torch
-        if not x.is_cuda:
-            raise ValueError(f"{what} must be a numpy array or a CUDA tensor (got a CPU tensor)")
-        if x.dtype != torch.float64 or x.dim() != 2:
-            raise ValueError(f"{what} must be a float64 2-D tensor, got {x.dtype} with {x.dim()} dimensions")
-        G, M = (int(v) for v in x.shape)
-        if (M > 1 and x.stride(1) != 1) or (G > 1 and x.stride(0) < M):
-            raise ValueError(f"{what} must have unit column stride and rows that do not overlap")
-        return x, G, M, int(x.stride(0)) if G > 1 else M, True
-    if not isinstance(x, np.ndarray):
-        raise ValueError(f"{what} must be a numpy array or a CUDA tensor, got {type(x).__name__}")
-    if x.dtype != np.float64 or x.ndim != 2:
-        raise ValueError(f"{what} must be a float64 2-D array, got {x.dtype} with {x.ndim} dimensions")
-    G, M = x.shape
-    if not ((M <= 1 or x.strides[1] == 8) and (G <= 1 or (x.strides[0] % 8 == 0 and x.strides[0] >= 8 * M))):
-        if not copy_ok:
-            raise ValueError(f"{what} must have unit column stride and rows that do not overlap")
-        x = np.ascontiguousarray(x)
-    return x, G, M, x.strides[0] // 8 if G > 1 else M, False
-
-
 def _current_device() -> int:
     try:
-        import torch
-        if torch.cuda.is_available():
-            return torch.cuda.current_device()
+        if _torch().cuda.is_available():
+            return _torch().cuda.current_device()
     except Exception:
         pass
     return 0

@@ -31,6 +31,28 @@ def test_dense_odd_strides_are_copied(view):
     assert (n_rows, n_cols, ld, dt) == (*X.shape, X.shape[1], _lib.I32)
 
 
+@pytest.mark.parametrize("view", [lambda r: np.broadcast_to(r, (8, 6)), lambda r: np.lib.stride_tricks.as_strided(np.arange(13, dtype=r.dtype), (8, 6), (r.itemsize,) * 2)],
+                         ids=["zero_row_stride", "overlapping_rows"])
+def test_dense_rows_closer_than_their_length_are_copied(view):
+    X = view(np.arange(6, dtype=np.float32))
+    assert X.strides[0] < 6 * X.itemsize
+    ptr, _, keep, n_rows, n_cols, ld, dt = _lib._dense_input(X)
+    assert keep is not X and keep.flags.c_contiguous and ptr == keep.ctypes.data
+    np.testing.assert_array_equal(keep, X)
+    assert (n_rows, n_cols, ld, dt) == (8, 6, 6, _lib.F32)
+
+
+def test_dense_cpu_tensor_is_host_memory_and_never_copied():
+    import torch
+    T = torch.arange(80, dtype=torch.float32).reshape(8, 10)
+    for X, ld in ((T, 10), (T[:, 2:8], 10), (T[3:4, 2:8], 6)):
+        ptr, on_dev, keep, n_rows, n_cols, got_ld, dt = _lib._dense_input(X)
+        assert keep is X and (ptr, on_dev, n_rows, n_cols, got_ld, dt) == (X.data_ptr(), False, *X.shape, ld, _lib.F32)
+    for X in (torch.arange(6.).expand(8, 6), T.as_strided((8, 6), (1, 1)), T[:, ::2], T.t(), T[0], T.reshape(2, 4, 10)):
+        with pytest.raises(ValueError):
+            _lib._dense_input(X)
+
+
 def test_dense_one_row():
     P = np.arange(10, dtype=np.float32).reshape(1, 10)
     for X in (P, P[:, 3:7]):
