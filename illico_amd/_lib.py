@@ -46,6 +46,7 @@ _RUN = [_i64, _i64, _ci, _ci, _vp, _vp, _vp, _i64]          # alternative; p, U,
 _RUN_EX = _RUN[:-1] + [_vp, _i64]                            # ... and z
 _GROUP = [_i64, _i64, _ci, _vp, _vp, _vp, _vp, _i64]        # four planes, any of them null
 _HISTS = [_i64, _i64, _ci, _vp, _vp]                         # H, flags
+_RANKED = [_i64, _i64, _vp, _i64, _vp, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _i64, _vp]  # sel, sums, flags, alternative; p, U, fc, z; left
 
 #: every symbol include/illico_hip.h declares: name -> (argtypes, restype)
 SIGNATURES = {
@@ -95,6 +96,11 @@ SIGNATURES = {
     "illico_profile_input_bytes": ([_vp, ctypes.POINTER(_i64)], _ci),
 }
 SYMBOLS = list(SIGNATURES)
+#: the symbols include/illico_hip_ranked.h declares (the ranked pair route), exported by the same library
+RANKED_SIGNATURES = {
+    "illico_pairwise_ranked_dense": (_DENSE + _RANKED, _ci),
+    "illico_pairwise_ranked_csc": (_SPARSE + _RANKED, _ci),
+}
 
 _lib = None
 _lock = threading.Lock()
@@ -111,7 +117,7 @@ def load() -> ctypes.CDLL:
                 f"{_SO} is missing: the HIP engine has not been built. Run `python __graft_entry__.py` or "
                 "`python illico_amd/csrc/build.py`. There is no CPU fallback.")
         lib = ctypes.CDLL(str(_SO))
-        for name, (argtypes, restype) in SIGNATURES.items():  # a symbol the library lacks fails here, not at first use
+        for name, (argtypes, restype) in {**SIGNATURES, **RANKED_SIGNATURES}.items():  # a symbol the library lacks fails here, not at first use
             f = getattr(lib, name)
             f.argtypes, f.restype = argtypes, restype
         _lib = lib
@@ -797,6 +803,78 @@ class Engine:
         self._check(self.lib.illico_pairwise_from_hists(self.h, _ptr(H), _ptr(flags), counts.ctypes.data, G, W, sel_ptr, K, sums_ptr, sums_ld,
                                                         fl, alt, *ptrs, *[None] * (4 - n), max(W, 1)))
         return planes
+
+    # ---- all-pairs Wilcoxon tests for any float32 / int32 values (include/illico_hip_ranked.h: illico_pairwise_ranked_*) ----
+    #: selected groups the ranked pair route takes at most
+    RANKED_MAX_GROUPS = 64
+
+    def _ranked_args(self, W, on_dev, sums, sel, is_log1p, use_continuity, tie_correct, alternative, scores, out):
+        """What the two ranked entry points share: (planes, left, the C arguments after col_ub, keepalives)."""
+        alt = self._alt(alternative)
+        if not isinstance(scores, (bool, np.bool_)):
+            raise ValueError(f"scores must be a bool, got {scores!r}")
+        G = self.n_groups
+        if sums is None:
+            raise ValueError("sums is required: the per-group value sums of group_stats (under is_log1p its expm1 sums)")
+        sums = _plane(sums, "sums", shape=(G, W), copy_ok=True)
+        if sums.on_device != on_dev:
+            raise ValueError("sums must live on the side of the matrix (host or device)")
+        if sel is None:
+            K, sel_arr, sel_ptr = G, None, None
+        else:
+            sel_arr = np.ascontiguousarray(sel, dtype=np.int64).reshape(-1)
+            K, sel_ptr = int(sel_arr.size), sel_arr.ctypes.data
+        n = 4 if scores else 3
+        if out is None:
+            dev = f"cuda:{self.device}" if on_dev else None
+            planes = tuple(_empty((K, K, W), np.float64, dev) for _ in range(n))
+            left = _empty((W,), np.int32 if on_dev else np.uint32, dev)
+        else:
+            out = tuple(out)
+            if len(out) != n + 1:
+                raise ValueError(f"out must hold {n} planes (p, U, fold change{', z' if scores else ''}) and left")
+            planes, left = out[:n], out[n]
+        out_dev = _host_or_cuda(left, "left")
+        ptrs = [_block(q, "an output plane", (np.float64,), (K, K, W), on_device=out_dev, writeable=True)[0] for q in planes]
+        left_ptr = _block(left, "left", (np.int32, np.uint32) if out_dev else (np.uint32,), (W,), on_device=out_dev, writeable=True)[0]
+        fl = self._flags(is_log1p, use_continuity, tie_correct) | (FLAG_INPUT_DEVICE if on_dev else 0) | (FLAG_OUTPUT_DEVICE if out_dev else 0)
+        args = [sel_ptr, K, sums.ptr, sums.pitch, fl, alt, *ptrs, *[None] * (4 - n), max(W, 1), left_ptr]
+        return planes, left, args, (sel_arr, sums.array)
+
+    def pairwise_ranked(self, X, col_lb, col_ub, *, sums, sel=None, is_log1p=False, use_continuity=True, tie_correct=True,
+                        alternative="two-sided", scores=False, out=None):
+        """The Wilcoxon rank-sum test of every ordered pair of groups over the dense columns [col_lb, col_ub), whatever their values
+        (illico_pairwise_ranked_dense), for the engine's current groups (their reference / one-versus-rest mode plays no part).
+
+        ``X``: a row-major float32 / int32 numpy array or CUDA tensor.  ``sums``: the float64 ``[G, W]`` plane of per-group value sums
+        for the fold change, on the side of ``X`` (``group_stats(...)[1]``; under ``is_log1p`` that of ``group_stats(..., is_log1p=True)``:
+        ``is_log1p`` itself changes nothing here).  ``sel``: the K <= 64 group ids to compare (default: all G, in order).  Returns
+        ``(p, U, fold_change[, z], left)``: float64 planes ``[K, K, W]`` indexed ``[r, g, j]`` as ``pairwise_from_hists`` gives them,
+        and ``left`` ``[W]`` (uint32 numpy / int32 CUDA tensor): non-zero for a column the route could not take -- a NaN, more
+        different values than fit crowded into one sliver of the value range -- whose entries are left as they are in ``out`` (a
+        tuple of the 3 or 4 planes and ``left``, all on one side; uninitialised when allocated here).  ``NotImplementedError``: other
+        value types, more than 64 selected groups, two selected groups of 2097152 cells or more together."""
+        ptr, on_dev, keep, n_rows, n_cols, ld, dt = _dense_input(X)
+        _check_chunk_bounds(col_lb, col_ub, n_cols)
+        W = col_ub - col_lb
+        planes, left, args, keepalive = self._ranked_args(W, on_dev, sums, sel, is_log1p, use_continuity, tie_correct, alternative, scores, out)
+        self._bind_torch_stream(keep, keepalive[1], left, *planes)
+        self._check(self.lib.illico_pairwise_ranked_dense(self.h, ptr, dt, n_rows, n_cols, ld, col_lb, col_ub, *args))
+        return (*planes, left)
+
+    def pairwise_ranked_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, *, sums, sel=None, is_log1p=False, use_continuity=True,
+                               tie_correct=True, alternative="two-sided", scores=False, out=None):
+        """``pairwise_ranked`` of a CSC matrix (``fmt="csc"``) given as its three arrays (numpy or CUDA tensors): the dense answer --
+        a stored zero is a zero.  The row indices of a column must ascend (scipy: ``sort_indices()``)."""
+        if fmt != "csc":
+            raise ValueError(f"fmt must be 'csc', got {fmt!r}")
+        d, i, p, idx, n_rows, n_cols = _sparse_input(data, indices, indptr, shape)
+        _check_chunk_bounds(col_lb, col_ub, n_cols)
+        W = col_ub - col_lb
+        planes, left, args, keepalive = self._ranked_args(W, d.on_device, sums, sel, is_log1p, use_continuity, tie_correct, alternative, scores, out)
+        self._bind_torch_stream(d.keep, i.keep, p.keep, keepalive[1], left, *planes)
+        self._check(self.lib.illico_pairwise_ranked_csc(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols, col_lb, col_ub, *args))
+        return (*planes, left)
 
     def csr_indices_sorted(self, indices, indptr, n_rows) -> bool:
         i, p = _Buf(indices), _Buf(indptr)

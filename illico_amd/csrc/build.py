@@ -1,9 +1,10 @@
 """Build libillico_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
 
-The library is seventeen translation units -- the context / C-ABI (core.hip), the launchers that depend on the key type only
+The library is eighteen translation units -- the context / C-ABI (core.hip), the launchers that depend on the key type only
 (keyed_u32 / keyed_u64), one unit per value type for the dense and for the sparse drivers, the p-value adjustment (adjust.hip) and
 the per-group expression statistics (group_stats.hip), the per-group moments with Welch's t-test
-(group_moments.hip) and the all-pairs Wilcoxon tests from value histograms (pairwise.hip) -- compiled in parallel into
+(group_moments.hip) and the all-pairs Wilcoxon tests from value histograms (pairwise.hip) and from one sorted walk per gene
+(pairwise_ranked.hip) -- compiled in parallel into
 _build/*.o and linked.  A unit is recompiled when it, or a header its last compile read (the -MD dependency file), changed:
 an edit to one kernel family rebuilds the units that include it, side by side, in about a minute instead of five.
 """
@@ -19,8 +20,8 @@ HERE = Path(__file__).resolve().parent
 SO = HERE / "libillico_hip.so"
 OBJ = HERE / "_build"
 UNITS = ["core", "keyed_u32", "keyed_u64", "keyed_coop", "dense_f32", "dense_f64", "dense_i32", "dense_i64", "dense_u8",
-         "sparse_f32", "sparse_f64", "sparse_i32", "sparse_i64", "adjust", "group_stats", "group_moments", "pairwise"]
-DEV_UNITS = ["core", "keyed_u32", "keyed_coop", "dense_f32", "dense_u8", "sparse_f32", "adjust", "group_stats", "group_moments", "pairwise"]  # ILLICO_DEV_F32_ONLY=1: float32 values, int32 indices
+         "sparse_f32", "sparse_f64", "sparse_i32", "sparse_i64", "adjust", "group_stats", "group_moments", "pairwise", "pairwise_ranked"]
+DEV_UNITS = ["core", "keyed_u32", "keyed_coop", "dense_f32", "dense_u8", "sparse_f32", "adjust", "group_stats", "group_moments", "pairwise", "pairwise_ranked"]  # ILLICO_DEV_F32_ONLY=1: float32 values, int32 indices
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value"]
 LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared", "-Wl,-z,defs", f"-Wl,--version-script={HERE / 'exports.map'}"]
 

@@ -10,7 +10,8 @@ const char *const kKernelNames[KID_COUNT] = {"k_transpose_permute", "k_ovo_rank"
                                               "k_gs_vmax", "k_gs_dense", "k_gs_csc", "k_gs_csr", "k_gs_totals", "k_gs_finalize",
                                               "k_finalize_z", "k_top_validate", "k_top_sort", "k_top_merge", "k_top_scan",
                                               "k_gm_vmax", "k_gm_dense", "k_gm_csc", "k_gm_csr", "k_gm_totals", "k_gm_finalize", "k_ttest",
-                                              "k_pw_hists_dense", "k_pw_hists_csc", "k_pw_hists_csr", "k_pw_hists_finish", "k_pw_pairs", "k_ovo_fused_st16"};
+                                              "k_pw_hists_dense", "k_pw_hists_csc", "k_pw_hists_csr", "k_pw_hists_finish", "k_pw_pairs", "k_ovo_fused_st16",
+                                              "k_pw_rank_pairs", "k_pw_rank_emit"};
 
 // The message of a failed call is kept per calling thread (and in the context, for single-threaded callers): a second
 // thread's failure must not replace the text the first is about to read through illico_last_error.
@@ -235,6 +236,7 @@ int illico_ctx_set_option(illico_ctx *c, const char *key, int64_t value) {
     else if (!strcmp(key, "no_csc_regroup_lds")) c->no_csc_regroup_lds = value != 0;
     else if (!strcmp(key, "no_csc_gene_path")) c->no_csc_gene_path = value != 0;
     else if (!strcmp(key, "ovr_parts_cap")) c->ovr_parts_cap = value;
+    else if (!strcmp(key, "pair_rank_cap")) c->pair_rank_cap = value > 0 ? std::max<int64_t>(1024, value) : 0;
     else if (!strcmp(key, "ovr_rank_whole")) c->ovr_rank_whole = value != 0;
     else if (!strcmp(key, "no_ovo_ref_buckets")) c->no_ovo_ref_buckets = value != 0;
     else if (!strcmp(key, "no_ovr_parts_path")) c->no_ovr_parts_path = value != 0;

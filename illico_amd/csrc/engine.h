@@ -91,6 +91,8 @@ enum {
     KID_PW_HIST_FINISH,
     KID_PW_PAIRS, // illico_pairwise_from_hists
     KID_OVO_FUSED_ST16, // k_ovo_fused's first pass in a 16-byte-store form ("fused_mem_policy" 8 / 12 where the planes allow it)
+    KID_PW_RANK_PAIRS, // illico_pairwise_ranked_* (kernels_pairwise_ranked.h)
+    KID_PW_RANK_EMIT,
     KID_COUNT
 };
 extern const char *const kKernelNames[KID_COUNT];
@@ -224,6 +226,7 @@ struct illico_ctx {
     bool no_csc_gene_path = false;
     bool ovr_rank_whole = false;       // dense OVR rank kernel: one 1024-thread workgroup per CU with all of the LDS (as before round 5) instead of two of 512
     int64_t ovr_parts_cap = 0;         // > 0: keys per part at most in the value-range parts route (tests: many small parts)
+    int64_t pair_rank_cap = 0;         // > 0: records per part at most in the ranked pair route (tests: many small parts)
     bool no_ovo_ref_buckets = false;   // 1: the OVO sort route always sorts the reference column (no value-bucket form)
     bool no_ovr_parts_path = false;    // 1: dense OVR (any values) never takes the value-range parts route (k_ovr_partition + k_csc_ovr_gene)
     bool no_csc_ovr_gene_path = false; // 1: CSC OVR never takes the single-kernel LDS-sort route (k_csc_ovr_gene)

@@ -7,8 +7,9 @@ perturbation screen that compares perturbations with each other.  Row ``(g, r, g
 For count-valued genes (integers 0 .. 255) the statistics of a test are functions of the two groups' value histograms alone: the
 histograms of all groups are formed on the device in one read of the matrix (include/illico_hip.h: illico_group_value_hists_*), and
 every ordered pair follows from them (illico_pairwise_from_hists).  Genes with other values (continuous, negative, beyond 255) are
-gathered once and completed by one one-versus-reference engine call per reference: a log-normalised matrix takes that path whole and
-costs K such calls.
+gathered once; float32 / int32 values and up to 64 groups take one sorted walk per gene that gives every pair
+(illico_pairwise_ranked_*): a log-normalised float32 matrix takes that path whole.  What it cannot take -- other value types, more
+groups, a gene with a NaN -- is completed by one one-versus-reference engine call per reference.
 """
 from __future__ import annotations
 
@@ -106,9 +107,45 @@ def _windows(lb: int, ub: int, w: int):
     return [(a, min(ub, a + w)) for a in range(lb, ub, w)]
 
 
+def _ranked_route_takes(eng, Xf, K: int) -> bool:
+    """Whether the ranked pair route takes the gathered genes ``Xf``: float32 / int32 values, at most 64 selected groups."""
+    dt = Xf.data.dtype if hasattr(Xf, "indptr") else Xf.dtype
+    return K <= eng.RANKED_MAX_GROUPS and str(dt).replace("torch.", "") in ("float32", "int32")
+
+
+def _ranked_pairs(eng, Xf, sel: np.ndarray, planes: np.ndarray, cols: np.ndarray, opts: dict) -> np.ndarray:
+    """The gathered genes ``Xf`` (gene j is column ``cols[j]`` of ``planes``) through ``Engine.pairwise_ranked``, window by window,
+    under the engine's current groups.  Returns the genes (indices into ``Xf``'s columns) the route left: their columns are not written."""
+    import torch
+    K, n_planes, nf = int(sel.size), int(planes.shape[0]), int(Xf.shape[1])
+    sparse_f = hasattr(Xf, "indptr")
+    if sparse_f:
+        Xf.sort_indices()
+    width = max(64, (PAIR_WINDOW_BYTES // (n_planes * K * K * 8)) // 64 * 64)
+    left_genes = []
+    for a, b in _windows(0, nf, width):
+        try:
+            if sparse_f:
+                sums = eng.group_stats_sparse("csc", Xf.data, Xf.indices, Xf.indptr, Xf.shape, a, b, is_log1p=opts["is_log1p"])[1]
+                got = eng.pairwise_ranked_sparse("csc", Xf.data, Xf.indices, Xf.indptr, Xf.shape, a, b, sums=sums, sel=sel, **opts)
+            else:
+                sums = eng.group_stats(Xf, a, b, is_log1p=opts["is_log1p"])[1]
+                got = eng.pairwise_ranked(Xf, a, b, sums=sums, sel=sel, **opts)
+        except (MemoryError, torch.cuda.OutOfMemoryError):
+            left_genes.append(np.arange(a, b))
+            continue
+        got = [q.cpu().numpy() if hasattr(q, "cpu") else q for q in got]
+        done = np.flatnonzero(got[-1] == 0)
+        for k in range(n_planes):
+            planes[k][:, :, cols[a + done]] = got[k][:, :, done]
+        left_genes.append(a + np.flatnonzero(got[-1] != 0))
+    return np.concatenate(left_genes) if left_genes else np.empty(0, dtype=np.int64)
+
+
 def pairwise_planes(X, handler, group_container, sel: np.ndarray, is_log1p: bool, alternative: str, use_continuity: bool, tie_correct: bool,
                     scores: bool):
-    """(planes float64 [3 or 4, K, K, n_genes] indexed [plane, r, g, gene], number of flagged genes) for the groups ``sel``."""
+    """(planes float64 [3 or 4, K, K, n_genes] indexed [plane, r, g, gene], number of flagged genes, number of them completed by the
+    per-reference fallback) for the groups ``sel``."""
     import torch
     from illico_amd import _lib
     from illico_amd.group_stats import _chunks
@@ -167,22 +204,28 @@ def pairwise_planes(X, handler, group_container, sel: np.ndarray, is_log1p: bool
             flagged_parts.append(_gather_columns(src, off + chunk_flagged))
             flagged_cols.append(lb + chunk_flagged)
     n_flagged = int(sum(c.size for c in flagged_cols))
+    n_fallback = 0
     if n_flagged:
-        # what a user does by hand today: one one-versus-reference call per reference, here on the flagged genes alone
         cols = np.concatenate(flagged_cols)
         Xf = _hstack(flagged_parts)
-        sparse_f = hasattr(Xf, "indptr")
-        for ri, r in enumerate(sel):
-            eng.set_groups(group_container._replace(encoded_ref_group=int(r)))
-            kw = dict(is_log1p=is_log1p, use_continuity=use_continuity, tie_correct=tie_correct, alternative=alternative, scores=scores)
-            if sparse_f:
-                got = eng.run_sparse("csc", Xf.data, Xf.indices, Xf.indptr, Xf.shape, 0, n_flagged, **kw)
-            else:
-                got = eng.run_dense(Xf, 0, n_flagged, **kw)
-            for k in range(n_planes):
-                q = got[k].cpu().numpy() if hasattr(got[k], "cpu") else got[k]
-                planes[k][ri][:, cols] = q[sel]
-    return planes, n_flagged
+        opts = dict(is_log1p=is_log1p, use_continuity=use_continuity, tie_correct=tie_correct, alternative=alternative, scores=scores)
+        # any float32 / int32 values, up to 64 groups: every pair from one sorted walk per gene (illico_pairwise_ranked_*) ...
+        rest = _ranked_pairs(eng, Xf, sel, planes, cols, opts) if _ranked_route_takes(eng, Xf, K) else np.arange(n_flagged)
+        n_fallback = int(rest.size)
+        if n_fallback:
+            # ... and for what it leaves, what a user does by hand: one one-versus-reference call per reference
+            Xr = Xf if n_fallback == n_flagged else _gather_columns(Xf, rest)
+            sparse_f = hasattr(Xr, "indptr")
+            for ri, r in enumerate(sel):
+                eng.set_groups(group_container._replace(encoded_ref_group=int(r)))
+                if sparse_f:
+                    got = eng.run_sparse("csc", Xr.data, Xr.indices, Xr.indptr, Xr.shape, 0, n_fallback, **opts)
+                else:
+                    got = eng.run_dense(Xr, 0, n_fallback, **opts)
+                for k in range(n_planes):
+                    q = got[k].cpu().numpy() if hasattr(got[k], "cpu") else got[k]
+                    planes[k][ri][:, cols[rest]] = q[sel]
+    return planes, n_flagged, n_fallback
 
 
 def pairwise_wilcoxon(adata, is_log1p: bool, group_keys: str, *, groups=None, alternative: str = "two-sided", use_continuity: bool = True,
@@ -200,7 +243,8 @@ def pairwise_wilcoxon(adata, is_log1p: bool, group_keys: str, *, groups=None, al
     ``p_value_adj`` with ``corr_method`` (``"benjamini-hochberg"`` / ``"bh"``, ``"benjamini-yekutieli"`` / ``"by"``,
     ``"bonferroni"``): each (pert, reference) pair adjusted across its genes.  Row ``(g, r, gene)`` is row ``(g, gene)`` of
     ``asymptotic_wilcoxon(..., reference=r)``.  ``df.attrs["n_flagged_genes"]``: the genes that hold a value which is no integer in
-    [0, 255] -- they are completed by one one-versus-reference engine call per reference.
+    [0, 255]; ``df.attrs["n_ranked_genes"]`` of them took the sorted walk that gives every pair (float32 / int32 values, up to 64
+    groups), ``df.attrs["n_fallback_genes"]`` were completed by one one-versus-reference engine call per reference.
 
     ``ValueError``: a label of ``groups`` that is not present or named twice, fewer than two groups, a bad ``alternative``, a
     non-bool ``is_log1p``, and a result of more than ``max_result_bytes`` bytes (K (K - 1) x genes x 8 bytes x columns), raised before
@@ -218,8 +262,8 @@ def pairwise_wilcoxon(adata, is_log1p: bool, group_keys: str, *, groups=None, al
                          f"max_result_bytes = {int(max_result_bytes)}: restrict `groups`, or raise max_result_bytes")
     from illico_amd.utils.registry import data_handler_registry
     handler = data_handler_registry.get(X)
-    planes, n_flagged = pairwise_planes(X, handler, group_container, sel, bool(is_log1p), alternative, bool(use_continuity),
-                                        bool(tie_correct), bool(scores))
+    planes, n_flagged, n_fallback = pairwise_planes(X, handler, group_container, sel, bool(is_log1p), alternative, bool(use_continuity),
+                                                    bool(tie_correct), bool(scores))
     r_idx, g_idx = np.divmod(np.arange(K * K), K)
     off = r_idx != g_idx
     rows = np.flatnonzero(off)
@@ -235,4 +279,6 @@ def pairwise_wilcoxon(adata, is_log1p: bool, group_keys: str, *, groups=None, al
     index = _pair_index(labels, np.asarray(adata.var_names), r_idx[rows], g_idx[rows])
     df = pd.DataFrame(cols, index=index, copy=False)
     df.attrs["n_flagged_genes"] = n_flagged
+    df.attrs["n_ranked_genes"] = n_flagged - n_fallback
+    df.attrs["n_fallback_genes"] = n_fallback
     return df

@@ -389,6 +389,10 @@ int illico_pairwise_from_hists(illico_ctx *ctx, const uint32_t *H, const uint32_
                                int64_t n_cols, const int64_t *sel, int64_t n_sel, const double *sums, int64_t sums_ld, int flags,
                                int alternative, double *out_p, double *out_u, double *out_fc, double *out_z, int64_t out_ld);
 
+/* ---- all-pairs Wilcoxon rank-sum tests for any values of a 4-byte type: one sorted walk per gene -----------
+ * The illico_pairwise_ranked_* entry points (dense and CSC input) are declared and documented in illico_hip_ranked.h, which includes
+ * this header. */
+
 /* ---- measurement hooks (bench.py roofline leg) ------------------------------------------- */
 int illico_profile_num_kernels(void);
 const char *illico_profile_kernel_name(int kernel_id);

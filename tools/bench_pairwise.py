@@ -2,7 +2,7 @@
 """All-pairs Wilcoxon tests on device-resident count input: the one-pass pair route against the loop of one one-versus-reference call
 per group that it replaces: one JSON line.
 
-   python tools/bench_pairwise.py [--reps 10] [--only ten_clusters_dense_dev,csr_30_clusters_dev] [--loop-only]
+   python tools/bench_pairwise.py [--reps 10] [--only ten_clusters_dense_dev,csr_30_clusters_dev] [--loop-only] [--values counts|continuous]
 
 Shapes (the README's): 1M x 2400 dense float32 counts with ten clusters of 100 000 cells; 100 000 x 30 000 counts, 90 % zeros, as CSR
 with 30 clusters.  Per shape, one warm-up of each leg, then --reps rounds in which the legs run one after the other, each host-timed
@@ -35,6 +35,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--only", default="")
     ap.add_argument("--loop-only", action="store_true")
+    ap.add_argument("--values", choices=["counts", "continuous"], default="counts")
     a = ap.parse_args()
     import torch
     from illico_amd._lib import get_engine
@@ -55,8 +56,15 @@ def main():
         ovr = encode_and_count_groups(groups=codes, ref_group=None)[1]
         return ovr, [ovr._replace(encoded_ref_group=r) for r in range(K)]
 
-    def run(name, K, M, ovr, refs, hists, ovo):
-        """hists(out): the histogram pass writing (H, flags); ovo(out): one one-versus-reference call writing three device planes"""
+    def continuous(n, m, seed):
+        gen = torch.Generator(device="cuda").manual_seed(seed)
+        X = torch.exp(torch.randn((n, m), device="cuda", generator=gen))
+        X[torch.rand((n, m), device="cuda", generator=gen) >= 0.1] = 0
+        return X
+
+    def run(name, K, M, ovr, refs, hists, ovo, ranked=None):
+        """hists(out): the histogram pass writing (H, flags); ovo(out): one one-versus-reference call writing three device planes;
+        ranked(sums, out): with --values continuous, the ranked pair call writing three planes and left"""
         loop_planes = tuple(torch.empty((K, M), dtype=torch.float64, device="cuda") for _ in range(3))
 
         def loop(runs=None):
@@ -68,7 +76,17 @@ def main():
                     runs.append(sync_ms(lambda: ovo(loop_planes)))
 
         legs = {"loop_ms": loop}
-        if not a.loop_only:
+        if not a.loop_only and ranked is not None:
+            planes = tuple(torch.empty((K, K, M), dtype=torch.float64, device="cuda") for _ in range(3))
+            fl = torch.empty((M,), dtype=torch.int32, device="cuda")   # (here: the genes the ranked route left)
+            sums = torch.empty((K, M), dtype=torch.float64, device="cuda")
+
+            def pair():
+                eng.set_groups(ovr)
+                ranked(sums, (*planes, fl))
+
+            legs = {"pair_ms": pair, **legs}
+        elif not a.loop_only:
             H = torch.empty((K, M, 256), dtype=torch.int32, device="cuda")
             fl = torch.empty((M,), dtype=torch.int32, device="cuda")
             planes = tuple(torch.empty((K, K, M), dtype=torch.float64, device="cuda") for _ in range(3))
@@ -99,26 +117,40 @@ def main():
         eng.profile(False)
         if not a.loop_only:
             out["loop_over_pair"] = round(out["loop_runs_ms"] / out["pair_ms"], 3)
-            out["flagged_genes"] = int((fl != 0).sum().item())
+            out["left_genes" if ranked is not None else "flagged_genes"] = int((fl != 0).sum().item())
         out["pairs"] = K * (K - 1)
         res["shapes"][name] = out
 
+    cont = a.values == "continuous"
+    res["values"] = a.values
     if not only or "ten_clusters_dense_dev" in only:
         N, M, K = 1_000_000, 2400, 10
-        X = dense_counts(N, M, 0.5, seed=3)
+        X = continuous(N, M, 3) if cont else dense_counts(N, M, 0.5, seed=3)
         ovr, refs = clusters(N, K, 4)
-        run("ten_clusters_dense_dev", K, M, ovr, refs, lambda o: eng.group_value_hists(X, 0, M, out=o), lambda o: eng.run_dense(X, 0, M, out=o))
+
+        def ranked_dense(sums, out):
+            eng.group_stats(X, 0, M, out=(None, sums))
+            eng.pairwise_ranked(X, 0, M, sums=sums, out=out)
+
+        run("ten_clusters_dense_dev", K, M, ovr, refs, lambda o: eng.group_value_hists(X, 0, M, out=o), lambda o: eng.run_dense(X, 0, M, out=o),
+            ranked_dense if cont else None)
         del X
         torch.cuda.empty_cache()
     if not only or "csr_30_clusters_dev" in only:
         N, M, K = 100_000, 30_000, 30
-        X = dense_counts(N, M, 0.9, seed=5)
+        X = continuous(N, M, 5) if cont else dense_counts(N, M, 0.9, seed=5)
         d, i, p = to_sparse(X, "csr")
+        cd, ci, cp = to_sparse(X, "csc") if cont and not a.loop_only else (None, None, None)
         del X
         torch.cuda.empty_cache()
         ovr, refs = clusters(N, K, 6)
+
+        def ranked_csc(sums, out):
+            eng.group_stats_sparse("csc", cd, ci, cp, (N, M), 0, M, out=(None, sums))
+            eng.pairwise_ranked_sparse("csc", cd, ci, cp, (N, M), 0, M, sums=sums, out=out)
+
         run("csr_30_clusters_dev", K, M, ovr, refs, lambda o: eng.group_value_hists_sparse("csr", d, i, p, (N, M), 0, M, out=o),
-            lambda o: eng.run_sparse("csr", d, i, p, (N, M), 0, M, out=o))
+            lambda o: eng.run_sparse("csr", d, i, p, (N, M), 0, M, out=o), ranked_csc if cont else None)
     print(json.dumps(res))
 
 
