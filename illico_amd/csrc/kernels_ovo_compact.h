@@ -81,7 +81,7 @@ struct GroupCompactParams {
 };
 
 template <typename InT> __device__ __forceinline__ double gcmp_value(InT v, int is_log1p);
-template <> __device__ __forceinline__ double gcmp_value<float>(float v, int is_log1p) { return is_log1p ? (double)expm1f(v) : (double)v; }
+template <> __device__ __forceinline__ double gcmp_value<float>(float v, int is_log1p) { return is_log1p ? (double)expm1f_fdlibm(v) : (double)v; }
 template <> __device__ __forceinline__ double gcmp_value<double>(double v, int is_log1p) { return is_log1p ? expm1(v) : v; }
 template <> __device__ __forceinline__ double gcmp_value<int32_t>(int32_t v, int is_log1p) { return is_log1p ? expm1((double)v) : (double)v; }
 template <> __device__ __forceinline__ double gcmp_value<int64_t>(int64_t v, int is_log1p) { return is_log1p ? expm1((double)v) : (double)v; }
