@@ -327,6 +327,38 @@ def _check_chunk_bounds(col_lb, col_ub, n_cols):
         raise ValueError(f"Invalid chunk bounds: {(col_lb, col_ub)} for data with {n_cols} columns.")
 
 
+def _n_result_planes(scores) -> int:
+    """3 result planes (p, U, fold change), or 4 with the z-score plane; ``ValueError`` unless ``scores`` is a bool."""
+    if not isinstance(scores, (bool, np.bool_)):
+        raise ValueError(f"scores must be a bool, got {scores!r}")
+    return 4 if scores else 3
+
+
+def _pair_selection(sel, G):
+    """``(K, keepalive, pointer)`` of the group ids a pair call compares; None selects all ``G``, in order."""
+    if sel is None:
+        return G, None, None
+    sel = np.ascontiguousarray(sel, dtype=np.int64).reshape(-1)
+    return int(sel.size), sel, sel.ctypes.data
+
+
+def _pair_planes(out, n, K, W, on_dev, device, with_left):
+    """``(planes, left, plane pointers, left pointer, on the device)`` of the ``n`` float64 ``[K, K, W]`` result planes of a pair
+    call, and with ``with_left`` of the ``[W]`` words behind them.  ``out`` None: allocated, on ``device`` if ``on_dev``.  Given
+    planes must be on the side ``on_dev`` names -- with ``left`` on the side of ``left``, wherever the input is."""
+    if out is None:
+        dev = device if on_dev else None
+        out = [_empty((K, K, W), np.float64, dev) for _ in range(n)] + ([_empty((W,), np.int32 if on_dev else np.uint32, dev)] if with_left else [])
+    out = tuple(out)
+    if len(out) != n + with_left:
+        raise ValueError(f"out must hold {n} planes (p, U, fold change{', z' if n == 4 else ''}){' and left' if with_left else ''}")
+    planes, left = out[:n], out[n] if with_left else None
+    on_dev = _host_or_cuda(left, "left") if with_left else on_dev
+    ptrs = [_block(q, "an output plane", (np.float64,), (K, K, W), on_device=on_dev, writeable=True)[0] for q in planes]
+    left_ptr = _block(left, "left", (np.int32, np.uint32) if on_dev else (np.uint32,), (W,), on_device=on_dev, writeable=True)[0] if with_left else None
+    return planes, left, ptrs, left_ptr, on_dev
+
+
 class Engine:
     """One illico_ctx: one device, one stream, device scratch, the current GroupContainer."""
 
@@ -413,10 +445,9 @@ class Engine:
     def _outputs(self, out, G, W, want_device, scores=False):
         """out: None (allocate host planes; four with ``scores``), a tuple of three host ndarrays (views with a common row stride
         are fine) or three device tensors -- or four: the fourth receives the z-score plane."""
-        if not isinstance(scores, (bool, np.bool_)):
-            raise ValueError(f"scores must be a bool, got {scores!r}")
+        n = _n_result_planes(scores)
         if out is None:
-            planes = tuple(_empty((G, W), np.float64, f"cuda:{self.device}" if want_device else None) for _ in range(4 if scores else 3))
+            planes = tuple(_empty((G, W), np.float64, f"cuda:{self.device}" if want_device else None) for _ in range(n))
         else:
             planes = tuple(out)
             if len(planes) not in (3, 4) or (scores and len(planes) != 4):
@@ -758,9 +789,7 @@ class Engine:
         ``[K, W]`` plane of a one-versus-reference call with that reference.  Diagonal: p = 1, U = n^2 / 2, z = 0.  The columns of
         flagged genes are left as they are in ``out`` (a tuple of 3 or 4 contiguous planes on the side of ``H``; uninitialised when
         the planes are allocated here)."""
-        alt = self._alt(alternative)
-        if not isinstance(scores, (bool, np.bool_)):
-            raise ValueError(f"scores must be a bool, got {scores!r}")
+        alt, n = self._alt(alternative), _n_result_planes(scores)
         on_dev = _is_torch_tensor(H)
         if on_dev != _is_torch_tensor(flags) or (sums is not None and on_dev != _is_torch_tensor(sums)):
             raise ValueError("H, flags and sums must live on the same side (host or device)")
@@ -782,26 +811,15 @@ class Engine:
         counts = np.ascontiguousarray(counts, dtype=np.int64)
         if counts.shape != (G,):
             raise ValueError(f"H holds {G} groups but counts has shape {counts.shape}")
-        if sel is None:
-            K, sel_arr, sel_ptr = G, None, None
-        else:
-            sel_arr = np.ascontiguousarray(sel, dtype=np.int64).reshape(-1)
-            K, sel_ptr = int(sel_arr.size), sel_arr.ctypes.data
+        K, sel_arr, sel_ptr = _pair_selection(sel, G)
         if sums is not None:
             sums = _plane(sums, "sums", shape=(G, W), copy_ok=True)
-        n = 4 if scores else 3
-        if out is None:
-            planes = tuple(_empty((K, K, W), np.float64, H.device if on_dev else None) for _ in range(n))
-        else:
-            planes = tuple(out)
-            if len(planes) != n:
-                raise ValueError(f"out must hold {n} planes (p, U, fold change{', z' if scores else ''})")
-        ptrs = [_block(q, "an output plane", (np.float64,), (K, K, W), on_device=on_dev, writeable=True)[0] for q in planes]
+        planes, _, ptrs, _, _ = _pair_planes(out, n, K, W, on_dev, H.device if on_dev else None, False)
         fl = self._flags(is_log1p, use_continuity, tie_correct) | ((FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0)
         sums_array, sums_ptr, sums_ld = (None, None, 0) if sums is None else (sums.array, sums.ptr, sums.pitch)
         self._bind_torch_stream(H, flags, sums_array, *planes)
-        self._check(self.lib.illico_pairwise_from_hists(self.h, _ptr(H), _ptr(flags), counts.ctypes.data, G, W, sel_ptr, K, sums_ptr, sums_ld,
-                                                        fl, alt, *ptrs, *[None] * (4 - n), max(W, 1)))
+        self._check(self.lib.illico_pairwise_from_hists(self.h, _ptr(H), _ptr(flags), counts.ctypes.data, G, W, sel_ptr, K, sums_ptr, sums_ld, fl, alt,
+                                                        *ptrs, *[None] * (4 - n), max(W, 1)))
         return planes
 
     # ---- all-pairs Wilcoxon tests for any float32 / int32 values (include/illico_hip_ranked.h: illico_pairwise_ranked_*) ----
@@ -810,33 +828,14 @@ class Engine:
 
     def _ranked_args(self, W, on_dev, sums, sel, is_log1p, use_continuity, tie_correct, alternative, scores, out):
         """What the two ranked entry points share: (planes, left, the C arguments after col_ub, keepalives)."""
-        alt = self._alt(alternative)
-        if not isinstance(scores, (bool, np.bool_)):
-            raise ValueError(f"scores must be a bool, got {scores!r}")
-        G = self.n_groups
+        alt, n = self._alt(alternative), _n_result_planes(scores)
         if sums is None:
             raise ValueError("sums is required: the per-group value sums of group_stats (under is_log1p its expm1 sums)")
-        sums = _plane(sums, "sums", shape=(G, W), copy_ok=True)
+        sums = _plane(sums, "sums", shape=(self.n_groups, W), copy_ok=True)
         if sums.on_device != on_dev:
             raise ValueError("sums must live on the side of the matrix (host or device)")
-        if sel is None:
-            K, sel_arr, sel_ptr = G, None, None
-        else:
-            sel_arr = np.ascontiguousarray(sel, dtype=np.int64).reshape(-1)
-            K, sel_ptr = int(sel_arr.size), sel_arr.ctypes.data
-        n = 4 if scores else 3
-        if out is None:
-            dev = f"cuda:{self.device}" if on_dev else None
-            planes = tuple(_empty((K, K, W), np.float64, dev) for _ in range(n))
-            left = _empty((W,), np.int32 if on_dev else np.uint32, dev)
-        else:
-            out = tuple(out)
-            if len(out) != n + 1:
-                raise ValueError(f"out must hold {n} planes (p, U, fold change{', z' if scores else ''}) and left")
-            planes, left = out[:n], out[n]
-        out_dev = _host_or_cuda(left, "left")
-        ptrs = [_block(q, "an output plane", (np.float64,), (K, K, W), on_device=out_dev, writeable=True)[0] for q in planes]
-        left_ptr = _block(left, "left", (np.int32, np.uint32) if out_dev else (np.uint32,), (W,), on_device=out_dev, writeable=True)[0]
+        K, sel_arr, sel_ptr = _pair_selection(sel, self.n_groups)
+        planes, left, ptrs, left_ptr, out_dev = _pair_planes(out, n, K, W, on_dev, f"cuda:{self.device}", True)
         fl = self._flags(is_log1p, use_continuity, tie_correct) | (FLAG_INPUT_DEVICE if on_dev else 0) | (FLAG_OUTPUT_DEVICE if out_dev else 0)
         args = [sel_ptr, K, sums.ptr, sums.pitch, fl, alt, *ptrs, *[None] * (4 - n), max(W, 1), left_ptr]
         return planes, left, args, (sel_arr, sums.array)

@@ -496,3 +496,10 @@ int run_sparse_t(illico_ctx *c, bool is_csr, const void *data, const void *indic
 // the run_sparse_t of a type given by its codes (core.hip; what a deferred CSC pass's leftovers and the drivers' own re-entries call)
 int run_sparse_inner(illico_ctx *c, bool is_csr, const void *data, int dtype, const void *indices, const void *indptr, int idx_dtype, int64_t n_rows,
                      int64_t n_cols, int64_t col_lb, int64_t col_ub, int flags, int alternative, const OutPlanes &o);
+
+// the alternative code, as the t-test and the pair entry points check it
+static inline int check_alternative(illico_ctx *c, int alternative) {
+    if (alternative != ILLICO_ALT_TWO_SIDED && alternative != ILLICO_ALT_LESS && alternative != ILLICO_ALT_GREATER)
+        return fail(c, ILLICO_ERR_ALTERNATIVE, "Unsupported alternative hypothesis code: %d", alternative);
+    return ILLICO_OK;
+}

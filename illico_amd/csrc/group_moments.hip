@@ -138,17 +138,11 @@ int gm_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
         // the six planes, the two magnitude rows and the flags lie back to back: one clear (a narrower last window clears a little more than it uses)
         HIPCHK(c, hipMemsetAsync(P.L0, 0, GW * 48 + (size_t)WW * 20, c->stream));
         if (!in.sparse) {
-            const unsigned char *X = (const unsigned char *)in.X + (size_t)w0 * esz;
-            int64_t ld = in.ld;
-            if (!in.on_dev) {
-                HIPCHK(c, hipMemcpy2DAsync(xwin, (size_t)wn * esz, X, (size_t)in.ld * esz, (size_t)wn * esz, (size_t)N, hipMemcpyHostToDevice, c->stream));
-                c->h2d_input_bytes += (int64_t)((size_t)N * wn * esz);
-                X = (const unsigned char *)xwin;
-                ld = wn;
-            }
+            DenseWindow xw;
+            if ((rc = stage_dense_window(c, in, w0, wn, wn, xwin, &xw))) return rc;
             rc = dispatch_value_type(dt, [&](auto t) {
                 using InT = typename decltype(t)::type;
-                return gm_dense_window<InT>(c, (const InT *)X, ld, N, wn, d_ch, n_ch, P);
+                return gm_dense_window<InT>(c, (const InT *)xw.X + xw.col0, xw.ld, N, wn, d_ch, n_ch, P);
             });
         } else {
             const long long col0 = w0 - sp.ptr_col0;
@@ -184,9 +178,7 @@ int gm_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
         }
         if (!out_dev) {
             for (int k = 0; k < 4; ++k)
-                if (outs[k])
-                    HIPCHK(c, hipMemcpy2DAsync((unsigned char *)outs[k] + (size_t)off * 8, (size_t)o.ld * 8, st[k], (size_t)wn * 8, (size_t)wn * 8, (size_t)G,
-                                               hipMemcpyDeviceToHost, c->stream));
+                if (outs[k] && (rc = planes_to_host(c, outs[k] + off, o.ld, st[k], G, wn))) return rc;
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
     }
@@ -198,20 +190,8 @@ int gm_entry(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_u
     CTX_LOCK(c);
     int rc = gm_check(c, in, col_lb, col_ub, flags, o);
     if (rc) return rc;
-    if (in.sparse) {
-        if (!in.data || !in.indices || !in.indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
-    } else {
-        if (!in.X) return fail(c, ILLICO_ERR_ARG, "null X");
-        if (in.ld < in.n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
-    }
+    if ((rc = check_matrix_arrays(c, in))) return rc;
     return gm_run(c, in, col_lb, col_ub, flags, o);
-}
-
-// ---- the t-test from moment planes -------------------------------------------------------------------------------------------------
-int tt_alt_ok(illico_ctx *c, int alternative) {
-    if (alternative != ILLICO_ALT_TWO_SIDED && alternative != ILLICO_ALT_LESS && alternative != ILLICO_ALT_GREATER)
-        return fail(c, ILLICO_ERR_ALTERNATIVE, "Unsupported alternative hypothesis code: %d", alternative);
-    return ILLICO_OK;
 }
 
 } // namespace
@@ -243,6 +223,7 @@ extern "C" int illico_group_moments_bound(illico_ctx *c, const illico_matrix *m,
                     {out_sum, out_sumsq, out_sum_rest, out_sumsq_rest, out_ld});
 }
 
+// ---- the t-test from moment planes -------------------------------------------------------------------------------------------------
 extern "C" int illico_ttest_from_moments(illico_ctx *c, const double *sum, const double *sumsq, const double *sum_rest, const double *sumsq_rest, int64_t n_cols,
                                          int64_t in_ld, int variant, int alternative, int flags, double *out_p, double *out_t, double *out_df, double *out_mean,
                                          double *out_var, double *out_mean_ref, double *out_var_ref, int64_t out_ld) {
@@ -250,7 +231,7 @@ extern "C" int illico_ttest_from_moments(illico_ctx *c, const double *sum, const
     CTX_LOCK(c);
     if (!c->has_groups) return fail(c, ILLICO_ERR_NO_GROUPS, "illico_set_groups has not been called");
     if (variant != ILLICO_TT_WELCH && variant != ILLICO_TT_OVERESTIM_VAR) return fail(c, ILLICO_ERR_ARG, "unknown t-test variant code %d", variant);
-    int rc = tt_alt_ok(c, alternative);
+    int rc = check_alternative(c, alternative);
     if (rc) return rc;
     const bool ovr = c->ref < 0;
     if (!sum || !sumsq) return fail(c, ILLICO_ERR_ARG, "null sum / sumsq plane");
@@ -287,7 +268,7 @@ extern "C" int illico_ttest_from_moments(illico_ctx *c, const double *sum, const
             if (!ins[k]) continue;
             if (in_dev) din[k] = ins[k] + w0;
             else {
-                HIPCHK(c, hipMemcpy2DAsync(s, (size_t)wn * 8, ins[k] + w0, (size_t)in_ld * 8, (size_t)wn * 8, (size_t)G, hipMemcpyHostToDevice, c->stream));
+                if ((rc = planes_to_device(c, s, ins[k] + w0, in_ld, G, wn))) return rc;
                 din[k] = (const double *)s;
                 s += (size_t)G * wn * 8;
             }
@@ -310,8 +291,7 @@ extern "C" int illico_ttest_from_moments(illico_ctx *c, const double *sum, const
         }
         if (!out_dev) {
             for (int k = 0; k < TT_N_OUT; ++k)
-                if (outs[k])
-                    HIPCHK(c, hipMemcpy2DAsync(outs[k] + w0, (size_t)out_ld * 8, st[k], (size_t)wn * 8, (size_t)wn * 8, (size_t)G, hipMemcpyDeviceToHost, c->stream));
+                if (outs[k] && (rc = planes_to_host(c, outs[k] + w0, out_ld, st[k], G, wn))) return rc;
         }
         if (!in_dev || !out_dev) HIPCHK(c, hipStreamSynchronize(c->stream)); // (the staging area is reused by the next window; host planes complete on return)
     }
@@ -321,7 +301,7 @@ extern "C" int illico_ttest_from_moments(illico_ctx *c, const double *sum, const
 extern "C" int illico_student_t_pvalues(illico_ctx *c, const double *t, const double *df, int64_t n, int alternative, int flags, double *out_p) {
     if (!c) return ILLICO_ERR_ARG;
     CTX_LOCK(c);
-    int rc = tt_alt_ok(c, alternative);
+    int rc = check_alternative(c, alternative);
     if (rc) return rc;
     if (n < 0 || (n && (!t || !df || !out_p))) return fail(c, ILLICO_ERR_ARG, "null array or negative length");
     HIPCHK(c, hipSetDevice(c->device));

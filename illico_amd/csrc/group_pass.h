@@ -1,7 +1,8 @@
-// Host scaffolding of the passes that read the matrix once per group family -- group_stats.hip, group_moments.hip, pairwise.hip,
-// and nothing else: the description of the input, the checks every entry point makes first, the upload of host-resident sparse
-// arrays, the dispatch on the index type, and the groups' positions in chunks.  Everything is local to the including
-// unit (the three are linked into one library).  The kernels, the planes, the column windows and the outputs are each family's own.
+// Host scaffolding of the four units that read the matrix once per group family -- group_stats.hip, group_moments.hip, pairwise.hip,
+// pairwise_ranked.hip (the last two through pair_pass.h) -- and nothing else: the description of the input, the checks every entry point
+// makes, the upload of host-resident sparse arrays and dense windows, the copies of 8-byte planes, the dispatch on the index type, and the
+// groups' positions in chunks.  Everything is local to the including unit (the four are linked into one library).  The kernels, the
+// planes, the column windows, the outputs and the points at which the stream is synchronised are each family's own.
 #pragma once
 #include "engine.h"
 
@@ -42,6 +43,14 @@ inline int check_matrix_input(illico_ctx *c, const MatrixInput &in, int64_t col_
     return ILLICO_OK;
 }
 
+// the matrix's arrays; each family makes these checks at its own point among its own
+inline int check_matrix_arrays(illico_ctx *c, const MatrixInput &in) {
+    if (in.sparse) return in.data && in.indices && in.indptr ? ILLICO_OK : fail(c, ILLICO_ERR_ARG, "null sparse array");
+    if (!in.X) return fail(c, ILLICO_ERR_ARG, "null X");
+    if (in.ld < in.n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
+    return ILLICO_OK;
+}
+
 // the flags a bound matrix passes on: its arrays are on the device whatever the caller says
 inline int bound_matrix_flags(int flags) { return (flags & (ILLICO_FLAG_LOG1P | ILLICO_FLAG_OUTPUT_DEVICE)) | ILLICO_FLAG_INPUT_DEVICE; }
 
@@ -73,6 +82,33 @@ inline int stage_sparse_input(illico_ctx *c, const MatrixInput &in, int64_t col_
     HIPCHK(c, hipMemcpyAsync(dp, (const unsigned char *)in.indptr + (size_t)a * isz, nptr * isz, hipMemcpyHostToDevice, c->stream));
     c->h2d_input_bytes += (int64_t)(nnz * (esz + isz) + nptr * isz);
     *out = SparseOnDevice{dd, di, dp, k0, a};
+    return ILLICO_OK;
+}
+
+// columns [col0, col0 + wn) of a dense matrix as the kernels read them: a device matrix as it is (column col0 of X); a host matrix
+// copied into `xwin`, [n_rows][wn] at `pitch` elements a row (column 0 of xwin), the bytes counted.  Enqueued, not awaited.
+struct DenseWindow {
+    const void *X;
+    int64_t ld, col0;
+};
+inline int stage_dense_window(illico_ctx *c, const MatrixInput &in, int64_t col0, int64_t wn, int64_t pitch, void *xwin, DenseWindow *out) {
+    *out = DenseWindow{in.X, in.ld, col0};
+    if (in.on_dev) return ILLICO_OK;
+    const size_t esz = dtype_size(in.dtype);
+    HIPCHK(c, hipMemcpy2DAsync(xwin, (size_t)pitch * esz, (const unsigned char *)in.X + (size_t)col0 * esz, (size_t)in.ld * esz, (size_t)wn * esz,
+                               (size_t)in.n_rows, hipMemcpyHostToDevice, c->stream));
+    c->h2d_input_bytes += (int64_t)((size_t)in.n_rows * wn * esz);
+    *out = DenseWindow{xwin, pitch, 0};
+    return ILLICO_OK;
+}
+
+// [rows][w] planes of 8-byte elements between a host pitch and the packed device pitch w.  Enqueued, not awaited.
+inline int planes_to_device(illico_ctx *c, void *dev, const void *host, int64_t host_ld, int64_t rows, int64_t w) {
+    HIPCHK(c, hipMemcpy2DAsync(dev, (size_t)w * 8, host, (size_t)host_ld * 8, (size_t)w * 8, (size_t)rows, hipMemcpyHostToDevice, c->stream));
+    return ILLICO_OK;
+}
+inline int planes_to_host(illico_ctx *c, void *host, int64_t host_ld, const void *dev, int64_t rows, int64_t w) {
+    HIPCHK(c, hipMemcpy2DAsync(host, (size_t)host_ld * 8, dev, (size_t)w * 8, (size_t)w * 8, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
     return ILLICO_OK;
 }
 

@@ -140,17 +140,11 @@ int gs_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
         HIPCHK(c, hipMemsetAsync(P.vmax, 0, (size_t)wn * 8, c->stream));
         HIPCHK(c, hipMemsetAsync(P.nonfin, 0, (size_t)wn * 4, c->stream));
         if (!in.sparse) {
-            const unsigned char *X = (const unsigned char *)in.X + (size_t)w0 * esz;
-            int64_t ld = in.ld;
-            if (!in.on_dev) {
-                HIPCHK(c, hipMemcpy2DAsync(xwin, (size_t)wn * esz, X, (size_t)in.ld * esz, (size_t)wn * esz, (size_t)N, hipMemcpyHostToDevice, c->stream));
-                c->h2d_input_bytes += (int64_t)((size_t)N * wn * esz);
-                X = (const unsigned char *)xwin;
-                ld = wn;
-            }
+            DenseWindow xw;
+            if ((rc = stage_dense_window(c, in, w0, wn, wn, xwin, &xw))) return rc;
             rc = dispatch_value_type(dt, [&](auto t) {
                 using InT = typename decltype(t)::type;
-                return gs_dense_window<InT>(c, (const InT *)X, ld, N, wn, dt, log1p, d_ch, n_ch, P);
+                return gs_dense_window<InT>(c, (const InT *)xw.X + xw.col0, xw.ld, N, wn, dt, log1p, d_ch, n_ch, P);
             });
         } else {
             const long long col0 = w0 - sp.ptr_col0;
@@ -185,12 +179,7 @@ int gs_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
             HIPCHK(c, hipGetLastError());
         }
         if (!out_dev) {
-            auto down = [&](void *dst, const void *src) -> int {
-                if (dst)
-                    HIPCHK(c, hipMemcpy2DAsync((unsigned char *)dst + (size_t)off * 8, (size_t)o.ld * 8, src, (size_t)wn * 8, (size_t)wn * 8, (size_t)G,
-                                               hipMemcpyDeviceToHost, c->stream));
-                return ILLICO_OK;
-            };
+            auto down = [&](void *dst, const void *src) { return dst ? planes_to_host(c, (unsigned char *)dst + (size_t)off * 8, o.ld, src, G, wn) : ILLICO_OK; };
             if ((rc = down(o.nnz, st_nnz)) || (rc = down(o.sum, st_sum)) || (rc = down(o.nnz_rest, st_nnz_rest)) || (rc = down(o.sum_rest, st_sum_rest)))
                 return rc;
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -204,12 +193,7 @@ int gs_entry(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_u
     CTX_LOCK(c);
     int rc = gs_check(c, in, col_lb, col_ub, o);
     if (rc) return rc;
-    if (in.sparse) {
-        if (!in.data || !in.indices || !in.indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
-    } else {
-        if (!in.X) return fail(c, ILLICO_ERR_ARG, "null X");
-        if (in.ld < in.n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
-    }
+    if ((rc = check_matrix_arrays(c, in))) return rc;
     return gs_run(c, in, col_lb, col_ub, flags, o);
 }
 

@@ -1,8 +1,9 @@
 // illico_group_value_hists_{dense,csc,csr}: per-(group, gene) histograms of the values 0 .. 255 from one pass over the matrix;
 // illico_pairwise_from_hists: the Wilcoxon rank-sum test of every ordered pair of groups from those histograms (kernels_pairwise.h).
 // A translation unit of its own: siblings of the one-versus-reference routes, which it does not touch; the host scaffolding of the
-// histogram pass (input description, common checks, sparse upload, type dispatch) is shared with the other group passes (group_pass.h).
-#include "group_pass.h"
+// histogram pass (input description, common checks, input staging, type dispatch) is shared with the other group passes (group_pass.h),
+// the pair selection and the staging of the pair planes with the ranked pair route (pair_pass.h).
+#include "pair_pass.h"
 #include "kernels_pairwise.h"
 
 namespace {
@@ -99,16 +100,11 @@ int pw_hists_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t c
         if ((rc = get_scratch(c, "pw_tiled", t_bytes, &v))) return rc;
         u32 *T = (u32 *)v;
         HIPCHK(c, hipMemsetAsync(T, 0, t_bytes, c->stream));
-        const void *X = in.X;
-        int64_t ld = in.ld, col0 = col_lb;
-        if (!in.on_dev) {
-            if ((rc = get_scratch(c, "pw_xwin", x_bytes, &v))) return rc;
-            HIPCHK(c, hipMemcpy2DAsync(v, (size_t)W * esz, (const unsigned char *)in.X + (size_t)col_lb * esz, (size_t)in.ld * esz, (size_t)W * esz, (size_t)N,
-                                       hipMemcpyHostToDevice, c->stream));
-            c->h2d_input_bytes += (int64_t)x_bytes;
-            X = v; ld = W; col0 = 0;
-        }
-        rc = dispatch_value_type(dt, [&](auto t) { return pw_dense<typename decltype(t)::type>(c, X, ld, col0, wn, tiles, T, d_flags); });
+        DenseWindow xw;
+        void *xwin = nullptr;
+        if (!in.on_dev && (rc = get_scratch(c, "pw_xwin", x_bytes, &xwin))) return rc;
+        if ((rc = stage_dense_window(c, in, col_lb, W, W, xwin, &xw))) return rc;
+        rc = dispatch_value_type(dt, [&](auto t) { return pw_dense<typename decltype(t)::type>(c, xw.X, xw.ld, xw.col0, wn, tiles, T, d_flags); });
         if (rc) return rc;
         ProfScope ps(c, KID_PW_HIST_FINISH);
         hipLaunchKernelGGL(k_pw_transpose<true>, dim3(tiles, (unsigned)G), dim3(PW_NT), 0, c->stream, d_H, T, (const int *)nullptr, wn, tiles);
@@ -137,12 +133,7 @@ int pw_hists_entry(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t
     CTX_LOCK(c);
     int rc = pw_check(c, in, col_lb, col_ub, out_H, out_flags);
     if (rc) return rc;
-    if (in.sparse) {
-        if (!in.data || !in.indices || !in.indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
-    } else {
-        if (!in.X) return fail(c, ILLICO_ERR_ARG, "null X");
-        if (in.ld < in.n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
-    }
+    if ((rc = check_matrix_arrays(c, in))) return rc;
     return pw_hists_run(c, in, col_lb, col_ub, flags, out_H, out_flags);
 }
 
@@ -166,40 +157,21 @@ extern "C" int illico_pairwise_from_hists(illico_ctx *c, const uint32_t *H, cons
                                           double *out_u, double *out_fc, double *out_z, int64_t out_ld) {
     if (!c) return ILLICO_ERR_ARG;
     CTX_LOCK(c);
-    if (alternative != ILLICO_ALT_TWO_SIDED && alternative != ILLICO_ALT_LESS && alternative != ILLICO_ALT_GREATER)
-        return fail(c, ILLICO_ERR_ALTERNATIVE, "Unsupported alternative hypothesis code: %d", alternative);
+    int rc = check_alternative(c, alternative);
+    if (rc) return rc;
     if (!counts || n_groups <= 0 || n_groups > 0x7FFFFFFF) return fail(c, ILLICO_ERR_ARG, "null counts or bad n_groups");
     const int64_t G = n_groups, W = n_cols, K = sel ? n_sel : G;
     if (K < 2) return fail(c, ILLICO_ERR_ARG, "%lld groups selected: a pair needs two", (long long)K);
     if (K > 46340) return fail(c, ILLICO_ERR_ARG, "%lld groups selected: more pairs than a launch holds", (long long)K);
-    std::vector<int> h_sel((size_t)K);
-    std::vector<long long> h_n((size_t)K);
-    {
-        std::vector<char> seen((size_t)G, 0);
-        for (int64_t k = 0; k < K; ++k) {
-            const int64_t g = sel ? sel[k] : k;
-            if (g < 0 || g >= G) return fail(c, ILLICO_ERR_ARG, "sel[%lld] = %lld is no group id (0 .. %lld)", (long long)k, (long long)g, (long long)G - 1);
-            if (seen[g]) return fail(c, ILLICO_ERR_ARG, "group %lld is selected twice", (long long)g);
-            seen[g] = 1;
-            if (counts[g] < 0) return fail(c, ILLICO_ERR_ARG, "counts[%lld] is negative", (long long)g);
-            h_sel[k] = (int)g;
-            h_n[k] = counts[g];
-        }
-    }
-    {   // the two largest selected groups: their pair is the largest test
-        long long a = 0, b = 0;
-        for (long long n : h_n) { if (n > a) { b = a; a = n; } else if (n > b) b = n; }
-        if (a + b >= 2097152ll)
-            return fail(c, ILLICO_ERR_UNSUPPORTED, "%lld cells in one pair: the integer rank and tie sums hold below 2097152 cells per test", a + b);
-    }
+    PairSelection S;
+    if ((rc = select_pair_groups(c, G, sel, K, [&](int64_t g) { return (long long)counts[g]; }, &S))) return rc;
     if (W < 0 || out_ld < W) return fail(c, ILLICO_ERR_ARG, "out_ld smaller than n_cols (or n_cols negative)");
     if (sums && sums_ld < W) return fail(c, ILLICO_ERR_ARG, "sums_ld smaller than n_cols");
     if (W == 0) return ILLICO_OK;
     if (!H || !gene_flags || !out_p || !out_u || !out_fc) return fail(c, ILLICO_ERR_ARG, "null H, gene_flags or output plane");
     if (W > (int64_t)1 << 21) return fail(c, ILLICO_ERR_OOM, "a window of %lld genes: pass narrower gene windows", (long long)W);
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = resolve_pending(c);
-    if (rc) return rc;
+    if ((rc = resolve_pending(c))) return rc;
     const bool in_dev = flags & ILLICO_FLAG_INPUT_DEVICE, out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
     const int wn = (int)W, tiles = (wn + 63) / 64, n_out = out_z ? 4 : 3;
     const size_t t_bytes = (size_t)K * tiles * PW_TILE_WORDS * 4, h_bytes = (size_t)G * W * PW_RT * 4, s_bytes = sums ? (size_t)G * W * 8 : 0;
@@ -210,8 +182,7 @@ extern "C" int illico_pairwise_from_hists(illico_ctx *c, const uint32_t *H, cons
     u32 *T = (u32 *)v;
     long long *d_n = (long long *)((unsigned char *)v + t_bytes);
     int *d_sel = (int *)(d_n + K);
-    HIPCHK(c, hipMemcpyAsync(d_n, h_n.data(), (size_t)K * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_sel, h_sel.data(), (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = upload_pair_selection(c, S, d_n, d_sel))) return rc;
     const u32 *d_H = H, *d_flags = gene_flags;
     const double *d_sums = sums;
     int64_t d_sums_ld = sums_ld;
@@ -219,32 +190,26 @@ extern "C" int illico_pairwise_from_hists(illico_ctx *c, const uint32_t *H, cons
         if ((rc = get_scratch(c, "pw_stage_in", h_bytes + (size_t)W * 4 + s_bytes + 64, &v))) return rc;
         unsigned char *u = (unsigned char *)v;
         if (sums) {
-            HIPCHK(c, hipMemcpy2DAsync(u, (size_t)W * 8, sums, (size_t)sums_ld * 8, (size_t)W * 8, (size_t)G, hipMemcpyHostToDevice, c->stream));
-            d_sums = (const double *)u; d_sums_ld = W;
+            if ((rc = stage_pair_sums(c, sums, sums_ld, G, W, u, &d_sums, &d_sums_ld))) return rc;
             u += s_bytes;
         }
         HIPCHK(c, hipMemcpyAsync(u, H, h_bytes, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(u + h_bytes, gene_flags, (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
         d_H = (const u32 *)u; d_flags = (const u32 *)(u + h_bytes);
     }
-    double *outs[4] = {out_p, out_u, out_fc, out_z}, *d_out[4] = {out_p, out_u, out_fc, out_z};
-    int64_t d_out_ld = out_ld;
-    if (!out_dev) { // the caller's planes go up first: the columns of flagged genes come back as they were
-        if ((rc = get_scratch(c, "pw_stage_out", plane * n_out + 64, &v))) return rc;
-        for (int k = 0; k < n_out; ++k) {
-            d_out[k] = (double *)v + (size_t)k * K * K * W;
-            HIPCHK(c, hipMemcpy2DAsync(d_out[k], (size_t)W * 8, outs[k], (size_t)out_ld * 8, (size_t)W * 8, (size_t)(K * K), hipMemcpyHostToDevice, c->stream));
-        }
-        d_out_ld = W;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream)); // (h_n / h_sel and the staged arrays came from pageable host memory)
+    double *const outs[4] = {out_p, out_u, out_fc, out_z};
+    PairOutputs O; // the caller's planes go up first: the columns of flagged genes come back as they were
+    v = nullptr;
+    if (!out_dev && (rc = get_scratch(c, "pw_stage_out", plane * n_out + 64, &v))) return rc;
+    if ((rc = O.up(c, outs, out_ld, K * K, W, out_dev, v))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (the selection and the staged arrays came from pageable host memory)
     PwParams P;
     P.T = T; P.gene_flags = d_flags; P.n = d_n; P.sel = d_sel; P.sums = d_sums; P.sums_ld = d_sums_ld;
     P.K = (int)K; P.W = wn; P.tiles = tiles; P.nrb = ((int)K + PW_RB - 1) / PW_RB;
     P.use_continuity = (flags & ILLICO_FLAG_CONTINUITY) ? 1 : 0;
     P.tie_correct = (flags & ILLICO_FLAG_TIE_CORRECT) ? 1 : 0;
     P.alternative = alternative;
-    P.out_p = d_out[0]; P.out_u = d_out[1]; P.out_fc = d_out[2]; P.out_z = d_out[3]; P.out_ld = d_out_ld;
+    P.out_p = O.d_out[0]; P.out_u = O.d_out[1]; P.out_fc = O.d_out[2]; P.out_z = O.d_out[3]; P.out_ld = O.d_out_ld;
     {
         ProfScope ps(c, KID_PW_PAIRS);
         hipLaunchKernelGGL(k_pw_transpose<false>, dim3(tiles, (unsigned)K), dim3(PW_NT), 0, c->stream, const_cast<u32 *>(d_H), T, (const int *)d_sel, wn, tiles);
@@ -254,10 +219,7 @@ extern "C" int illico_pairwise_from_hists(illico_ctx *c, const uint32_t *H, cons
         else hipLaunchKernelGGL(k_pw_pairs<false>, grid, dim3(PW_NT), 0, c->stream, P);
         HIPCHK(c, hipGetLastError());
     }
-    if (!out_dev) {
-        for (int k = 0; k < n_out; ++k)
-            HIPCHK(c, hipMemcpy2DAsync(outs[k], (size_t)out_ld * 8, d_out[k], (size_t)W * 8, (size_t)W * 8, (size_t)(K * K), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    if ((rc = O.down(c))) return rc;
+    if (!out_dev) HIPCHK(c, hipStreamSynchronize(c->stream));
     return ILLICO_OK;
 }

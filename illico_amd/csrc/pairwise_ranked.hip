@@ -3,7 +3,7 @@
 // sibling of pairwise.hip: per gene batch the transposition (k_transpose_permute*), the value-range partition (k_ovr_partition<u32>) --
 // both instantiated here, as the dense one-versus-rest route launches them -- then k_pw_rank_pairs and k_pw_rank_emit.  CSC input is
 // written out dense on the device batch by batch (k_csc_densify) and takes the same steps.
-#include "group_pass.h"
+#include "pair_pass.h"
 #include "../../include/illico_hip_ranked.h"
 #include "kernels_pairwise_ranked.h"
 
@@ -55,12 +55,11 @@ int pwr_csc_in_order(illico_ctx *c, const SparseOnDevice &sp, int64_t c0, int64_
 }
 
 template <typename InT>
-int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub, const RankedArgs &a, const std::vector<int> &h_sel,
-            const std::vector<long long> &h_n) {
+int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub, const RankedArgs &a, const PairSelection &S) {
     HIPCHK(c, hipSetDevice(c->device));
     int rc = resolve_pending(c);
     if (rc) return rc;
-    const int64_t W = col_ub - col_lb, G = c->n_groups, N = in.n_rows, K = (int64_t)h_sel.size(), KK = K * K;
+    const int64_t W = col_ub - col_lb, G = c->n_groups, N = in.n_rows, K = (int64_t)S.sel.size(), KK = K * K;
     const bool in_dev = in.on_dev, out_dev = a.flags & ILLICO_FLAG_OUTPUT_DEVICE;
     const int n_out = a.out[3] ? 4 : 3;
     const int64_t stride = (N + 63) & ~63ll;
@@ -81,29 +80,23 @@ int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub
     long long *d_n = (long long *)v;
     int *d_sel = (int *)(d_n + K), *d_slot = d_sel + K;
     std::vector<int> h_slot((size_t)G, -1);
-    for (int64_t k = 0; k < K; ++k) h_slot[h_sel[k]] = (int)k;
-    HIPCHK(c, hipMemcpyAsync(d_n, h_n.data(), (size_t)K * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_sel, h_sel.data(), (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+    for (int64_t k = 0; k < K; ++k) h_slot[S.sel[k]] = (int)k;
+    if ((rc = upload_pair_selection(c, S, d_n, d_sel))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_slot, h_slot.data(), (size_t)G * 4, hipMemcpyHostToDevice, c->stream));
     const double *d_sums = a.sums;
     int64_t d_sums_ld = a.sums_ld;
     if (!in_dev) {
         if ((rc = get_scratch(c, "pwr_sums", s_bytes, &v))) return rc;
-        HIPCHK(c, hipMemcpy2DAsync(v, (size_t)W * 8, a.sums, (size_t)a.sums_ld * 8, (size_t)W * 8, (size_t)G, hipMemcpyHostToDevice, c->stream));
-        d_sums = (const double *)v; d_sums_ld = W;
+        if ((rc = stage_pair_sums(c, a.sums, a.sums_ld, G, W, v, &d_sums, &d_sums_ld))) return rc;
     }
-    double *d_out[4] = {a.out[0], a.out[1], a.out[2], a.out[3]};
-    int64_t d_out_ld = a.out_ld;
+    PairOutputs O; // the caller's planes go up first: the columns of genes that leave come back as they were
     u32 *d_left = a.out_left;
-    if (!out_dev) { // the caller's planes go up first: the columns of genes that leave come back as they were
+    v = nullptr;
+    if (!out_dev) {
         if ((rc = get_scratch(c, "pwr_stage_out", plane * n_out + (size_t)W * 4, &v))) return rc;
-        for (int k = 0; k < n_out; ++k) {
-            d_out[k] = (double *)v + (size_t)k * KK * W;
-            HIPCHK(c, hipMemcpy2DAsync(d_out[k], (size_t)W * 8, a.out[k], (size_t)a.out_ld * 8, (size_t)W * 8, (size_t)KK, hipMemcpyHostToDevice, c->stream));
-        }
         d_left = (u32 *)((double *)v + (size_t)n_out * KK * W);
-        d_out_ld = W;
     }
+    if ((rc = O.up(c, a.out, a.out_ld, KK, W, out_dev, v))) return rc;
     SparseOnDevice sp{};
     int64_t sp_c0 = 0; // column col_lb in sp.indptr
     if (in.sparse) {
@@ -142,20 +135,12 @@ int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub
     for (int64_t b0 = 0; b0 < W; b0 += batch) {
         const int nb = (int)std::min<int64_t>(batch, W - b0);
         const int64_t ldw = (nb + 63) & ~63ll;
-        const void *X = in.X;
-        int64_t ld = in.ld, col0 = col_lb + b0;
-        if (in.sparse) {
-            if (in.idx_dtype == ILLICO_IDX_I32) rc = pwr_densify<InT, int32_t>(c, sp, sp_c0 + b0, nb, N, xwin, ldw);
-            else rc = pwr_densify<InT, int64_t>(c, sp, sp_c0 + b0, nb, N, xwin, ldw);
-            if (rc) return rc;
-            X = xwin; ld = ldw; col0 = 0;
-        } else if (!in_dev) {
-            HIPCHK(c, hipMemcpy2DAsync(xwin, (size_t)ldw * sizeof(InT), (const InT *)in.X + col0, (size_t)in.ld * sizeof(InT), (size_t)nb * sizeof(InT), (size_t)N,
-                                       hipMemcpyHostToDevice, c->stream));
-            c->h2d_input_bytes += (int64_t)((size_t)N * nb * sizeof(InT));
-            X = xwin; ld = ldw; col0 = 0;
-        }
-        if ((rc = pwr_transpose<InT>(c, X, ld, col0, nb, (int)N, Xt, stride))) return rc;
+        DenseWindow xw{xwin, ldw, 0}; // (CSC: the batch written out dense)
+        if (!in.sparse) rc = stage_dense_window(c, in, col_lb + b0, nb, ldw, xwin, &xw);
+        else if (in.idx_dtype == ILLICO_IDX_I32) rc = pwr_densify<InT, int32_t>(c, sp, sp_c0 + b0, nb, N, xwin, ldw);
+        else rc = pwr_densify<InT, int64_t>(c, sp, sp_c0 + b0, nb, N, xwin, ldw);
+        if (rc) return rc;
+        if ((rc = pwr_transpose<InT>(c, xw.X, xw.ld, xw.col0, nb, (int)N, Xt, stride))) return rc;
         {
             OvrPartParams Q;
             Q.Xt = Xt; Q.stride = stride; Q.n_genes = nb; Q.n_cells = (int)N; Q.code_by_pos = c->d_code_by_pos; Q.cap = cap;
@@ -179,19 +164,16 @@ int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub
             E.s2 = s2; E.tie = tie; E.left = d_left + b0; E.n = d_n; E.sel = d_sel; E.sums = d_sums; E.sums_ld = d_sums_ld; E.K = (int)K; E.nb = nb;
             E.col_off = b0; E.use_continuity = (a.flags & ILLICO_FLAG_CONTINUITY) ? 1 : 0; E.tie_correct = (a.flags & ILLICO_FLAG_TIE_CORRECT) ? 1 : 0;
             E.alternative = a.alternative;
-            E.out_p = d_out[0]; E.out_u = d_out[1]; E.out_fc = d_out[2]; E.out_z = d_out[3]; E.out_ld = d_out_ld;
+            E.out_p = O.d_out[0]; E.out_u = O.d_out[1]; E.out_fc = O.d_out[2]; E.out_z = O.d_out[3]; E.out_ld = O.d_out_ld;
             const dim3 grid((unsigned)((nb + 63) / 64), (unsigned)((KK + PWE_PAIRS - 1) / PWE_PAIRS));
             ProfScope ps(c, KID_PW_RANK_EMIT);
-            if (d_out[3]) hipLaunchKernelGGL(k_pw_rank_emit<true>, grid, dim3(PWE_NT), 0, c->stream, E);
+            if (O.d_out[3]) hipLaunchKernelGGL(k_pw_rank_emit<true>, grid, dim3(PWE_NT), 0, c->stream, E);
             else hipLaunchKernelGGL(k_pw_rank_emit<false>, grid, dim3(PWE_NT), 0, c->stream, E);
             HIPCHK(c, hipGetLastError());
         }
     }
-    if (!out_dev) {
-        for (int k = 0; k < n_out; ++k)
-            HIPCHK(c, hipMemcpy2DAsync(a.out[k], (size_t)a.out_ld * 8, d_out[k], (size_t)W * 8, (size_t)W * 8, (size_t)KK, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(a.out_left, d_left, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
-    }
+    if ((rc = O.down(c))) return rc;
+    if (!out_dev) HIPCHK(c, hipMemcpyAsync(a.out_left, d_left, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
     if (!out_dev || !in_dev) HIPCHK(c, hipStreamSynchronize(c->stream));
     return ILLICO_OK;
 }
@@ -199,48 +181,26 @@ int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub
 int pwr_entry(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub, const RankedArgs &a) {
     if (!c) return ILLICO_ERR_ARG;
     CTX_LOCK(c);
-    if (a.alternative != ILLICO_ALT_TWO_SIDED && a.alternative != ILLICO_ALT_LESS && a.alternative != ILLICO_ALT_GREATER)
-        return fail(c, ILLICO_ERR_ALTERNATIVE, "Unsupported alternative hypothesis code: %d", a.alternative);
-    int rc = check_matrix_input(c, in, col_lb, col_ub);
-    if (rc) return rc;
+    int rc = check_alternative(c, a.alternative);
+    if (rc || (rc = check_matrix_input(c, in, col_lb, col_ub))) return rc;
     if (in.dtype != ILLICO_F32 && in.dtype != ILLICO_I32)
         return fail(c, ILLICO_ERR_UNSUPPORTED, "illico_pairwise_ranked takes float32 / int32 values (an 8-byte key does not pack into its 8-byte record)");
-    if (in.sparse) {
-        if (!in.data || !in.indices || !in.indptr) return fail(c, ILLICO_ERR_ARG, "null sparse array");
-    } else {
-        if (!in.X) return fail(c, ILLICO_ERR_ARG, "null X");
-        if (in.ld < in.n_cols) return fail(c, ILLICO_ERR_ARG, "ld smaller than n_cols");
-    }
+    if ((rc = check_matrix_arrays(c, in))) return rc;
     const int64_t G = c->n_groups, W = col_ub - col_lb, K = a.sel ? a.n_sel : G;
     if (K < 2) return fail(c, ILLICO_ERR_ARG, "%lld groups selected: a pair needs two", (long long)K);
     if (K > PWR_KMAX) return fail(c, ILLICO_ERR_UNSUPPORTED, "%lld groups selected: the ranked pair route takes up to %d", (long long)K, PWR_KMAX);
     if (G > 65535) return fail(c, ILLICO_ERR_UNSUPPORTED, "%lld groups: the ranked pair route takes up to 65535", (long long)G);
     if (in.n_rows >= (1ll << 31) - 64) return fail(c, ILLICO_ERR_UNSUPPORTED, "%lld cells: the ranked pair route takes fewer than 2^31", (long long)in.n_rows);
-    std::vector<int> h_sel((size_t)K);
-    std::vector<long long> h_n((size_t)K);
-    {
-        std::vector<char> seen((size_t)G, 0);
-        for (int64_t k = 0; k < K; ++k) {
-            const int64_t g = a.sel ? a.sel[k] : k;
-            if (g < 0 || g >= G) return fail(c, ILLICO_ERR_ARG, "sel[%lld] = %lld is no group id (0 .. %lld)", (long long)k, (long long)g, (long long)G - 1);
-            if (seen[g]) return fail(c, ILLICO_ERR_ARG, "group %lld is selected twice", (long long)g);
-            seen[g] = 1;
-            h_sel[k] = (int)g;
-            h_n[k] = c->h_counts[g];
-        }
-        long long p = 0, q = 0; // the two largest selected groups: their pair is the largest test
-        for (long long n : h_n) { if (n > p) { q = p; p = n; } else if (n > q) q = n; }
-        if (p + q >= 2097152ll)
-            return fail(c, ILLICO_ERR_UNSUPPORTED, "%lld cells in one pair: the integer rank and tie sums hold below 2097152 cells per test", p + q);
-    }
+    PairSelection S;
+    if ((rc = select_pair_groups(c, G, a.sel, K, [&](int64_t g) { return (long long)c->h_counts[g]; }, &S))) return rc;
     if (a.out_ld < W) return fail(c, ILLICO_ERR_ARG, "out_ld smaller than the window");
     if (a.sums_ld < W) return fail(c, ILLICO_ERR_ARG, "sums_ld smaller than the window");
     if (W == 0) return ILLICO_OK;
     if (!a.sums || !a.out[0] || !a.out[1] || !a.out[2] || !a.out_left) return fail(c, ILLICO_ERR_ARG, "null sums, output plane or out_left");
     if (W > (int64_t)1 << 21) return fail(c, ILLICO_ERR_OOM, "a window of %lld genes: pass narrower gene windows", (long long)W);
     if (!in.sparse && (uint64_t)in.ld * 4 > 0xFFFFFFFFull) return fail(c, ILLICO_ERR_UNSUPPORTED, "a row pitch of 4 GiB or more");
-    if (in.dtype == ILLICO_F32) return pwr_run<float>(c, in, col_lb, col_ub, a, h_sel, h_n);
-    return pwr_run<int32_t>(c, in, col_lb, col_ub, a, h_sel, h_n);
+    if (in.dtype == ILLICO_F32) return pwr_run<float>(c, in, col_lb, col_ub, a, S);
+    return pwr_run<int32_t>(c, in, col_lb, col_ub, a, S);
 }
 
 } // namespace

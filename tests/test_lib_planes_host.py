@@ -1,4 +1,4 @@
-"""The plane helpers of illico_amd._lib (_plane, _plane_set, Engine._outputs) and its signature table, on numpy arrays and CPU
+"""The plane helpers of illico_amd._lib (_plane, _plane_set, _pair_selection, _pair_planes, Engine._outputs) and its signature table, on numpy arrays and CPU
 tensors: they need neither the library nor a device."""
 import ctypes
 import re
@@ -160,6 +160,42 @@ def test_block_takes_exactly_the_named_dtypes():
     assert _lib._block(H.astype(np.int32), "H", (np.int32, np.uint32), H.shape)[1] is False
     with pytest.raises(ValueError):
         _lib._block(H, "H", (np.uint32,), H.shape, on_device=True)
+
+
+def test_pair_selection():
+    assert _lib._pair_selection(None, 5) == (5, None, None)
+    K, keep, ptr = _lib._pair_selection([3, 0, 4], 5)
+    assert K == 3 and keep.dtype == np.int64 and keep.tolist() == [3, 0, 4] and ptr == keep.ctypes.data
+
+
+@pytest.mark.parametrize("with_left", [False, True])
+def test_pair_planes(with_left):
+    K, W = 2, 3
+    given = [np.zeros((K, K, W)) for _ in range(4)] + ([np.zeros(W, np.uint32)] if with_left else [])
+    planes, left, ptrs, left_ptr, on_dev = _lib._pair_planes(given, 4, K, W, False, None, with_left)
+    assert all(p is q for p, q in zip(planes, given)) and ptrs == [q.ctypes.data for q in given[:4]] and on_dev is False
+    assert (left is given[4] and left_ptr == left.ctypes.data) if with_left else (left is None and left_ptr is None)
+    planes, left, ptrs, left_ptr, on_dev = _lib._pair_planes(None, 3, K, W, False, "cuda:0", with_left)   # (host input: host planes)
+    assert len(planes) == 3 and all(p.shape == (K, K, W) and p.dtype == np.float64 for p in planes) and on_dev is False
+    assert (left.shape == (W,) and left.dtype == np.uint32) if with_left else left is None
+    tail = given[4:]
+    for n, bad, text in [(3, given, "out must hold 3 planes (p, U, fold change)"),                    # one plane too many
+                         (4, given[:3] + tail, "out must hold 4 planes (p, U, fold change, z)"),      # one too few
+                         (4, [np.zeros((K, K, W + 1))] + given[1:], "array of shape (2, 2, 3)"),      # wrong shape
+                         (4, given[:3] + [np.zeros((K * K, W))] + tail, "array of shape (2, 2, 3)"),
+                         (4, given[:3] + [torch.zeros((K, K, W), dtype=torch.float64)] + tail, "numpy array or a CUDA tensor")]:
+        with pytest.raises(ValueError, match=re.escape(text)) as e:
+            _lib._pair_planes(bad, n, K, W, False, None, with_left)
+        assert ("and left" in str(e.value)) == (with_left and "out must hold" in text)
+    if with_left:   # the side is that of left: a CPU tensor is neither, and host planes behind host left are host planes whatever the input
+        with pytest.raises(ValueError, match="left must be a numpy array or a CUDA tensor"):
+            _lib._pair_planes(given[:4] + [torch.zeros(W, dtype=torch.int32)], 4, K, W, False, None, True)
+        assert _lib._pair_planes(given, 4, K, W, True, "cuda:0", True)[4] is False
+        with pytest.raises(ValueError, match="left must be a writeable contiguous host uint32"):
+            _lib._pair_planes(given[:4] + [np.zeros(W, np.int32)], 4, K, W, False, None, True)
+    else:           # mixed sides: host planes where the input, and with it the planes, are on the device
+        with pytest.raises(ValueError, match="an output plane must be a writeable contiguous CUDA float64 array"):
+            _lib._pair_planes(given, 4, K, W, True, "cuda:0", False)
 
 
 def test_outputs_of_an_empty_chunk():
