@@ -4,14 +4,7 @@
 // the per-type translation units (dense_*.hip, sparse_*.hip, keyed_*.hip); the dispatch on the value / index types is engine.h's.
 #include "engine.h"
 
-const char *const kKernelNames[KID_COUNT] = {"k_transpose_permute", "k_ovo_rank", "k_ovo_counts", "k_ovo_fused", "k_ovr_fused",
-                                              "k_fused_tables", "k_finalize", "k_ovr_gene", "k_sparse_seg", "k_csc_gene", "k_gene_totals", "k_csc_counts", "k_csc_ovr_gene", "k_ovr_partition", "k_ovr_rank_parts", "k_value_sums", "k_ovo_fused_wide", "k_group_compact", "k_ovo_rank_compact", "k_ovr_counts", "k_gather_columns", "k_csr_counts", "k_densify", "k_group_value_hists",
-                                              "k_adj_validate", "k_adj_sort_lds", "k_adj_merge", "k_adj_scan", "k_adj_bonferroni",
-                                              "k_gs_vmax", "k_gs_dense", "k_gs_csc", "k_gs_csr", "k_gs_totals", "k_gs_finalize",
-                                              "k_finalize_z", "k_top_validate", "k_top_sort", "k_top_merge", "k_top_scan",
-                                              "k_gm_vmax", "k_gm_dense", "k_gm_csc", "k_gm_csr", "k_gm_totals", "k_gm_finalize", "k_ttest",
-                                              "k_pw_hists_dense", "k_pw_hists_csc", "k_pw_hists_csr", "k_pw_hists_finish", "k_pw_pairs", "k_ovo_fused_st16",
-                                              "k_pw_rank_pairs", "k_pw_rank_emit"};
+const char *const kKernelNames[KID_COUNT] = {ILLICO_KERNELS(ILLICO_KERNEL_NAME)}; // kernel_ids.h: the one list of ids and names
 
 // The message of a failed call is kept per calling thread (and in the context, for single-threaded callers): a second
 // thread's failure must not replace the text the first is about to read through illico_last_error.
@@ -168,99 +161,37 @@ int illico_ctx_set_stream(illico_ctx *c, void *hip_stream) {
     return ILLICO_OK;
 }
 
+// "prewarm_host_window_bytes", the one option that acts instead of storing a value: what a context's FIRST call on a host-resident
+// dense matrix otherwise pays for (~80 ms of a 190-ms first drop-in call at C2): the three pinned slots and the three device windows
+// of the host-window pipelines
+static int prewarm_host_windows(illico_ctx *c, int64_t value) {
+    if (value <= 0) return ILLICO_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return ILLICO_ERR_HIP;
+    HostStage *hs = host_stage_of(c);
+    const size_t want = (size_t)value;
+    if (hs->pin_bytes < want) {
+        for (int j = 0; j < HS_SLOTS; ++j) { if (hs->pin[j]) hipHostFree(hs->pin[j]); hs->pin[j] = nullptr; }
+        hs->pin_bytes = 0;
+        for (int j = 0; j < HS_SLOTS; ++j)
+            if (hipHostMalloc(&hs->pin[j], want, hipHostMallocDefault) != hipSuccess) return fail(c, ILLICO_ERR_OOM, "pinning %zu bytes failed", want);
+        hs->pin_bytes = want;
+    }
+    static const char *names[HS_SLOTS] = {"xin0", "xin1", "xin2"};
+    void *v;
+    for (int j = 0; j < HS_SLOTS; ++j) { const int rc = get_scratch(c, names[j], want, &v); if (rc) return rc; }
+    return ILLICO_OK;
+}
+
+// every other option is a line of kEngineOptions (options.h)
 int illico_ctx_set_option(illico_ctx *c, const char *key, int64_t value) {
     if (!c || !key) return ILLICO_ERR_ARG;
     CTX_LOCK(c);
-    if (!strcmp(key, "gene_batch")) c->gene_batch = value;
-    else if (!strcmp(key, "scratch_bytes")) c->scratch_bytes = value;
-    else if (!strcmp(key, "profile")) c->profile = value != 0;
-    else if (!strcmp(key, "profile_only")) c->profile_only = (value >= 0 && value < KID_COUNT) ? (int)value : -1;
-    else if (!strcmp(key, "no_counts_path")) c->no_counts_path = value != 0;
-    else if (!strcmp(key, "no_fused_path")) c->no_fused_path = value != 0;
-    else if (!strcmp(key, "no_fused_wide")) c->no_fused_wide = value != 0;
-    else if (!strcmp(key, "no_leftover_gather")) c->no_leftover_gather = value != 0;
-    else if (!strcmp(key, "no_wide_gather")) c->no_wide_gather = value != 0;
-    else if (!strcmp(key, "bound_ahead_genes")) c->bound_ahead_genes = value < 0 ? 0 : value;
-    else if (!strcmp(key, "no_csc_counts_windows")) c->no_csc_counts_windows = value != 0;
-    else if (!strcmp(key, "no_csc_counts_wide")) c->no_csc_counts_wide = value != 0;
-    else if (!strcmp(key, "ovr_full_dump")) c->ovr_full_dump = value != 0;
-    else if (!strcmp(key, "no_packed_dense")) c->no_packed_dense = value != 0;
-    else if (!strcmp(key, "packed_eq_buckets")) c->packed_eq_buckets = (int)value;
-    else if (!strcmp(key, "no_ovo_parts")) c->no_ovo_parts = value != 0;
-    else if (!strcmp(key, "no_packed_small_wg")) c->no_packed_small_wg = value != 0;
-    else if (!strcmp(key, "no_deal_runs")) c->no_deal_runs = value != 0;
-    else if (!strcmp(key, "no_coop_runs")) c->no_coop_runs = value != 0;
-    else if (!strcmp(key, "no_csc_ovr_small_lds")) c->no_csc_ovr_small_lds = value != 0;
-    else if (!strcmp(key, "no_csr_transpose_split")) c->no_csr_transpose_split = value != 0;
-    else if (!strcmp(key, "no_group_hist_route")) c->no_group_hist_route = value != 0;
-    else if (!strcmp(key, "group_hist_max_wgs")) c->group_hist_max_wgs = value > 0 ? value : 1024;
-    else if (!strcmp(key, "group_hist_min_cells")) c->group_hist_min_cells = value > 0 ? value : 32768;
-    else if (!strcmp(key, "no_ovr_part_coop")) c->no_ovr_part_coop = value != 0;
-    else if (!strcmp(key, "no_ovr_packed_big")) c->no_ovr_packed_big = value != 0;
-    else if (!strcmp(key, "big_runs_slice_bytes")) c->big_runs_slice_bytes = (int)value;
-    else if (!strcmp(key, "no_big_runs_wide")) c->no_big_runs_wide = value != 0;
-    else if (!strcmp(key, "no_compact_order")) c->no_compact_order = value != 0;
-    else if (!strcmp(key, "no_compact_narrow")) c->no_compact_narrow = value != 0;
-    else if (!strcmp(key, "compact_narrow_wgs")) c->compact_narrow_wgs = value > 0 ? value : 2048;
-    else if (!strcmp(key, "compact_narrow_rows")) c->compact_narrow_rows = value > 0 ? value : 8192;
-    else if (!strcmp(key, "no_big_runs_global")) c->no_big_runs_global = value != 0;
-    else if (!strcmp(key, "packed_ref_cap")) c->packed_ref_cap = (int)value;
-    else if (!strcmp(key, "debug_routes")) c->debug_routes = value != 0;
-    else if (!strcmp(key, "host_fill_threads")) c->host_fill_threads = (int)value;
-    else if (!strcmp(key, "prewarm_host_window_bytes")) { // what a context's FIRST call on a host-resident dense matrix otherwise pays for (~80 ms
-        // of a 190-ms first drop-in call at C2): the three pinned slots and the three device windows of the host-window pipelines
-        if (value > 0) {
-            if (hipSetDevice(c->device) != hipSuccess) return ILLICO_ERR_HIP;
-            HostStage *hs = host_stage_of(c);
-            const size_t want = (size_t)value;
-            if (hs->pin_bytes < want) {
-                for (int j = 0; j < HS_SLOTS; ++j) { if (hs->pin[j]) hipHostFree(hs->pin[j]); hs->pin[j] = nullptr; }
-                hs->pin_bytes = 0;
-                for (int j = 0; j < HS_SLOTS; ++j)
-                    if (hipHostMalloc(&hs->pin[j], want, hipHostMallocDefault) != hipSuccess) return fail(c, ILLICO_ERR_OOM, "pinning %zu bytes failed", want);
-                hs->pin_bytes = want;
-            }
-            static const char *names[HS_SLOTS] = {"xin0", "xin1", "xin2"};
-            void *v;
-            for (int j = 0; j < HS_SLOTS; ++j) { const int rc = get_scratch(c, names[j], want, &v); if (rc) return rc; }
-        }
-    }
-    else if (!strcmp(key, "no_host_numa")) c->no_host_numa = value != 0;
-    else if (!strcmp(key, "no_sparse_byte_values")) c->no_sparse_byte_values = value != 0;
-    else if (!strcmp(key, "csc_counts_max_windows")) c->csc_counts_max_windows = (int)value;
-    else if (!strcmp(key, "no_sparse_packed_small")) c->no_sparse_packed_small = value != 0;
-    else if (!strcmp(key, "big_runs_cap")) c->big_runs_cap = (int)value;
-    else if (!strcmp(key, "no_ovr_packed_partition")) c->no_ovr_packed_partition = value != 0;
-    else if (!strcmp(key, "no_csc_counts_path")) c->no_csc_counts_path = value != 0;
-    else if (!strcmp(key, "no_csc_counts_mixed")) c->no_csc_counts_mixed = value != 0;
-    else if (!strcmp(key, "no_csc_regroup_lds")) c->no_csc_regroup_lds = value != 0;
-    else if (!strcmp(key, "no_csc_gene_path")) c->no_csc_gene_path = value != 0;
-    else if (!strcmp(key, "ovr_parts_cap")) c->ovr_parts_cap = value;
-    else if (!strcmp(key, "pair_rank_cap")) c->pair_rank_cap = value > 0 ? std::max<int64_t>(1024, value) : 0;
-    else if (!strcmp(key, "ovr_rank_whole")) c->ovr_rank_whole = value != 0;
-    else if (!strcmp(key, "no_ovo_ref_buckets")) c->no_ovo_ref_buckets = value != 0;
-    else if (!strcmp(key, "no_ovr_parts_path")) c->no_ovr_parts_path = value != 0;
-    else if (!strcmp(key, "no_csc_ovr_gene_path")) c->no_csc_ovr_gene_path = value != 0;
-    else if (!strcmp(key, "csc_ovr_sorted_form")) c->csc_ovr_sorted_form = value != 0;
-    else if (!strcmp(key, "no_ovr_one_pass")) c->no_ovr_one_pass = value != 0;
-    else if (!strcmp(key, "no_ovr_library_sort")) (void)value; // accepted and ignored: there is no library sort any more
-    else if (!strcmp(key, "no_csr_tile_gather")) c->no_csr_tile_gather = value != 0;
-    else if (!strcmp(key, "no_csr_transpose_path")) c->no_csr_transpose_path = value != 0;
-    else if (!strcmp(key, "no_csr_densify_any")) c->no_csr_densify_any = value != 0;
-    else if (!strcmp(key, "no_f64_narrowing")) c->no_f64_narrowing = value != 0;
-    else if (!strcmp(key, "dense_window_f32")) c->dense_window_f32 = value != 0;
-    else if (!strcmp(key, "host_narrow")) c->host_narrow = value > 0 ? 1 : (value < 0 ? -1 : 0);
-    else if (!strcmp(key, "no_csr_counts_path")) c->no_csr_counts_path = value != 0;
-    else if (!strcmp(key, "csr_counts_abl")) c->csr_counts_abl = (int)value;
-    else if (!strcmp(key, "no_dense_window_path")) c->no_dense_window_path = value != 0;
-    else if (!strcmp(key, "ovr_hist_groups_per_wg")) c->ovr_hist_groups_per_wg = (int)std::max<int64_t>(0, value);
-    else if (!strcmp(key, "fused_groups_per_wg")) c->fused_groups_per_wg = (int)std::max<int64_t>(0, value);
-    else if (!strcmp(key, "fused_mem_policy")) {
-        if (value < 0 || value > 15 || (value & 3) == 3) return fail(c, ILLICO_ERR_ARG, "fused_mem_policy: loads 0 / 1 / 2 plus stores 0 / 4 / 8 / 12, not %lld", (long long)value);
-        c->fused_mem_policy = (int)value;
-    }
-    else return fail(c, ILLICO_ERR_ARG, "unknown option '%s'", key);
-    return ILLICO_OK;
+    if (!strcmp(key, "prewarm_host_window_bytes")) return prewarm_host_windows(c, value);
+    std::string why;
+    const int rc = set_engine_option(*c, key, value, &why);
+    if (rc == ILLICO_ERR_ARG) return fail(c, rc, "%s", why.c_str());
+    if (rc == ENGINE_OPTION_UNKNOWN) return fail(c, ILLICO_ERR_ARG, "unknown option '%s'", key);
+    return rc;
 }
 
 const char *illico_last_error(const illico_ctx *c) {

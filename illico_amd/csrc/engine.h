@@ -20,6 +20,7 @@
 
 #include "../../include/illico_hip.h"
 #include "common.h"
+#include "options.h" // EngineOptions; with kernel_ids.h: the KID_* ids and kKernelNames
 #include "kernels_finalize.h"
 #include "kernels_ovo.h"
 #include "kernels_ovo_compact.h"
@@ -35,67 +36,6 @@
 #include "kernels_sums.h"
 #include "kernels_leftover.h"
 #include "kernels_csr_counts.h"
-
-// ---- profiled kernel ids ---------------------------------------------------------------------
-enum {
-    KID_TRANSPOSE = 0,
-    KID_OVO_RANK,
-    KID_OVO_COUNTS,
-    KID_OVO_FUSED,
-    KID_OVR_FUSED,
-    KID_FUSED_REF,
-    KID_FINALIZE,
-    KID_OVR_SCAN,
-    KID_SPARSE_SEG,
-    KID_CSC_GENE,
-    KID_GENE_TOTALS,
-    KID_CSC_COUNTS,
-    KID_CSC_OVR,
-    KID_OVR_PART,
-    KID_OVR_RANK_PARTS,
-    KID_VALUE_SUMS,
-    KID_OVO_FUSED_WIDE,
-    KID_GROUP_COMPACT,
-    KID_OVO_RANK_COMPACT,
-    KID_OVR_COUNTS,
-    KID_GATHER_COLS,
-    KID_CSR_COUNTS,
-    KID_DENSIFY,
-    KID_GROUP_HISTS,
-    KID_ADJ_VALIDATE, // illico_adjust_pvalues (kernels_adjust.h)
-    KID_ADJ_SORT,
-    KID_ADJ_MERGE,
-    KID_ADJ_SCAN,
-    KID_ADJ_BONF,
-    KID_GS_VMAX, // illico_group_stats_* (kernels_group_stats.h)
-    KID_GS_DENSE,
-    KID_GS_CSC,
-    KID_GS_CSR,
-    KID_GS_TOTALS,
-    KID_GS_FINALIZE,
-    KID_FINALIZE_Z, // k_finalize<true>, profiled as "k_finalize_z": with the z-score plane
-    KID_TOP_VALIDATE, // illico_top_by_score (kernels_adjust.h)
-    KID_TOP_SORT,
-    KID_TOP_MERGE,
-    KID_TOP_SCAN,
-    KID_GM_VMAX, // illico_group_moments_* (kernels_group_moments.h)
-    KID_GM_DENSE,
-    KID_GM_CSC,
-    KID_GM_CSR,
-    KID_GM_TOTALS,
-    KID_GM_FINALIZE,
-    KID_TTEST, // illico_ttest_from_moments / illico_student_t_pvalues (kernels_ttest.h)
-    KID_PW_HIST_DENSE, // illico_group_value_hists_* (kernels_pairwise.h)
-    KID_PW_HIST_CSC,
-    KID_PW_HIST_CSR,
-    KID_PW_HIST_FINISH,
-    KID_PW_PAIRS, // illico_pairwise_from_hists
-    KID_OVO_FUSED_ST16, // k_ovo_fused's first pass in a 16-byte-store form ("fused_mem_policy" 8 / 12 where the planes allow it)
-    KID_PW_RANK_PAIRS, // illico_pairwise_ranked_* (kernels_pairwise_ranked.h)
-    KID_PW_RANK_EMIT,
-    KID_COUNT
-};
-extern const char *const kKernelNames[KID_COUNT];
 
 struct OutPlanes {
     double *p, *u, *fc; // device
@@ -138,7 +78,8 @@ struct ProfEvent {
     hipEvent_t a, b;
 };
 
-struct illico_ctx {
+// (the option fields -- c->no_fused_path, c->profile, c->scratch_bytes ... -- are EngineOptions': options.h)
+struct illico_ctx : EngineOptions {
     // Every entry point that takes the context holds this lock for the whole call: two host threads driving ONE context
     // (the reference's joblib threads share one dispatcher, asymptotic_wilcoxon.py:236-241) are serialised, not raced.
     std::recursive_mutex mu;
@@ -180,73 +121,7 @@ struct illico_ctx {
     int csr_n_chunks = 0, csr_n_big = 0; // csr_n_big < 0: more big groups than the route takes
     bool cur_sorted_known = false;       // the running call is on a bound CSR matrix whose rows were found in order when it was bound
     bool fused_tie_sparse = false;       // the fused OVR kernels run on a window of CSR input: tie sums as the reference's SPARSE path forms them
-    int csr_counts_abl = 0;              // timing experiments (CsrCountsParams::abl)
     bool hold_csr_counts = false;        // set while a deferred call's leftover genes are recomputed (they must not come back to the route)
-    // options
-    int64_t gene_batch = 0;
-    int64_t scratch_bytes = 24ll << 30; // (illico_ctx_create: min(64 GiB, a quarter of the device's memory))
-    bool no_counts_path = false;
-    bool no_fused_path = false;
-    bool no_ovr_packed_partition = false; // 1: dense OVR partitions the padded rows (every key) instead of the packed ones
-    bool no_packed_dense = false;      // 1: dense OVO on continuous values takes the transpose + k_ovo_rank route (no group-wise packing)
-    bool no_sparse_packed_small = false; // sparse OVO, eight-byte keys: genes beyond k_csc_gene's LDS go to k_ovo_rank / the dense window (as before round 5), not to the packed rank kernel
-    int csc_counts_max_windows = 0;    // > 0: count-valued CSC with more windows of groups than this leaves the histogram route (8: as before round 5)
-    bool no_sparse_byte_values = false; // host-resident sparse input: the stored values always go up in their own type (count values: as bytes otherwise)
-    bool no_host_numa = false;         // host-window pipelines: do not confine the fill threads to the NUMA node the caller's matrix lives on
-    int host_fill_threads = 0;         // > 0: host threads that fill the pinned slots of the host-window pipelines (default: 12 float32 / 16 byte windows)
-    bool debug_routes = false;         // stderr: what the packed OVO rank kernel left to the general routes, and why
-    int packed_ref_cap = 0;            // > 0: caps the packed rank kernel's key slots for the reference (tests: value-range parts at small sizes)
-    int big_runs_cap = 0;              // > 0: caps k_bucket_big_runs' LDS key slots (tests: the route through HBM at small sizes)
-    int big_runs_slice_bytes = 0;      // > 0: the LDS bytes of k_bucket_big_runs_global's slice buffer (default: what the CU's LDS leaves beside the counters)
-    bool no_big_runs_wide = false;     // k_bucket_big_runs: 256 threads whatever the runs' length
-    bool no_big_runs_global = false;   // packed routes: a (gene, group) run beyond k_bucket_big_runs' LDS slots sends its gene to the general route (as before round 5)
-    bool no_compact_order = false;     // k_group_compact: workgroups in grid order whatever the blocks' lengths
-    bool no_compact_narrow = false;    // k_group_compact: never the 32-gene tiles for few, long blocks
-    int64_t compact_narrow_wgs = 2048;  // ... and the launch would have fewer 64-gene workgroups than this (8 per compute unit)
-    int64_t compact_narrow_rows = 8192; // ... from this many rows in the longest block
-    bool no_ovr_part_coop = false;     // k_ovr_partition_packed: one wavefront per block whatever the blocks' lengths
-    bool no_ovr_packed_big = false;    // dense OVR: groups above 65535 cells take the padded rows (every key, zeros included), as before
-    bool no_group_hist_route = false;  // count-valued dense input with few, large groups: the fused kernels (a wavefront per group), as before
-    int64_t group_hist_max_wgs = 1024;  // ... while the fused launch would have fewer workgroups than this
-    int64_t group_hist_min_cells = 32768; // ... from this many cells (tests lower it)
-    bool no_csr_transpose_split = false; // CSR -> CSC on the device: one workgroup per row block whatever their number
-    bool no_csc_ovr_small_lds = false; // k_csc_ovr_gene: a CU's whole LDS per workgroup whatever the columns' lengths
-    bool no_coop_runs = false;         // packed rank kernel: a long run is walked by one wavefront (as before) instead of all of the workgroup's
-    bool no_deal_runs = false;         // packed rank kernel in parts: never deal the short runs by part first (every part then looks every key up, masked)
-    bool no_packed_small_wg = false;   // packed rank kernel: never the 256-thread form for small references with few groups
-    bool no_ovo_parts = false;         // packed rank kernel: never take a reference in value-range parts (genes beyond the LDS slots go to the general routes, as before round 5)
-    int packed_eq_buckets = -1;        // packed rank kernel: distribution-following bucket function; -1 = for references above 16384 cells
-    bool no_csc_counts_windows = false; // 1: count-valued CSC with more groups than LDS holds tables for never takes k_csc_counts (windows of groups)
-    bool no_csc_counts_wide = false;   // 1: count-valued CSC with more than 8 groups above 255 cells never takes k_csc_counts (16-bit cells)
-    bool ovr_full_dump = false;        // 1: the one-pass OVR route dumps whole group histograms (A/B of the shortened dump)
-    bool no_wide_gather = false;       // 1: the 256-value stage always runs over the window as it lies (never left to the host's gather)
-    bool no_leftover_gather = false;   // 1: the genes the fused passes leave are recomputed as column runs of the input (no gather into a narrow matrix)
-    bool no_fused_wide = false;        // 1: no second, 256-value pass of the fused OVO route (genes beyond 63 go to the two-pass routes)
-    bool no_csc_regroup_lds = false;   // 1: the two-kernel CSC route regroups with k_csc_segment only
-    bool no_csc_gene_path = false;
-    bool ovr_rank_whole = false;       // dense OVR rank kernel: one 1024-thread workgroup per CU with all of the LDS (as before round 5) instead of two of 512
-    int64_t ovr_parts_cap = 0;         // > 0: keys per part at most in the value-range parts route (tests: many small parts)
-    int64_t pair_rank_cap = 0;         // > 0: records per part at most in the ranked pair route (tests: many small parts)
-    bool no_ovo_ref_buckets = false;   // 1: the OVO sort route always sorts the reference column (no value-bucket form)
-    bool no_ovr_parts_path = false;    // 1: dense OVR (any values) never takes the value-range parts route (k_ovr_partition + k_csc_ovr_gene)
-    bool no_csc_ovr_gene_path = false; // 1: CSC OVR never takes the single-kernel LDS-sort route (k_csc_ovr_gene)
-    bool csc_ovr_sorted_form = false;  // 1: k_csc_ovr_gene sorts every gene's keys in LDS (the form tie-heavy columns take) instead of bucketing them
-    bool no_csc_counts_path = false;   // 1: count-valued CSC genes do not take the LDS-histogram kernel (k_csc_counts)
-    bool no_csc_counts_mixed = false;  // 1: k_csc_counts with 8-bit cells for every value only (the form 4-bit overflows fall back to)
-    bool no_ovr_one_pass = false;      // 1: dense OVR reads X twice (column histogram, then rank sums) instead of once
-    bool no_csr_tile_gather = false;    // 1: CSR -> CSC always by the scatter form (k_csr_block_scatter), as for unsorted rows
-    bool no_f64_narrowing = false;      // 1: float64 sparse values that are all float32 values stay with the float64 kernels (A/B)
-    bool no_csr_densify_any = false;    // 1: CSR windows with long columns of any values are never handed to the dense routes (A/B)
-    bool no_csr_transpose_path = false; // 1: CSR is regrouped by (gene, group) with global atomics instead of being transposed to CSC
-    bool dense_window_f32 = false;      // 1: CSR dense windows hold float32 cells instead of bytes
-    int host_narrow = 0;               // host-resident count matrices as byte windows: 0 = when a value sample says counts, 1 = always, -1 = never
-    bool no_csr_counts_path = false;   // 1: count-valued CSR never takes the group-major single pass (k_csr_counts)
-    bool no_dense_window_path = false; // 1: CSR never goes through dense float32 windows + the fused kernels
-    int fused_groups_per_wg = 0; // 0 = auto
-    int fused_mem_policy = 0;    // first OVO pass of the fused route: loads 0 = default / 1 = plain / 2 = non-temporal, + stores 4 = 8 B / 8 = 16 B / 12 = 16 B write-through
-    int ovr_hist_groups_per_wg = 0; // k_ovr_from_hists; 0 = auto
-    bool profile = false;
-    int profile_only = -1;        // >= 0: time this kernel id only (the others run without events around them)
     PendingDense pend;            // deferred dense call (ILLICO_FLAG_DEFER), see resolve_pending
     void *pend_pinned[2] = {nullptr, nullptr}; // its route flags arrive here (two buffers: the next call may be enqueued first)
     size_t pend_pinned_bytes[2] = {0, 0};
@@ -259,10 +134,6 @@ struct illico_ctx {
     size_t pinned_bytes = 0;
     int64_t h2d_input_bytes = 0;  // matrix bytes copied host -> device (illico_profile_input_bytes)
     std::vector<illico_matrix *> bound; // matrices bound to this context and not yet released
-    // "bound_ahead_genes" > 0: a call for FEWER genes of a bound CSR matrix computes the aligned window of that many genes around them
-    // into planes of the context's own and hands out slices -- the reference's driver asks for ~256 genes at a time
-    // (asymptotic_wilcoxon.py:213-241), and a CSR call walks every row whatever the width of its window (core.hip: run_bound_ahead)
-    int64_t bound_ahead_genes = 0;
     uint64_t groups_gen = 0;      // counts illico_set_groups calls (the windows below belong to one set of groups)
     struct AheadWindow {
         const illico_matrix *m = nullptr;

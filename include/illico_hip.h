@@ -84,21 +84,32 @@ int illico_ctx_set_stream(illico_ctx *ctx, void *hip_stream);
  * instead of the leading non-zero ones), "no_csc_counts_path" (count-valued CSC on LDS histograms;
  * "no_csc_counts_mixed" = 1: its 8-bit cell form only; "no_csc_counts_wide" = 1: never its 16-bit-cell form, i.e. the route is off when
  * more than 8 ranked groups exceed 255 cells; "no_csc_counts_windows" = 1: never in windows of groups, i.e. off when the groups' tables
- * do not fit LDS at once),
+ * do not fit LDS at once; "csc_counts_max_windows" > 0: nor in more windows of groups than this),
  * "no_packed_dense" (dense two-pass routes: group-wise packing of the non-zero keys + look-ups in a counted bitmap of the reference
  * for OVO, the transposition with the group sums folded in for OVR; 1 = the plain transposition and the kernels behind it;
  * "no_ovr_packed_partition" = 1: dense OVR splits the padded key rows -- every key -- instead of the packed ones;
  * "packed_eq_buckets": the packed OVO kernel's value buckets follow the reference's distribution, 1 = always, 0 = never,
  * -1 = for references of more than 16384 cells, the default; "no_ovo_parts" = 1: a reference whose non-zero keys outgrow the kernel's
  * LDS slots is never taken in value-range parts -- such genes go to the general sort routes; "no_big_runs_global" = 1: a ranked
- * group's run of more keys than LDS holds is not dealt into value buckets through HBM -- its gene goes to the general sort routes),
+ * group's run of more keys than LDS holds is not dealt into value buckets through HBM -- its gene goes to the general sort routes;
+ * "no_packed_small_wg" = 1: the packed OVO kernel never takes its 256-thread form for small references with few groups;
+ * "no_coop_runs" = 1: it walks a long run with one wavefront instead of all of the workgroup's; "no_deal_runs" = 1: in value-range
+ * parts it never deals the short runs by part first -- every part then looks every key up, masked; "packed_ref_cap" / "big_runs_cap"
+ * > 0: cap the kernel's LDS key slots for the reference / k_bucket_big_runs' LDS key slots, so that tests reach the value-range
+ * parts / the route through HBM at small sizes; "no_sparse_packed_small" = 1: sparse OVO genes with eight-byte keys beyond
+ * k_csc_gene's LDS go to k_ovo_rank or the dense windows instead of the packed kernel; "debug_routes" = 1: stderr says what the
+ * packed OVO kernel left to the general routes, and why),
  * "no_compact_narrow" (k_group_compact never takes its 32-gene tiles for few, long blocks; "compact_narrow_rows": rows of the longest
- * block from which it does, default 8192), "no_big_runs_wide" (runs above 8192 keys get no 1024-thread launch of their own),
+ * block from which it does, default 8192; "compact_narrow_wgs": and only while the launch would have fewer 64-gene workgroups than
+ * this, default 2048; a value of 0 or less restores either default), "no_compact_order" (k_group_compact numbers its workgroups in
+ * grid order whatever the blocks' lengths instead of starting the longest block first), "no_big_runs_wide" (runs above 8192 keys get no 1024-thread launch of their own),
  * "big_runs_slice_bytes" (> 0: LDS bytes of k_bucket_big_runs_global's slice buffer), "no_ovr_packed_big" (dense OVR with a group above
  * 65535 cells partitions the padded rows, as before), "no_ovr_part_coop" (the packed partition walks every block with one wavefront),
+ * "ovr_rank_whole" (dense OVR rank kernel: one 1024-thread workgroup per CU with all of its LDS instead of two of 512 threads),
  * "no_group_hist_route" (count-valued dense input with few large groups, or OVR / OVO with a group above 65535 cells: the fused kernels
  * instead of the (group, gene) value histograms of kernels_group_hists.h; "group_hist_min_cells": cells from which the route is
- * taken, default 32768), "no_csr_transpose_split" (CSR -> CSC on the device: one workgroup per row block whatever their number),
+ * taken, default 32768; "group_hist_max_wgs": and only while the fused launch would have fewer workgroups than this, default 1024;
+ * a value of 0 or less restores either default), "no_csr_transpose_split" (CSR -> CSC on the device: one workgroup per row block whatever their number),
  * "no_csc_ovr_small_lds" (k_csc_ovr_gene takes a CU's whole LDS per workgroup whatever the columns' lengths),
  * "no_ovo_ref_buckets" (OVO sort route: reference column in value buckets instead of sorted), "no_ovr_parts_path" (dense OVR, any values: value-range parts ranked in LDS; "ovr_parts_cap" > 0 caps the keys per part), "no_csc_gene_path" (CSC OVO single-kernel route), "no_csc_ovr_gene_path" (CSC OVR single-kernel route; "csc_ovr_sorted_form" = 1 makes it sort every
  * gene in LDS, the form tie-heavy columns take, instead of bucketing the keys), "no_csc_regroup_lds" (two-kernel CSC route: regroup with scattered
@@ -114,7 +125,15 @@ int illico_ctx_set_stream(illico_ctx *ctx, void *hip_stream);
  * Not route switches: "host_narrow" (-1 automatic / 1 / 0: host-resident count matrices go up as bytes), "bound_ahead_genes" (0 = off:
  * a call for fewer genes of a bound CSR matrix computes the aligned window of that many genes around them once and later calls inside
  * the window are slices of it -- for bindings that keep the reference's 256-gene chunk loop),
- * "fused_mem_policy" (cache policy of the fused dense OVO pass, same bits whatever the value: 0 = the engine's choice -- non-temporal loads for 4- and 8-byte values, default loads for byte windows, 8-byte stores; loads of X 1 = default policy, 2 = non-temporal; plus result stores 4 = 8 bytes per lane, 8 = 16 bytes per lane, 12 = 16 bytes write-through).
+ * "fused_mem_policy" (cache policy of the fused dense OVO pass, same bits whatever the value: 0 = the engine's choice -- non-temporal loads for 4- and 8-byte values, default loads for byte windows, 8-byte stores; loads of X 1 = default policy, 2 = non-temporal; plus result stores 4 = 8 bytes per lane, 8 = 16 bytes per lane, 12 = 16 bytes write-through),
+ * "host_fill_threads" (> 0: host threads that fill the pinned slots of the host-window pipelines; default 12 for float32 and 16 for
+ * byte windows), "no_host_numa" (1 = those threads are not confined to the NUMA node the caller's matrix lives on),
+ * "no_sparse_byte_values" (1 = the stored values of host-resident sparse input always go up in their own type; count values go up as
+ * bytes otherwise), "prewarm_host_window_bytes" (an action, not a setting: a value > 0 pins the three host slots and allocates the
+ * three device windows of the host-window pipelines at that many bytes each now, instead of in the context's first call on a
+ * host-resident dense matrix; 0 does nothing), "pair_rank_cap" (> 0: records per part at most in the ranked pair route, never below
+ * 1024 -- tests force many small parts with it), "csr_counts_abl" (a timing experiment: bits that leave out stages of k_csr_counts,
+ * whose results are then wrong; 0 = the whole kernel), "no_ovr_library_sort" (accepted and ignored: there is no library sort any more).
  * Unknown keys return ILLICO_ERR_ARG. */
 int illico_ctx_set_option(illico_ctx *ctx, const char *key, int64_t value);
 const char *illico_last_error(const illico_ctx *ctx);

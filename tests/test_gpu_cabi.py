@@ -57,3 +57,26 @@ def test_cabi_status_codes_and_profile_hooks():
     assert lib.illico_profile_get(ctx, 10_000, None, None) == _lib.ERR_ARG
     assert lib.illico_ctx_synchronize(ctx) == 0
     assert lib.illico_ctx_destroy(ctx) == 0
+
+
+def test_set_option_takes_every_table_name():
+    """illico_ctx_set_option on a context of its own: every name of the option table, what "fused_mem_policy" refuses, unknown and null keys."""
+    from illico_amd import _lib
+    from option_names import engine_option_names
+    lib = _lib.load()
+    ctx = ctypes.c_void_p()
+    assert lib.illico_ctx_create(0, ctypes.byref(ctx)) == 0 and ctx.value
+    try:
+        err = lambda: lib.illico_last_error(ctx).decode()
+        for name in engine_option_names():  # ("prewarm_host_window_bytes" acts on a positive value only: 0 allocates nothing)
+            assert lib.illico_ctx_set_option(ctx, name.encode(), 0) == 0, name
+        for bad in (3, 7, 16, -1):
+            assert lib.illico_ctx_set_option(ctx, b"fused_mem_policy", bad) == _lib.ERR_ARG, bad
+            assert err().startswith("fused_mem_policy:"), err()
+        for good in (0, 1, 2, 4, 8, 12, 14):
+            assert lib.illico_ctx_set_option(ctx, b"fused_mem_policy", good) == 0, good
+        assert lib.illico_ctx_set_option(ctx, b"no_such_option", 0) == _lib.ERR_ARG
+        assert err() == "unknown option 'no_such_option'"
+        assert lib.illico_ctx_set_option(ctx, None, 0) == _lib.ERR_ARG
+    finally:
+        assert lib.illico_ctx_destroy(ctx) == 0

@@ -27,6 +27,46 @@ def test_cabi_exports_every_declared_symbol():
     assert lib.illico_profile_kernel_name(0)
 
 
+KERNEL_NAMES = [  # id = position: "profile_only" selects by it, profiles/traffic.json keys by the name
+    "k_transpose_permute", "k_ovo_rank", "k_ovo_counts", "k_ovo_fused", "k_ovr_fused", "k_fused_tables", "k_finalize", "k_ovr_gene",
+    "k_sparse_seg", "k_csc_gene", "k_gene_totals", "k_csc_counts", "k_csc_ovr_gene", "k_ovr_partition", "k_ovr_rank_parts",
+    "k_value_sums", "k_ovo_fused_wide", "k_group_compact", "k_ovo_rank_compact", "k_ovr_counts", "k_gather_columns", "k_csr_counts",
+    "k_densify", "k_group_value_hists",
+    "k_adj_validate", "k_adj_sort_lds", "k_adj_merge", "k_adj_scan", "k_adj_bonferroni",
+    "k_gs_vmax", "k_gs_dense", "k_gs_csc", "k_gs_csr", "k_gs_totals", "k_gs_finalize",
+    "k_finalize_z", "k_top_validate", "k_top_sort", "k_top_merge", "k_top_scan",
+    "k_gm_vmax", "k_gm_dense", "k_gm_csc", "k_gm_csr", "k_gm_totals", "k_gm_finalize", "k_ttest",
+    "k_pw_hists_dense", "k_pw_hists_csc", "k_pw_hists_csr", "k_pw_hists_finish", "k_pw_pairs", "k_ovo_fused_st16",
+    "k_pw_rank_pairs", "k_pw_rank_emit"]
+
+
+def test_kernel_ids_are_one_list():
+    """Every profiled kernel id has a name, no name twice, and ids and names are the sequence measurements were recorded under."""
+    from illico_amd import _lib
+    lib = _lib.load()
+    n = lib.illico_profile_num_kernels()
+    names = [lib.illico_profile_kernel_name(k) for k in range(n)]
+    assert all(names), "a kernel id without a name"
+    names = [s.decode() for s in names]
+    assert len(set(names)) == n
+    assert names == KERNEL_NAMES
+    assert lib.illico_profile_kernel_name(n) == b"" and lib.illico_profile_kernel_name(-1) == b""
+
+
+def test_every_option_is_documented():
+    """The option table (options.h) and the options comment of include/illico_hip.h name the same switches."""
+    from option_names import engine_option_names
+    names = engine_option_names()
+    assert names and len(set(names)) == len(names)
+    assert {"no_fused_path", "fused_mem_policy", "prewarm_host_window_bytes", "pair_rank_cap"} <= set(names)
+    header = (ROOT / "include" / "illico_hip.h").read_text()
+    missing = [k for k in names if f'"{k}"' not in header]
+    assert not missing, f"accepted by illico_ctx_set_option but not described in illico_hip.h: {missing}"
+    comment = header[header.index("/* Tunables:"):header.index("int illico_ctx_set_option")]
+    stale = sorted(set(re.findall(r'"(no_\w+)"', comment)) - set(names))
+    assert not stale, f"described in illico_hip.h but not in the option table: {stale}"
+
+
 def test_no_cpu_fallback_without_gpu():
     """Without a device the product path fails loudly; it never routes through the oracle."""
     import torch
