@@ -50,10 +50,8 @@ static int adj_validate(illico_ctx *c, const double *p, int64_t ld, int64_t nb, 
         const int gx = (int)std::min<int64_t>((m + 255) / 256, 64);
         for (int64_t r = 0; r < nb; r += 65535) {
             const int ny = (int)std::min<int64_t>(65535, nb - r);
-            hipLaunchKernelGGL(score ? k_top_validate : k_adj_validate, dim3(gx, ny), dim3(256), 0, c->stream, p + r * ld, (long long)ld, (int)m,
-                               (long long)(row0 + r), d_err);
+            KERNELCHK(c, score ? k_top_validate : k_adj_validate, dim3(gx, ny), dim3(256), 0, p + r * ld, (long long)ld, (int)m, (long long)(row0 + r), d_err);
         }
-        HIPCHK(c, hipGetLastError());
     }
     u64 err = 0;
     HIPCHK(c, hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, c->stream));
@@ -98,14 +96,10 @@ static int adjust_or_top(illico_ctx *c, const double *p, int64_t n_rows, int64_t
     const size_t per_row = b_in + b_out + b_top + b_runs;
     int64_t rows_b = std::min<int64_t>(n_rows, 65535);
     if (per_row) rows_b = std::max<int64_t>(1, std::min<int64_t>(rows_b, (int64_t)((size_t)std::max<int64_t>(c->scratch_bytes, 1) / per_row)));
-    void *v = nullptr;
-    if ((rc = get_scratch(c, "adj_err", 16, &v))) return rc;
-    u64 *d_err = (u64 *)v;
+    u64 *d_err;
+    if ((rc = scratch(c, "adj_err", 2, &d_err))) return rc;
     unsigned char *work = nullptr;
-    if (per_row) {
-        if ((rc = get_scratch(c, "adj_work", per_row * (size_t)rows_b, &v))) return rc;
-        work = (unsigned char *)v;
-    }
+    if (per_row && (rc = scratch(c, "adj_work", per_row * (size_t)rows_b, &work))) return rc;
     double *d_in = (double *)work;
     double *d_out = (double *)(work + b_in * rows_b);
     long long *d_top = (long long *)(work + (b_in + b_out) * rows_b);
@@ -151,10 +145,7 @@ static int adjust_or_top(illico_ctx *c, const double *p, int64_t n_rows, int64_t
                 const int nt = std::min(1024, P.n2 / 2);
                 const size_t lds = (size_t)P.n2 * 12 + 16 * 8;
                 ProfScope ps(c, score ? KID_TOP_SORT : KID_ADJ_SORT);
-                auto kern = score ? k_top_sort_lds<true> : k_adj_sort_lds<true>;
-                HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(kern, dim3(1, (int)nb), dim3(nt), lds, c->stream, P);
-                HIPCHK(c, hipGetLastError());
+                KERNELCHK(c, score ? k_top_sort_lds<true> : k_adj_sort_lds<true>, dim3(1, (int)nb), dim3(nt), lds, P);
             } else {
                 // runs of ADJ_LDS_COLS sorted in LDS, merged pairwise through HBM, then scanned row by row
                 P.n2 = ADJ_LDS_COLS;
@@ -163,29 +154,22 @@ static int adjust_or_top(illico_ctx *c, const double *p, int64_t n_rows, int64_t
                 const size_t lds = (size_t)P.n2 * 12 + 16 * 8;
                 {
                     ProfScope ps(c, score ? KID_TOP_SORT : KID_ADJ_SORT);
-                    auto kern = score ? k_top_sort_lds<false> : k_adj_sort_lds<false>;
-                    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL(kern, dim3((int)((m + ADJ_LDS_COLS - 1) / ADJ_LDS_COLS), (int)nb), dim3(1024), lds, c->stream, P);
-                    HIPCHK(c, hipGetLastError());
+                    KERNELCHK(c, score ? k_top_sort_lds<false> : k_adj_sort_lds<false>, dim3((int)((m + ADJ_LDS_COLS - 1) / ADJ_LDS_COLS), (int)nb), dim3(1024), lds, P);
                 }
                 int cur = 0;
                 for (int64_t w = ADJ_LDS_COLS; w < m; w *= 2, cur ^= 1) {
                     ProfScope ps(c, score ? KID_TOP_MERGE : KID_ADJ_MERGE);
-                    hipLaunchKernelGGL(k_adj_merge, dim3((int)((m + 255) / 256), (int)nb), dim3(256), 0, c->stream, run_k[cur], run_i[cur],
-                                       run_k[cur ^ 1], run_i[cur ^ 1], (int)m, (int)w);
-                    HIPCHK(c, hipGetLastError());
+                    KERNELCHK(c, k_adj_merge, dim3((int)((m + 255) / 256), (int)nb), dim3(256), 0, run_k[cur], run_i[cur], run_k[cur ^ 1], run_i[cur ^ 1], (int)m, (int)w);
                 }
                 P.skey = run_k[cur];
                 P.sidx = run_i[cur];
                 ProfScope ps(c, score ? KID_TOP_SCAN : KID_ADJ_SCAN);
-                hipLaunchKernelGGL(k_adj_scan, dim3(1, (int)nb), dim3(ADJ_SCAN_NT), 0, c->stream, P);
-                HIPCHK(c, hipGetLastError());
+                KERNELCHK(c, k_adj_scan, dim3(1, (int)nb), dim3(ADJ_SCAN_NT), 0, P);
             }
         }
         if (method == ILLICO_ADJ_BONFERRONI && dout) { // (after the sort, which reads the input: in place, this overwrites it)
             ProfScope ps(c, KID_ADJ_BONF);
-            hipLaunchKernelGGL(k_adj_bonferroni, dim3(gx, (int)nb), dim3(256), 0, c->stream, dp, (long long)dld, (int)m, dout, (long long)dold);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_adj_bonferroni, dim3(gx, (int)nb), dim3(256), 0, dp, (long long)dld, (int)m, dout, (long long)dold);
         }
         if (!out_dev) {
             if (out_adj)

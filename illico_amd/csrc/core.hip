@@ -425,9 +425,7 @@ extern "C" int illico_set_groups(illico_ctx *c, const int64_t *encoded_groups, c
 
 int launch_gene_totals(illico_ctx *c, const double *ssum, int G, int nb, double *gtot) {
     ProfScope ps(c, KID_GENE_TOTALS);
-    hipLaunchKernelGGL(k_gene_totals, dim3((nb + 63) / 64), dim3(256), 0, c->stream, ssum, G, nb, gtot);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, k_gene_totals, dim3((nb + 63) / 64), dim3(256), 0, ssum, G, nb, gtot);
 }
 // table size of the two-pass histogram route (k_ovo_counts): 4096 values with 8-bit multiplicities while no ranked group exceeds 255
 // cells, else 2048 with 16-bit ones; the ingest kernels flag genes against the same limit
@@ -462,10 +460,7 @@ int launch_finalize(illico_ctx *c, const long long *s2u, const u64 *stie, const 
     F.out_z = o.z ? o.z + col_off : nullptr;
     ProfScope ps(c, o.z ? KID_FINALIZE_Z : KID_FINALIZE);
     dim3 grid((nb + 31) / 32, ((int)c->n_groups + 31) / 32);
-    if (o.z) hipLaunchKernelGGL(k_finalize<true>, grid, dim3(256), 0, c->stream, F); // (a fourth LDS tile: its own instantiation)
-    else hipLaunchKernelGGL(k_finalize<false>, grid, dim3(256), 0, c->stream, F);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, o.z ? k_finalize<true> : k_finalize<false>, grid, dim3(256), 0, F); // (z: a fourth LDS tile, its own instantiation)
 }
 static int begin_outputs(illico_ctx *c, int flags, int64_t W, double *out_p, double *out_u, double *out_fc, int64_t out_ld, OutPlanes *o,
                          double *out_z = nullptr) {
@@ -891,9 +886,8 @@ static int csr_rows_sorted_on_device(illico_ctx *c, const void *indices, const v
     u32 bad = 0;
     const int rc = device_probe(c, &bad, 1, [&](u32 *d_bad) {
         if (idx_dtype == ILLICO_IDX_I32)
-            hipLaunchKernelGGL((k_csr_sorted_check<int32_t>), dim3(grid), dim3(256), 0, c->stream, (const int32_t *)indices, (const int32_t *)indptr, (int)n_rows, (int *)d_bad);
-        else
-            hipLaunchKernelGGL((k_csr_sorted_check<int64_t>), dim3(grid), dim3(256), 0, c->stream, (const int64_t *)indices, (const int64_t *)indptr, (int)n_rows, (int *)d_bad);
+            return launch_kernel(c, k_csr_sorted_check<int32_t>, dim3(grid), dim3(256), 0, (const int32_t *)indices, (const int32_t *)indptr, (int)n_rows, (int *)d_bad);
+        return launch_kernel(c, k_csr_sorted_check<int64_t>, dim3(grid), dim3(256), 0, (const int64_t *)indices, (const int64_t *)indptr, (int)n_rows, (int *)d_bad);
     });
     if (rc) return rc;
     *sorted = bad ? 0 : 1;
@@ -1015,9 +1009,8 @@ static int run_bound_ahead(illico_ctx *c, const illico_matrix *m, int64_t col_lb
     const size_t plane = G * (size_t)cw;
     double *const dst[3] = {o.p, o.u, o.fc};
     // one launch for the three slices (three strided copies cost three launches per chunk: 1 ms of the 32 chunks' 2.5)
-    hipLaunchKernelGGL(k_copy_plane_slices, dim3((unsigned)std::min<size_t>(G, 65535)), dim3(256), 0, c->stream, (const double *)(w->planes + (col_lb - w->lb)), (long long)plane,
-                       (long long)cw, dst[0], dst[1], dst[2], (long long)o.ld, (int)W, (int)G);
-    HIPCHK(c, hipGetLastError());
+    KERNELCHK(c, k_copy_plane_slices, dim3((unsigned)std::min<size_t>(G, 65535)), dim3(256), 0, (const double *)(w->planes + (col_lb - w->lb)), (long long)plane,
+              (long long)cw, dst[0], dst[1], dst[2], (long long)o.ld, (int)W, (int)G);
     if (!o.staged) {
         if (!(flags & ILLICO_FLAG_DEFER)) HIPCHK(c, hipStreamSynchronize(c->stream));
         return ILLICO_OK;

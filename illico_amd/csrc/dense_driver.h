@@ -19,18 +19,12 @@ static int launch_group_compact(illico_ctx *c, GroupCompactParams Q, int nb, int
     const int tw = narrow ? 32 : 64;
     const dim3 grid(((Q.nseg + 7) & ~7) + Q.nblk, (nb + tw - 1) / tw);
     ProfScope ps(c, KID_GROUP_COMPACT);
-#define GC_LAUNCH(V, L, K) do { if (narrow) hipLaunchKernelGGL((k_group_compact<InT, KeyT, V, L, K, 32>), grid, dim3(GCMP_NT), 0, c->stream, Q); \
-                                else hipLaunchKernelGGL((k_group_compact<InT, KeyT, V, L, K, 64>), grid, dim3(GCMP_NT), 0, c->stream, Q); } while (0)
-    if (pack) {
-        if (aligned && !lg) GC_LAUNCH(true, false, true); else if (aligned) GC_LAUNCH(true, true, true);
-        else if (!lg) GC_LAUNCH(false, false, true); else GC_LAUNCH(false, true, true);
-    } else {
-        if (aligned && !lg) GC_LAUNCH(true, false, false); else if (aligned) GC_LAUNCH(true, true, false);
-        else if (!lg) GC_LAUNCH(false, false, false); else GC_LAUNCH(false, true, false);
-    }
-#undef GC_LAUNCH
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return dispatch_flags([&](auto vec, auto log1p, auto packed) {
+        return dispatch_int<32, 64>(tw, [&](auto tile) {
+            return launch_kernel(c, k_group_compact<InT, KeyT, decltype(vec)::value, decltype(log1p)::value, decltype(packed)::value, decltype(tile)::value>, grid,
+                                 dim3(GCMP_NT), 0, Q);
+        });
+    }, aligned, lg, pack);
 }
 
 template <typename InT, typename KeyT>
@@ -40,12 +34,12 @@ static int run_ovo_packed(illico_ctx *c, const void *X, int64_t ld, int64_t col0
     const int64_t n_ref = c->h_counts[ref];
     const int nseg = gcmp_ref_segments(n_ref);
     int rc;
-    void *v;
-    if ((rc = get_scratch(c, "packed_nnz", (size_t)nb * G * 2 + (size_t)nb * nseg * 2 + 64, &v))) return rc;
-    u16 *nnz = (u16 *)v;
+    unsigned char *nnz_block, *seg_sum_block;
+    if ((rc = scratch(c, "packed_nnz", (size_t)nb * G * 2 + (size_t)nb * nseg * 2 + 64, &nnz_block))) return rc;
+    u16 *nnz = (u16 *)nnz_block;
     u16 *seg_nnz = nnz + (((size_t)nb * G + 7) & ~(size_t)7);
-    if ((rc = get_scratch(c, "packed_seg_sum", (size_t)nb * nseg * 8 + (size_t)nb * 4 + (size_t)nb * G * 4, &v))) return rc;
-    double *seg_sum = (double *)v;
+    if ((rc = scratch(c, "packed_seg_sum", (size_t)nb * nseg * 8 + (size_t)nb * 4 + (size_t)nb * G * 4, &seg_sum_block))) return rc;
+    double *seg_sum = (double *)seg_sum_block;
     u32 *route = (u32 *)(seg_sum + (size_t)nb * nseg);
     u32 *gofs = route + nb;
     HIPCHK(c, hipMemsetAsync(route, 0, (size_t)nb * 4, c->stream));
@@ -58,8 +52,7 @@ static int run_ovo_packed(illico_ctx *c, const void *X, int64_t ld, int64_t col0
         Q.Xt = Xt; Q.xt_stride = stride; Q.nnz = nnz; Q.gofs = gofs; Q.blk_cnt = nullptr; Q.out_sum = ssum; Q.seg_nnz = seg_nnz; Q.seg_sum = seg_sum;
         Q.cand_of = nullptr; Q.run_n = nullptr; Q.n_cand = c->pk_nbig;
         if (c->pk_nbig > 0 && c->max_nonref >= 65535) { // a (gene, group) run can outgrow the 16-bit lengths: exact ones beside them
-            if ((rc = get_scratch(c, "packed_run_n", (size_t)nb * c->pk_nbig * 4, &v))) return rc;
-            run_n = (u32 *)v;
+            if ((rc = scratch(c, "packed_run_n", (size_t)nb * c->pk_nbig, &run_n))) return rc;
             Q.cand_of = c->d_pk_big + c->pk_nbig; Q.run_n = run_n;
         }
         if ((rc = launch_group_compact<InT, KeyT>(c, Q, nb, flags, true))) return rc;
@@ -67,17 +60,15 @@ static int run_ovo_packed(illico_ctx *c, const void *X, int64_t ld, int64_t col0
     bool parts = false;
     BigRunFn<KeyT> *big_fn = nullptr;
     u32 *run_cuts = nullptr;
-    void *big_tmp = nullptr; // groups with more cells than k_bucket_big_runs' LDS slots: a second key buffer, into which such runs are dealt
+    KeyT *big_tmp = nullptr; // groups with more cells than k_bucket_big_runs' LDS slots: a second key buffer, into which such runs are dealt
     if (c->pk_nbig > 0) { // runs of more than 256 non-zero keys are dealt into value buckets in place: the rank kernel walks them in pieces
-        if ((rc = get_scratch(c, "packed_big_fn", (size_t)nb * c->pk_nbig * sizeof(BigRunFn<KeyT>), &v))) return rc;
-        big_fn = (BigRunFn<KeyT> *)v;
+        if ((rc = scratch(c, "packed_big_fn", (size_t)nb * c->pk_nbig, &big_fn))) return rc;
         ProfScope ps(c, KID_GROUP_COMPACT);
         int cap = (int)std::min<int64_t>(srt_cap<KeyT>(), (c->max_nonref + 63) & ~63ll); // (a run holds at most its group's cells)
         if (c->big_runs_cap > 0) cap = std::min(cap, std::max(c->big_runs_cap, 512) & ~63);
-        if (c->max_nonref > cap && !c->no_big_runs_global && get_scratch(c, "packed_big_tmp", (size_t)nb * (size_t)stride * sizeof(KeyT), &v) == ILLICO_OK) big_tmp = v;
+        if (c->max_nonref > cap && !c->no_big_runs_global && scratch(c, "packed_big_tmp", (size_t)nb * (size_t)stride, &big_tmp) != ILLICO_OK) big_tmp = nullptr;
         if (c->max_nonref > OCR_COOP_MIN && !c->no_coop_runs) { // runs long enough for the rank kernel to walk them with all its wavefronts: the bucket kernels leave cuts
-            if ((rc = get_scratch(c, "packed_run_cuts", (size_t)nb * c->pk_nbig * OCR_CUTS * 4, &v))) return rc;
-            run_cuts = (u32 *)v;
+            if ((rc = scratch(c, "packed_run_cuts", (size_t)nb * c->pk_nbig * OCR_CUTS, &run_cuts))) return rc;
         }
         if ((rc = launch_bucket_big_runs<KeyT>(c, (void *)Xt, big_tmp, (long long)stride, nnz, gofs, nb, G, cap, big_fn, route, c->max_nonref, run_n, run_cuts))) return rc;
     }
@@ -127,14 +118,8 @@ static int launch_transpose(illico_ctx *c, const void *X, int64_t ld, int64_t co
     dim3 grid((N + 63) / 64, (ncols + 63) / 64);
     constexpr int VEC = 16 / (int)sizeof(InT);
     const bool aligned = ((uintptr_t)X % 16 == 0) && (ld % VEC == 0) && (col0 % VEC == 0) && ((uintptr_t)Xt % 16 == 0) && (stride % 64 == 0);
-    if (aligned)
-        hipLaunchKernelGGL((k_transpose_permute_vec<InT, KeyT, VEC>), grid, dim3(256), 0, c->stream, (const InT *)X, (long long)ld,
-                           (long long)col0, ncols, (const int *)c->d_perm, N, Xt, (long long)stride, flags, limit);
-    else
-        hipLaunchKernelGGL((k_transpose_permute<InT, KeyT>), grid, dim3(256), 0, c->stream, (const InT *)X, (long long)ld,
-                           (long long)col0, ncols, (const int *)c->d_perm, N, Xt, (long long)stride, flags, limit);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, aligned ? k_transpose_permute_vec<InT, KeyT, VEC> : k_transpose_permute<InT, KeyT>, grid, dim3(256), 0, (const InT *)X, (long long)ld,
+                         (long long)col0, ncols, (const int *)c->d_perm, N, Xt, (long long)stride, flags, limit);
 }
 
 
@@ -172,7 +157,7 @@ struct FusedState {
 };
 // ref_TA [nb], ref_sum [nb], ref_cum [nb64][rt + 1] at the head of a table allocation: their bytes, and what follows them
 static size_t ref_tables_bytes(const FusedState &S, int rt) { return S.nb64 * (rt + 1) * 4 + (size_t)S.nb * 8 * 2; }
-static u32 *carve_ref_tables(FusedParams &P, void *v, const FusedState &S, int rt) {
+static u32 *carve_ref_tables(FusedParams &P, unsigned char *v, const FusedState &S, int rt) {
     P.ref_TA = (u64 *)v; P.ref_sum = P.ref_TA + S.nb; P.ref_cum = (u32 *)(P.ref_sum + S.nb);
     return P.ref_cum + S.nb64 * (rt + 1);
 }
@@ -195,9 +180,9 @@ static int carve_fused_tables(illico_ctx *c, const FusedCall &q, FusedState &S) 
     FusedParams &P = S.P;
     S.nb = q.nb; S.tiles = (q.nb + 63) / 64; S.nb64 = (size_t)S.tiles * 64;
     S.ovr = c->ref < 0; S.zp = o.z != nullptr; S.wide_only = q.init_flags != nullptr;
-    void *v;
+    unsigned char *v;
     int rc;
-    if ((rc = get_scratch(c, "fused_tables", ref_tables_bytes(S, RT) + (size_t)q.nb * 4 + (size_t)q.nb * RT * 4 + 64, &v))) return rc;
+    if ((rc = scratch(c, "fused_tables", ref_tables_bytes(S, RT) + (size_t)q.nb * 4 + (size_t)q.nb * RT * 4 + 64, &v))) return rc;
     P.X = q.X; P.ld = q.ld; P.col0 = q.b0; P.ncols = q.nb; P.perm = c->d_perm; P.pos_ptr = c->d_posptr; P.counts = c->d_counts; P.gconst = c->d_gconst;
     P.G = (int)c->n_groups; P.ref = (int)c->ref;
     P.gene_flags = carve_ref_tables(P, v, S, RT);
@@ -240,23 +225,20 @@ static bool takes_group_hist_route(const illico_ctx *c, const FusedState &S) {
 // k_fused_ref, which reads every reference row first)
 template <typename InT> static int fused_probe(illico_ctx *c, const FusedState &S) {
     ProfScope ps(c, KID_FUSED_REF);
-    hipLaunchKernelGGL((k_fused_probe<InT, FUSED_RT>), dim3(S.tiles), dim3(FUSED_PROBE_NT), 0, c->stream, S.P);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, k_fused_probe<InT, FUSED_RT>, dim3(S.tiles), dim3(FUSED_PROBE_NT), 0, S.P);
 }
 // k_fused_tables_all over the first pass's tables (inside the caller's KID_FUSED_REF scope)
-static void launch_fused_tables_all(illico_ctx *c, const FusedState &S) {
-    hipLaunchKernelGGL((k_fused_tables_all<FUSED_RT>), dim3((S.nb + 255) / 256), dim3(256), 0, c->stream, S.P);
+static int launch_fused_tables_all(illico_ctx *c, const FusedState &S) {
+    return launch_kernel(c, k_fused_tables_all<FUSED_RT>, dim3((S.nb + 255) / 256), dim3(256), 0, S.P);
 }
 template <typename InT> static int fused_hist_route(illico_ctx *c, const FusedState &S) {
     constexpr int RT = FUSED_RT;
     const FusedParams &P = S.P;
     const int tiles = S.tiles;
-    void *v;
+    u32 *H;
     int rc;
     const size_t h_bytes = (size_t)c->n_groups * tiles * RT * 64 * 4;
-    if ((rc = get_scratch(c, "group_value_hists", h_bytes, &v))) return rc;
-    u32 *H = (u32 *)v;
+    if ((rc = scratch(c, "group_value_hists", h_bytes / 4, &H))) return rc;
     HIPCHK(c, hipMemsetAsync(H, 0, h_bytes, c->stream));
     constexpr int NWH = GH_NT / 64;
     // positions per wavefront: ~2048 workgroups, at most 4096 positions (16-bit cells)
@@ -264,21 +246,18 @@ template <typename InT> static int fused_hist_route(illico_ctx *c, const FusedSt
     const int chunks = (int)((c->n_cells + (int64_t)NWH * wave_rows - 1) / ((int64_t)NWH * wave_rows));
     {
         ProfScope ps(c, KID_GROUP_HISTS);
-        hipLaunchKernelGGL((k_group_value_hists<InT, RT>), dim3(tiles, chunks), dim3(GH_NT), 0, c->stream, P, H, wave_rows);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_group_value_hists<InT, RT>, dim3(tiles, chunks), dim3(GH_NT), 0, P, H, wave_rows);
     }
     ProfScope ps(c, KID_FUSED_REF);
     if (S.ovr) {
         HIPCHK(c, hipMemsetAsync(P.hist_all, 0, (size_t)S.nb * RT * 4, c->stream));
-        hipLaunchKernelGGL((k_group_hists_to_column<RT, true>), dim3(tiles, ((int)c->n_groups + 63) / 64), dim3(256), 0, c->stream, P, (const u32 *)H);
-    } else hipLaunchKernelGGL((k_group_hists_to_column<RT, false>), dim3(tiles), dim3(256), 0, c->stream, P, (const u32 *)H);
-    launch_fused_tables_all(c, S);
+        KERNELCHK(c, k_group_hists_to_column<RT, true>, dim3(tiles, ((int)c->n_groups + 63) / 64), dim3(256), 0, P, (const u32 *)H);
+    } else KERNELCHK(c, k_group_hists_to_column<RT, false>, dim3(tiles), dim3(256), 0, P, (const u32 *)H);
+    if ((rc = launch_fused_tables_all(c, S))) return rc;
     const dim3 ge(tiles, ((int)c->n_groups + 3) / 4);
     auto emit = S.ovr ? (S.zp ? k_emit_from_group_hists<RT, true, true> : k_emit_from_group_hists<RT, true>)
                       : (S.zp ? k_emit_from_group_hists<RT, false, true> : k_emit_from_group_hists<RT, false>);
-    hipLaunchKernelGGL(emit, ge, dim3(256), 0, c->stream, P, (const u32 *)H);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, emit, ge, dim3(256), 0, P, (const u32 *)H);
 }
 // OVO: the reference group's tables
 template <typename InT> static int fused_ovo_reference(illico_ctx *c, FusedState &S) {
@@ -286,8 +265,7 @@ template <typename InT> static int fused_ovo_reference(illico_ctx *c, FusedState
     FusedParams &P = S.P;
     ProfScope ps(c, KID_FUSED_REF);
     if (S.tiles >= 100) { // one 1024-thread workgroup per tile builds the tables (C2: 125 tiles, 0.074 ms)
-        auto kern = S.zp ? k_fused_ref<InT, RT, false, true> : k_fused_ref<InT, RT>;
-        hipLaunchKernelGGL(kern, dim3(S.tiles), dim3(FUSED_REF_NT), fused_ref_lds_bytes(RT), c->stream, P);
+        return launch_kernel(c, S.zp ? k_fused_ref<InT, RT, false, true> : k_fused_ref<InT, RT>, dim3(S.tiles), dim3(FUSED_REF_NT), fused_ref_lds_bytes(RT), P);
     } else { // few tiles (a C5 shard: 59): the reference rows split over (tiles, row chunks), then one thread per gene for
         // the tables -- 0.20 -> 0.11 ms there, 0.074 -> 0.083 ms at C2, hence the switch
         HIPCHK(c, hipMemsetAsync(P.hist_all, 0, (size_t)S.nb * RT * 4, c->stream));
@@ -295,11 +273,9 @@ template <typename InT> static int fused_ovo_reference(illico_ctx *c, FusedState
         const int want_chunks = std::max(1, 768 / std::max(S.tiles, 1)); // enough workgroups for 256 CUs, few enough flushes
         P.rows_per_wg = (int)std::max<int64_t>(FUSED_REF_ROWS, (n_ref + want_chunks - 1) / want_chunks); // (kept for the passes that follow)
         const int chunks = (int)std::max<int64_t>(1, (n_ref + P.rows_per_wg - 1) / P.rows_per_wg);
-        hipLaunchKernelGGL((k_fused_ref_hist<InT, RT>), dim3(S.tiles, chunks), dim3(FUSED_NT), 0, c->stream, P);
-        launch_fused_tables_all(c, S);
+        KERNELCHK(c, k_fused_ref_hist<InT, RT>, dim3(S.tiles, chunks), dim3(FUSED_NT), 0, P);
+        return launch_fused_tables_all(c, S);
     }
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
 }
 template <typename InT> static int fused_ovo_main(illico_ctx *c, const FusedState &S) {
     constexpr int RT = FUSED_RT;
@@ -314,36 +290,25 @@ template <typename InT> static int fused_ovo_main(illico_ctx *c, const FusedStat
     if (st != 4 && (P.out_ld & 1) == 0 && aligned16(P.out_p) && aligned16(P.out_u) && aligned16(P.out_fc) && (!S.zp || aligned16(P.out_z)))
         mp |= st == 12 ? FUSED_MP_ST16WT : FUSED_MP_ST16;
     ProfScope ps(c, (mp & (FUSED_MP_ST16 | FUSED_MP_ST16WT)) ? KID_OVO_FUSED_ST16 : KID_OVO_FUSED); // (a name of its own: tests tell the forms apart)
-    if (c->max_nonref <= 255) // 8-bit running multiplicities: 34 KB of LDS per workgroup instead of 50 KB
-        hipLaunchKernelGGL((fused_ovo_main_fn<InT, RT, 8>(S.zp, mp)), S.main_grid, dim3(FUSED_NT), (fused_main_lds_bytes<RT, false, 8>()), c->stream, P);
-    else if (c->max_nonref <= 65535)
-        hipLaunchKernelGGL((fused_ovo_main_fn<InT, RT, 16>(S.zp, mp)), S.main_grid, dim3(FUSED_NT), (fused_main_lds_bytes<RT, false, 16>()), c->stream, P);
-    else { // clusters of more than 65535 cells: 32-bit multiplicities (82 KB: one workgroup per CU)
-        auto kern = fused_ovo_main_fn<InT, RT, 32>(S.zp, mp);
-        const size_t lds32 = fused_main_lds_bytes<RT, false, 32>();
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32));
-        hipLaunchKernelGGL(kern, S.main_grid, dim3(FUSED_NT), lds32, c->stream, P);
-    }
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    // 8-bit running multiplicities: 34 KB of LDS per workgroup instead of 50 KB; clusters of more than 65535 cells: 32-bit ones (82 KB:
+    // one workgroup per CU)
+    return dispatch_int<8, 16, 32>(c->max_nonref <= 255 ? 8 : c->max_nonref <= 65535 ? 16 : 32, [&](auto cb) {
+        constexpr int CB = decltype(cb)::value;
+        return launch_kernel(c, fused_ovo_main_fn<InT, RT, CB>(S.zp, mp), S.main_grid, dim3(FUSED_NT), fused_main_lds_bytes<RT, false, CB>(), P);
+    });
 }
 // is the 256-value stage left to the host?  (decided on the device, after the first pass: nothing waits for it here)
 static int wide_decide(illico_ctx *c, const FusedCall &q, const FusedState &S) {
     if (S.wide_only || q.max_gather <= 0 || c->no_wide_gather) return ILLICO_OK;
     ProfScope ps(c, KID_FUSED_REF);
-    hipLaunchKernelGGL(k_wide_decide, dim3(1), dim3(1024), 0, c->stream, (const u32 *)S.P.gene_flags, S.nb, (int)std::min<int64_t>(q.max_gather, 0x7FFFFFFF), S.skipw);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, k_wide_decide, dim3(1), dim3(1024), 0, (const u32 *)S.P.gene_flags, S.nb, (int)std::min<int64_t>(q.max_gather, 0x7FFFFFFF), S.skipw);
 }
 // A 256-value kernel as resident workgroups, per_cu of them on every CU, working through the tiles that Q.wide_tiles lists
 static int launch_resident_wide(illico_ctx *c, fused_main_fn kern, size_t lds, int per_cu, const FusedParams &Q) {
     ProfScope ps(c, KID_OVO_FUSED_WIDE);
-    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int n_cu = 256;
     hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-    hipLaunchKernelGGL(kern, dim3((unsigned)std::max(per_cu * n_cu, 1)), dim3(FUSED_NT), lds, c->stream, Q);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, kern, dim3((unsigned)std::max(per_cu * n_cu, 1)), dim3(FUSED_NT), lds, Q);
 }
 // OVO second pass, 256-value tables, over the tiles that hold genes the first pass flagged (counts of 64 .. 255: highly
 // expressed genes of real count matrices): same kernels, one workgroup per CU (130 KB of LDS), resident workgroups
@@ -352,19 +317,16 @@ static int launch_resident_wide(illico_ctx *c, fused_main_fn kern, size_t lds, i
 template <typename InT> static int fused_ovo_wide_stage(illico_ctx *c, const FusedCall &q, const FusedState &S) {
     constexpr int WRT = FUSED_WIDE_RT;
     if (c->max_nonref > 255 || c->no_fused_wide) return ILLICO_OK;
-    void *v;
+    unsigned char *v;
     int rc;
     if ((rc = wide_decide(c, q, S))) return rc;
-    if ((rc = get_scratch(c, "fused_tables_wide", ref_tables_bytes(S, WRT) + (size_t)(S.tiles + 1) * 4 + 64, &v))) return rc;
+    if ((rc = scratch(c, "fused_tables_wide", ref_tables_bytes(S, WRT) + (size_t)(S.tiles + 1) * 4 + 64, &v))) return rc;
     FusedParams Q = S.P;
     Q.wide_tiles = carve_ref_tables(Q, v, S, WRT);
     HIPCHK(c, hipMemsetAsync(Q.wide_tiles, 0, 4, c->stream));
     {
         ProfScope ps(c, KID_FUSED_REF);
-        auto kern = S.zp ? k_fused_ref<InT, WRT, true, true> : k_fused_ref<InT, WRT, true>;
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_ref_lds_bytes(WRT)));
-        hipLaunchKernelGGL(kern, dim3(S.tiles), dim3(FUSED_REF_NT), fused_ref_lds_bytes(WRT), c->stream, Q);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, S.zp ? k_fused_ref<InT, WRT, true, true> : k_fused_ref<InT, WRT, true>, dim3(S.tiles), dim3(FUSED_REF_NT), fused_ref_lds_bytes(WRT), Q);
     }
     fused_main_fn kern = S.zp ? k_ovo_fused<InT, WRT, false, 8, FUSED_U, true, true> : k_ovo_fused<InT, WRT, false, 8, FUSED_U, true>;
     return launch_resident_wide(c, kern, fused_main_lds_bytes<WRT, false, 8>(), 1, Q);
@@ -375,7 +337,6 @@ template <typename InT> static int fused_ovr_one_pass(illico_ctx *c, FusedState 
     constexpr int RT = FUSED_RT;
     FusedParams &P = S.P;
     const int tiles = S.tiles;
-    void *v;
     int rc;
     // 8-bit cells when no group is larger than 255 cells, else the width per group (0): a few large groups do not double
     // the histogram bytes of all the small ones
@@ -383,30 +344,23 @@ template <typename InT> static int fused_ovr_one_pass(illico_ctx *c, FusedState 
     const size_t hist_bytes = cbits ? (size_t)c->n_groups * tiles * (RT * cbits / 32) * 64 * 4 : (size_t)c->hist_words * tiles * 64 * 4;
     if (c->no_ovr_one_pass || c->max_nonref > 65535 || hist_bytes > (size_t)c->scratch_bytes) return ILLICO_OK; // (16-bit cells: no group beyond 65535 cells)
     *done = true;
-    if ((rc = get_scratch(c, "group_hist", hist_bytes, &v))) return rc;
-    P.group_hist = (u32 *)v;
-    if ((rc = get_scratch(c, "group_hist_words", (size_t)c->n_groups * tiles, &v))) return rc;
-    P.hist_words = (unsigned char *)v;
+    if ((rc = scratch(c, "group_hist", hist_bytes / 4, &P.group_hist))) return rc;
+    if ((rc = scratch(c, "group_hist_words", (size_t)c->n_groups * tiles, &P.hist_words))) return rc;
     P.hist_off = c->d_hist_off;
     {
         ProfScope ps(c, KID_OVR_FUSED);
-        if (cbits == 8) hipLaunchKernelGGL((k_ovr_group_hists<InT, RT, 8>), S.main_grid, dim3(FUSED_NT), 0, c->stream, P);
-        else hipLaunchKernelGGL((k_ovr_group_hists<InT, RT, 0>), S.main_grid, dim3(FUSED_NT), 0, c->stream, P);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, cbits == 8 ? k_ovr_group_hists<InT, RT, 8> : k_ovr_group_hists<InT, RT, 0>, S.main_grid, dim3(FUSED_NT), 0, P);
     }
     ProfScope ps(c, KID_FUSED_REF);
-    launch_fused_tables_all(c, S);
+    if ((rc = launch_fused_tables_all(c, S))) return rc;
     // the rank-sum kernel keeps a 64-entry table per lane in registers: more groups per workgroup amortise its fill
     FusedParams P2 = P;
     P2.groups_per_wg = c->ovr_hist_groups_per_wg > 0 ? c->ovr_hist_groups_per_wg : 32;
     while (P2.groups_per_wg > 8 && (int64_t)tiles * ((c->n_groups + P2.groups_per_wg - 1) / P2.groups_per_wg) < 2048) P2.groups_per_wg >>= 1;
     const dim3 grid2(tiles, ((int)c->n_groups + P2.groups_per_wg - 1) / P2.groups_per_wg);
-    const bool np3 = c->n_cells < (1ll << 23), zp = S.zp; // s < 2^24: three byte planes
-    auto k_from = cbits == 8 ? (np3 ? (zp ? k_ovr_from_hists<RT, 8, 3, true> : k_ovr_from_hists<RT, 8, 3>) : (zp ? k_ovr_from_hists<RT, 8, 4, true> : k_ovr_from_hists<RT, 8, 4>))
-                             : (np3 ? (zp ? k_ovr_from_hists<RT, 0, 3, true> : k_ovr_from_hists<RT, 0, 3>) : (zp ? k_ovr_from_hists<RT, 0, 4, true> : k_ovr_from_hists<RT, 0, 4>));
-    hipLaunchKernelGGL(k_from, grid2, dim3(FUSED_NT), 0, c->stream, P2);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return dispatch_flags([&](auto cells8, auto np3, auto zp) { // (np3: s < 2^24, three byte planes)
+        return launch_kernel(c, k_ovr_from_hists<RT, decltype(cells8)::value ? 8 : 0, decltype(np3)::value ? 3 : 4, decltype(zp)::value>, grid2, dim3(FUSED_NT), 0, P2);
+    }, cbits == 8, c->n_cells < (1ll << 23), S.zp);
 }
 // OVR, two passes over X: the column histograms and their tables, then k_ovo_fused<OVR>
 template <typename InT> static int fused_ovr_two_pass(illico_ctx *c, const FusedState &S) {
@@ -415,15 +369,13 @@ template <typename InT> static int fused_ovr_two_pass(illico_ctx *c, const Fused
     {
         ProfScope ps(c, KID_FUSED_REF);
         const int chunks = (int)((c->n_cells + P.rows_per_wg - 1) / P.rows_per_wg);
-        hipLaunchKernelGGL((k_fused_hist_all<InT, RT>), dim3(S.tiles, chunks), dim3(FUSED_NT), fused_ref_lds_bytes(RT), c->stream, P);
-        launch_fused_tables_all(c, S);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_fused_hist_all<InT, RT>, dim3(S.tiles, chunks), dim3(FUSED_NT), fused_ref_lds_bytes(RT), P);
+        int rc = launch_fused_tables_all(c, S);
+        if (rc) return rc;
     }
     ProfScope ps(c, KID_OVR_FUSED);
-    hipLaunchKernelGGL((S.zp ? k_ovo_fused<InT, RT, true, 16, FUSED_U, false, true> : k_ovo_fused<InT, RT, true, 16>), S.main_grid, dim3(FUSED_NT),
-                       (fused_main_lds_bytes<RT, true, 16>()), c->stream, P);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, S.zp ? k_ovo_fused<InT, RT, true, 16, FUSED_U, false, true> : k_ovo_fused<InT, RT, true, 16>, S.main_grid, dim3(FUSED_NT),
+                         fused_main_lds_bytes<RT, true, 16>(), P);
 }
 template <typename InT> static int fused_ovr_first_pass(illico_ctx *c, FusedState &S) {
     int rc;
@@ -440,10 +392,10 @@ template <typename InT> static int fused_ovr_wide_stage(illico_ctx *c, const Fus
     constexpr int WRT = FUSED_WIDE_RT;
     if (c->no_fused_wide) return ILLICO_OK;
     const int nb = S.nb, tiles = S.tiles;
-    void *v;
+    unsigned char *v;
     int rc;
     if ((rc = wide_decide(c, q, S))) return rc;
-    if ((rc = get_scratch(c, "fused_tables_wide", ref_tables_bytes(S, WRT) + (size_t)nb * WRT * 4 + (size_t)(nb + tiles) * 4 + (size_t)(tiles + 1) * 4 + 64, &v))) return rc;
+    if ((rc = scratch(c, "fused_tables_wide", ref_tables_bytes(S, WRT) + (size_t)nb * WRT * 4 + (size_t)(nb + tiles) * 4 + (size_t)(tiles + 1) * 4 + 64, &v))) return rc;
     FusedParams Q = S.P;
     Q.hist_all = carve_ref_tables(Q, v, S, WRT);
     Q.wide_bad = Q.hist_all + (size_t)nb * WRT;          // [nb] + [tiles] tile marks
@@ -452,11 +404,8 @@ template <typename InT> static int fused_ovr_wide_stage(illico_ctx *c, const Fus
     {
         ProfScope ps(c, KID_FUSED_REF);
         const int chunks = (int)((c->n_cells + S.P.rows_per_wg - 1) / S.P.rows_per_wg);
-        auto kh = k_fused_hist_all<InT, WRT, true>;
-        HIPCHK(c, hipFuncSetAttribute((const void *)kh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_ref_lds_bytes(WRT)));
-        hipLaunchKernelGGL(kh, dim3(tiles, chunks), dim3(FUSED_NT), fused_ref_lds_bytes(WRT), c->stream, Q);
-        hipLaunchKernelGGL((k_fused_tables_all<WRT, true>), dim3((nb + 255) / 256), dim3(256), 0, c->stream, Q);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_fused_hist_all<InT, WRT, true>, dim3(tiles, chunks), dim3(FUSED_NT), fused_ref_lds_bytes(WRT), Q);
+        KERNELCHK(c, k_fused_tables_all<WRT, true>, dim3((nb + 255) / 256), dim3(256), 0, Q);
     }
     fused_main_fn kern = S.zp ? k_ovo_fused<InT, WRT, true, 16, FUSED_U, true, true> : k_ovo_fused<InT, WRT, true, 16, FUSED_U, true>;
     return launch_resident_wide(c, kern, fused_main_lds_bytes<WRT, true, 16>(), 2, Q);
@@ -541,14 +490,14 @@ template <typename InT> struct OwnTypeWindows { // windows in the matrix's own t
     // so that no window travels twice
     int prepare(illico_ctx *c, HostStage *hs, int64_t N, int64_t W) {
         int rc;
-        void *v;
         left.cap = c->no_leftover_gather ? 0 : std::min<int64_t>((W / 4 + 63) & ~63ll, (int64_t)((size_t)c->scratch_bytes / 4 / ((size_t)N * sizeof(InT))) & ~63ll);
         if (left.cap < 64) { left.cap = 0; return ILLICO_OK; }
-        if ((rc = get_scratch(c, "xleft", (size_t)N * (size_t)left.cap * sizeof(InT), &v))) return rc;
-        left.xl = v;
+        InT *xl;
+        if ((rc = scratch(c, "xleft", (size_t)N * (size_t)left.cap, &xl))) return rc;
+        left.xl = xl;
         HIPCHK(c, hipMemsetAsync(left.xl, 0, (size_t)N * (size_t)left.cap * sizeof(InT), c->stream));
-        if ((rc = get_scratch(c, "xleft_cols", (size_t)left.cap * 8, &v))) return rc;
-        d_src = (int *)v; left.d_dst = d_src + left.cap;
+        if ((rc = scratch(c, "xleft_cols", (size_t)left.cap * 2, &d_src))) return rc;
+        left.d_dst = d_src + left.cap;
         if (hs->lists_ints < (size_t)left.cap * 2) {
             if (hs->lists) hipHostFree(hs->lists);
             hs->lists = nullptr; hs->lists_ints = 0;
@@ -573,9 +522,8 @@ template <typename InT> struct OwnTypeWindows { // windows in the matrix's own t
             rc = fail(c, ILLICO_ERR_HIP, "uploading a column list failed");
         if (!rc) {
             ProfScope ps(c, KID_GATHER_COLS);
-            hipLaunchKernelGGL((k_gather_columns<InT>), dim3((unsigned)((N + 63) / 64)), dim3(256), 0, c->stream, win, (long long)wn,
-                               (int)N, (const int *)(d_src + left.n), cnt, cnt, (InT *)left.xl, (long long)left.cap, (long long)left.n);
-            if (hipGetLastError() != hipSuccess) rc = fail(c, ILLICO_ERR_HIP, "k_gather_columns launch failed");
+            rc = launch_kernel(c, k_gather_columns<InT>, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, win, (long long)wn, (int)N, (const int *)(d_src + left.n), cnt, cnt,
+                               (InT *)left.xl, (long long)left.cap, (long long)left.n);
         }
         left.n += cnt;
         return rc;
@@ -679,7 +627,6 @@ template <typename InT, typename Pol> static int host_windows_pipeline(illico_ct
                                  const OutPlanes &o, std::vector<std::pair<int64_t, int64_t>> &runs, Pol &pol) {
     typedef typename Pol::Cell Cell;
     int rc;
-    void *v;
     // windows of ~256 MB (a multiple of 64 genes): long enough for the link's rate, short enough that the first pass starts early
     // (wmax is a multiple of 64 unless "gene_batch" says otherwise: every window's row pitch fits its slot)
     int64_t wmax = std::max<int64_t>(64, (int64_t)(((size_t)256 << 20) / ((size_t)N * sizeof(Cell))) & ~63ll);
@@ -690,10 +637,8 @@ template <typename InT, typename Pol> static int host_windows_pipeline(illico_ct
     if ((rc = prepare_host_stage(c, hs, slot_bytes)) || (rc = pol.prepare(c, hs, N, col_ub - col_lb))) return rc;
     Cell *dev[HS_SLOTS];
     static const char *names[HS_SLOTS] = {"xin0", "xin1", "xin2"};
-    for (int j = 0; j < HS_SLOTS; ++j) {
-        if ((rc = get_scratch(c, names[j], slot_bytes, &v))) return rc;
-        dev[j] = (Cell *)v;
-    }
+    for (int j = 0; j < HS_SLOTS; ++j)
+        if ((rc = scratch(c, names[j], (size_t)wmax * (size_t)N, &dev[j]))) return rc;
     HostWindowQueue Q;
     Q.N = N; Q.col_lb = col_lb; Q.col_ub = col_ub; Q.wmax = wmax; Q.n_win = (col_ub - col_lb + wmax - 1) / wmax;
     const int x_node = c->no_host_numa ? -1 : numa_node_of_buffer(X, (size_t)N * (size_t)ld * sizeof(InT));
@@ -750,11 +695,9 @@ template <typename InT> static int gather_columns_narrow(illico_ctx *c, const vo
                                  const char *x_name, const char *list_name, InT **xl, int **d_dst = nullptr) {
     const int64_t n = (int64_t)src.size(), n_pad = (n + 63) & ~63ll;
     int rc;
-    void *v;
-    if ((rc = get_scratch(c, x_name, (size_t)N * (size_t)n_pad * sizeof(InT), &v))) return rc;
-    *xl = (InT *)v;
-    if ((rc = get_scratch(c, list_name, (size_t)n * (dst ? 8 : 4), &v))) return rc;
-    int *d_src = (int *)v;
+    int *d_src;
+    if ((rc = scratch(c, x_name, (size_t)N * (size_t)n_pad, xl))) return rc;
+    if ((rc = scratch(c, list_name, (size_t)n * (dst ? 2 : 1), &d_src))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_src, src.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     if (dst) {
         *d_dst = d_src + n;
@@ -762,9 +705,8 @@ template <typename InT> static int gather_columns_narrow(illico_ctx *c, const vo
     }
     {
         ProfScope ps(c, KID_GATHER_COLS);
-        hipLaunchKernelGGL((k_gather_columns<InT>), dim3((unsigned)((N + 63) / 64)), dim3(256), 0, c->stream, (const InT *)X, (long long)ld, (int)N,
-                           (const int *)d_src, (int)n, (int)n_pad, *xl, (long long)n_pad, 0ll);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_gather_columns<InT>, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, (const InT *)X, (long long)ld, (int)N, (const int *)d_src, (int)n, (int)n_pad,
+                  *xl, (long long)n_pad, 0ll);
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ILLICO_OK;
@@ -778,9 +720,8 @@ template <typename InT, typename KeyT> static int leftovers_on_narrow(illico_ctx
                                const std::vector<u32> &init, const std::vector<int> &dst, bool wide_skipped, bool is_outer) {
     const int G = (int)c->n_groups;
     int rc;
-    void *v;
-    if ((rc = get_scratch(c, is_outer ? "xleft2_cols" : "xleft_cols", (size_t)n * 8, &v))) return rc;
-    int *d_dst = (int *)v;
+    int *d_dst;
+    if ((rc = scratch(c, is_outer ? "xleft2_cols" : "xleft_cols", (size_t)n * 2, &d_dst))) return rc;
     u32 *d_flags2 = (u32 *)(d_dst + n);
     HIPCHK(c, hipMemcpyAsync(d_dst, dst.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host list may go out of scope)
@@ -790,19 +731,18 @@ template <typename InT, typename KeyT> static int leftovers_on_narrow(illico_ctx
         bool any = false;
         for (int64_t j = 0; j < n; ++j) any = any || init[j] == 1u;
         if (any) {
-            if ((rc = get_scratch(c, "wide_tmp", (size_t)(o.z ? 4 : 3) * G * (size_t)n_pad * 8, &v))) return rc;
-            double *tp = (double *)v;
+            double *tp;
+            if ((rc = scratch(c, "wide_tmp", (size_t)(o.z ? 4 : 3) * G * (size_t)n_pad, &tp))) return rc;
             const OutPlanes ot{tp, tp + (size_t)G * n_pad, tp + (size_t)2 * G * n_pad, n_pad, false, o.z ? tp + (size_t)3 * G * n_pad : nullptr};
             if ((rc = run_fused_ovo<InT>(c, {xl, n_pad, 0, (int)n, lflags, alternative, ot, 0, -1, false, 0, init.data()}, hf2))) return rc;
             HIPCHK(c, hipMemcpyAsync(d_flags2, hf2.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
             {
                 ProfScope ps(c, KID_GATHER_COLS);
                 const dim3 grid((unsigned)((n + 255) / 256), (unsigned)std::min(G, 1024));
-                hipLaunchKernelGGL(k_scatter_planes, grid, dim3(256), 0, c->stream, (const double *)ot.p, (const double *)ot.u, (const double *)ot.fc, (long long)n_pad,
-                                   (const int *)d_dst, (const u32 *)d_flags2, 2u, (int)n, G, o.p, o.u, o.fc, (long long)o.ld);
-                if (o.z) hipLaunchKernelGGL(k_scatter_plane, grid, dim3(256), 0, c->stream, (const double *)ot.z, (long long)n_pad, (const int *)d_dst,
-                                            (const u32 *)d_flags2, 2u, (int)n, G, o.z, (long long)o.ld);
-                HIPCHK(c, hipGetLastError());
+                KERNELCHK(c, k_scatter_planes, grid, dim3(256), 0, (const double *)ot.p, (const double *)ot.u, (const double *)ot.fc, (long long)n_pad, (const int *)d_dst,
+                          (const u32 *)d_flags2, 2u, (int)n, G, o.p, o.u, o.fc, (long long)o.ld);
+                if (o.z) KERNELCHK(c, k_scatter_plane, grid, dim3(256), 0, (const double *)ot.z, (long long)n_pad, (const int *)d_dst, (const u32 *)d_flags2, 2u, (int)n, G,
+                                   o.z, (long long)o.ld);
             }
             HIPCHK(c, hipStreamSynchronize(c->stream));
             std::vector<u32> hf3((size_t)n);
@@ -823,7 +763,6 @@ template <typename InT, typename KeyT> int run_leftovers(illico_ctx *c, const vo
                   const OutPlanes &o, const u32 *hf, bool wide_skipped, const int *outer) {
     const int64_t W = col_ub - col_lb;
     int rc;
-    void *v;
     std::vector<int> src, dst;
     for (int64_t j = 0; j < W; ++j)
         if (hf[j] == 1u || hf[j] == 3u) { src.push_back((int)(col_lb + j)); dst.push_back(outer ? outer[j] : (int)j); }
@@ -838,11 +777,12 @@ template <typename InT, typename KeyT> int run_leftovers(illico_ctx *c, const vo
             for (int64_t j = 0; j < W; ++j) merged[j] = ((hf[j] == 1u || hf[j] == 3u) && hf2[j] != 2u) ? 1u : 0u;
         }
         if (outer) { // a narrow matrix whose leftovers cannot be gathered again: all of it as one window, through the map
-            if ((rc = get_scratch(c, "xleft_outer", (size_t)W * 4, &v))) return rc;
+            int *v;
+            if ((rc = scratch(c, "xleft_outer", (size_t)W, &v))) return rc;
             HIPCHK(c, hipMemcpyAsync(v, outer, (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             std::vector<std::pair<int64_t, int64_t>> all{{col_lb, col_ub}};
-            return run_dense_twopass<InT, KeyT>(c, X, dtype, N, ld, col_lb, col_ub, flags, alternative, o, all, (const int *)v, true);
+            return run_dense_twopass<InT, KeyT>(c, X, dtype, N, ld, col_lb, col_ub, flags, alternative, o, all, v, true);
         }
         std::vector<std::pair<int64_t, int64_t>> runs;
         flagged_runs(merged.data(), W, col_lb, runs);
@@ -990,28 +930,19 @@ template <typename InT, typename KeyT> static int plan_twopass(TwoPassPlan<InT, 
     if (nb_max > 64) nb_max &= ~63ll;
     p.nb_max = nb_max = std::max<int64_t>(nb_max, 1);
     int rc;
-    void *v;
-    if ((rc = get_scratch(c, "xt", (size_t)nb_max * p.stride * sizeof(KeyT), &v))) return rc;
-    p.Xt = (KeyT *)v;
+    if ((rc = scratch(c, "xt", (size_t)nb_max * p.stride, &p.Xt))) return rc;
     if ((rc = carve_stats(c, nb_max, G, false, &p.st))) return rc;
     p.gflags = nullptr;
-    if ((counts_path_allowed(c, p.flags) && !p.packed && !ovr) || p.ovr_counts) {
-        if ((rc = get_scratch(c, "gene_flags", (size_t)nb_max * 4, &v))) return rc;
-        p.gflags = (u32 *)v;
-    }
+    if (((counts_path_allowed(c, p.flags) && !p.packed && !ovr) || p.ovr_counts) && (rc = scratch(c, "gene_flags", (size_t)nb_max, &p.gflags))) return rc;
     if (need_glob) {
-        if ((rc = get_scratch(c, "ovr_kb", (size_t)nb_max * p.stride * sizeof(KeyT), &v))) return rc;
-        p.gb.kb = v;
-        if ((rc = get_scratch(c, "ovr_va", (size_t)nb_max * p.stride * 4, &v))) return rc;
-        p.gb.va = (u32 *)v;
-        if ((rc = get_scratch(c, "ovr_vb", (size_t)nb_max * p.stride * 4, &v))) return rc;
-        p.gb.vb = (u32 *)v;
+        KeyT *kb;
+        if ((rc = scratch(c, "ovr_kb", (size_t)nb_max * p.stride, &kb))) return rc;
+        p.gb.kb = kb;
+        if ((rc = scratch(c, "ovr_va", (size_t)nb_max * p.stride, &p.gb.va))) return rc;
+        if ((rc = scratch(c, "ovr_vb", (size_t)nb_max * p.stride, &p.gb.vb))) return rc;
     }
     p.xin = nullptr;
-    if (!p.in_dev) {
-        if ((rc = get_scratch(c, "xin", (size_t)nb_max * N * sizeof(InT), &v))) return rc;
-        p.xin = (InT *)v;
-    }
+    if (!p.in_dev && (rc = scratch(c, "xin", (size_t)nb_max * N, &p.xin))) return rc;
     return ILLICO_OK;
 }
 // host input: the batch's columns go up into xin
@@ -1083,10 +1014,7 @@ template <typename InT, typename KeyT> static int twopass_ovr_counts_batch(const
         Q.Xt = p.Xt; Q.stride = stride; Q.pos_ptr = c->d_posptr; Q.counts = c->d_counts; Q.G = G; Q.n_genes = nb; Q.dt = p.dtype; Q.n_cells = p.N;
         Q.gene_flags = p.gflags; Q.out_2u = st.s2u; Q.out_tie = st.stie; Q.out_sum = st.ssum; Q.gene_total = st.gtot;
         ProfScope ps(c, KID_OVR_COUNTS);
-        auto kern = k_ovr_counts<KeyT>;
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, OVRC_R * 4));
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(OVRC_NT), OVRC_R * 4, c->stream, Q);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_ovr_counts<KeyT>, dim3(nb), dim3(OVRC_NT), OVRC_R * 4, Q);
     }
     std::vector<u32> hg(nb);
     HIPCHK(c, hipMemcpyAsync(hg.data(), p.gflags, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1114,7 +1042,6 @@ template <typename InT, typename KeyT> static int twopass_ovr_batch(const TwoPas
     const StatsPlanes &st = p.st;
     KeyT *Xt = p.Xt;
     int rc;
-    void *v;
     OvrPackedInput pki;
     if (p.padded) {
         GroupCompactParams Q;
@@ -1123,10 +1050,8 @@ template <typename InT, typename KeyT> static int twopass_ovr_batch(const TwoPas
         Q.blk_g0 = c->d_pk_blk; Q.blk_g1 = c->d_pk_blk + c->pk_nblk; Q.blk_out = c->d_pk_blk + 2 * c->pk_nblk; Q.nblk = c->pk_nblk;
         Q.Xt = Xt; Q.xt_stride = stride; Q.out_sum = st.ssum;
         if (p.ovr_packed) { // packed rows (non-zero keys only) for the partition; flagged genes are written again, padded, below
-            if ((rc = get_scratch(c, "packed_nnz", (size_t)nb * G * 2 + 64, &v))) return rc;
-            Q.nnz = (u16 *)v;
-            if ((rc = get_scratch(c, "packed_seg_sum", (size_t)nb * G * 4 + (size_t)nb * c->pk_nblk * 4 + 64, &v))) return rc;
-            Q.gofs = (u32 *)v;
+            if ((rc = scratch(c, "packed_nnz", (size_t)nb * G + 32, &Q.nnz))) return rc;
+            if ((rc = scratch(c, "packed_seg_sum", (size_t)nb * G + (size_t)nb * c->pk_nblk + 16, &Q.gofs))) return rc;
             Q.blk_cnt = Q.gofs + (size_t)nb * G;
             pki.nnz = Q.nnz; pki.blk_cnt = Q.blk_cnt;
             const GroupCompactParams Q0 = Q;

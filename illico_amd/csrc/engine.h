@@ -169,6 +169,48 @@ int fail(illico_ctx *c, int code, const char *fmt, ...);
     } while (0)
 
 int get_scratch(illico_ctx *c, const char *name, size_t bytes, void **out);
+// `count` elements of T from the grow-only scratch block `name`.  A block that is carved into several arrays is
+// asked for as bytes (T = unsigned char) or in units of its first array, and carved by the caller.
+template <typename T> int scratch(illico_ctx *c, const char *name, size_t count, T **out) {
+    void *v;
+    int rc = get_scratch(c, name, count * sizeof(T), &v);
+    *out = (T *)v;
+    return rc;
+}
+
+// A kernel's dynamic-LDS limit on `device` raised to `lds`, unless it has been raised that far already: the limit is the kernel's, not a
+// context's, so what has been set is kept once for the process (a context that set a smaller one later would lower it under the others).
+// The runtime call made before every launch showed in the steady per-step time of the dense OVO pass.
+inline hipError_t raise_lds_limit(int device, const void *kern, size_t lds) {
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> raised;
+    std::lock_guard<std::mutex> g(mu);
+    size_t &have = raised[{device, kern}];
+    if (lds <= have) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) have = lds;
+    return e;
+}
+// One kernel launch on the context's stream, checked where it is made: with dynamic LDS the kernel's limit is
+// raised to `lds` first.  No ProfScope: the caller places it, often around several launches.  launch_kernel(c, kern, grid, block, lds,
+// args...) returns ILLICO_OK or the code of fail(); KERNELCHK(...) returns from the calling function on failure, as HIPCHK does.
+template <typename... KArgs, typename... Args>
+int launch_kernel_at(illico_ctx *c, const char *file, int line, const char *what, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t lds, Args &&...args) {
+    hipError_t e = lds > 0 ? raise_lds_limit(c->device, (const void *)kern, lds) : hipSuccess;
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(kern, grid, block, lds, c->stream, std::forward<Args>(args)...);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) return ILLICO_OK;
+    return fail(c, e == hipErrorOutOfMemory ? ILLICO_ERR_OOM : ILLICO_ERR_HIP, "launch_kernel(%s) failed: %s (%s:%d)", what, hipGetErrorString(e), file, line);
+}
+#define launch_kernel(ctx, ...) launch_kernel_at(ctx, __FILE__, __LINE__, #__VA_ARGS__, __VA_ARGS__)
+#define KERNELCHK(ctx, ...)                                \
+    do {                                                   \
+        int rc__ = launch_kernel(ctx, __VA_ARGS__);        \
+        if (rc__) return rc__;                             \
+    } while (0)
+
 hipEvent_t take_event(illico_ctx *c);
 
 struct ProfScope {
@@ -193,23 +235,20 @@ struct ProfScope {
 
 // ---- small host idioms shared by the drivers ----
 // Ask the device up to four words.  clear_flag_words: the "flag" scratch, zeroed, on the context's stream.  device_probe: that, then
-// `launch(words)` (the caller's kernel launches), the first `n` words copied to `out` -- and the wait for them, unless `wait` is false
-// (the caller then waits itself, with further copies behind the same wait).  The scratch is shared by name: a probe's words are
-// read before the next probe is enqueued.
+// `launch(words)` (the caller's kernel launches, through launch_kernel: it returns their status), the first `n` words copied to `out`
+// -- and the wait for them, unless `wait` is false (the caller then waits itself, with further copies behind the same wait).  The
+// scratch is shared by name: a probe's words are read before the next probe is enqueued.
 static inline int clear_flag_words(illico_ctx *c, u32 **words) {
-    void *v;
-    int rc = get_scratch(c, "flag", 16, &v);
+    int rc = scratch(c, "flag", 4, words);
     if (rc) return rc;
-    HIPCHK(c, hipMemsetAsync(v, 0, 16, c->stream));
-    *words = (u32 *)v;
+    HIPCHK(c, hipMemsetAsync(*words, 0, 16, c->stream));
     return ILLICO_OK;
 }
 template <typename Launch> static int device_probe(illico_ctx *c, u32 *out, int n, Launch &&launch, bool wait = true) {
     u32 *words;
     int rc = clear_flag_words(c, &words);
     if (rc) return rc;
-    launch(words);
-    HIPCHK(c, hipGetLastError());
+    if ((rc = launch(words))) return rc;
     HIPCHK(c, hipMemcpyAsync(out, words, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     if (wait) HIPCHK(c, hipStreamSynchronize(c->stream));
     return ILLICO_OK;
@@ -241,18 +280,15 @@ static inline int64_t stats_batch_genes(int64_t n, int G) {
     return std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)((size_t)(4ll << 30) / ((size_t)G * 24 + 16))));
 }
 static inline int carve_stats(illico_ctx *c, int64_t nb, int G, bool with_flags, StatsPlanes *s) {
-    void *v;
-    int rc = get_scratch(c, "stats", (size_t)nb * G * 24 + (size_t)nb * 8, &v);
+    unsigned char *v;
+    int rc = scratch(c, "stats", (size_t)nb * G * 24 + (size_t)nb * 8, &v);
     if (rc) return rc;
     s->s2u = (long long *)v;
     s->stie = (u64 *)(s->s2u + (size_t)nb * G);
     s->ssum = (double *)(s->stie + (size_t)nb * G);
     s->gtot = s->ssum + (size_t)nb * G;
     s->flags = nullptr;
-    if (with_flags) {
-        if ((rc = get_scratch(c, "gene_flags", (size_t)nb * 4, &v))) return rc;
-        s->flags = (u32 *)v;
-    }
+    if (with_flags && (rc = scratch(c, "gene_flags", (size_t)nb, &s->flags))) return rc;
     return ILLICO_OK;
 }
 
@@ -300,6 +336,19 @@ template <typename F> int dispatch_value_type(int dt, F &&f) {
     case ILLICO_I32: return f(Tag<int32_t>{});
     default: return f(Tag<int64_t>{});
     }
+}
+// Run-time flags as template arguments: dispatch_flags(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}) -- a generic
+// lambda that reads them as `decltype(x)::value` / x.value.  dispatch_int<64, 32>(v, f): f(std::integral_constant<int, V>{}) for the
+// listed value that v equals, the last one otherwise.  f is instantiated for every combination: where a kernel exists for some of them
+// only, the lambda guards the others with `if constexpr`.
+template <typename F> int dispatch_flags(F &&f) { return f(); }
+template <typename F, typename... Bs> int dispatch_flags(F &&f, bool b, Bs... rest) {
+    return b ? dispatch_flags([&](auto... cs) { return f(std::true_type{}, cs...); }, rest...)
+             : dispatch_flags([&](auto... cs) { return f(std::false_type{}, cs...); }, rest...);
+}
+template <int V0, int... Vs, typename F> int dispatch_int(int v, F &&f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+    else return v == V0 ? f(std::integral_constant<int, V0>{}) : dispatch_int<Vs...>(v, f);
 }
 // The Wilcoxon drivers: f(Tag<InT>{}, Tag<KeyT>{}), or with an index dtype code f(Tag<InT>{}, Tag<IdxT>{}, Tag<KeyT>{}) -- for the
 // types the build holds.  A development build (ILLICO_DEV_F32_ONLY=1 python build.py: 4x faster) compiles the float32 / int32-index

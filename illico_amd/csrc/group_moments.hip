@@ -32,13 +32,11 @@ int gm_dense_window(illico_ctx *c, const InT *X, int64_t ld, int64_t N, int wn, 
         ProfScope ps(c, KID_GM_VMAX);
         const int gx = (wn + GM_NT - 1) / GM_NT;
         const int gy = (int)std::max<int64_t>(1, std::min<int64_t>((N + 63) / 64, (4096 + gx - 1) / gx));
-        hipLaunchKernelGGL(k_gm_dense_vmax<InT>, dim3(gx, gy), dim3(GM_NT), 0, c->stream, X, (long long)ld, (long long)N, wn, P.vmax, P.vmaxq, P.nonfin);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_gm_dense_vmax<InT>, dim3(gx, gy), dim3(GM_NT), 0, X, (long long)ld, (long long)N, wn, P.vmax, P.vmaxq, P.nonfin);
     }
     if (n_ch) {
         ProfScope ps(c, KID_GM_DENSE);
-        hipLaunchKernelGGL(k_gm_dense<InT>, dim3(n_ch, (wn + GM_TILE - 1) / GM_TILE), dim3(GM_NT), 0, c->stream, X, (long long)ld, wn, c->d_perm, d_ch, P);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_gm_dense<InT>, dim3(n_ch, (wn + GM_TILE - 1) / GM_TILE), dim3(GM_NT), 0, X, (long long)ld, wn, c->d_perm, d_ch, P);
     }
     return ILLICO_OK;
 }
@@ -53,27 +51,17 @@ int gm_sparse_window(illico_ctx *c, bool is_csr, const void *data, const void *i
         const size_t lds = gm_csc_lds_bytes(G, ldsg);
         ProfScope ps(c, KID_GM_CSC);
         const dim3 grid((unsigned)std::min<int64_t>(wn, 1 << 20));
-        if (ldsg) {
-            HIPCHK(c, hipFuncSetAttribute((const void *)k_gm_csc<InT, IdxT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_gm_csc<InT, IdxT, true>), grid, dim3(GM_NT), lds, c->stream, C, P);
-        } else
-            hipLaunchKernelGGL((k_gm_csc<InT, IdxT, false>), grid, dim3(GM_NT), lds, c->stream, C, P);
-        HIPCHK(c, hipGetLastError());
-        return ILLICO_OK;
+        return launch_kernel(c, ldsg ? k_gm_csc<InT, IdxT, true> : k_gm_csc<InT, IdxT, false>, grid, dim3(GM_NT), lds, C, P);
     }
     {
         ProfScope ps(c, KID_GM_VMAX);
         const int gy = (wn + GM_VMAX_CW - 1) / GM_VMAX_CW;
         const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((N + 15) / 16, (2048 + gy - 1) / gy));
-        hipLaunchKernelGGL((k_gm_csr_vmax<InT, IdxT>), dim3(gx, gy), dim3(GM_NT), 0, c->stream, (const InT *)data, (const IdxT *)indices, (const IdxT *)indptr,
-                           kshift, (long long)N, col0, wn, P.vmax, P.vmaxq, P.nonfin);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_gm_csr_vmax<InT, IdxT>, dim3(gx, gy), dim3(GM_NT), 0, (const InT *)data, (const IdxT *)indices, (const IdxT *)indptr, kshift, (long long)N, col0, wn, P.vmax, P.vmaxq, P.nonfin);
     }
     if (n_ch) {
         ProfScope ps(c, KID_GM_CSR);
-        hipLaunchKernelGGL((k_gm_csr<InT, IdxT>), dim3(n_ch, (wn + GM_CSR_CW - 1) / GM_CSR_CW), dim3(GM_NT), 0, c->stream, (const InT *)data, (const IdxT *)indices,
-                           (const IdxT *)indptr, kshift, col0, wn, c->d_perm, d_ch, P);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_gm_csr<InT, IdxT>, dim3(n_ch, (wn + GM_CSR_CW - 1) / GM_CSR_CW), dim3(GM_NT), 0, (const InT *)data, (const IdxT *)indices, (const IdxT *)indptr, kshift, col0, wn, c->d_perm, d_ch, P);
     }
     return ILLICO_OK;
 }
@@ -87,7 +75,6 @@ int gm_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
     const bool out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
     const int dt = in.dtype;
     const size_t esz = dtype_size(dt);
-    void *v = nullptr;
 
     // chunks of the groups' positions (dense, CSR)
     std::vector<GmChunk> hch;
@@ -95,8 +82,7 @@ int gm_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
     const int n_ch = (int)hch.size();
     GmChunk *d_ch = nullptr;
     if (n_ch) {
-        if ((rc = get_scratch(c, "gm_chunks", hch.size() * sizeof(GmChunk), &v))) return rc;
-        d_ch = (GmChunk *)v;
+        if ((rc = scratch(c, "gm_chunks", hch.size(), &d_ch))) return rc;
         HIPCHK(c, hipMemcpyAsync(d_ch, hch.data(), hch.size() * sizeof(GmChunk), hipMemcpyHostToDevice, c->stream));
     }
 
@@ -111,8 +97,8 @@ int gm_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
     const size_t per_col = (size_t)G * 48 + 64 + (out_dev ? 0 : (size_t)G * 8 * n_out) + ((!in.sparse && !in.on_dev) ? (size_t)N * esz : 0);
     const int64_t WW = std::max<int64_t>(1, std::min<int64_t>({W, (int64_t)((size_t)std::max<int64_t>(c->scratch_bytes, 1) / per_col), (int64_t)1 << 24}));
     const int n_part = (int)std::min<int64_t>(G, 32);
-    if ((rc = get_scratch(c, "gm_planes", (size_t)WW * per_col + (size_t)n_part * WW * sizeof(GmTotal) + 256, &v))) return rc;
-    unsigned char *base = (unsigned char *)v;
+    unsigned char *base;
+    if ((rc = scratch(c, "gm_planes", (size_t)WW * per_col + (size_t)n_part * WW * sizeof(GmTotal) + 256, &base))) return rc;
     const size_t GW = (size_t)G * WW;
     GmPlanes P;
     P.L0 = (long long *)base;
@@ -155,8 +141,7 @@ int gm_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
         const int gx = (wn + GM_NT - 1) / GM_NT;
         {
             ProfScope ps(c, KID_GM_TOTALS);
-            hipLaunchKernelGGL(k_gm_totals, dim3(gx, n_part), dim3(GM_NT), 0, c->stream, P, (int)G, wn, part);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_gm_totals, dim3(gx, n_part), dim3(GM_NT), 0, P, (int)G, wn, part);
         }
         GmOut O;
         const int64_t off = w0 - col_lb;
@@ -173,8 +158,7 @@ int gm_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
         {
             ProfScope ps(c, KID_GM_FINALIZE);
             const int gy = (int)std::max<int64_t>(1, std::min<int64_t>(G, (8192 + gx - 1) / gx));
-            hipLaunchKernelGGL(k_gm_finalize, dim3(gx, gy), dim3(GM_NT), 0, c->stream, P, (int)G, wn, part, n_part, O);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_gm_finalize, dim3(gx, gy), dim3(GM_NT), 0, P, (int)G, wn, part, n_part, O);
         }
         if (!out_dev) {
             for (int k = 0; k < 4; ++k)
@@ -252,11 +236,7 @@ extern "C" int illico_ttest_from_moments(illico_ctx *c, const double *sum, const
     const size_t per_col = (in_dev ? 0 : (size_t)G * 8 * n_in) + (out_dev ? 0 : (size_t)G * 8 * n_out);
     const int64_t WW = per_col ? std::max<int64_t>(1, std::min<int64_t>(W, (int64_t)((size_t)std::max<int64_t>(c->scratch_bytes, 1) / per_col))) : W;
     unsigned char *stage = nullptr;
-    if (per_col) {
-        void *v = nullptr;
-        if ((rc = get_scratch(c, "tt_stage", (size_t)WW * per_col + 64, &v))) return rc;
-        stage = (unsigned char *)v;
-    }
+    if (per_col && (rc = scratch(c, "tt_stage", (size_t)WW * per_col + 64, &stage))) return rc;
     for (int64_t w0 = 0; w0 < W; w0 += WW) {
         const int wn = (int)std::min<int64_t>(WW, W - w0);
         TtParams T;
@@ -286,8 +266,7 @@ extern "C" int illico_ttest_from_moments(illico_ctx *c, const double *sum, const
         {
             ProfScope ps(c, KID_TTEST);
             const int gx = (wn + TT_NT - 1) / TT_NT;
-            hipLaunchKernelGGL(k_ttest_from_moments, dim3(gx, (unsigned)std::min<int64_t>(G, 65535)), dim3(TT_NT), 0, c->stream, T);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_ttest_from_moments, dim3(gx, (unsigned)std::min<int64_t>(G, 65535)), dim3(TT_NT), 0, T);
         }
         if (!out_dev) {
             for (int k = 0; k < TT_N_OUT; ++k)
@@ -311,9 +290,8 @@ extern "C" int illico_student_t_pvalues(illico_ctx *c, const double *t, const do
     const int64_t chunk = (int64_t)1 << 24;
     double *dt_ = nullptr, *ddf = nullptr, *dp = nullptr;
     if (!in_dev || !out_dev) {
-        void *v = nullptr;
-        if ((rc = get_scratch(c, "tt_stage", (size_t)std::min(n, chunk) * 24 + 64, &v))) return rc;
-        dt_ = (double *)v; ddf = dt_ + std::min(n, chunk); dp = ddf + std::min(n, chunk);
+        if ((rc = scratch(c, "tt_stage", (size_t)std::min(n, chunk) * 3 + 8, &dt_))) return rc;
+        ddf = dt_ + std::min(n, chunk); dp = ddf + std::min(n, chunk);
     }
     for (int64_t i0 = 0; i0 < n; i0 += chunk) {
         const int64_t m = std::min(chunk, n - i0);
@@ -327,8 +305,7 @@ extern "C" int illico_student_t_pvalues(illico_ctx *c, const double *t, const do
         if (!out_dev) kp = dp;
         {
             ProfScope ps(c, KID_TTEST);
-            hipLaunchKernelGGL(k_student_t_pvalues, dim3((unsigned)((m + TT_NT - 1) / TT_NT)), dim3(TT_NT), 0, c->stream, kt, kd, (long long)m, alternative, kp);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_student_t_pvalues, dim3((unsigned)((m + TT_NT - 1) / TT_NT)), dim3(TT_NT), 0, kt, kd, (long long)m, alternative, kp);
         }
         if (!out_dev) HIPCHK(c, hipMemcpyAsync(out_p + i0, dp, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
         if (!in_dev || !out_dev) HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -72,10 +72,9 @@ inline int stage_sparse_input(illico_ctx *c, const MatrixInput &in, int64_t col_
     const int64_t k0 = idx_at(in.indptr, in.idx_dtype, a), k1 = idx_at(in.indptr, in.idx_dtype, b);
     if (k0 < 0 || k1 < k0) return fail(c, ILLICO_ERR_ARG, "indptr is not non-decreasing");
     const size_t nnz = (size_t)(k1 - k0), nptr = (size_t)(b - a + 1);
-    void *v = nullptr;
-    int rc = get_scratch(c, scratch_name, std::max<size_t>(nnz, 1) * (esz + isz) + nptr * isz + 64, &v);
+    unsigned char *u;
+    int rc = scratch(c, scratch_name, std::max<size_t>(nnz, 1) * (esz + isz) + nptr * isz + 64, &u);
     if (rc) return rc;
-    unsigned char *u = (unsigned char *)v;
     void *dd = u, *di = u + ((nnz * esz + 15) & ~(size_t)15), *dp = (unsigned char *)di + ((nnz * isz + 15) & ~(size_t)15);
     HIPCHK(c, hipMemcpyAsync(dd, (const unsigned char *)in.data + (size_t)k0 * esz, nnz * esz, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(di, (const unsigned char *)in.indices + (size_t)k0 * isz, nnz * isz, hipMemcpyHostToDevice, c->stream));

@@ -29,13 +29,11 @@ int gs_dense_window(illico_ctx *c, const InT *X, int64_t ld, int64_t N, int wn, 
         ProfScope ps(c, KID_GS_VMAX);
         const int gx = (wn + GS_NT - 1) / GS_NT;
         const int gy = (int)std::max<int64_t>(1, std::min<int64_t>((N + 63) / 64, (4096 + gx - 1) / gx));
-        hipLaunchKernelGGL(k_gs_dense_vmax<InT>, dim3(gx, gy), dim3(GS_NT), 0, c->stream, X, (long long)ld, (long long)N, wn, dt, log1p, P.vmax, P.nonfin);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_gs_dense_vmax<InT>, dim3(gx, gy), dim3(GS_NT), 0, X, (long long)ld, (long long)N, wn, dt, log1p, P.vmax, P.nonfin);
     }
     if (n_ch) {
         ProfScope ps(c, KID_GS_DENSE);
-        hipLaunchKernelGGL(k_gs_dense<InT>, dim3(n_ch, (wn + GS_TILE - 1) / GS_TILE), dim3(GS_NT), 0, c->stream, X, (long long)ld, wn, c->d_perm, d_ch, dt, log1p, P);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_gs_dense<InT>, dim3(n_ch, (wn + GS_TILE - 1) / GS_TILE), dim3(GS_NT), 0, X, (long long)ld, wn, c->d_perm, d_ch, dt, log1p, P);
     }
     return ILLICO_OK;
 }
@@ -50,27 +48,17 @@ int gs_sparse_window(illico_ctx *c, bool is_csr, const void *data, const void *i
         const size_t lds = gs_csc_lds_bytes(G, ldsg);
         ProfScope ps(c, KID_GS_CSC);
         const dim3 grid((unsigned)std::min<int64_t>(wn, 1 << 20));
-        if (ldsg) {
-            HIPCHK(c, hipFuncSetAttribute((const void *)k_gs_csc<InT, IdxT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_gs_csc<InT, IdxT, true>), grid, dim3(GS_NT), lds, c->stream, C, P);
-        } else
-            hipLaunchKernelGGL((k_gs_csc<InT, IdxT, false>), grid, dim3(GS_NT), lds, c->stream, C, P);
-        HIPCHK(c, hipGetLastError());
-        return ILLICO_OK;
+        return launch_kernel(c, ldsg ? k_gs_csc<InT, IdxT, true> : k_gs_csc<InT, IdxT, false>, grid, dim3(GS_NT), lds, C, P);
     }
     {
         ProfScope ps(c, KID_GS_VMAX);
         const int gy = (wn + GS_VMAX_CW - 1) / GS_VMAX_CW;
         const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((N + 15) / 16, (2048 + gy - 1) / gy));
-        hipLaunchKernelGGL((k_gs_csr_vmax<InT, IdxT>), dim3(gx, gy), dim3(GS_NT), 0, c->stream, (const InT *)data, (const IdxT *)indices, (const IdxT *)indptr,
-                           kshift, (long long)N, col0, wn, dt, log1p, P.vmax, P.nonfin);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_gs_csr_vmax<InT, IdxT>, dim3(gx, gy), dim3(GS_NT), 0, (const InT *)data, (const IdxT *)indices, (const IdxT *)indptr, kshift, (long long)N, col0, wn, dt, log1p, P.vmax, P.nonfin);
     }
     if (n_ch) {
         ProfScope ps(c, KID_GS_CSR);
-        hipLaunchKernelGGL((k_gs_csr<InT, IdxT>), dim3(n_ch, (wn + GS_CSR_CW - 1) / GS_CSR_CW), dim3(GS_NT), 0, c->stream, (const InT *)data, (const IdxT *)indices,
-                           (const IdxT *)indptr, kshift, col0, wn, c->d_perm, d_ch, dt, log1p, P);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_gs_csr<InT, IdxT>, dim3(n_ch, (wn + GS_CSR_CW - 1) / GS_CSR_CW), dim3(GS_NT), 0, (const InT *)data, (const IdxT *)indices, (const IdxT *)indptr, kshift, col0, wn, c->d_perm, d_ch, dt, log1p, P);
     }
     return ILLICO_OK;
 }
@@ -84,7 +72,6 @@ int gs_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
     const bool out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
     const int log1p = (flags & ILLICO_FLAG_LOG1P) ? 1 : 0, dt = in.dtype;
     const size_t esz = dtype_size(dt);
-    void *v = nullptr;
 
     // chunks of the groups' positions (dense, CSR)
     std::vector<GsChunk> hch;
@@ -92,8 +79,7 @@ int gs_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
     const int n_ch = (int)hch.size();
     GsChunk *d_ch = nullptr;
     if (n_ch) {
-        if ((rc = get_scratch(c, "gs_chunks", hch.size() * sizeof(GsChunk), &v))) return rc;
-        d_ch = (GsChunk *)v;
+        if ((rc = scratch(c, "gs_chunks", hch.size(), &d_ch))) return rc;
         HIPCHK(c, hipMemcpyAsync(d_ch, hch.data(), hch.size() * sizeof(GsChunk), hipMemcpyHostToDevice, c->stream));
     }
 
@@ -106,8 +92,8 @@ int gs_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
     const size_t per_col = (size_t)G * 32 + 64 + (out_dev ? 0 : (size_t)G * 8 * n_out) + ((!in.sparse && !in.on_dev) ? (size_t)N * esz : 0);
     const int64_t WW = std::max<int64_t>(1, std::min<int64_t>({W, (int64_t)((size_t)std::max<int64_t>(c->scratch_bytes, 1) / per_col), (int64_t)1 << 24}));
     const int n_part = (int)std::min<int64_t>(G, 32);
-    if ((rc = get_scratch(c, "gs_planes", (size_t)WW * per_col + (size_t)n_part * WW * sizeof(GsTotal) + 256, &v))) return rc;
-    unsigned char *base = (unsigned char *)v;
+    unsigned char *base;
+    if ((rc = scratch(c, "gs_planes", (size_t)WW * per_col + (size_t)n_part * WW * sizeof(GsTotal) + 256, &base))) return rc;
     GsPlanes P;
     P.L0 = (long long *)base;
     P.L1 = P.L0 + (size_t)G * WW;
@@ -157,8 +143,7 @@ int gs_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
         const int gx = (wn + GS_NT - 1) / GS_NT;
         {
             ProfScope ps(c, KID_GS_TOTALS);
-            hipLaunchKernelGGL(k_gs_totals, dim3(gx, n_part), dim3(GS_NT), 0, c->stream, P, (int)G, wn, part);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_gs_totals, dim3(gx, n_part), dim3(GS_NT), 0, P, (int)G, wn, part);
         }
         GsOut O;
         const int64_t off = w0 - col_lb;
@@ -175,8 +160,7 @@ int gs_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
         {
             ProfScope ps(c, KID_GS_FINALIZE);
             const int gy = (int)std::max<int64_t>(1, std::min<int64_t>(G, (8192 + gx - 1) / gx));
-            hipLaunchKernelGGL(k_gs_finalize, dim3(gx, gy), dim3(GS_NT), 0, c->stream, P, (int)G, wn, part, n_part, O);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_gs_finalize, dim3(gx, gy), dim3(GS_NT), 0, P, (int)G, wn, part, n_part, O);
         }
         if (!out_dev) {
             auto down = [&](void *dst, const void *src) { return dst ? planes_to_host(c, (unsigned char *)dst + (size_t)off * 8, o.ld, src, G, wn) : ILLICO_OK; };

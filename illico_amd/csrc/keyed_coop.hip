@@ -4,11 +4,7 @@
 
 template <typename KeyT>
 int launch_ovr_partition_packed_coop(illico_ctx *c, const OvrPartPackedParams &Q, int nb) {
-    auto kern = k_ovr_partition_packed<KeyT, true>;
-    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ovrp_lds_bytes()));
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(OVRP_NT), ovrp_lds_bytes(), c->stream, Q);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, k_ovr_partition_packed<KeyT, true>, dim3(nb), dim3(OVRP_NT), ovrp_lds_bytes(), Q);
 }
 template int launch_ovr_partition_packed_coop<u32>(illico_ctx *, const OvrPartPackedParams &, int);
 #ifndef ILLICO_DEV_F32_ONLY

@@ -83,23 +83,12 @@ static int launch_bucket_big_runs(illico_ctx *c, void *Xs, void *tmp, long long 
     // runs up to 8192 keys: 256 threads each; longer ones (they take the LDS of half a CU and more): 1024 threads, a launch of their own
     // (10 groups of 30 000 cells half non-zero: 6.9 -> 5.6 ms; at 1024 threads, runs of 3000 keys took 9.1 instead of 8.2)
     const int cap_a = c->no_big_runs_wide ? cap : std::min(cap, 8192);
-    {
-        auto kern = k_bucket_big_runs<KeyT, SRT_NT>;
-        const size_t lds = srt_lds_bytes(sizeof(KeyT), cap_a);
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(gx, nb), dim3(SRT_NT), lds, c->stream, Xs, stride, nnz, gofs, (const int *)c->d_pk_big, c->pk_nbig, G, cap_a, big_fn, route,
-                           (global || cap > cap_a) ? 1 : 0, 64 * OCR_KMAX, run_cuts);
-        HIPCHK(c, hipGetLastError());
-    }
-    if (cap > cap_a) {
-        auto kern = k_bucket_big_runs<KeyT, 1024>;
-        const size_t lds = srt_lds_bytes(sizeof(KeyT), cap);
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(gx, nb), dim3(1024), lds, c->stream, Xs, stride, nnz, gofs, (const int *)c->d_pk_big, c->pk_nbig, G, cap, big_fn, route, global ? 1 : 0, cap_a, run_cuts);
-        HIPCHK(c, hipGetLastError());
-    }
+    KERNELCHK(c, k_bucket_big_runs<KeyT, SRT_NT>, dim3(gx, nb), dim3(SRT_NT), srt_lds_bytes(sizeof(KeyT), cap_a), Xs, stride, nnz, gofs, (const int *)c->d_pk_big,
+              c->pk_nbig, G, cap_a, big_fn, route, (global || cap > cap_a) ? 1 : 0, 64 * OCR_KMAX, run_cuts);
+    if (cap > cap_a)
+        KERNELCHK(c, k_bucket_big_runs<KeyT, 1024>, dim3(gx, nb), dim3(1024), srt_lds_bytes(sizeof(KeyT), cap), Xs, stride, nnz, gofs, (const int *)c->d_pk_big,
+                  c->pk_nbig, G, cap, big_fn, route, global ? 1 : 0, cap_a, run_cuts);
     if (global) {
-        auto kg = k_bucket_big_runs_global<KeyT>;
         int lg = 6;
         while (lg < SRT_LG_MAX_G && (4ll << lg) < longest_run) ++lg;
         if (c->big_runs_cap > 0) lg = std::min(lg, 11); // (tests: few counters as well)
@@ -111,9 +100,8 @@ static int launch_bucket_big_runs(illico_ctx *c, void *Xs, void *tmp, long long 
         slice_bytes = std::min(std::max(slice_bytes, (size_t)512 * sizeof(KeyT)), (size_t)kMaxLds - cnt_bytes - 8192);
         const int slice_keys = (int)(slice_bytes / sizeof(KeyT));
         const size_t ldsg = cnt_bytes + (size_t)slice_keys * sizeof(KeyT);
-        HIPCHK(c, hipFuncSetAttribute((const void *)kg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg));
-        hipLaunchKernelGGL(kg, dim3(gx, nb), dim3(SRTG_NT), ldsg, c->stream, Xs, tmp, stride, nnz, gofs, (const int *)c->d_pk_big, c->pk_nbig, G, cap, lg, big_fn, route, run_n, slice_keys, run_cuts);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_bucket_big_runs_global<KeyT>, dim3(gx, nb), dim3(SRTG_NT), ldsg, Xs, tmp, stride, nnz, gofs, (const int *)c->d_pk_big, c->pk_nbig, G, cap, lg,
+                  big_fn, route, run_n, slice_keys, run_cuts);
     }
     return ILLICO_OK;
 }
@@ -123,26 +111,19 @@ static int launch_bucket_big_runs(illico_ctx *c, void *Xs, void *tmp, long long 
 // kernel handed over (k_ref_cuts), and -- for genes of at most four parts -- their short runs dealt by part (k_deal_runs).
 template <typename KeyT>
 static int launch_rank_parts(illico_ctx *c, OvoCompactParams C, int nb, size_t lds) {
-    void *v;
     int rc;
-    if ((rc = get_scratch(c, "packed_cuts", (size_t)nb * sizeof(PartCuts<KeyT>), &v))) return rc;
-    PartCuts<KeyT> *cuts = (PartCuts<KeyT> *)v;
+    PartCuts<KeyT> *cuts;
+    if ((rc = scratch(c, "packed_cuts", (size_t)nb, &cuts))) return rc;
     C.cuts = cuts; C.pofs = nullptr;
-    hipLaunchKernelGGL((k_ref_cuts<KeyT>), dim3((unsigned)nb), dim3(1024), 0, c->stream, C, cuts);
-    HIPCHK(c, hipGetLastError());
+    KERNELCHK(c, k_ref_cuts<KeyT>, dim3((unsigned)nb), dim3(1024), 0, C, cuts);
     if (!c->no_deal_runs && C.n_parts <= 4) { // (more parts: the masked look-ups of the parts kernel)
-        if ((rc = get_scratch(c, "packed_pofs", (size_t)nb * (size_t)C.G * 8, &v))) return rc;
-        u16 *pofs = (u16 *)v;
+        u16 *pofs; // (four per gene and group)
+        if ((rc = scratch(c, "packed_pofs", (size_t)nb * (size_t)C.G * 4, &pofs))) return rc;
         const unsigned gx = (unsigned)std::max(1, std::min((C.G + DEAL_NT / 64 - 1) / (DEAL_NT / 64), 64));
-        hipLaunchKernelGGL((k_deal_runs<KeyT>), dim3(gx, (unsigned)nb), dim3(DEAL_NT), 0, c->stream, C, (const PartCuts<KeyT> *)cuts, pofs);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_deal_runs<KeyT>, dim3(gx, (unsigned)nb), dim3(DEAL_NT), 0, C, (const PartCuts<KeyT> *)cuts, pofs);
         C.pofs = pofs;
     }
-    auto kp = k_ovo_rank_compact<KeyT, true, true>;
-    HIPCHK(c, hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kp, dim3((unsigned)nb * (unsigned)C.n_parts), dim3(OCR_NT), lds, c->stream, C);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, k_ovo_rank_compact<KeyT, true, true>, dim3((unsigned)nb * (unsigned)C.n_parts), dim3(OCR_NT), lds, C);
 }
 
 // The packed rank kernel (k_ovo_rank_compact) over `nb` genes, with its PARTS launch where the reference needs one; *parts says whether.
@@ -154,7 +135,6 @@ template <typename KeyT, bool SMALL_WG>
 static int launch_packed_rank(illico_ctx *c, OvoCompactParams &C, int nb, int64_t n_ref, long long *s2u, u64 *stie, bool *parts) {
     const int G = (int)c->n_groups;
     int rc;
-    void *v;
     C.counts = c->d_counts; C.G = G; C.ref = (int)c->ref; C.n_genes = nb;
     packed_ref_sizing<KeyT>(n_ref, &C.ref_cap, &C.nbk_lg);
     if (c->packed_ref_cap > 0) C.ref_cap = std::min(C.ref_cap, std::max(c->packed_ref_cap, 1024));
@@ -175,18 +155,15 @@ static int launch_packed_rank(illico_ctx *c, OvoCompactParams &C, int nb, int64_
     *parts = C.n_parts > 1;
     C.needs_parts = nullptr;
     if (*parts) {
-        if ((rc = get_scratch(c, "packed_needs_parts", (size_t)nb * 4, &v))) return rc;
-        C.needs_parts = (u32 *)v;
+        if ((rc = scratch(c, "packed_needs_parts", (size_t)nb, &C.needs_parts))) return rc;
         HIPCHK(c, hipMemsetAsync(C.needs_parts, 0, (size_t)nb * 4, c->stream));
         HIPCHK(c, hipMemsetAsync(s2u, 0, (size_t)nb * G * sizeof(long long), c->stream));
         HIPCHK(c, hipMemsetAsync(stie, 0, (size_t)nb * G * sizeof(u64), c->stream));
     }
     auto kern = eq ? k_ovo_rank_compact<KeyT, true> : k_ovo_rank_compact<KeyT, false>;
     if constexpr (SMALL_WG) { if (small_wg) kern = k_ovo_rank_compact<KeyT, false, false, 256>; }
-    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ProfScope ps(c, KID_OVO_RANK_COMPACT);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(small_wg ? 256 : OCR_NT), lds, c->stream, C);
-    HIPCHK(c, hipGetLastError());
+    KERNELCHK(c, kern, dim3((unsigned)nb), dim3(small_wg ? 256 : OCR_NT), lds, C);
     if (*parts && (rc = launch_rank_parts<KeyT>(c, C, nb, lds))) return rc;
     return ILLICO_OK;
 }

@@ -7,17 +7,13 @@ int launch_seg_value_sums(illico_ctx *c, const KeyT *Xs, const u32 *seg, int nb,
     SegSumsParams P;
     P.Xs = Xs; P.seg_ptr = seg; P.nb = nb; P.G = (int)c->n_groups; P.dt = dtype; P.is_log1p = (flags & ILLICO_FLAG_LOG1P) ? 1 : 0; P.out_sum = ssum;
     ProfScope ps(c, KID_VALUE_SUMS);
-    hipLaunchKernelGGL((k_seg_value_sums<KeyT>), dim3(nb), dim3(SUMS_NT), 0, c->stream, P);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, k_seg_value_sums<KeyT>, dim3(nb), dim3(SUMS_NT), 0, P);
 }
 template <typename KeyT>
 int launch_group_sums_rows(illico_ctx *c, const KeyT *Xt, int64_t stride, int nb, int dtype, int flags, double *ssum) {
     ProfScope ps(c, KID_VALUE_SUMS);
-    hipLaunchKernelGGL((k_group_sums_rows<KeyT>), dim3(nb), dim3(SUMS_NT), 0, c->stream, Xt, (long long)stride, nb, (const int *)c->d_posptr,
-                       (int)c->n_groups, dtype, (flags & ILLICO_FLAG_LOG1P) ? 1 : 0, ssum);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, k_group_sums_rows<KeyT>, dim3(nb), dim3(SUMS_NT), 0, Xt, (long long)stride, nb, (const int *)c->d_posptr, (int)c->n_groups, dtype,
+                         (flags & ILLICO_FLAG_LOG1P) ? 1 : 0, ssum);
 }
 // Per-group accumulators in LDS when they fit, else in HBM (one [3*G] u64 block per gene of the batch).
 template <typename KeyT, bool SPARSE, bool OVO>
@@ -29,10 +25,8 @@ int launch_ovr_gene(illico_ctx *c, OvrParams P) {
     P.seg_begin = P.seg_end = nullptr;
     P.seg_n = nullptr;
     if (accg) {
-        void *v;
-        int rc = get_scratch(c, "ovr_acc", (size_t)P.n_genes * 3 * P.G * 8, &v);
+        int rc = scratch(c, "ovr_acc", (size_t)P.n_genes * 3 * P.G, &P.acc_global);
         if (rc) return rc;
-        P.acc_global = (u64 *)v;
     }
     // One kernel per gene does everything: per-group sums, zero compaction, a stable LSD radix sort of the (key, group)
     // pairs in HBM (2048-element rounds, one 256-thread workgroup per gene) and the rank sweeps.  (Round 1 sorted with
@@ -40,17 +34,9 @@ int launch_ovr_gene(illico_ctx *c, OvrParams P) {
     // this route only takes what the LDS routes leave -- tie-heavy dense columns outside the 64-value table, CSC genes larger
     // than the LDS key buffer -- and no BASELINE configuration reaches it.)
     ProfScope ps(c, KID_OVR_SCAN);
-    if (accg) {
-        auto kern = k_ovr_gene<KeyT, SPARSE, OVO, kOvrThreads, true, DC>;
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(P.n_genes), dim3(kOvrThreads), lds, c->stream, P);
-    } else {
-        auto kern = k_ovr_gene<KeyT, SPARSE, OVO, kOvrThreads, false, DC>;
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(P.n_genes), dim3(kOvrThreads), lds, c->stream, P);
-    }
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return dispatch_flags([&](auto ag) {
+        return launch_kernel(c, k_ovr_gene<KeyT, SPARSE, OVO, kOvrThreads, decltype(ag)::value, DC>, dim3(P.n_genes), dim3(kOvrThreads), lds, P);
+    }, accg);
 }
 
 // padded = true: Xt is the padded dense layout of k_group_compact (slot codes c->d_pk_code, c->pk_stride slots per gene; the value
@@ -58,14 +44,12 @@ int launch_ovr_gene(illico_ctx *c, OvrParams P) {
 template <typename KeyT>
 int run_ovr_dense_batch(illico_ctx *c, KeyT *Xt, int64_t stride, int nb, int N, int dtype, int flags,
                         long long *s2u, u64 *stie, double *ssum, double *gtot, bool padded) {
-    void *v;
     int rc;
-    if ((rc = get_scratch(c, "ovr_kb", (size_t)nb * stride * sizeof(KeyT), &v))) return rc;
-    void *kb = v;
-    if ((rc = get_scratch(c, "ovr_va", (size_t)nb * stride * 4, &v))) return rc;
-    u32 *va = (u32 *)v;
-    if ((rc = get_scratch(c, "ovr_vb", (size_t)nb * stride * 4, &v))) return rc;
-    u32 *vb = (u32 *)v;
+    KeyT *kb;
+    u32 *va, *vb;
+    if ((rc = scratch(c, "ovr_kb", (size_t)nb * stride, &kb))) return rc;
+    if ((rc = scratch(c, "ovr_va", (size_t)nb * stride, &va))) return rc;
+    if ((rc = scratch(c, "ovr_vb", (size_t)nb * stride, &vb))) return rc;
     OvrParams P;
     P.keys_a = Xt; P.keys_b = kb; P.vals_a = va; P.vals_b = vb;
     P.code_by_pos = padded ? c->d_pk_code : c->d_code_by_pos; P.seg_ptr = nullptr; P.stride = stride; P.pos_ptr = c->d_posptr;
@@ -108,14 +92,14 @@ int run_ovr_dense_parts(illico_ctx *c, KeyT *Xt, int64_t stride, int nb, int N, 
     if (c->ovr_parts_cap > 0) cap = (int)std::min<int64_t>(cap, std::max<int64_t>(1024, c->ovr_parts_cap & ~1023ll)); // tests: many small parts
     if ((int64_t)cap * OVRP_PMAX < N) return ILLICO_OK;
     int rc;
-    void *v;
-    if ((rc = get_scratch(c, "ovr_kb", (size_t)nb * stride * sizeof(KeyT), &v))) return rc;
-    void *pkeys = v;
-    if ((rc = get_scratch(c, "ovr_va", (size_t)nb * stride * 4, &v))) return rc;
-    u16 *pcodes = (u16 *)v;
+    KeyT *pkeys;
+    u16 *pcodes; // (in the block of the general route's 32-bit values: half of it)
+    unsigned char *meta_block;
+    if ((rc = scratch(c, "ovr_kb", (size_t)nb * stride, &pkeys))) return rc;
+    if ((rc = scratch(c, "ovr_va", (size_t)nb * stride * 2, &pcodes))) return rc;
     const size_t meta = (size_t)nb * ((OVRP_PMAX + 1) * 4 + 16 + 4) + 64;
-    if ((rc = get_scratch(c, "ovr_parts_meta", meta, &v))) return rc;
-    u32 *part_start = (u32 *)v;
+    if ((rc = scratch(c, "ovr_parts_meta", meta, &meta_block))) return rc;
+    u32 *part_start = (u32 *)meta_block;
     u32 *gene_info = part_start + (size_t)nb * (OVRP_PMAX + 1);
     u32 *gflag = gene_info + (size_t)nb * 4;
     u32 *gene_ctr = gflag + nb; // the rank kernel's queue head
@@ -134,20 +118,14 @@ int run_ovr_dense_parts(illico_ctx *c, KeyT *Xt, int64_t stride, int nb, int N, 
         if (Q.n_long > 0) { // (the COOP form lives in keyed_coop.hip)
             if ((rc = launch_ovr_partition_packed_coop<KeyT>(c, Q, nb))) return rc;
         } else {
-            auto kern = k_ovr_partition_packed<KeyT, false>;
-            HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ovrp_lds_bytes()));
-            hipLaunchKernelGGL(kern, dim3(nb), dim3(OVRP_NT), ovrp_lds_bytes(), c->stream, Q);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_ovr_partition_packed<KeyT, false>, dim3(nb), dim3(OVRP_NT), ovrp_lds_bytes(), Q);
         }
     } else {
         OvrPartParams Q;
         Q.Xt = Xt; Q.stride = stride; Q.n_genes = nb; Q.n_cells = padded ? (int)c->pk_len : N; Q.code_by_pos = padded ? c->d_pk_code : c->d_code_by_pos; Q.cap = cap;
         Q.out_keys = pkeys; Q.out_codes = pcodes; Q.part_start = part_start; Q.gene_info = gene_info;
         ProfScope ps(c, KID_OVR_PART);
-        auto kern = k_ovr_partition<KeyT>;
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ovrp_lds_bytes()));
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(OVRP_NT), ovrp_lds_bytes(), c->stream, Q);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_ovr_partition<KeyT>, dim3(nb), dim3(OVRP_NT), ovrp_lds_bytes(), Q);
     }
     {
         // one workgroup per gene (drawn from a queue), the gene's parts one after the other: kernels_ovr_parts.h
@@ -161,18 +139,9 @@ int run_ovr_dense_parts(illico_ctx *c, KeyT *Xt, int64_t stride, int nb, int N, 
         ProfScope ps(c, KID_OVR_RANK_PARTS);
         int n_cu = 256;
         hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-        if (half) {
-            auto kern = k_ovr_rank_gene_parts<KeyT, 512>;
-            HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            const unsigned grid = (unsigned)std::min<long long>((long long)nb, 2ll * std::max(n_cu, 1)); // two resident workgroups per CU
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, c->stream, P);
-        } else {
-            auto kern = k_ovr_rank_gene_parts<KeyT>;
-            HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            const unsigned grid = (unsigned)std::min<long long>((long long)nb, std::max(n_cu, 1)); // one resident workgroup per CU (LDS)
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(CSCO_NT), lds, c->stream, P);
-        }
-        HIPCHK(c, hipGetLastError());
+        // resident workgroups per CU (LDS): two of 512 threads, or one of CSCO_NT
+        const unsigned grid = (unsigned)std::min<long long>((long long)nb, (half ? 2ll : 1ll) * std::max(n_cu, 1));
+        KERNELCHK(c, half ? k_ovr_rank_gene_parts<KeyT, 512> : k_ovr_rank_gene_parts<KeyT>, dim3(grid), dim3(half ? 512 : CSCO_NT), lds, P);
     }
     // genes that left the route (a coarse bucket too full, a part that fits neither form): the general route, over the
     // gene range that covers them
@@ -196,15 +165,6 @@ int run_ovr_dense_parts(illico_ctx *c, KeyT *Xt, int64_t stride, int nb, int N, 
     *done = true;
     return launch_gene_totals(c, ssum, G, nb, gtot);
 }
-template <typename KeyT, int KMAX, bool RUNEND, bool LG>
-static int launch_ovo_t(illico_ctx *c, const OvoParams &P, size_t lds, const u32 *flags) {
-    auto kern = k_ovo_rank<KeyT, KMAX, RUNEND, kOvoThreads, LG>;
-    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ProfScope ps(c, KID_OVO_RANK);
-    hipLaunchKernelGGL(kern, dim3(P.n_genes), dim3(kOvoThreads), lds, c->stream, P, flags);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
-}
 // flags: per-gene routing word written by the ingest kernels (0 = count-valued gene -> k_ovo_counts,
 // non-zero -> sort route); nullptr routes every gene through the sort route.  The sort route is k_ovo_rank when
 // the reference column and the groups fit LDS / registers, else the per-gene global radix sort (k_ovr_gene in
@@ -218,9 +178,7 @@ int launch_ovo(illico_ctx *c, OvoParams P, int64_t max_ref_nnz, int64_t max_grp_
         ProfScope ps(c, KID_OVO_COUNTS);
         // few genes (the leftovers of a count matrix): a gene's groups over several workgroups, 512 groups (eight wavefronts x 64) each at least
         const int splits = std::max(1, std::min({(1024 + P.n_genes - 1) / std::max(P.n_genes, 1), (P.G + 511) / 512, 16}));
-        if (ovo_counts_limit(c) == COUNTS_R8) hipLaunchKernelGGL((k_ovo_counts<KeyT, COUNTS_R8, 8>), dim3(P.n_genes, splits), dim3(COUNTS_NT), 0, c->stream, P, flags);
-        else hipLaunchKernelGGL((k_ovo_counts<KeyT, COUNTS_R, 16>), dim3(P.n_genes, splits), dim3(COUNTS_NT), 0, c->stream, P, flags);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, ovo_counts_limit(c) == COUNTS_R8 ? k_ovo_counts<KeyT, COUNTS_R8, 8> : k_ovo_counts<KeyT, COUNTS_R, 16>, dim3(P.n_genes, splits), dim3(COUNTS_NT), 0, P, flags);
     }
     if (!ovo_sort_route_fits<KeyT>(max_ref_nnz, max_grp_nnz)) {
         if (!gb || !gb->kb) return fail(c, ILLICO_ERR_UNSUPPORTED, "internal: global-sort scratch missing");
@@ -239,11 +197,10 @@ int launch_ovo(illico_ctx *c, OvoParams P, int64_t max_ref_nnz, int64_t max_grp_
     size_t lds = ovo_lds_bytes<KeyT>(ref_cap, runend, kOvoThreads, buckets);
     P.ref_cap = ref_cap;
     P.ref_buckets = buckets ? 1 : 0;
-    bool big = max_grp_nnz > 256;
-    if (sparse) { // sparse layouts get the lane-per-group form as well
-        if (big) return runend ? launch_ovo_t<KeyT, 16, true, true>(c, P, lds, flags) : launch_ovo_t<KeyT, 16, false, true>(c, P, lds, flags);
-        return runend ? launch_ovo_t<KeyT, 4, true, true>(c, P, lds, flags) : launch_ovo_t<KeyT, 4, false, true>(c, P, lds, flags);
-    }
-    if (big) return runend ? launch_ovo_t<KeyT, 16, true, false>(c, P, lds, flags) : launch_ovo_t<KeyT, 16, false, false>(c, P, lds, flags);
-    return runend ? launch_ovo_t<KeyT, 4, true, false>(c, P, lds, flags) : launch_ovo_t<KeyT, 4, false, false>(c, P, lds, flags);
+    // groups above 256 keys: 16 keys per lane, else 4; sparse layouts get the lane-per-group form as well
+    return dispatch_flags([&](auto big, auto runend_c, auto lane_per_group) {
+        ProfScope ps(c, KID_OVO_RANK);
+        return launch_kernel(c, k_ovo_rank<KeyT, decltype(big)::value ? 16 : 4, decltype(runend_c)::value, kOvoThreads, decltype(lane_per_group)::value>, dim3(P.n_genes),
+                             dim3(kOvoThreads), lds, P, flags);
+    }, max_grp_nnz > 256, runend, sparse);
 }

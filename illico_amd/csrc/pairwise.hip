@@ -28,8 +28,7 @@ int pw_dense(illico_ctx *c, const void *X, int64_t ld, int64_t col0, int wn, int
     const int64_t chunks = (c->n_cells + (int64_t)NWH * wave_rows - 1) / ((int64_t)NWH * wave_rows);
     if (chunks > 65535) return fail(c, ILLICO_ERR_UNSUPPORTED, "%lld cells are more row stretches than one launch holds", (long long)c->n_cells);
     ProfScope ps(c, KID_PW_HIST_DENSE);
-    hipLaunchKernelGGL((k_group_value_hists<InT, PW_RT>), dim3(tiles, (unsigned)chunks), dim3(GH_NT), 0, c->stream, P, T, wave_rows);
-    HIPCHK(c, hipGetLastError());
+    KERNELCHK(c, k_group_value_hists<InT, PW_RT>, dim3(tiles, (unsigned)chunks), dim3(GH_NT), 0, P, T, wave_rows);
     return ILLICO_OK;
 }
 
@@ -41,27 +40,21 @@ int pw_sparse(illico_ctx *c, bool is_csr, const void *data, const void *indices,
     if (!is_csr) {
         const int gw = std::min(G, 128);
         const size_t lds = (size_t)gw * PW_RT * 4;
-        HIPCHK(c, hipFuncSetAttribute((const void *)k_pw_hists_csc<InT, IdxT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         ProfScope ps(c, KID_PW_HIST_CSC);
-        hipLaunchKernelGGL((k_pw_hists_csc<InT, IdxT>), dim3((unsigned)std::min(wn, 1 << 20)), dim3(PW_NT), lds, c->stream, (const InT *)data,
-                           (const IdxT *)indices, (const IdxT *)indptr, kshift, col0, c->d_codes, c->d_counts, N, G, wn, gw, H, d_flags);
-        HIPCHK(c, hipGetLastError());
-        return ILLICO_OK;
+        return launch_kernel(c, k_pw_hists_csc<InT, IdxT>, dim3((unsigned)std::min(wn, 1 << 20)), dim3(PW_NT), lds, (const InT *)data, (const IdxT *)indices,
+                             (const IdxT *)indptr, kshift, col0, c->d_codes, c->d_counts, N, G, wn, gw, H, d_flags);
     }
     HIPCHK(c, hipMemsetAsync(H, 0, (size_t)G * wn * PW_RT * 4, c->stream));
     {
         ProfScope ps(c, KID_PW_HIST_CSR);
         const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((N + 3) / 4, 1 << 16));
-        hipLaunchKernelGGL((k_pw_hists_csr<InT, IdxT>), dim3(gx), dim3(PW_NT), 0, c->stream, (const InT *)data, (const IdxT *)indices, (const IdxT *)indptr,
-                           kshift, col0, c->d_codes, N, G, wn, H, d_flags);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_pw_hists_csr<InT, IdxT>, dim3(gx), dim3(PW_NT), 0, (const InT *)data, (const IdxT *)indices, (const IdxT *)indptr, kshift, col0, c->d_codes, N, G,
+                  wn, H, d_flags);
     }
     {
         ProfScope ps(c, KID_PW_HIST_FINISH);
         const long long rows = (long long)G * wn;
-        hipLaunchKernelGGL(k_pw_hists_bin0, dim3((unsigned)std::max<long long>(1, std::min<long long>((rows + 3) / 4, 1 << 16))), dim3(PW_NT), 0, c->stream, H,
-                           c->d_counts, rows, wn);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_pw_hists_bin0, dim3((unsigned)std::max<long long>(1, std::min<long long>((rows + 3) / 4, 1 << 16))), dim3(PW_NT), 0, H, c->d_counts, rows, wn);
     }
     return ILLICO_OK;
 }
@@ -88,27 +81,24 @@ int pw_hists_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t c
     const size_t x_bytes = (!in.sparse && !in.on_dev) ? (size_t)N * W * esz : 0;
     if ((rc = pw_budget(c, (out_dev ? 0 : h_bytes + (size_t)W * 4) + t_bytes + x_bytes, "illico_group_value_hists"))) return rc;
     if (!in.sparse && (uint64_t)in.ld * esz > 0xFFFFFFFFull) return fail(c, ILLICO_ERR_UNSUPPORTED, "a row pitch of 4 GiB or more");
-    void *v = nullptr;
     u32 *d_H = out_H, *d_flags = out_flags;
     if (!out_dev) {
-        if ((rc = get_scratch(c, "pw_hist_out", h_bytes + (size_t)W * 4, &v))) return rc;
-        d_H = (u32 *)v;
+        if ((rc = scratch(c, "pw_hist_out", h_bytes / 4 + (size_t)W, &d_H))) return rc;
         d_flags = d_H + (size_t)G * W * PW_RT;
     }
     HIPCHK(c, hipMemsetAsync(d_flags, 0, (size_t)W * 4, c->stream));
     if (!in.sparse) {
-        if ((rc = get_scratch(c, "pw_tiled", t_bytes, &v))) return rc;
-        u32 *T = (u32 *)v;
+        u32 *T;
+        if ((rc = scratch(c, "pw_tiled", t_bytes / 4, &T))) return rc;
         HIPCHK(c, hipMemsetAsync(T, 0, t_bytes, c->stream));
         DenseWindow xw;
-        void *xwin = nullptr;
-        if (!in.on_dev && (rc = get_scratch(c, "pw_xwin", x_bytes, &xwin))) return rc;
+        unsigned char *xwin = nullptr;
+        if (!in.on_dev && (rc = scratch(c, "pw_xwin", x_bytes, &xwin))) return rc;
         if ((rc = stage_dense_window(c, in, col_lb, W, W, xwin, &xw))) return rc;
         rc = dispatch_value_type(dt, [&](auto t) { return pw_dense<typename decltype(t)::type>(c, xw.X, xw.ld, xw.col0, wn, tiles, T, d_flags); });
         if (rc) return rc;
         ProfScope ps(c, KID_PW_HIST_FINISH);
-        hipLaunchKernelGGL(k_pw_transpose<true>, dim3(tiles, (unsigned)G), dim3(PW_NT), 0, c->stream, d_H, T, (const int *)nullptr, wn, tiles);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_pw_transpose<true>, dim3(tiles, (unsigned)G), dim3(PW_NT), 0, d_H, T, (const int *)nullptr, wn, tiles);
     } else {
         SparseOnDevice sp; // host-resident sparse input goes up once: CSC the entries of [col_lb, col_ub), CSR every row
         if ((rc = stage_sparse_input(c, in, col_lb, col_ub, "pw_upload", &sp))) return rc;
@@ -177,18 +167,18 @@ extern "C" int illico_pairwise_from_hists(illico_ctx *c, const uint32_t *H, cons
     const size_t t_bytes = (size_t)K * tiles * PW_TILE_WORDS * 4, h_bytes = (size_t)G * W * PW_RT * 4, s_bytes = sums ? (size_t)G * W * 8 : 0;
     const size_t plane = (size_t)K * K * W * 8;
     if ((rc = pw_budget(c, t_bytes + (in_dev ? 0 : h_bytes + (size_t)W * 4 + s_bytes) + (out_dev ? 0 : plane * n_out), "illico_pairwise_from_hists"))) return rc;
-    void *v = nullptr;
-    if ((rc = get_scratch(c, "pw_pairs", t_bytes + (size_t)K * 16 + 64, &v))) return rc;
-    u32 *T = (u32 *)v;
-    long long *d_n = (long long *)((unsigned char *)v + t_bytes);
+    unsigned char *pairs_block;
+    if ((rc = scratch(c, "pw_pairs", t_bytes + (size_t)K * 16 + 64, &pairs_block))) return rc;
+    u32 *T = (u32 *)pairs_block;
+    long long *d_n = (long long *)(pairs_block + t_bytes);
     int *d_sel = (int *)(d_n + K);
     if ((rc = upload_pair_selection(c, S, d_n, d_sel))) return rc;
     const u32 *d_H = H, *d_flags = gene_flags;
     const double *d_sums = sums;
     int64_t d_sums_ld = sums_ld;
     if (!in_dev) {
-        if ((rc = get_scratch(c, "pw_stage_in", h_bytes + (size_t)W * 4 + s_bytes + 64, &v))) return rc;
-        unsigned char *u = (unsigned char *)v;
+        unsigned char *u;
+        if ((rc = scratch(c, "pw_stage_in", h_bytes + (size_t)W * 4 + s_bytes + 64, &u))) return rc;
         if (sums) {
             if ((rc = stage_pair_sums(c, sums, sums_ld, G, W, u, &d_sums, &d_sums_ld))) return rc;
             u += s_bytes;
@@ -199,9 +189,9 @@ extern "C" int illico_pairwise_from_hists(illico_ctx *c, const uint32_t *H, cons
     }
     double *const outs[4] = {out_p, out_u, out_fc, out_z};
     PairOutputs O; // the caller's planes go up first: the columns of flagged genes come back as they were
-    v = nullptr;
-    if (!out_dev && (rc = get_scratch(c, "pw_stage_out", plane * n_out + 64, &v))) return rc;
-    if ((rc = O.up(c, outs, out_ld, K * K, W, out_dev, v))) return rc;
+    double *stage_out = nullptr;
+    if (!out_dev && (rc = scratch(c, "pw_stage_out", plane / 8 * n_out + 8, &stage_out))) return rc;
+    if ((rc = O.up(c, outs, out_ld, K * K, W, out_dev, stage_out))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the selection and the staged arrays came from pageable host memory)
     PwParams P;
     P.T = T; P.gene_flags = d_flags; P.n = d_n; P.sel = d_sel; P.sums = d_sums; P.sums_ld = d_sums_ld;
@@ -212,12 +202,10 @@ extern "C" int illico_pairwise_from_hists(illico_ctx *c, const uint32_t *H, cons
     P.out_p = O.d_out[0]; P.out_u = O.d_out[1]; P.out_fc = O.d_out[2]; P.out_z = O.d_out[3]; P.out_ld = O.d_out_ld;
     {
         ProfScope ps(c, KID_PW_PAIRS);
-        hipLaunchKernelGGL(k_pw_transpose<false>, dim3(tiles, (unsigned)K), dim3(PW_NT), 0, c->stream, const_cast<u32 *>(d_H), T, (const int *)d_sel, wn, tiles);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_pw_transpose<false>, dim3(tiles, (unsigned)K), dim3(PW_NT), 0, const_cast<u32 *>(d_H), T, (const int *)d_sel, wn, tiles);
         const dim3 grid((unsigned)((K * P.nrb + PW_NT / 64 - 1) / (PW_NT / 64)), (unsigned)tiles);
-        if (out_z) hipLaunchKernelGGL(k_pw_pairs<true>, grid, dim3(PW_NT), 0, c->stream, P);
-        else hipLaunchKernelGGL(k_pw_pairs<false>, grid, dim3(PW_NT), 0, c->stream, P);
-        HIPCHK(c, hipGetLastError());
+        if (out_z) KERNELCHK(c, k_pw_pairs<true>, grid, dim3(PW_NT), 0, P);
+        else KERNELCHK(c, k_pw_pairs<false>, grid, dim3(PW_NT), 0, P);
     }
     if ((rc = O.down(c))) return rc;
     if (!out_dev) HIPCHK(c, hipStreamSynchronize(c->stream));

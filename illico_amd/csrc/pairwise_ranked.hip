@@ -24,13 +24,10 @@ int pwr_transpose(illico_ctx *c, const void *X, int64_t ld, int64_t col0, int nc
     constexpr int VEC = 16 / (int)sizeof(InT);
     const bool aligned = ((uintptr_t)X % 16 == 0) && (ld % VEC == 0) && (col0 % VEC == 0) && ((uintptr_t)Xt % 16 == 0) && (stride % 64 == 0);
     if (aligned)
-        hipLaunchKernelGGL((k_transpose_permute_vec<InT, u32, VEC>), grid, dim3(256), 0, c->stream, (const InT *)X, (long long)ld, (long long)col0, ncols,
-                           (const int *)c->d_perm, N, Xt, (long long)stride, (u32 *)nullptr, 0);
-    else
-        hipLaunchKernelGGL((k_transpose_permute<InT, u32>), grid, dim3(256), 0, c->stream, (const InT *)X, (long long)ld, (long long)col0, ncols,
-                           (const int *)c->d_perm, N, Xt, (long long)stride, (u32 *)nullptr, 0);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+        return launch_kernel(c, k_transpose_permute_vec<InT, u32, VEC>, grid, dim3(256), 0, (const InT *)X, (long long)ld, (long long)col0, ncols, (const int *)c->d_perm, N, Xt,
+                             (long long)stride, (u32 *)nullptr, 0);
+    return launch_kernel(c, k_transpose_permute<InT, u32>, grid, dim3(256), 0, (const InT *)X, (long long)ld, (long long)col0, ncols, (const int *)c->d_perm, N, Xt,
+                         (long long)stride, (u32 *)nullptr, 0);
 }
 
 template <typename InT, typename IdxT>
@@ -38,17 +35,14 @@ int pwr_densify(illico_ctx *c, const SparseOnDevice &sp, int64_t c0, int wn, int
     constexpr int RC = 128; // (33 KB tiles of 4-byte values)
     ProfScope ps(c, KID_DENSIFY);
     const dim3 grid((unsigned)(ldD / 64), (unsigned)((n_rows + RC * CDN_SUP - 1) / (RC * CDN_SUP)));
-    hipLaunchKernelGGL((k_csc_densify<InT, IdxT, RC>), grid, dim3(CDN_NT), 0, c->stream, (const InT *)sp.data, (const IdxT *)sp.indices, (const IdxT *)sp.indptr,
-                       (long long)sp.kshift, (long long)c0, wn, (int)n_rows, D, (long long)ldD);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, k_csc_densify<InT, IdxT, RC>, grid, dim3(CDN_NT), 0, (const InT *)sp.data, (const IdxT *)sp.indices, (const IdxT *)sp.indptr,
+                         (long long)sp.kshift, (long long)c0, wn, (int)n_rows, D, (long long)ldD);
 }
 template <typename IdxT>
 int pwr_csc_in_order(illico_ctx *c, const SparseOnDevice &sp, int64_t c0, int64_t W, bool *in_order) {
     u32 h_order[2] = {0u, 0u};
     int rc = device_probe(c, h_order, 2, [&](u32 *d_bad) {
-        hipLaunchKernelGGL((k_flat_descents<IdxT>), dim3(1024), dim3(256), 0, c->stream, (const IdxT *)sp.indices, (const IdxT *)sp.indptr + c0, (int)W,
-                           (long long)sp.kshift, d_bad);
+        return launch_kernel(c, k_flat_descents<IdxT>, dim3(1024), dim3(256), 0, (const IdxT *)sp.indices, (const IdxT *)sp.indptr + c0, (int)W, (long long)sp.kshift, d_bad);
     });
     *in_order = h_order[0] == h_order[1];
     return rc;
@@ -75,9 +69,9 @@ int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub
         return fail(c, ILLICO_ERR_OOM, "illico_pairwise_ranked needs %zu bytes of device scratch for one batch of 64 genes, the budget (\"scratch_bytes\") is %lld",
                     fixed + 64 * per_gene, (long long)c->scratch_bytes);
     const int64_t batch = std::min<int64_t>({(W + 63) & ~63ll, (int64_t)((budget - fixed) / per_gene) & ~63ll, (int64_t)1 << 16});
-    void *v = nullptr;
-    if ((rc = get_scratch(c, "pwr_small", (size_t)G * 4 + (size_t)K * 12 + 64, &v))) return rc;
-    long long *d_n = (long long *)v;
+    unsigned char *small_block;
+    if ((rc = scratch(c, "pwr_small", (size_t)G * 4 + (size_t)K * 12 + 64, &small_block))) return rc;
+    long long *d_n = (long long *)small_block;
     int *d_sel = (int *)(d_n + K), *d_slot = d_sel + K;
     std::vector<int> h_slot((size_t)G, -1);
     for (int64_t k = 0; k < K; ++k) h_slot[S.sel[k]] = (int)k;
@@ -86,17 +80,18 @@ int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub
     const double *d_sums = a.sums;
     int64_t d_sums_ld = a.sums_ld;
     if (!in_dev) {
-        if ((rc = get_scratch(c, "pwr_sums", s_bytes, &v))) return rc;
-        if ((rc = stage_pair_sums(c, a.sums, a.sums_ld, G, W, v, &d_sums, &d_sums_ld))) return rc;
+        double *sums_stage;
+        if ((rc = scratch(c, "pwr_sums", s_bytes / 8, &sums_stage))) return rc;
+        if ((rc = stage_pair_sums(c, a.sums, a.sums_ld, G, W, sums_stage, &d_sums, &d_sums_ld))) return rc;
     }
     PairOutputs O; // the caller's planes go up first: the columns of genes that leave come back as they were
     u32 *d_left = a.out_left;
-    v = nullptr;
+    unsigned char *stage_out = nullptr;
     if (!out_dev) {
-        if ((rc = get_scratch(c, "pwr_stage_out", plane * n_out + (size_t)W * 4, &v))) return rc;
-        d_left = (u32 *)((double *)v + (size_t)n_out * KK * W);
+        if ((rc = scratch(c, "pwr_stage_out", plane * n_out + (size_t)W * 4, &stage_out))) return rc;
+        d_left = (u32 *)((double *)stage_out + (size_t)n_out * KK * W);
     }
-    if ((rc = O.up(c, a.out, a.out_ld, KK, W, out_dev, v))) return rc;
+    if ((rc = O.up(c, a.out, a.out_ld, KK, W, out_dev, stage_out))) return rc;
     SparseOnDevice sp{};
     int64_t sp_c0 = 0; // column col_lb in sp.indptr
     if (in.sparse) {
@@ -111,27 +106,21 @@ int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub
         if (!in_order) return fail(c, ILLICO_ERR_UNSORTED, "the row indices of a CSC column do not ascend: sort them (scipy: sort_indices())");
     }
     // ---- per batch ----
-    if ((rc = get_scratch(c, "pwr_xt", (size_t)batch * stride * 4, &v))) return rc;
-    u32 *Xt = (u32 *)v;
-    if ((rc = get_scratch(c, "pwr_pkeys", (size_t)batch * stride * 4, &v))) return rc;
-    u32 *pkeys = (u32 *)v;
-    if ((rc = get_scratch(c, "pwr_pcodes", (size_t)batch * stride * 2, &v))) return rc;
-    u16 *pcodes = (u16 *)v;
-    if ((rc = get_scratch(c, "pwr_meta", (size_t)batch * ((OVRP_PMAX + 1) * 4 + 16) + 64, &v))) return rc;
-    u32 *part_start = (u32 *)v, *gene_info = part_start + (size_t)batch * (OVRP_PMAX + 1), *gene_ctr = gene_info + (size_t)batch * 4;
-    if ((rc = get_scratch(c, "pwr_stats", (size_t)batch * KK * 16, &v))) return rc;
-    long long *s2 = (long long *)v;
+    u32 *Xt, *pkeys, *part_start;
+    u16 *pcodes;
+    long long *s2;
+    if ((rc = scratch(c, "pwr_xt", (size_t)batch * stride, &Xt))) return rc;
+    if ((rc = scratch(c, "pwr_pkeys", (size_t)batch * stride, &pkeys))) return rc;
+    if ((rc = scratch(c, "pwr_pcodes", (size_t)batch * stride, &pcodes))) return rc;
+    if ((rc = scratch(c, "pwr_meta", (size_t)batch * ((OVRP_PMAX + 1) + 4) + 16, &part_start))) return rc;
+    u32 *gene_info = part_start + (size_t)batch * (OVRP_PMAX + 1), *gene_ctr = gene_info + (size_t)batch * 4;
+    if ((rc = scratch(c, "pwr_stats", (size_t)batch * KK * 2, &s2))) return rc;
     u64 *tie = (u64 *)(s2 + (size_t)batch * KK);
     InT *xwin = nullptr;
-    if (stage_x) {
-        if ((rc = get_scratch(c, "pwr_xwin", (size_t)N * batch * sizeof(InT), &v))) return rc;
-        xwin = (InT *)v;
-    }
+    if (stage_x && (rc = scratch(c, "pwr_xwin", (size_t)N * batch, &xwin))) return rc;
     int n_cu = 256;
     hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
     const size_t lds = pwr_lds_bytes((int)K, cap);
-    HIPCHK(c, hipFuncSetAttribute((const void *)k_pw_rank_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipFuncSetAttribute((const void *)k_ovr_partition<u32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ovrp_lds_bytes()));
     for (int64_t b0 = 0; b0 < W; b0 += batch) {
         const int nb = (int)std::min<int64_t>(batch, W - b0);
         const int64_t ldw = (nb + 63) & ~63ll;
@@ -146,8 +135,7 @@ int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub
             Q.Xt = Xt; Q.stride = stride; Q.n_genes = nb; Q.n_cells = (int)N; Q.code_by_pos = c->d_code_by_pos; Q.cap = cap;
             Q.out_keys = pkeys; Q.out_codes = pcodes; Q.part_start = part_start; Q.gene_info = gene_info;
             ProfScope ps(c, KID_OVR_PART);
-            hipLaunchKernelGGL(k_ovr_partition<u32>, dim3(nb), dim3(OVRP_NT), ovrp_lds_bytes(), c->stream, Q);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_ovr_partition<u32>, dim3(nb), dim3(OVRP_NT), ovrp_lds_bytes(), Q);
         }
         HIPCHK(c, hipMemsetAsync(gene_ctr, 0, 4, c->stream));
         {
@@ -156,8 +144,7 @@ int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub
             P.gene_counter = gene_ctr; P.nb = nb; P.K = (int)K; P.cap = cap; P.is_float = in.dtype == ILLICO_F32 ? 1 : 0;
             P.out_s2 = s2; P.out_tie = tie; P.left = d_left + b0;
             ProfScope ps(c, KID_PW_RANK_PAIRS);
-            hipLaunchKernelGGL(k_pw_rank_pairs, dim3((unsigned)std::min(nb, std::max(n_cu, 1))), dim3(PWR_NT), lds, c->stream, P); // one resident workgroup per CU (LDS)
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_pw_rank_pairs, dim3((unsigned)std::min(nb, std::max(n_cu, 1))), dim3(PWR_NT), lds, P); // one resident workgroup per CU (LDS)
         }
         {
             PwRankEmitParams E;
@@ -167,9 +154,8 @@ int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub
             E.out_p = O.d_out[0]; E.out_u = O.d_out[1]; E.out_fc = O.d_out[2]; E.out_z = O.d_out[3]; E.out_ld = O.d_out_ld;
             const dim3 grid((unsigned)((nb + 63) / 64), (unsigned)((KK + PWE_PAIRS - 1) / PWE_PAIRS));
             ProfScope ps(c, KID_PW_RANK_EMIT);
-            if (O.d_out[3]) hipLaunchKernelGGL(k_pw_rank_emit<true>, grid, dim3(PWE_NT), 0, c->stream, E);
-            else hipLaunchKernelGGL(k_pw_rank_emit<false>, grid, dim3(PWE_NT), 0, c->stream, E);
-            HIPCHK(c, hipGetLastError());
+            if (O.d_out[3]) KERNELCHK(c, k_pw_rank_emit<true>, grid, dim3(PWE_NT), 0, E);
+            else KERNELCHK(c, k_pw_rank_emit<false>, grid, dim3(PWE_NT), 0, E);
         }
     }
     if ((rc = O.down(c))) return rc;

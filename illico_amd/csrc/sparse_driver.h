@@ -174,23 +174,12 @@ static int launch_csc_value_sums(const SparseCall<InT, IdxT> &S, int64_t col0, c
     const bool accg = csc_sums_lds_bytes(P.G, false) + 2048 > kMaxLds;
     const size_t lds = csc_sums_lds_bytes(P.G, accg);
     if (accg) {
-        void *v;
-        int rc = get_scratch(c, "sums_acc", (size_t)nb * 2 * P.G * 8, &v);
+        int rc = scratch(c, "sums_acc", (size_t)nb * 2 * P.G, &P.acc_global);
         if (rc) return rc;
-        P.acc_global = (long long *)v;
-        HIPCHK(c, hipMemsetAsync(v, 0, (size_t)nb * 2 * P.G * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(P.acc_global, 0, (size_t)nb * 2 * P.G * 8, c->stream));
     }
     ProfScope ps(c, KID_VALUE_SUMS);
-    if (accg) {
-        auto kern = k_csc_value_sums<InT, IdxT, true>;
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(CSUM_NT), lds, c->stream, P);
-    } else {
-        auto kern = k_csc_value_sums<InT, IdxT, false>;
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(CSUM_NT), lds, c->stream, P);
-    }
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return dispatch_flags([&](auto ag) { return launch_kernel(c, k_csc_value_sums<InT, IdxT, decltype(ag)::value>, dim3(nb), dim3(CSUM_NT), lds, P); }, accg);
 }
 
 struct SparseBatch {
@@ -228,13 +217,13 @@ static std::vector<SparseBatch> plan_batches(const std::vector<int64_t> &gene_nn
 static int upload_cols(illico_ctx *c, const std::vector<int64_t> &cols, const int **d_cols) {
     *d_cols = nullptr;
     if (cols.back() - cols.front() + 1 == (int64_t)cols.size()) return ILLICO_OK;
-    void *v;
-    int rc = get_scratch(c, "sp_collist", std::max<size_t>(cols.size(), 1) * 4, &v);
+    int *d;
+    int rc = scratch(c, "sp_collist", std::max<size_t>(cols.size(), 1), &d);
     if (rc) return rc;
     std::vector<int> h(cols.begin(), cols.end());
-    HIPCHK(c, hipMemcpyAsync(v, h.data(), h.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // h goes out of scope
-    *d_cols = (const int *)v;
+    *d_cols = d;
     return ILLICO_OK;
 }
 
@@ -244,36 +233,19 @@ static int launch_csc_counts(illico_ctx *c, const CscCountsParams &P, int rt, bo
     ProfScope ps(c, KID_CSC_COUNTS);
     const bool win = P.G != P.G_total; // a window of the groups (instantiated for 16-bit group codes only: the host's case)
     if (win && !P.codes16) return fail(c, ILLICO_ERR_UNSUPPORTED, "group windows need the 16-bit code table");
-    if (w16) { // 16-bit cells for every group (more than CSCC_MAX_BIG groups above 255 cells)
-#define CSCC_LAUNCH16(OVRF, RTV, C16F, WINF)                                                                                    \
-    do {                                                                                                                   \
-        auto kern = k_csc_counts<InT, IdxT, OVRF, RTV, false, false, C16F, CSCC_WT, 0, CSCC_NT, CSCC_LEAN, false, true, WINF>; \
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));          \
-        hipLaunchKernelGGL(kern, dim3(P.nb), dim3(CSCC_NT), lds, c->stream, P);                                            \
-    } while (0)
-#define CSCC_LAUNCH16B(OVRF, RTV) do { if (win) CSCC_LAUNCH16(OVRF, RTV, true, true); else if (P.codes16) CSCC_LAUNCH16(OVRF, RTV, true, false); else CSCC_LAUNCH16(OVRF, RTV, false, false); } while (0)
-        if (ovr) { if (rt == 64) CSCC_LAUNCH16B(true, 64); else CSCC_LAUNCH16B(true, 32); }
-        else { if (rt == 64) CSCC_LAUNCH16B(false, 64); else CSCC_LAUNCH16B(false, 32); }
-#undef CSCC_LAUNCH16B
-#undef CSCC_LAUNCH16
-        HIPCHK(c, hipGetLastError());
-        return ILLICO_OK;
-    }
-#define CSCC_LAUNCH1(OVRF, RTV, BIG, C16F, WINF)                                                                           \
-    do {                                                                                                                   \
-        auto kern = k_csc_counts<InT, IdxT, OVRF, RTV, BIG, MIXED && RTV == 64, C16F, CSCC_WT, 0, CSCC_NT, CSCC_LEAN, CSCC_PUTB(OVRF), false, WINF>; \
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));          \
-        hipLaunchKernelGGL(kern, dim3(P.nb), dim3(CSCC_NT), lds, c->stream, P);                                            \
-    } while (0)
-#define CSCC_LAUNCH(OVRF, RTV, BIG) do { if (win) CSCC_LAUNCH1(OVRF, RTV, BIG, true, true); else if (P.codes16) CSCC_LAUNCH1(OVRF, RTV, BIG, true, false); else CSCC_LAUNCH1(OVRF, RTV, BIG, false, false); } while (0)
-#define CSCC_LAUNCH2(OVRF, RTV) do { if (has_big) CSCC_LAUNCH(OVRF, RTV, true); else CSCC_LAUNCH(OVRF, RTV, false); } while (0)
-    if (ovr) { if (rt == 64) CSCC_LAUNCH2(true, 64); else CSCC_LAUNCH2(true, 32); }
-    else { if (rt == 64) CSCC_LAUNCH2(false, 64); else CSCC_LAUNCH2(false, 32); }
-#undef CSCC_LAUNCH2
-#undef CSCC_LAUNCH
-#undef CSCC_LAUNCH1
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    // (C16F, WINF) takes three values: a window implies the 16-bit codes.  16-bit cells for every group (w16: more than CSCC_MAX_BIG
+    // groups above 255 cells) fix BIG and MIXED.
+    return dispatch_flags([&](auto ovr_c, auto big_c, auto c16_c, auto win_c) {
+        constexpr bool OVRF = decltype(ovr_c)::value, BIG = decltype(big_c)::value, C16F = decltype(c16_c)::value, WINF = decltype(win_c)::value;
+        return dispatch_int<64, 32>(rt, [&](auto rt_c) -> int {
+            constexpr int RTV = decltype(rt_c)::value;
+            if constexpr (WINF && !C16F) return ILLICO_OK; // (never called: checked above)
+            else if (w16)
+                return launch_kernel(c, k_csc_counts<InT, IdxT, OVRF, RTV, false, false, C16F, CSCC_WT, 0, CSCC_NT, CSCC_LEAN, false, true, WINF>, dim3(P.nb), dim3(CSCC_NT), lds, P);
+            else
+                return launch_kernel(c, k_csc_counts<InT, IdxT, OVRF, RTV, BIG, MIXED && RTV == 64, C16F, CSCC_WT, 0, CSCC_NT, CSCC_LEAN, CSCC_PUTB(OVRF), false, WINF>, dim3(P.nb), dim3(CSCC_NT), lds, P);
+        });
+    }, ovr, has_big, win || P.codes16 != nullptr, win);
 }
 
 // k_finalize for batch genes cols[b0 ..) of a column list: through the uploaded list when there is one, else they are contiguous
@@ -288,12 +260,12 @@ static int finalize_listed(const SparseCall<InT, IdxT> &S, const StatsPlanes &st
 static int upload_csc_slots(illico_ctx *c, const CscCountsLayout &L, const signed char **d_slot) {
     *d_slot = nullptr;
     if (!L.n_big_all || L.n_big_all > CSCC_MAX_BIG) return ILLICO_OK;
-    void *v;
-    int rc = get_scratch(c, "cscc_slot", L.h_slot.size(), &v);
+    signed char *d;
+    int rc = scratch(c, "cscc_slot", L.h_slot.size(), &d);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(v, L.h_slot.data(), L.h_slot.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d, L.h_slot.data(), L.h_slot.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (!L.w16) *d_slot = (const signed char *)v;
+    if (!L.w16) *d_slot = d;
     return ILLICO_OK;
 }
 // what every launch of a call has in common; the caller adds col0 / gene_cols / nb, fallback and verdict
@@ -376,19 +348,16 @@ static int run_csc_counts_deferred(const SparseCall<InT, IdxT> &S) {
     const CscCountsLayout &L = S.cscc;
     const int64_t W = S.W;
     int rc;
-    void *v;
     const signed char *d_slot;
     if ((rc = upload_csc_slots(c, L, &d_slot))) return rc;
-    u32 *d_cnt;
+    u32 *d_cnt, *fb;
     if ((rc = clear_flag_words(c, &d_cnt))) return rc;
-    hipLaunchKernelGGL((k_sample_noncount_cols<InT, IdxT>), dim3((1 << 16) / 256), dim3(256), 0, c->stream, S.d_data, S.d_indptr, (long long)S.col_lb,
-                       (long long)S.col_ub, 1 << 16, CSCC_RT, d_cnt);
-    HIPCHK(c, hipGetLastError());
+    KERNELCHK(c, k_sample_noncount_cols<InT, IdxT>, dim3((1 << 16) / 256), dim3(256), 0, S.d_data, S.d_indptr, (long long)S.col_lb,
+              (long long)S.col_ub, 1 << 16, CSCC_RT, d_cnt);
     const int64_t nb_max = stats_batch_genes(W, S.G);
     StatsPlanes st;
     if ((rc = carve_stats(c, nb_max, S.G, false, &st))) return rc;
-    if ((rc = get_scratch(c, "sp_defer_flags", (size_t)W * 4, &v))) return rc;
-    u32 *fb = (u32 *)v;
+    if ((rc = scratch(c, "sp_defer_flags", (size_t)W, &fb))) return rc;
     HIPCHK(c, hipMemsetAsync(fb, 0, (size_t)W * 4, c->stream));
     for (int64_t b0 = 0; b0 < W; b0 += nb_max) {
         const int nb = (int)std::min<int64_t>(nb_max, W - b0);
@@ -398,8 +367,9 @@ static int run_csc_counts_deferred(const SparseCall<InT, IdxT> &S) {
         if ((rc = launch_finalize(c, st.s2u, st.stie, st.ssum, S.ovr ? st.gtot : nullptr, nb, S.flags, S.alternative, S.o, b0, nullptr, L.pack16, S.ovr))) return rc;
     }
     int slot;
-    if ((rc = reserve_deferred_slot(c, (size_t)W * 4, &slot, &v))) return rc;
-    HIPCHK(c, hipMemcpyAsync(v, fb, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
+    void *pin;
+    if ((rc = reserve_deferred_slot(c, (size_t)W * 4, &slot, &pin))) return rc;
+    HIPCHK(c, hipMemcpyAsync(pin, fb, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
     if ((rc = post_deferred_call(c, slot, 1, S.dtype, S.flags, S.alternative, S.n_rows, S.col_lb, S.col_ub, S.o))) return rc;
     PendingDense &q = c->pend;
     q.sp_data = S.data; q.sp_indices = S.indices; q.sp_indptr = S.indptr; q.idx_dtype = S.idx_dtype(); q.n_cols = S.n_cols;
@@ -433,8 +403,6 @@ static int run_csc_gene_route(const SparseCall<InT, IdxT> &S, std::vector<int64_
     const int64_t n = (int64_t)cols.size(), nb_max = stats_batch_genes(n, G);
     StatsPlanes st;
     if ((rc = carve_stats(c, nb_max, G, true, &st))) return rc;
-    auto kern = k_csc_gene<InT, IdxT, KeyT>;
-    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     std::vector<int64_t> left;
     for (int64_t b0 = 0; b0 < n; b0 += nb_max) {
         const int nb = (int)std::min<int64_t>(nb_max, n - b0);
@@ -446,8 +414,7 @@ static int run_csc_gene_route(const SparseCall<InT, IdxT> &S, std::vector<int64_
         P.key_cap = key_cap; P.runend_cap = runend_cap; P.ref_buckets = ref_buckets ? 1 : 0; P.fallback = st.flags; P.out_2u = st.s2u; P.out_tie = st.stie; P.out_sum = st.ssum;
         {
             ProfScope ps(c, KID_CSC_GENE);
-            hipLaunchKernelGGL(kern, dim3(nb), dim3(CSCG_NT), lds, c->stream, P);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_csc_gene<InT, IdxT, KeyT>, dim3(nb), dim3(CSCG_NT), lds, P);
         }
         // the kernel adds a group's values in the order its LDS regroup happened to leave them: replace its sums by the
         // order-independent ones
@@ -501,7 +468,6 @@ static int run_csc_ovr_route(const SparseCall<InT, IdxT> &S, int64_t max_nnz, st
         if (cap_s >= max_nnz) { lg = lg_s; key_cap = cap_s; }
     }
     int rc;
-    void *v;
     const int *d_cols;
     if ((rc = upload_cols(c, cols, &d_cols))) return rc;
     const size_t lds = csco_fixed_lds_bytes(g_lds, lg, false, accg) + (size_t)(key_cap + 4) * sizeof(KeyT);
@@ -509,12 +475,8 @@ static int run_csc_ovr_route(const SparseCall<InT, IdxT> &S, int64_t max_nnz, st
     StatsPlanes st;
     if ((rc = carve_stats(c, nb_max, G, true, &st))) return rc;
     auto kern = accg ? k_csc_ovr_gene<InT, IdxT, KeyT, true> : k_csc_ovr_gene<InT, IdxT, KeyT, false>;
-    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     u64 *acc_g = nullptr;
-    if (accg) {
-        if ((rc = get_scratch(c, "csco_acc", (size_t)nb_max * G * 8, &v))) return rc;
-        acc_g = (u64 *)v;
-    }
+    if (accg && (rc = scratch(c, "csco_acc", (size_t)nb_max * G, &acc_g))) return rc;
     std::vector<int64_t> left;
     for (int64_t b0 = 0; b0 < n; b0 += nb_max) {
         const int nb = (int)std::min<int64_t>(nb_max, n - b0);
@@ -529,8 +491,7 @@ static int run_csc_ovr_route(const SparseCall<InT, IdxT> &S, int64_t max_nnz, st
         if (accg) HIPCHK(c, hipMemsetAsync(acc_g, 0, (size_t)nb * G * 8, c->stream));
         {
             ProfScope ps(c, KID_CSC_OVR);
-            hipLaunchKernelGGL(kern, dim3(nb), dim3(CSCO_NT), lds, c->stream, P);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, kern, dim3(nb), dim3(CSCO_NT), lds, P);
         }
         if ((rc = launch_csc_value_sums(S, cols[b0], d_cols ? d_cols + b0 : nullptr, nb, st.ssum))) return rc;
         if ((rc = launch_gene_totals(c, st.ssum, G, nb, st.gtot))) return rc;
@@ -561,28 +522,26 @@ static int launch_csr_counts_route(const SparseCall<InT, IdxT> &S, u32 *d_flags)
     const int64_t W = col_ub - col_lb, Wpad = (W + 63) & ~63ll;
     const int n_big = c->csr_n_big, n_chunks = c->csr_n_chunks;
     int rc;
-    void *v;
     u32 *d_verdict = d_flags + W;
     HIPCHK(c, hipMemsetAsync(d_flags, 0, (size_t)(W + 4) * 4, c->stream));
-    hipLaunchKernelGGL((k_sample_noncount_cols<InT, IdxT>), dim3((1 << 16) / 256), dim3(256), 0, c->stream, d_data, d_indptr, 0ll, (long long)n_rows,
-                       1 << 16, CSRC_RT, d_verdict);
-    hipLaunchKernelGGL((k_csr_density_verdict<IdxT>), dim3(1), dim3(1), 0, c->stream, d_indptr, (long long)n_rows, (long long)n_cols, 0.3, d_verdict);
+    KERNELCHK(c, k_sample_noncount_cols<InT, IdxT>, dim3((1 << 16) / 256), dim3(256), 0, d_data, d_indptr, 0ll, (long long)n_rows, 1 << 16, CSRC_RT, d_verdict);
+    KERNELCHK(c, k_csr_density_verdict<IdxT>, dim3(1), dim3(1), 0, d_indptr, (long long)n_rows, (long long)n_cols, 0.3, d_verdict);
     // rows out of order: a call over every column finds them in its entry loops (a row's stretches then cover the row: an entry that
     // is not where the boundaries put it shows up outside its window); a column window asks the whole index array first -- unless the
     // matrix is a bound one, whose order was looked at when it was bound
     if (!(col_lb == 0 && col_ub == n_cols) && !c->cur_sorted_known)
-        hipLaunchKernelGGL((k_csr_sorted_check<IdxT>), dim3((unsigned)std::min<int64_t>((n_rows + 3) / 4 + 1, 8192)), dim3(256), 0, c->stream, d_indices,
-                           d_indptr, (int)n_rows, (int *)(d_verdict + 3));
-    HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_csr_sorted_check<IdxT>, dim3((unsigned)std::min<int64_t>((n_rows + 3) / 4 + 1, 8192)), dim3(256), 0, d_indices, d_indptr, (int)n_rows,
+                  (int *)(d_verdict + 3));
     // windows of about 2048 genes: 72 KB of mixed cells, two workgroups per CU; equal widths
     const int n_win = (int)((W + 2047) / 2048);
     const int Wg = (int)((((W + n_win - 1) / n_win) + 63) & ~63ll);
     const int n_bnd = n_win + 1;
-    if ((rc = get_scratch(c, "csrc_bounds", (size_t)n_bnd * n_rows * 4, &v))) return rc;
-    u32 *bounds = (u32 *)v;
+    u32 *bounds;
+    if ((rc = scratch(c, "csrc_bounds", (size_t)n_bnd * n_rows, &bounds))) return rc;
     const size_t slab = (size_t)Wpad * 64;
-    if ((rc = get_scratch(c, "csrc_tables", slab * 4 * (size_t)(2 + n_big) + (size_t)Wpad * (16 + 8), &v))) return rc;
-    u32 *hist = (u32 *)v, *tab = hist + slab * (size_t)(1 + n_big);
+    unsigned char *tables;
+    if ((rc = scratch(c, "csrc_tables", slab * 4 * (size_t)(2 + n_big) + (size_t)Wpad * (16 + 8), &tables))) return rc;
+    u32 *hist = (u32 *)tables, *tab = hist + slab * (size_t)(1 + n_big);
     uint4 *ginfo = (uint4 *)(tab + slab);
     double *gtot = (double *)(ginfo + Wpad);
     HIPCHK(c, hipMemsetAsync(hist, 0, slab * 4 * (size_t)(1 + n_big), c->stream));
@@ -598,49 +557,35 @@ static int launch_csr_counts_route(const SparseCall<InT, IdxT> &S, u32 *d_flags)
     {
         ProfScope ps(c, KID_SPARSE_SEG);
         const long long tot = (long long)n_rows * n_bnd;
-        hipLaunchKernelGGL((k_csr_row_bounds<IdxT>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, d_indices, d_indptr, (int)n_rows,
-                           (long long)n_cols, (long long)col_lb, (long long)col_ub, Wg, n_bnd, bounds, (const u32 *)d_verdict);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_csr_row_bounds<IdxT>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, d_indices, d_indptr, (int)n_rows, (long long)n_cols,
+                  (long long)col_lb, (long long)col_ub, Wg, n_bnd, bounds, (const u32 *)d_verdict);
     }
     {
         ProfScope ps(c, KID_FUSED_REF);
-        auto kern = k_csr_hist<InT, IdxT>;
-        const size_t lds = csrh_lds_bytes(Wg);
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (n_chunks > 0) hipLaunchKernelGGL(kern, dim3(n_win, n_chunks), dim3(CSRH_NT), lds, c->stream, P); // the reference group (OVO), the big groups
-        if (!ovr) hipLaunchKernelGGL((k_csr_tables<false>), dim3((unsigned)((W + 255) / 256)), dim3(256), 0, c->stream, (const u32 *)hist, (long long)Wpad, (int)W, (long long)c->h_counts[c->ref], 0, tab, ginfo, gtot, (const u32 *)d_verdict);
-        HIPCHK(c, hipGetLastError());
+        if (n_chunks > 0) KERNELCHK(c, k_csr_hist<InT, IdxT>, dim3(n_win, n_chunks), dim3(CSRH_NT), csrh_lds_bytes(Wg), P); // the reference group (OVO), the big groups
+        if (!ovr) KERNELCHK(c, k_csr_tables<false>, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, (const u32 *)hist, (long long)Wpad, (int)W, (long long)c->h_counts[c->ref], 0, tab, ginfo, gtot, (const u32 *)d_verdict);
     }
     const size_t lds = csrc_lds_bytes(Wg);
     if (ovr) {
-        if ((rc = get_scratch(c, "csrc_dump", (size_t)G * n_win * CSRC_WPG * Wg * 4, &v))) return rc;
-        P.dump = (u32 *)v;
+        if ((rc = scratch(c, "csrc_dump", (size_t)G * n_win * CSRC_WPG * Wg, &P.dump))) return rc;
         {
             ProfScope ps(c, KID_CSR_COUNTS);
-            auto kern = k_csr_counts<InT, IdxT, true>;
-            HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, dim3(n_win, G), dim3(CSRC_NT), lds, c->stream, P);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_csr_counts<InT, IdxT, true>, dim3(n_win, G), dim3(CSRC_NT), lds, P);
         }
         {
             ProfScope ps(c, KID_FUSED_REF);
             const int slices = std::max(1, std::min(G, (int)std::min<int64_t>(64, (1 << 20) / std::max<int64_t>(W, 1) + 1))); // ~a million threads
             const int gps = (G + slices - 1) / slices;
-            hipLaunchKernelGGL(k_csr_colhist, dim3((unsigned)((W + 255) / 256), (unsigned)((G + gps - 1) / gps)), dim3(256), 0, c->stream, P, n_win, gps);
-            hipLaunchKernelGGL((k_csr_tables<true>), dim3((unsigned)((W + 255) / 256)), dim3(256), 0, c->stream, (const u32 *)hist, (long long)Wpad, (int)W, (long long)n_rows, n_big, tab, ginfo, gtot, (const u32 *)d_verdict);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_csr_colhist, dim3((unsigned)((W + 255) / 256), (unsigned)((G + gps - 1) / gps)), dim3(256), 0, P, n_win, gps);
+            KERNELCHK(c, k_csr_tables<true>, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, (const u32 *)hist, (long long)Wpad, (int)W, (long long)n_rows, n_big, tab, ginfo, gtot, (const u32 *)d_verdict);
         }
         ProfScope ps(c, KID_OVR_SCAN);
-        hipLaunchKernelGGL((o.z ? k_csr_ovr_sweep<true> : k_csr_ovr_sweep<false>), dim3(n_win, G), dim3(CSRC_NT), 0, c->stream, P);
-        if (n_big > 0) hipLaunchKernelGGL((o.z ? k_csr_big_sweep<true, true> : k_csr_big_sweep<true>), dim3((unsigned)((W + 255) / 256), n_big), dim3(256), 0, c->stream, P);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, o.z ? k_csr_ovr_sweep<true> : k_csr_ovr_sweep<false>, dim3(n_win, G), dim3(CSRC_NT), 0, P);
+        if (n_big > 0) KERNELCHK(c, o.z ? k_csr_big_sweep<true, true> : k_csr_big_sweep<true>, dim3((unsigned)((W + 255) / 256), n_big), dim3(256), 0, P);
     } else {
         ProfScope ps(c, KID_CSR_COUNTS);
-        auto kern = k_csr_counts<InT, IdxT, false>;
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(n_win, G), dim3(CSRC_NT), lds, c->stream, P);
-        if (n_big > 0) hipLaunchKernelGGL((o.z ? k_csr_big_sweep<false, true> : k_csr_big_sweep<false>), dim3((unsigned)((W + 255) / 256), n_big), dim3(256), 0, c->stream, P);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_csr_counts<InT, IdxT, false>, dim3(n_win, G), dim3(CSRC_NT), lds, P);
+        if (n_big > 0) KERNELCHK(c, o.z ? k_csr_big_sweep<false, true> : k_csr_big_sweep<false>, dim3((unsigned)((W + 255) / 256), n_big), dim3(256), 0, P);
     }
     return ILLICO_OK;
 }
@@ -669,10 +614,9 @@ static int upload_values_as_bytes(illico_ctx *c, const InT *data, int64_t k0, in
         if (!hs->sp_pin[j]) HIPCHK(c, hipHostMalloc(&hs->sp_pin[j], (size_t)SPB_CHUNK, hipHostMallocDefault));
         if (!hs->sp_up[j]) HIPCHK(c, hipEventCreateWithFlags(&hs->sp_up[j], hipEventDisableTiming));
     }
-    void *v;
     int rc;
-    if ((rc = get_scratch(c, "sp_bytes", (size_t)n, &v))) return rc;
-    uint8_t *d_bytes = (uint8_t *)v;
+    uint8_t *d_bytes;
+    if ((rc = scratch(c, "sp_bytes", (size_t)n, &d_bytes))) return rc;
     const int node = c->no_host_numa ? -1 : numa_node_of_buffer(data + k0, (size_t)n * sizeof(InT));
     const int T = (int)std::max<int64_t>(1, std::min<int64_t>(c->host_fill_threads > 0 ? c->host_fill_threads : 16, 64));
     bool bad = false;
@@ -709,8 +653,7 @@ static int upload_values_as_bytes(illico_ctx *c, const InT *data, int64_t k0, in
     if (rc_meanwhile) return rc_meanwhile;
     if (hip_err) return fail(c, ILLICO_ERR_HIP, "upload of a sparse matrix's values as bytes failed");
     if (bad) { HIPCHK(c, hipStreamSynchronize(c->stream)); return ILLICO_OK; } // (the pinned chunks are free again; the caller uploads the values as they are)
-    hipLaunchKernelGGL((k_bytes_to_values<InT>), dim3(4096), dim3(256), 0, c->stream, (const uint8_t *)d_bytes, (long long)n, d_out);
-    HIPCHK(c, hipGetLastError());
+    KERNELCHK(c, k_bytes_to_values<InT>, dim3(4096), dim3(256), 0, (const uint8_t *)d_bytes, (long long)n, d_out);
     c->h2d_input_bytes += n;
     *done = true;
     return ILLICO_OK;
@@ -722,12 +665,12 @@ static int run_csr_counts_deferred(const SparseCall<InT, IdxT> &S) {
     illico_ctx *c = S.c;
     const size_t bytes = (size_t)(S.W + 4) * 4;
     int rc, slot;
-    void *v;
-    if ((rc = get_scratch(c, "csrc_flags", bytes, &v))) return rc;
-    u32 *d_flags = (u32 *)v;
+    u32 *d_flags;
+    void *pin;
+    if ((rc = scratch(c, "csrc_flags", (size_t)(S.W + 4), &d_flags))) return rc;
     if ((rc = launch_csr_counts_route(S, d_flags))) return rc;
-    if ((rc = reserve_deferred_slot(c, bytes, &slot, &v))) return rc;
-    HIPCHK(c, hipMemcpyAsync(v, d_flags, bytes, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = reserve_deferred_slot(c, bytes, &slot, &pin))) return rc;
+    HIPCHK(c, hipMemcpyAsync(pin, d_flags, bytes, hipMemcpyDeviceToHost, c->stream));
     if ((rc = post_deferred_call(c, slot, 1, S.dtype, S.flags, S.alternative, S.n_rows, S.col_lb, S.col_ub, S.o))) return rc;
     PendingDense &q = c->pend;
     q.is_csr = true; q.sp_data = S.data; q.sp_indices = S.indices; q.sp_indptr = S.indptr; q.sorted_known = c->cur_sorted_known;
@@ -750,8 +693,8 @@ static int fetch_indptr(SparseCall<InT, IdxT> &S) {
     if (S.in_dev) {
         if ((S.counts_route && S.W > 0) || S.window_route) {
             int rc = device_probe(c, S.h_sample, 4, [&](u32 *d_cnt) {
-                hipLaunchKernelGGL((k_sample_noncount_cols<InT, IdxT>), dim3((1 << 16) / 256), dim3(256), 0, c->stream, S.d_data, S.d_indptr,
-                                   (long long)(S.is_csr ? 0 : S.col_lb), (long long)(S.is_csr ? S.n_rows : S.col_ub), 1 << 16, S.is_csr ? FUSED_RT : CSCC_RT, d_cnt);
+                return launch_kernel(c, k_sample_noncount_cols<InT, IdxT>, dim3((1 << 16) / 256), dim3(256), 0, S.d_data, S.d_indptr,
+                                     (long long)(S.is_csr ? 0 : S.col_lb), (long long)(S.is_csr ? S.n_rows : S.col_ub), 1 << 16, S.is_csr ? FUSED_RT : CSCC_RT, d_cnt);
             }, false);
             if (rc) return rc;
             S.sampled = true;
@@ -783,33 +726,34 @@ template <typename InT, typename IdxT>
 static int upload_host_arrays(SparseCall<InT, IdxT> &S) {
     illico_ctx *c = S.c;
     int rc;
-    void *v, *v_idx;
-    if ((rc = get_scratch(c, "sp_indptr", S.n_ptr * sizeof(IdxT), &v))) return rc;
-    HIPCHK(c, hipMemcpyAsync(v, S.indptr, S.n_ptr * sizeof(IdxT), hipMemcpyHostToDevice, c->stream));
-    S.d_indptr = (const IdxT *)v;
+    IdxT *d_ptr, *d_idx;
+    InT *d_val;
+    if ((rc = scratch(c, "sp_indptr", S.n_ptr, &d_ptr))) return rc;
+    HIPCHK(c, hipMemcpyAsync(d_ptr, S.indptr, S.n_ptr * sizeof(IdxT), hipMemcpyHostToDevice, c->stream));
+    S.d_indptr = d_ptr;
     const int64_t k0 = S.is_csr ? 0 : (int64_t)S.h_indptr[S.col_lb];
     const int64_t k1 = S.is_csr ? S.total_nnz : (int64_t)S.h_indptr[S.col_ub];
     const size_t cnt = (size_t)std::max<int64_t>(k1 - k0, 1);
-    if ((rc = get_scratch(c, "sp_data", cnt * sizeof(InT), &v))) return rc;
-    if ((rc = get_scratch(c, "sp_indices", cnt * sizeof(IdxT), &v_idx))) return rc;
+    if ((rc = scratch(c, "sp_data", cnt, &d_val))) return rc;
+    if ((rc = scratch(c, "sp_indices", cnt, &d_idx))) return rc;
     HostStage *hs = host_stage_of(c);
     if (!hs->copy) HIPCHK(c, hipStreamCreateWithFlags(&hs->copy, hipStreamNonBlocking));
     if (!hs->up[0]) HIPCHK(c, hipEventCreateWithFlags(&hs->up[0], hipEventDisableTiming));
     auto upload_indices = [&]() -> int {
-        HIPCHK(c, hipMemcpyAsync(v_idx, (const IdxT *)S.indices + k0, (size_t)(k1 - k0) * sizeof(IdxT), hipMemcpyHostToDevice, hs->copy));
+        HIPCHK(c, hipMemcpyAsync(d_idx, (const IdxT *)S.indices + k0, (size_t)(k1 - k0) * sizeof(IdxT), hipMemcpyHostToDevice, hs->copy));
         HIPCHK(c, hipEventRecord(hs->up[0], hs->copy));
         HIPCHK(c, hipStreamWaitEvent(c->stream, hs->up[0], 0));
         return ILLICO_OK;
     };
     bool as_bytes = false;
-    if ((rc = upload_values_as_bytes<InT>(c, (const InT *)S.data, k0, k1, (InT *)v, &as_bytes, upload_indices))) return rc;
+    if ((rc = upload_values_as_bytes<InT>(c, (const InT *)S.data, k0, k1, d_val, &as_bytes, upload_indices))) return rc;
     if (!as_bytes) {
-        HIPCHK(c, hipMemcpyAsync(v, (const InT *)S.data + k0, (size_t)(k1 - k0) * sizeof(InT), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_val, (const InT *)S.data + k0, (size_t)(k1 - k0) * sizeof(InT), hipMemcpyHostToDevice, c->stream));
         c->h2d_input_bytes += (int64_t)((size_t)(k1 - k0) * sizeof(InT));
     }
-    S.d_data = (const InT *)v;
+    S.d_data = d_val;
     S.kshift = k0;
-    S.d_indices = (const IdxT *)v_idx;
+    S.d_indices = d_idx;
     c->h2d_input_bytes += (int64_t)(S.n_ptr * sizeof(IdxT) + (size_t)(k1 - k0) * sizeof(IdxT));
     return ILLICO_OK;
 }
@@ -819,7 +763,7 @@ template <typename InT, typename IdxT>
 static int sample_stored_values(SparseCall<InT, IdxT> &S, int64_t k0, int64_t n, int rt) {
     const int n_samples = (int)std::min<int64_t>(n, 1 << 16);
     int rc = device_probe(S.c, S.h_sample, 2, [&](u32 *d_cnt) {
-        hipLaunchKernelGGL((k_sample_noncount<InT>), dim3((n_samples + 255) / 256), dim3(256), 0, S.c->stream, S.d_data + (k0 - S.kshift), (long long)n, n_samples, rt, d_cnt);
+        return launch_kernel(S.c, k_sample_noncount<InT>, dim3((n_samples + 255) / 256), dim3(256), 0, S.d_data + (k0 - S.kshift), (long long)n, n_samples, rt, d_cnt);
     });
     S.h_sample[2] = (u32)n_samples;
     S.sampled = true;
@@ -835,9 +779,8 @@ static int route_csr_counts(SparseCall<InT, IdxT> &S, bool *done) {
     illico_ctx *c = S.c;
     const int64_t W = S.W;
     int rc;
-    void *v;
-    if ((rc = get_scratch(c, "csrc_flags", (size_t)(W + 4) * 4, &v))) return rc;
-    u32 *d_flags = (u32 *)v;
+    u32 *d_flags;
+    if ((rc = scratch(c, "csrc_flags", (size_t)(W + 4), &d_flags))) return rc;
     if ((rc = launch_csr_counts_route(S, d_flags))) return rc;
     std::vector<u32> hf((size_t)W + 4);
     HIPCHK(c, hipMemcpyAsync(hf.data(), d_flags, (size_t)(W + 4) * 4, hipMemcpyDeviceToHost, c->stream));
@@ -875,23 +818,23 @@ template <typename InT, typename IdxT, typename Body>
 static int for_dense_windows(const SparseCall<InT, IdxT> &S, size_t cell, Body &&body) {
     const int64_t wmax = dense_window_genes(S.c, S.n_rows, cell);
     int rc;
-    void *v;
+    unsigned char *window;
     for (int64_t w0 = S.col_lb; w0 < S.col_ub; w0 += wmax) {
         const int64_t wn = std::min<int64_t>(wmax, S.col_ub - w0), ldD = (wn + 63) & ~63ll;
-        if ((rc = get_scratch(S.c, "dense_window", (size_t)S.n_rows * ldD * cell, &v))) return rc;
-        if ((rc = body(w0, wn, ldD, v))) return rc;
+        if ((rc = scratch(S.c, "dense_window", (size_t)S.n_rows * ldD * cell, &window))) return rc;
+        if ((rc = body(w0, wn, ldD, window))) return rc;
     }
     return ILLICO_OK;
 }
-// windows in the matrix's own type + the dense routes; densify(w0, wn, ldD, window) launches the kernel that writes one
+// windows in the matrix's own type + the dense routes; densify(w0, wn, ldD, window) launches the kernel that writes one (its status)
 template <typename InT, typename IdxT, typename KeyT, typename Densify>
 static int run_dense_windows_own_type(const SparseCall<InT, IdxT> &S, Densify &&densify) {
     illico_ctx *c = S.c;
     return for_dense_windows(S, sizeof(InT), [&](int64_t w0, int64_t wn, int64_t ldD, void *v) -> int {
         {
             ProfScope ps(c, KID_DENSIFY);
-            densify(w0, wn, ldD, (InT *)v);
-            HIPCHK(c, hipGetLastError());
+            int rc = densify(w0, wn, ldD, (InT *)v);
+            if (rc) return rc;
         }
         return run_dense_t<InT, KeyT>(c, v, S.dtype, S.n_rows, ldD, 0, wn, (S.flags | ILLICO_FLAG_INPUT_DEVICE) & ~ILLICO_FLAG_DEFER, S.alternative, S.o.shifted(w0 - S.col_lb));
     });
@@ -920,12 +863,11 @@ static int route_csr_byte_windows(SparseCall<InT, IdxT> &S, bool *done) {
             ProfScope ps(c, KID_SPARSE_SEG);
             const dim3 grid((unsigned)std::min<int64_t>(S.n_rows, 1 << 16));
             if (bytes)
-                hipLaunchKernelGGL((k_csr_densify<InT, IdxT, uint8_t>), grid, dim3(DENS_NT), 0, c->stream, S.d_data, S.d_indices, S.d_indptr,
-                                   (int)S.n_rows, (long long)w0, (int)wn, (uint8_t *)v, (long long)ldD);
+                KERNELCHK(c, k_csr_densify<InT, IdxT, uint8_t>, grid, dim3(DENS_NT), 0, S.d_data, S.d_indices, S.d_indptr, (int)S.n_rows, (long long)w0, (int)wn,
+                          (uint8_t *)v, (long long)ldD);
             else
-                hipLaunchKernelGGL((k_csr_densify<InT, IdxT, float>), grid, dim3(DENS_NT), 0, c->stream, S.d_data, S.d_indices, S.d_indptr,
-                                   (int)S.n_rows, (long long)w0, (int)wn, (float *)v, (long long)ldD);
-            HIPCHK(c, hipGetLastError());
+                KERNELCHK(c, k_csr_densify<InT, IdxT, float>, grid, dim3(DENS_NT), 0, S.d_data, S.d_indices, S.d_indptr, (int)S.n_rows, (long long)w0, (int)wn,
+                          (float *)v, (long long)ldD);
         }
         c->fused_tie_sparse = true; // (the window holds CSR input: the reference ranks it by its sparse path)
         const FusedCall q{v, ldD, 0, (int)wn, S.flags, S.alternative, S.o, w0 - S.col_lb};
@@ -952,16 +894,15 @@ static int route_f64_as_f32(SparseCall<InT, IdxT> &S, long long k0, long long k1
     if constexpr (std::is_same<InT, double>::value) {
         illico_ctx *c = S.c;
         int rc;
-        void *v;
+        float *v;
         u32 inexact = 1;
         if ((rc = device_probe(c, &inexact, 1, [&](u32 *d_inexact) {
-                hipLaunchKernelGGL(k_f64_is_f32, dim3(4096), dim3(256), 0, c->stream, (const double *)S.d_data + k0, k1 - k0, d_inexact);
+                return launch_kernel(c, k_f64_is_f32, dim3(4096), dim3(256), 0, (const double *)S.d_data + k0, k1 - k0, d_inexact);
             }))) return rc;
         if (inexact) return ILLICO_OK;
         // (the copy covers the whole array up to k1, so that entry k of the caller's arrays stays entry k)
-        if ((rc = get_scratch(c, "sp_f32", (size_t)k1 * sizeof(float), &v))) return rc;
-        hipLaunchKernelGGL(k_f64_to_f32, dim3(4096), dim3(256), 0, c->stream, (const double *)S.d_data + k0, k1 - k0, (float *)v + k0);
-        HIPCHK(c, hipGetLastError());
+        if ((rc = scratch(c, "sp_f32", (size_t)k1, &v))) return rc;
+        KERNELCHK(c, k_f64_to_f32, dim3(4096), dim3(256), 0, (const double *)S.d_data + k0, k1 - k0, v + k0);
         *done = true;
         return run_sparse_t<float, IdxT, u32>(c, S.is_csr, v, S.indices, S.indptr, ILLICO_F32, S.n_rows, S.n_cols, S.col_lb, S.col_ub, S.flags & ~ILLICO_FLAG_DEFER,
                                               S.alternative, S.o, S.allow.in_float32());
@@ -987,8 +928,8 @@ static int route_csr_dense_window(SparseCall<InT, IdxT> &S, bool *done) {
         return ILLICO_OK;
     *done = true;
     return run_dense_windows_own_type<InT, IdxT, KeyT>(S, [&](int64_t w0, int64_t wn, int64_t ldD, InT *D) {
-        hipLaunchKernelGGL((k_csr_densify<InT, IdxT, InT>), dim3((unsigned)std::min<int64_t>(S.n_rows, 1 << 16)), dim3(DENS_NT), 0, c->stream, S.d_data, S.d_indices,
-                           S.d_indptr, (int)S.n_rows, (long long)w0, (int)wn, D, (long long)ldD);
+        return launch_kernel(c, k_csr_densify<InT, IdxT, InT>, dim3((unsigned)std::min<int64_t>(S.n_rows, 1 << 16)), dim3(DENS_NT), 0, S.d_data, S.d_indices,
+                             S.d_indptr, (int)S.n_rows, (long long)w0, (int)wn, D, (long long)ldD);
     });
 }
 // ---- CSC, the same (the columns' row indices must ascend: asked on the device; few, long parcels: the window's entries as one flat
@@ -1004,15 +945,15 @@ static int route_csc_dense_window(SparseCall<InT, IdxT> &S, const std::vector<in
         return ILLICO_OK;
     u32 h_order[2] = {0u, 0u};
     int rc = device_probe(c, h_order, 2, [&](u32 *d_bad) {
-        hipLaunchKernelGGL((k_flat_descents<IdxT>), dim3(4096), dim3(256), 0, c->stream, S.d_indices, S.d_indptr + S.col_lb, (int)W, (long long)S.kshift, d_bad);
+        return launch_kernel(c, k_flat_descents<IdxT>, dim3(4096), dim3(256), 0, S.d_indices, S.d_indptr + S.col_lb, (int)W, (long long)S.kshift, d_bad);
     });
     if (rc || h_order[0] != h_order[1]) return rc;
     *done = true;
     constexpr int RC = sizeof(InT) == 4 ? 128 : 64; // (33 KB tiles: four workgroups per CU)
     return run_dense_windows_own_type<InT, IdxT, KeyT>(S, [&](int64_t w0, int64_t wn, int64_t ldD, InT *D) {
         const dim3 grid((unsigned)(ldD / 64), (unsigned)((S.n_rows + RC * CDN_SUP - 1) / (RC * CDN_SUP)));
-        hipLaunchKernelGGL((k_csc_densify<InT, IdxT, RC>), grid, dim3(CDN_NT), 0, c->stream, S.d_data, S.d_indices, S.d_indptr, (long long)S.kshift, (long long)w0,
-                           (int)wn, (int)S.n_rows, D, (long long)ldD);
+        return launch_kernel(c, k_csc_densify<InT, IdxT, RC>, grid, dim3(CDN_NT), 0, S.d_data, S.d_indices, S.d_indptr, (long long)S.kshift, (long long)w0,
+                             (int)wn, (int)S.n_rows, D, (long long)ldD);
     });
 }
 
@@ -1027,14 +968,13 @@ static int route_csr_transpose(SparseCall<InT, IdxT> &S, bool *done) {
     const IdxT *d_indices = S.d_indices, *d_indptr = S.d_indptr;
     const int64_t n_rows = S.n_rows, col_ub = S.col_ub;
     int rc;
-    void *v;
     // sorted column indices (the reference's contract) allow the gather form of pass 2
     int sorted = (c->cur_sorted_known && !c->no_csr_tile_gather) ? 1 : 0; // (a bound matrix: looked at when it was bound)
     if (!sorted && !c->no_csr_tile_gather) {
         u32 bad = 0;
         if ((rc = device_probe(c, &bad, 1, [&](u32 *d_bad) {
-                hipLaunchKernelGGL((k_csr_sorted_check<IdxT>), dim3((unsigned)std::min<int64_t>((n_rows + 3) / 4 + 1, 8192)), dim3(256), 0, c->stream, d_indices, d_indptr,
-                                   (int)n_rows, (int *)d_bad);
+                return launch_kernel(c, k_csr_sorted_check<IdxT>, dim3((unsigned)std::min<int64_t>((n_rows + 3) / 4 + 1, 8192)), dim3(256), 0, d_indices, d_indptr,
+                                     (int)n_rows, (int *)d_bad);
             }))) return rc;
         sorted = bad ? 0 : 1;
     }
@@ -1053,22 +993,20 @@ static int route_csr_transpose(SparseCall<InT, IdxT> &S, bool *done) {
     int64_t wmax = std::min<int64_t>(S.W, (sorted && RB <= 512) ? 65536 : 32768);
     for (int64_t w0 = S.col_lb; w0 < col_ub;) {
         const int64_t wn = std::min<int64_t>(wmax, col_ub - w0);
-        if ((rc = get_scratch(c, "tr_counts", (size_t)n_blocks * wn * 4, &v))) return rc;
-        u32 *counts = (u32 *)v;
-        if ((rc = get_scratch(c, "tr_cols", (size_t)(wn + 1) * 8 + 16, &v))) return rc;
-        u32 *col_total = (u32 *)v, *col_ptr = col_total + (wn + 1), *d_over = col_ptr + (wn + 1);
+        u32 *counts, *col_total;
+        if ((rc = scratch(c, "tr_counts", (size_t)n_blocks * wn, &counts))) return rc;
+        if ((rc = scratch(c, "tr_cols", (size_t)(wn + 1) * 2 + 4, &col_total))) return rc;
+        u32 *col_ptr = col_total + (wn + 1), *d_over = col_ptr + (wn + 1);
         u32 total = 0;
         {
             ProfScope ps(c, KID_SPARSE_SEG);
             HIPCHK(c, hipMemsetAsync(col_total + wn, 0, 4, c->stream));
             HIPCHK(c, hipMemsetAsync(d_over, 0, 4, c->stream));
-            HIPCHK(c, hipFuncSetAttribute((const void *)k_csr_block_count<IdxT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((wn + 1) / 2) * 4)));
             if (ny > 1) HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)n_blocks * wn * 4, c->stream));
-            hipLaunchKernelGGL((k_csr_block_count<IdxT>), dim3(n_blocks, ny), dim3(TRC_NT), (size_t)((wn + 1) / 2) * 4, c->stream, d_indices, d_indptr,
-                               (int)n_rows, RB, (long long)w0, (int)wn, counts);
-            hipLaunchKernelGGL(k_col_block_scan, dim3((unsigned)((wn + 255) / 256)), dim3(256), 0, c->stream, counts, n_blocks, (int)wn, col_total);
-            hipLaunchKernelGGL(k_gene_base_scan, dim3(1), dim3(1024), 0, c->stream, (const u32 *)col_total, (int)wn + 1, col_ptr);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_csr_block_count<IdxT>, dim3(n_blocks, ny), dim3(TRC_NT), (size_t)((wn + 1) / 2) * 4, d_indices, d_indptr, (int)n_rows, RB, (long long)w0,
+                      (int)wn, counts);
+            KERNELCHK(c, k_col_block_scan, dim3((unsigned)((wn + 255) / 256)), dim3(256), 0, counts, n_blocks, (int)wn, col_total);
+            KERNELCHK(c, k_gene_base_scan, dim3(1), dim3(1024), 0, (const u32 *)col_total, (int)wn + 1, col_ptr);
         }
         HIPCHK(c, hipMemcpyAsync(&total, col_ptr + wn, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1079,19 +1017,16 @@ static int route_csr_transpose(SparseCall<InT, IdxT> &S, bool *done) {
             wmax = std::max<int64_t>(64, wn / 2);
             continue;
         }
-        if ((rc = get_scratch(c, "tr_data", (size_t)std::max<u32>(total, 1) * sizeof(InT), &v))) return rc;
-        InT *t_data = (InT *)v;
-        if ((rc = get_scratch(c, "tr_rows", (size_t)std::max<u32>(total, 1) * 4, &v))) return rc;
-        int *t_rows = (int *)v;
+        InT *t_data;
+        int *t_rows;
+        if ((rc = scratch(c, "tr_data", (size_t)std::max<u32>(total, 1), &t_data))) return rc;
+        if ((rc = scratch(c, "tr_rows", (size_t)std::max<u32>(total, 1), &t_rows))) return rc;
         bool gathered = false;
         if (sorted) {
             ProfScope ps(c, KID_SPARSE_SEG);
             const size_t lds = (size_t)cap * (sizeof(InT) + 4 + 1);
-            HIPCHK(c, hipFuncSetAttribute((const void *)k_csr_tile_gather<InT, IdxT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_csr_tile_gather<InT, IdxT>), dim3(n_blocks, ny), dim3(TRG_NT), lds, c->stream,
-                               d_data, d_indices, d_indptr, (int)n_rows, RB, (long long)w0, (int)wn, (const u32 *)counts, (const u32 *)col_total,
-                               (const u32 *)col_ptr, cap, (const int *)c->d_codes, t_data, t_rows, d_over);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_csr_tile_gather<InT, IdxT>, dim3(n_blocks, ny), dim3(TRG_NT), lds, d_data, d_indices, d_indptr, (int)n_rows, RB, (long long)w0, (int)wn,
+                      (const u32 *)counts, (const u32 *)col_total, (const u32 *)col_ptr, cap, (const int *)c->d_codes, t_data, t_rows, d_over);
             u32 over = 0;
             HIPCHK(c, hipMemcpyAsync(&over, d_over, 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1103,10 +1038,8 @@ static int route_csr_transpose(SparseCall<InT, IdxT> &S, bool *done) {
         }
         if (!gathered) {
             ProfScope ps(c, KID_SPARSE_SEG);
-            HIPCHK(c, hipFuncSetAttribute((const void *)k_csr_block_scatter<InT, IdxT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wn * 4)));
-            hipLaunchKernelGGL((k_csr_block_scatter<InT, IdxT>), dim3(n_blocks), dim3(TR_NT), (size_t)wn * 4, c->stream, d_data, d_indices,
-                               d_indptr, (int)n_rows, RB, (long long)w0, (int)wn, (const u32 *)counts, (const u32 *)col_ptr, (const int *)c->d_codes, t_data, t_rows);
-            HIPCHK(c, hipGetLastError());
+            KERNELCHK(c, k_csr_block_scatter<InT, IdxT>, dim3(n_blocks), dim3(TR_NT), (size_t)wn * 4, d_data, d_indices, d_indptr, (int)n_rows, RB, (long long)w0,
+                      (int)wn, (const u32 *)counts, (const u32 *)col_ptr, (const int *)c->d_codes, t_data, t_rows);
         }
         if ((rc = run_sparse_t<InT, int32_t, KeyT>(c, false, t_data, t_rows, col_ptr, S.dtype, n_rows, wn, 0, wn, S.flags | ILLICO_FLAG_INPUT_DEVICE, S.alternative,
                                                    S.o.shifted(w0 - S.col_lb), SparseAllow::transposed_codes())))
@@ -1127,14 +1060,12 @@ static int count_gene_nnz(const SparseCall<InT, IdxT> &S, std::vector<int64_t> &
         return ILLICO_OK;
     }
     int rc;
-    void *v;
-    if ((rc = get_scratch(c, "sp_colcnt", std::max<size_t>(W, 1) * 4, &v))) return rc;
-    u32 *d_cc = (u32 *)v;
+    u32 *d_cc;
+    if ((rc = scratch(c, "sp_colcnt", std::max<size_t>(W, 1), &d_cc))) return rc;
     HIPCHK(c, hipMemsetAsync(d_cc, 0, W * 4, c->stream));
     {
         ProfScope ps(c, KID_SPARSE_SEG);
-        hipLaunchKernelGGL((k_csr_col_nnz<IdxT>), dim3(2048), dim3(256), 0, c->stream, S.d_indices, (long long)S.total_nnz, (long long)S.col_lb, (long long)S.col_ub, d_cc);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_csr_col_nnz<IdxT>, dim3(2048), dim3(256), 0, S.d_indices, (long long)S.total_nnz, (long long)S.col_lb, (long long)S.col_ub, d_cc);
     }
     std::vector<u32> h_cc(W);
     HIPCHK(c, hipMemcpyAsync(h_cc.data(), d_cc, W * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1176,32 +1107,21 @@ static int regroup_csc_batch(const SparseCall<InT, IdxT> &S, const TwoKernelBatc
     illico_ctx *c = S.c;
     const int G = S.G, nb = B.nb;
     int rc;
-    void *v;
     ProfScope ps(c, KID_SPARSE_SEG);
     const size_t fixed = (size_t)((G + 1 + 3) & ~3) * 4 + (size_t)CSCG_NT * 4;
     const int key_cap = fixed + 4096 < kMaxLds ? (int)std::min<size_t>((kMaxLds - fixed) / sizeof(KeyT), (size_t)CSCG_NT * CSCR_CACHE) : 0;
     u32 *d_fb = nullptr;
     if (!c->no_csc_regroup_lds && key_cap >= 4096) {
-        if ((rc = get_scratch(c, "sp_fb", (size_t)nb * 4, &v))) return rc;
-        d_fb = (u32 *)v;
+        if ((rc = scratch(c, "sp_fb", (size_t)nb, &d_fb))) return rc;
         HIPCHK(c, hipMemsetAsync(d_fb, 0, (size_t)nb * 4, c->stream));
         CscRegroupParams R;
         R.data = S.d_data; R.indices = S.d_indices; R.indptr = S.d_indptr; R.kshift = S.kshift; R.col0 = B.g0; R.gene_cols = B.d_cols;
         R.gene_base = B.d_base; R.nb = nb; R.codes = S.d_codes; R.G = G; R.key_cap = key_cap; R.count_limit = ovo_counts_limit(c); R.Xs = B.Xs;
         R.vals = B.va; R.seg_ptr = B.seg; R.gene_flags = B.gflags; R.fallback = d_fb;
-        auto kern = k_csc_regroup<InT, IdxT, KeyT>;
-        const size_t lds = fixed + (size_t)key_cap * sizeof(KeyT);
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(CSCG_NT), lds, c->stream, R);
-        HIPCHK(c, hipGetLastError());
+        KERNELCHK(c, k_csc_regroup<InT, IdxT, KeyT>, dim3(nb), dim3(CSCG_NT), fixed + (size_t)key_cap * sizeof(KeyT), R);
     }
-    auto kern = k_csc_segment<InT, IdxT, KeyT>;
-    size_t lds = seg_lds_bytes(G);
-    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(SEG_NT), lds, c->stream, S.d_data, S.d_indices, S.d_indptr, (long long)B.g0, nb,
-                       S.d_codes, G, B.Xs, B.va, B.seg, B.gflags, ovo_counts_limit(c), B.d_cols, B.d_base, (long long)S.kshift, (const u32 *)d_fb);
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    return launch_kernel(c, k_csc_segment<InT, IdxT, KeyT>, dim3(nb), dim3(SEG_NT), seg_lds_bytes(G), S.d_data, S.d_indices, S.d_indptr, (long long)B.g0, nb,
+                         S.d_codes, G, B.Xs, B.va, B.seg, B.gflags, ovo_counts_limit(c), B.d_cols, B.d_base, (long long)S.kshift, (const u32 *)d_fb);
 }
 // CSR: count per (gene, group), scan, scatter (global atomics)
 template <typename InT, typename IdxT, typename KeyT>
@@ -1209,26 +1129,21 @@ static int regroup_csr_batch(const SparseCall<InT, IdxT> &S, const TwoKernelBatc
     illico_ctx *c = S.c;
     const int G = S.G, nb = B.nb;
     int rc;
-    void *v;
-    if ((rc = get_scratch(c, "sp_cursor", (size_t)nb * (G + 1) * 4 + (size_t)nb * 8, &v))) return rc;
-    u32 *cursor = (u32 *)v;
+    u32 *cursor;
+    if ((rc = scratch(c, "sp_cursor", (size_t)nb * (G + 1) + (size_t)nb * 2, &cursor))) return rc;
     u32 *gene_tot = cursor + (size_t)nb * (G + 1);
     u32 *gene_base = gene_tot + nb;
     HIPCHK(c, hipMemsetAsync(B.seg, 0, (size_t)nb * (G + 1) * 4, c->stream));
     ProfScope ps(c, KID_SPARSE_SEG);
     const int rows_grid = (int)std::min<int64_t>((S.n_rows + 3) / 4, 8192);
-    hipLaunchKernelGGL((k_csr_count<InT, IdxT>), dim3(rows_grid), dim3(256), 0, c->stream, S.d_data, S.d_indices, S.d_indptr,
-                       (int)S.n_rows, (long long)B.g0, (long long)B.g1, (const int *)c->d_codes, G, B.seg);
-    size_t lds = seg_lds_bytes(G);
-    HIPCHK(c, hipFuncSetAttribute((const void *)k_seg_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_seg_scan, dim3(nb), dim3(SEG_NT), lds, c->stream, B.seg, G, nb, gene_tot);
-    hipLaunchKernelGGL(k_gene_base_scan, dim3(1), dim3(1024), 0, c->stream, (const u32 *)gene_tot, nb, gene_base);
+    KERNELCHK(c, k_csr_count<InT, IdxT>, dim3(rows_grid), dim3(256), 0, S.d_data, S.d_indices, S.d_indptr, (int)S.n_rows, (long long)B.g0, (long long)B.g1,
+              (const int *)c->d_codes, G, B.seg);
+    KERNELCHK(c, k_seg_scan, dim3(nb), dim3(SEG_NT), seg_lds_bytes(G), B.seg, G, nb, gene_tot);
+    KERNELCHK(c, k_gene_base_scan, dim3(1), dim3(1024), 0, (const u32 *)gene_tot, nb, gene_base);
     long long tot = (long long)nb * (G + 1);
-    hipLaunchKernelGGL(k_seg_add_base, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, B.seg, cursor, (const u32 *)gene_base, G, nb);
-    hipLaunchKernelGGL((k_csr_scatter<InT, IdxT, KeyT>), dim3(rows_grid), dim3(256), 0, c->stream, S.d_data, S.d_indices, S.d_indptr, (int)S.n_rows,
-                       (long long)B.g0, (long long)B.g1, (const int *)c->d_codes, G, cursor, B.Xs, B.va, B.gflags, ovo_counts_limit(c));
-    HIPCHK(c, hipGetLastError());
-    return ILLICO_OK;
+    KERNELCHK(c, k_seg_add_base, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, B.seg, cursor, (const u32 *)gene_base, G, nb);
+    return launch_kernel(c, k_csr_scatter<InT, IdxT, KeyT>, dim3(rows_grid), dim3(256), 0, S.d_data, S.d_indices, S.d_indptr, (int)S.n_rows, (long long)B.g0,
+                         (long long)B.g1, (const int *)c->d_codes, G, cursor, B.Xs, B.va, B.gflags, ovo_counts_limit(c));
 }
 // Groups of hundreds / thousands of cells: the regrouped runs in the packed layout's terms, runs above 256 keys dealt into value
 // buckets, then k_ovo_rank_compact (look-ups in the bucketed reference, pieces of 256 keys); what it leaves -- tie-heavy reference
@@ -1237,27 +1152,26 @@ template <typename KeyT>
 static int rank_packed_batch(illico_ctx *c, const TwoKernelBatch<KeyT> &B, const u32 *route_flags, u32 **route_out) {
     const int G = (int)c->n_groups, nb = B.nb;
     int rc;
-    void *v;
-    if ((rc = get_scratch(c, "sp_pk_nnz", (size_t)nb * G * 2 + (size_t)nb * 2 + 64, &v))) return rc;
-    u16 *pk_nnz = (u16 *)v, *ref_nnz = pk_nnz + (((size_t)nb * G + 7) & ~(size_t)7);
-    if ((rc = get_scratch(c, "sp_pk_gofs", (size_t)nb * G * 4 + (size_t)nb * 4, &v))) return rc;
-    u32 *pk_gofs = (u32 *)v, *route = pk_gofs + (size_t)nb * G;
+    u16 *pk_nnz;
+    u32 *pk_gofs;
+    if ((rc = scratch(c, "sp_pk_nnz", (size_t)nb * G + (size_t)nb + 32, &pk_nnz))) return rc;
+    u16 *ref_nnz = pk_nnz + (((size_t)nb * G + 7) & ~(size_t)7);
+    if ((rc = scratch(c, "sp_pk_gofs", (size_t)nb * G + (size_t)nb, &pk_gofs))) return rc;
+    u32 *route = pk_gofs + (size_t)nb * G;
     HIPCHK(c, hipMemsetAsync(route, 0, (size_t)nb * 4, c->stream));
     BigRunFn<KeyT> *big_fn = nullptr;
     {
         ProfScope ps(c, KID_GROUP_COMPACT);
-        hipLaunchKernelGGL(k_seg_to_packed, dim3((unsigned)(((size_t)nb * G + 255) / 256)), dim3(256), 0, c->stream, (const u32 *)B.seg, G, nb, (int)c->ref,
-                           pk_nnz, pk_gofs, ref_nnz, route, (const int *)nullptr, (u32 *)nullptr, 0); // (groups of at most 65535 cells here: 16-bit run lengths hold)
+        KERNELCHK(c, k_seg_to_packed, dim3((unsigned)(((size_t)nb * G + 255) / 256)), dim3(256), 0, (const u32 *)B.seg, G, nb, (int)c->ref, pk_nnz, pk_gofs,
+                  ref_nnz, route, (const int *)nullptr, (u32 *)nullptr, 0); // (groups of at most 65535 cells here: 16-bit run lengths hold)
         if (c->pk_nbig > 0) {
-            if ((rc = get_scratch(c, "packed_big_fn", (size_t)nb * c->pk_nbig * sizeof(BigRunFn<KeyT>), &v))) return rc;
-            big_fn = (BigRunFn<KeyT> *)v;
+            if ((rc = scratch(c, "packed_big_fn", (size_t)nb * c->pk_nbig, &big_fn))) return rc;
             const int64_t longest = std::min<int64_t>(c->max_nonref, B.max_gene);
             int cap = (int)std::min<int64_t>(srt_cap<KeyT>(), (longest + 63) & ~63ll);
             if (c->big_runs_cap > 0) cap = std::min(cap, std::max(c->big_runs_cap, 512) & ~63);
             // (runs beyond the LDS slots are dealt through the global sort's second key buffer)
             if ((rc = launch_bucket_big_runs<KeyT>(c, (void *)B.Xs, c->no_big_runs_global ? nullptr : B.kb, 0ll, pk_nnz, pk_gofs, nb, G, cap, big_fn, route, longest, nullptr, nullptr))) return rc;
         }
-        HIPCHK(c, hipGetLastError());
     }
     OvoCompactParams C;
     memset(&C, 0, sizeof C);
@@ -1276,7 +1190,6 @@ static int run_two_kernel_batch(const SparseCall<InT, IdxT> &S, const SparseBatc
     const int G = S.G;
     const bool ovr = S.ovr, is_csr = S.is_csr;
     int rc;
-    void *v;
     TwoKernelBatch<KeyT> B;
     const int nb = B.nb = (int)(b.g1 - b.g0);
     const int64_t i0 = b.g0;
@@ -1284,20 +1197,17 @@ static int run_two_kernel_batch(const SparseCall<InT, IdxT> &S, const SparseBatc
     B.g1 = cols[i0 + nb - 1] + 1;
     B.max_gene = b.max_gene;
     const size_t nnz = (size_t)std::max<int64_t>(b.nnz, 1);
-    if ((rc = get_scratch(c, "xt", nnz * sizeof(KeyT), &v))) return rc;
-    B.Xs = (KeyT *)v;
-    if ((rc = get_scratch(c, "sp_seg", (size_t)nb * (G + 1) * 4, &v))) return rc;
-    B.seg = (u32 *)v;
+    if ((rc = scratch(c, "xt", nnz, &B.Xs))) return rc;
+    if ((rc = scratch(c, "sp_seg", (size_t)nb * (G + 1), &B.seg))) return rc;
     const int64_t ref_cap_b = ovr ? 0 : std::min<int64_t>(c->h_counts[c->ref], b.max_gene);
     const int64_t grp_cap_b = std::min<int64_t>(c->max_nonref, b.max_gene);
     const bool need_glob = !ovr && !ovo_sort_route_fits<KeyT>(ref_cap_b, grp_cap_b);
     if (ovr || need_glob) {
-        if ((rc = get_scratch(c, "ovr_kb", nnz * sizeof(KeyT), &v))) return rc;
-        B.kb = v;
-        if ((rc = get_scratch(c, "ovr_va", nnz * 4, &v))) return rc;
-        B.va = (u32 *)v;
-        if ((rc = get_scratch(c, "ovr_vb", nnz * 4, &v))) return rc;
-        B.vb = (u32 *)v;
+        KeyT *kb;
+        if ((rc = scratch(c, "ovr_kb", nnz, &kb))) return rc;
+        B.kb = kb;
+        if ((rc = scratch(c, "ovr_va", nnz, &B.va))) return rc;
+        if ((rc = scratch(c, "ovr_vb", nnz, &B.vb))) return rc;
     }
     const bool with_flags = counts_path_allowed(c, S.flags);
     if ((rc = carve_stats(c, nb, G, with_flags, &B.st))) return rc;
@@ -1312,12 +1222,13 @@ static int run_two_kernel_batch(const SparseCall<InT, IdxT> &S, const SparseBatc
             h_base[j] = run;
             run += (u32)list_nnz[i0 + j];
         }
-        if ((rc = get_scratch(c, "sp_cols", (size_t)nb * 8, &v))) return rc;
-        HIPCHK(c, hipMemcpyAsync(v, h_cols.data(), (size_t)nb * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync((char *)v + (size_t)nb * 4, h_base.data(), (size_t)nb * 4, hipMemcpyHostToDevice, c->stream));
+        int *d_cols; // [nb] the columns, then [nb] where each gene's keys start
+        if ((rc = scratch(c, "sp_cols", (size_t)nb * 2, &d_cols))) return rc;
+        HIPCHK(c, hipMemcpyAsync(d_cols, h_cols.data(), (size_t)nb * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_cols + nb, h_base.data(), (size_t)nb * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream)); // the host vectors go out of scope
-        B.d_cols = (const int *)v;
-        B.d_base = (const u32 *)((char *)v + (size_t)nb * 4);
+        B.d_cols = d_cols;
+        B.d_base = (const u32 *)(d_cols + nb);
     }
     const int64_t fin_off = is_csr ? B.g0 - S.col_lb : -S.col_lb; // CSC: col_map holds absolute columns
     if ((rc = is_csr ? regroup_csr_batch<InT, IdxT, KeyT>(S, B) : regroup_csc_batch<InT, IdxT, KeyT>(S, B))) return rc;

@@ -53,6 +53,23 @@ def test_kernel_ids_are_one_list():
     assert lib.illico_profile_kernel_name(n) == b"" and lib.illico_profile_kernel_name(-1) == b""
 
 
+def test_launches_and_scratch_go_through_engine_h():
+    """Kernels are launched, and their dynamic-LDS limit raised, in engine.h only (launch_kernel); raw scratch bytes are asked for in
+    engine.h and core.hip only (scratch<T> elsewhere); no local ...LAUNCH macro ladder is left."""
+    csrc = ROOT / "illico_amd" / "csrc"
+    sources = sorted(csrc.glob("*.h")) + sorted(csrc.glob("*.hip"))
+    assert len(sources) > 40
+    for path in sources:
+        text = path.read_text()
+        for word in ("hipLaunchKernelGGL", "<<<", "hipFuncSetAttribute"):
+            assert path.name == "engine.h" or word not in text, f"{word} in {path.name}: launch through launch_kernel (engine.h)"
+        assert path.name in ("engine.h", "core.hip") or "get_scratch(" not in text, f"get_scratch( in {path.name}: ask with scratch<T> (engine.h)"
+        for name in re.findall(r"#\s*define\s+(\w+)", text):
+            assert not re.search(r"LAUNCH($|[0-9A-Za-z])", name), f"#define {name} in {path.name}: fold the ladder with dispatch_flags (engine.h)"
+    engine = (csrc / "engine.h").read_text()
+    assert "hipLaunchKernelGGL" in engine and "hipFuncSetAttribute" in engine and "get_scratch(" in engine
+
+
 def test_every_option_is_documented():
     """The option table (options.h) and the options comment of include/illico_hip.h name the same switches."""
     from option_names import engine_option_names
