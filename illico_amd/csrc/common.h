@@ -244,6 +244,20 @@ __device__ __forceinline__ int wave_incl_scan_max(int x) { // identity: INT_MIN
     x = max(x, (int)dpp_u32<0x143, 0xC>(id, (u32)x));
     return x;
 }
+// the smallest / largest key of the 64 lanes, in every lane
+template <typename KeyT> __device__ __forceinline__ KeyT wave_min_key(KeyT x) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { KeyT o = __shfl_xor(x, d); x = o < x ? o : x; }
+    return x;
+}
+template <typename KeyT> __device__ __forceinline__ KeyT wave_max_key(KeyT x) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { KeyT o = __shfl_xor(x, d); x = o > x ? o : x; }
+    return x;
+}
+// bits of a key range (largest key - smallest key): 0 for a range of one key
+__device__ __forceinline__ int key_range_bits(u32 range) { return range ? 32 - __clz((int)range) : 0; }
+__device__ __forceinline__ int key_range_bits(u64 range) { return range ? 64 - __clzll((long long)range) : 0; }
 
 // Sort 64*K keys held K per lane; sorted position of (lane, r) is lane*K + r.  All-ascending
 // ("flip") bitonic network: intra-lane stages are plain register compare-exchanges, cross-lane

@@ -75,19 +75,6 @@ static inline int csco_key_cap(int G, int lg_buckets, size_t key_size, size_t ld
     return (int)std::min<size_t>((lds_max - fixed) / key_size - 4, 65535 - 4);
 }
 
-template <typename KeyT> __device__ __forceinline__ KeyT wave_min_key(KeyT x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { KeyT o = __shfl_xor(x, d); x = o < x ? o : x; }
-    return x;
-}
-template <typename KeyT> __device__ __forceinline__ KeyT wave_max_key(KeyT x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { KeyT o = __shfl_xor(x, d); x = o > x ? o : x; }
-    return x;
-}
-__device__ __forceinline__ int key_bits(u32 r) { return r ? 32 - __clz(r) : 0; }
-__device__ __forceinline__ int key_bits(u64 r) { return r ? 64 - __clzll((long long)r) : 0; }
-
 // exclusive scan of the 16-bit counters arr[0..n) in place; n = NT * per, per a multiple of 2; totals below 2^16.  tmp: [NT / 64] words.
 template <int NT> __device__ __forceinline__ void block_excl_scan_u16_waves(u16 *arr, int n, u32 *tmp, int tid) {
     constexpr int NW = NT / 64;
@@ -250,7 +237,7 @@ __global__ __launch_bounds__(CSCO_NT) void k_csc_ovr_gene(CscOvrParams P) {
         __syncthreads();
         const bool have_range = s_k[1] >= s_k[0];
         const KeyT kmin = have_range ? s_k[0] : (KeyT)0, kmax = have_range ? s_k[1] : (KeyT)0;
-        const int shift = max(0, key_bits((KeyT)(kmax - kmin)) - P.lg_buckets);
+        const int shift = max(0, key_range_bits((KeyT)(kmax - kmin)) - P.lg_buckets);
         // table entry of a key: 1 + its bucket (buckets 0 .. NBKT - 2).  Entry 0 stays 0, so that after the scan and the scattering
         // pass bucket b is [entry b, entry b + 1): two neighbouring 16-bit reads, no special case for the first bucket.
         const KeyT last_bucket = (KeyT)(NBKT - 2);
@@ -489,7 +476,7 @@ __global__ __launch_bounds__(OVRP_NT) void k_ovr_partition(OvrPartParams P) {
         __syncthreads();
         const bool have_range = s_k[1] >= s_k[0];
         const KeyT kmin = have_range ? s_k[0] : (KeyT)0, kmax = have_range ? s_k[1] : (KeyT)0;
-        const int shift = max(0, key_bits((KeyT)(kmax - kmin)) - OVRP_LG);
+        const int shift = max(0, key_range_bits((KeyT)(kmax - kmin)) - OVRP_LG);
         auto bucket_of = [&](KeyT key) -> u32 {
             const KeyT d = key > kmin ? (KeyT)((KeyT)(key - kmin) >> shift) : (KeyT)0;
             return (u32)(d < (KeyT)(NB - 1) ? d : (KeyT)(NB - 1));
@@ -661,7 +648,7 @@ __global__ __launch_bounds__(OVRP_NT) void k_ovr_partition_packed(OvrPartPackedP
     __syncthreads();
     const bool have_range = s_k[1] >= s_k[0];
     const KeyT kmin = have_range ? s_k[0] : (KeyT)0, kmax = have_range ? s_k[1] : (KeyT)0;
-    const int shift = max(0, key_bits((KeyT)(kmax - kmin)) - OVRP_LG);
+    const int shift = max(0, key_range_bits((KeyT)(kmax - kmin)) - OVRP_LG);
     auto bucket_of = [&](KeyT key) -> u32 {
         const KeyT d = key > kmin ? (KeyT)((KeyT)(key - kmin) >> shift) : (KeyT)0;
         return (u32)(d < (KeyT)(NB - 1) ? d : (KeyT)(NB - 1));

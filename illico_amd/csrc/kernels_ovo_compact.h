@@ -34,10 +34,6 @@
 #define OCR_NT 1024
 #endif
 #define OCR_KMAX 4          // 64-key rounds per group: groups of up to 256 non-zero keys
-#ifndef OCR_PAIR
-#define OCR_PAIR 1          // groups whose keys are requested ahead of their look-ups.  2 (requests two look-up rounds ahead) measured the same at C2 / C5
-                            // shapes and 20 % slower in the 256-thread form: what the wavefronts wait on is the chain table word -> keys in LDS, not HBM
-#endif
 #ifndef OCR_BLOOM_WORDS
 #define OCR_BLOOM_WORDS 256 // per wavefront: 8192 bits
 #endif
@@ -364,14 +360,38 @@ struct OvoCompactParams {
 // so a bucket's first key is at  prefix + (sum of the counters below it)  = two popcounts, and with ~30 buckets per key nearly
 // every bucket holds 0 or 1 keys: a look-up reads one table word and two keys.  Overfull words (and a bucket of exactly 3, and
 // keys that tie with the reference) take an exact per-lane walk over the word's / bucket's keys.
-__host__ __device__ static inline size_t ocr_lds_bytes(int ref_cap, int nbk_lg, size_t key_size, int nt = OCR_NT) {
-    size_t b = (((size_t)ref_cap + 4) * key_size + 15) & ~(size_t)15;
-    b += (((size_t)1 << nbk_lg) / 16 + 2) * 8;
-    b += (size_t)(nt / 64) * OCR_BLOOM_WORDS * 4;
-    b += 2048; // coarse cells of the distribution-following bucket function: table + counters
-    b += 256; // reduction words
-    return b;
-}
+//
+// The kernel's dynamic LDS, stated once for the host (ocr_lds_bytes) and the kernel (OcrSmem).  Byte offsets of
+//   A      [ref_cap + 4] keys (at 0): the reference's keys in bucket order and a pad of four
+//   tab    [2^nbk_lg / 16 + 2] 64-bit table words, two of them sentinels; starts on a 16-byte boundary
+//   bloom  [nt / 64][OCR_BLOOM_WORDS] words: one Bloom table per wavefront
+//   cells  ctab [256] | ccnt [256] words: the coarse cells of the distribution-following bucket function and their key counts
+//   red, kr, cnt, scan   the tail: s_red [nt / 64] 64-bit words | s_kr [2] keys: smallest, largest | s_cnt [8] words | s_scan [nt / 64] words
+// Once the table stands, ccnt is done with (ctab is not: the look-ups read it): the long runs' walk keeps its list and sums there (lr_list, lr_acc).
+struct OcrLds {
+    static constexpr size_t CELL_WORDS = 256, TAIL_BYTES = 256, CNT_WORDS = 8, LR_LIST_WORDS = 64 /* a count and 63 groups */, LR_ACC_WORDS = 5;
+    size_t tab, bloom, cells, red, kr, cnt, scan, total;
+    __host__ __device__ constexpr OcrLds(int ref_cap, int nbk_lg, size_t key_size, int nt)
+        : tab((((size_t)ref_cap + 4) * key_size + 15) & ~(size_t)15), bloom(tab + (((size_t)1 << nbk_lg) / 16 + 2) * 8),
+          cells(bloom + (size_t)(nt / 64) * OCR_BLOOM_WORDS * 4), red(cells + 2 * CELL_WORDS * 4), kr(red + (size_t)(nt / 64) * 8), cnt(kr + 2 * key_size),
+          scan(cnt + CNT_WORDS * 4), total(red + TAIL_BYTES) {}
+    __host__ __device__ constexpr bool tail_fits(int nt) const { return scan + (size_t)(nt / 64) * 4 <= total; }
+};
+static_assert(OcrLds::LR_LIST_WORDS * 4 + OcrLds::LR_ACC_WORDS * 8 <= OcrLds::CELL_WORDS * 4, "the long runs' list and sums must fit the coarse cells' counters");
+static_assert(OcrLds(0, 14, 8, OCR_NT).tail_fits(OCR_NT), "the tail of the largest form (1024 threads, 8-byte keys)");
+__host__ __device__ static inline size_t ocr_lds_bytes(int ref_cap, int nbk_lg, size_t key_size, int nt = OCR_NT) { return OcrLds(ref_cap, nbk_lg, key_size, nt).total; }
+// s_cnt: the reference's keys below zero; its non-zero keys; the fullest overfull table word; the longest ranked run; keys in overfull words
+enum { OCR_N_NEG = 0, OCR_N_KEYS = 1, OCR_FULLEST = 2, OCR_G_MAX = 3, OCR_IN_FULL = 4 };
+template <typename KeyT> struct OcrSmem { // the kernel's pointers into that layout
+    KeyT *A, *s_kr; u32 *tab, *bloom, *ctab, *ccnt, *s_cnt, *s_scan, *lr_list; u64 *s_red, *lr_acc;
+    __device__ __forceinline__ OcrSmem(unsigned char *smem, const OcrLds &L) {
+        A = (KeyT *)smem; tab = (u32 *)(smem + L.tab); bloom = (u32 *)(smem + L.bloom);
+        ctab = (u32 *)(smem + L.cells); ccnt = ctab + OcrLds::CELL_WORDS;
+        s_red = (u64 *)(smem + L.red); s_kr = (KeyT *)(smem + L.kr); s_cnt = (u32 *)(smem + L.cnt); s_scan = (u32 *)(smem + L.scan);
+        lr_list = ccnt;                                    // [0] long runs listed, [1 ..] their groups
+        lr_acc = (u64 *)(ccnt + OcrLds::LR_LIST_WORDS);    // [0] S2 part  [1] tie part  [2] negatives  [3] keys inside the part  [4] a bucket above 256 keys
+    }
+};
 
 __device__ __forceinline__ u32 ocr_hash(u32 k) { return k ^ (k >> 10); }
 __device__ __forceinline__ u32 ocr_hash(u64 k) { const u32 f = (u32)(k ^ (k >> 32)); return f ^ (f >> 10); }
@@ -557,7 +577,13 @@ __device__ __forceinline__ void ocr_group(const KeyT (&cur)[OCR_KMAX], int nB, c
     eq_out = eqs;
     TT_out = TT;
 }
-
+// ... with the number of rounds chosen by nB (1 .. 256 keys; uniform)
+template <typename KeyT, bool EQ, bool MASKED> __device__ __forceinline__ void ocr_lookup(const KeyT (&cur)[OCR_KMAX], int nB, const OcrRef<KeyT, EQ> &R, u32 *bloom, int lane, u64 lt_mask, u32 &less, u32 &eqs, u64 &TT, u32 &negs) {
+    if (nB <= 64) ocr_group<KeyT, 1, EQ, MASKED>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
+    else if (nB <= 128) ocr_group<KeyT, 2, EQ, MASKED>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
+    else if (nB <= 192) ocr_group<KeyT, 3, EQ, MASKED>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
+    else ocr_group<KeyT, 4, EQ, MASKED>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
+}
 
 // ---- groups of more than 256 non-zero keys -----------------------------------------------------------------------------------
 // The rank kernel below looks a group's keys up 256 at a time, and what it has to know about a group beyond the look-ups -- which of
@@ -603,6 +629,56 @@ template <typename KeyT, int NT, typename F> __device__ __forceinline__ void run
     if (tid < n - t0) f(run[t0 + tid], t0 + tid);
 }
 
+// ---- steps the bucket kernels, k_ref_cuts and the rank kernel share ------------------------------------------------------------------
+// The workgroup's smallest and largest key into kr[0] / kr[1] from every thread's own (set to MAXK / 0 and a barrier before; a barrier
+// before they are read).
+template <typename KeyT> __device__ __forceinline__ void wg_key_range(KeyT lo, KeyT hi, KeyT *kr, int lane) {
+    lo = wave_min_key(lo);
+    hi = wave_max_key(hi);
+    if (lane == 0) { atomicMin(&kr[0], lo); atomicMax(&kr[1], hi); }
+}
+// Exclusive scan over LDS counters dealt to the threads in order: from the sum of a thread's own counters, the sum of the counters of
+// all threads before it.  part: [threads / 64] words; a barrier inside.
+__device__ __forceinline__ u32 wg_excl_scan(u32 sum, u32 *part, int lane, int wave) {
+    const u32 inc = (u32)wave_incl_scan_add((int)sum);
+    if (lane == 63) part[wave] = inc;
+    __syncthreads();
+    u32 base = inc - sum;
+    for (int w = 0; w < wave; ++w) base += part[w];
+    return base;
+}
+// the first bucket of [lo, hi) that starts at or after position t (cnt: the buckets' starts, ascending), or hi
+__device__ __forceinline__ int first_start_at_or_after(const u32 *cnt, int lo, int hi, u32 t) {
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (cnt[mid] >= t) hi = mid; else lo = mid + 1; }
+    return lo;
+}
+// The rank kernel walks a long run with all its wavefronts: where stretch w of OCR_CUTS + 1 begins -- the first bucket that starts at or
+// behind w n / (OCR_CUTS + 1) -- by threads 1 .. OCR_CUTS, from the B buckets' starts while they are untouched.
+__device__ __forceinline__ void write_run_cuts(u32 *cuts, const u32 *cnt, int B, int n, int tid) {
+    if (tid >= 1 && tid <= OCR_CUTS) {
+        const int b = first_start_at_or_after(cnt, 0, B, (u32)((long long)n * tid / (OCR_CUTS + 1)));
+        cuts[tid - 1] = b < B ? cnt[b] : (u32)n;
+    }
+}
+// A workgroup's stretch of a gene's candidate groups is looked at a workgroup's threads at a time: those of candidates c0 + tid < c_end whose
+// run holds more than n_min keys into list[] (any order); returns how many.  (300 groups of 333 cells half non-zero are 1.5 M candidates
+// none of which holds 256 keys.)  Barriers inside.
+__device__ __forceinline__ int list_candidates(const u16 *nnz_gene, const int *cand, int c0, int c_end, int n_min, int *list, int *n_list, int tid) {
+    if (tid == 0) *n_list = 0;
+    __syncthreads();
+    if (c0 + tid < c_end && (int)nnz_gene[cand[c0 + tid]] > n_min) list[atomicAdd(n_list, 1)] = c0 + tid;
+    __syncthreads();
+    return *n_list;
+}
+// every non-zero key of the reference to f: its nseg packed segments of at most GCMP_SEG_ROWS keys, wavefront w of NW takes segments w, w + NW, ...
+template <int NW, typename KeyT, typename F> __device__ __forceinline__ void ocr_ref_for_keys(const KeyT *src, const u16 *seg_nnz, int nseg, int wave, int lane, F f) {
+    for (int sg = wave; sg < nseg; sg += NW) {
+        const int c = (int)seg_nnz[sg];
+        const KeyT *sp = src + (size_t)sg * GCMP_SEG_ROWS;
+        for (int i = lane; i < c; i += 64) f(sp[i]);
+    }
+}
+
 // A run longer than the LDS buffer (half of a 100 000-cell cluster non-zero: 50 000 keys) is dealt through HBM instead, by a kernel of
 // its own (k_bucket_big_runs leaves such runs alone when one follows): range and bucket counts from two reads of the run, the counters
 // -- up to 2^13 in LDS, ~6 keys per bucket at 50 000 -- scanned, the keys dealt slice by slice of the output through LDS key slots behind
@@ -620,17 +696,13 @@ __global__ __launch_bounds__(SRTG_NT) void k_bucket_big_runs_global(void *Xs, vo
     constexpr KeyT MAXK = KeyInfo<KeyT>::MAXK;
     constexpr int NT = SRTG_NT;
     u32 *cnt = (u32 *)srtg_smem;
-    __shared__ KeyT g_min, g_max;
+    __shared__ KeyT g_kr[2];
     __shared__ u32 g_part[NT / 64];
     __shared__ int s_list[NT], s_nl;
     const int gene = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int per = (n_cand + (int)gridDim.x - 1) / (int)gridDim.x, c_end = min(n_cand, ((int)blockIdx.x + 1) * per);
     for (int c0 = (int)blockIdx.x * per; c0 < c_end; c0 += NT) { // (the workgroup's stretch of the gene's candidates, as in k_bucket_big_runs)
-      if (tid == 0) s_nl = 0;
-      __syncthreads();
-      if (c0 + tid < c_end && (int)nnz[(size_t)gene * G + cand[c0 + tid]] > cap) s_list[atomicAdd(&s_nl, 1)] = c0 + tid;
-      __syncthreads();
-      const int nl = s_nl;
+      const int nl = list_candidates(nnz + (size_t)gene * G, cand, c0, c_end, cap, s_list, &s_nl, tid);
       for (int li = 0; li < nl; ++li) {
         const int cd = s_list[li], g = cand[cd];
         int n = (int)nnz[(size_t)gene * G + g];
@@ -640,21 +712,18 @@ __global__ __launch_bounds__(SRTG_NT) void k_bucket_big_runs_global(void *Xs, vo
         }
         const size_t off = (size_t)((long long)gene * gene_stride) + gofs[(size_t)gene * G + g];
         KeyT *run = (KeyT *)Xs + off, *out = (KeyT *)tmp + off;
-        if (tid == 0) { g_min = MAXK; g_max = (KeyT)0; }
+        if (tid == 0) { g_kr[0] = MAXK; g_kr[1] = (KeyT)0; }
         __syncthreads();
         KeyT lo = MAXK, hi = (KeyT)0;
         run_for_keys<KeyT, NT>(run, n, tid, [&](KeyT k, int) { lo = k < lo ? k : lo; hi = k > hi ? k : hi; });
-    #pragma unroll
-        for (int d = 32; d > 0; d >>= 1) { const KeyT a = __shfl_xor(lo, d), b = __shfl_xor(hi, d); lo = a < lo ? a : lo; hi = b > hi ? b : hi; }
-        if (lane == 0) { atomicMin(&g_min, lo); atomicMax(&g_max, hi); }
+        wg_key_range(lo, hi, g_kr, lane);
         __syncthreads();
         int lg = 6;
         while (lg < lg_max && (4 << lg) < n) ++lg;
         const int B = 1 << lg;
-        const KeyT range = (KeyT)(g_max - g_min);
-        const int bits = range ? (int)(sizeof(KeyT) * 8) - (sizeof(KeyT) == 8 ? __clzll((long long)range) : __clz((int)range)) : 0;
+        const int bits = key_range_bits((KeyT)(g_kr[1] - g_kr[0]));
         BigRunFn<KeyT> f;
-        f.kmin = g_min;
+        f.kmin = g_kr[0];
         f.shift = bits > lg ? bits - lg : 0;
         if (tid == 0) { BigRunFn<KeyT> fo = f; fo.shift |= BIG_RUN_IN_TMP; big_fn[(size_t)gene * n_cand + cd] = fo; } // (the rank kernel reads this run from `tmp`)
         for (int b = tid; b < B; b += NT) cnt[b] = 0u;
@@ -665,21 +734,12 @@ __global__ __launch_bounds__(SRTG_NT) void k_bucket_big_runs_global(void *Xs, vo
             const int per = (B + NT - 1) / NT;
             u32 sum = 0;
             for (int e = 0; e < per; ++e) { const int b = tid * per + e; sum += b < B ? cnt[b] : 0u; }
-            const u32 inc = (u32)wave_incl_scan_add((int)sum);
-            if (lane == 63) g_part[wave] = inc;
-            __syncthreads();
-            u32 base = inc - sum;
-            for (int w = 0; w < wave; ++w) base += g_part[w];
+            u32 base = wg_excl_scan(sum, g_part, lane, wave);
             for (int e = 0; e < per; ++e) { const int b = tid * per + e; if (b < B) { const u32 c = cnt[b]; cnt[b] = base; base += c; } }
         }
-        if (run_cuts) { // the rank kernel walks a long run with all its wavefronts: where stretch w of 16 begins (the first bucket that starts at or behind w n / 16)
+        if (run_cuts) {
             __syncthreads();
-            if (tid >= 1 && tid <= OCR_CUTS) {
-                const u32 t = (u32)((long long)n * tid / (OCR_CUTS + 1));
-                int lo_b = 0, hi_b = B;
-                while (lo_b < hi_b) { const int mid = (lo_b + hi_b) >> 1; if (cnt[mid] >= t) hi_b = mid; else lo_b = mid + 1; }
-                run_cuts[((size_t)gene * n_cand + cd) * OCR_CUTS + (tid - 1)] = lo_b < B ? cnt[lo_b] : (u32)n;
-            }
+            write_run_cuts(run_cuts + ((size_t)gene * n_cand + cd) * OCR_CUTS, cnt, B, n, tid);
         }
     // the scatter, in SLICES of the output through LDS: a slice = the buckets that start inside [s T, (s + 1) T) of the output, T = the slice
         // buffer less 256 keys (a bucket of more than 256 keys -- its gene leaves the rank kernel anyway -- may overhang: those keys go straight
@@ -692,12 +752,7 @@ __global__ __launch_bounds__(SRTG_NT) void k_bucket_big_runs_global(void *Xs, vo
         for (int b_lo = 0, b_hi; b_lo < B; b_lo = b_hi) { // (uniform)
             const u32 base = cnt[b_lo]; // (buckets from b_lo on: their starts, untouched so far)
             if (base >= (u32)n) break;
-            { // the first bucket behind b_lo that starts at or after base + T
-                int lo_b = b_lo + 1, hi_b = B;
-                const u32 t = base + (u32)T;
-                while (lo_b < hi_b) { const int mid = (lo_b + hi_b) >> 1; if (cnt[mid] >= t) hi_b = mid; else lo_b = mid + 1; }
-                b_hi = lo_b;
-            }
+            b_hi = first_start_at_or_after(cnt, b_lo + 1, B, base + (u32)T);
             const u32 end = b_hi < B ? cnt[b_hi] : (u32)n;
             __syncthreads(); // (every thread has read the starts before the first atomic moves one)
             run_for_keys<KeyT, NT>(run, n, tid, [&](KeyT k, int) {
@@ -728,41 +783,34 @@ __global__ __launch_bounds__(NT_) void k_bucket_big_runs(void *Xs, long long gen
     constexpr int NTK = NT_; // (256 threads; 1024 in a launch of its own for runs above 8192 keys: the LDS they take leaves room for two workgroups per CU)
     constexpr KeyT MAXK = KeyInfo<KeyT>::MAXK;
     KeyT *K = (KeyT *)srt_smem;
-    __shared__ KeyT s_min, s_max;
+    __shared__ KeyT s_kr[2];
     __shared__ u32 s_part[NTK / 64];
     __shared__ int s_list[NTK], s_nl;
     const int gene = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     u32 *cnt = (u32 *)(srt_smem + (size_t)cap * sizeof(KeyT)); // [buckets]
-    // the workgroup's stretch of the gene's candidate groups: their run lengths are looked at NTK at a time, the runs above 256 keys
-    // listed, the list walked (300 groups of 333 cells half non-zero are 1.5 M candidates none of which holds 256 keys)
+    // the workgroup's stretch of the gene's candidate groups: their run lengths are looked at NTK at a time, the runs above n_min keys
+    // listed, the list walked
     const int per = (n_cand + (int)gridDim.x - 1) / (int)gridDim.x, c_end = min(n_cand, ((int)blockIdx.x + 1) * per);
     for (int c0 = (int)blockIdx.x * per; c0 < c_end; c0 += NTK) {
-      if (tid == 0) s_nl = 0;
-      __syncthreads();
-      if (c0 + tid < c_end && (int)nnz[(size_t)gene * G + cand[c0 + tid]] > n_min) s_list[atomicAdd(&s_nl, 1)] = c0 + tid;
-      __syncthreads();
-      const int nl = s_nl;
+      const int nl = list_candidates(nnz + (size_t)gene * G, cand, c0, c_end, n_min, s_list, &s_nl, tid);
       for (int li = 0; li < nl; ++li) {
         const int cd = s_list[li], g = cand[cd];
         const int n = (int)nnz[(size_t)gene * G + g];
         KeyT *run = (KeyT *)Xs + (long long)gene * gene_stride + gofs[(size_t)gene * G + g];
         if (n > cap) { if (tid == 0 && !global_follows) route[gene] = 2u; continue; } // (uniform)
-        if (tid == 0) { s_min = MAXK; s_max = (KeyT)0; }
+        if (tid == 0) { s_kr[0] = MAXK; s_kr[1] = (KeyT)0; }
         __syncthreads();
         KeyT lo = MAXK, hi = (KeyT)0;
         run_for_keys<KeyT, NTK>(run, n, tid, [&](KeyT k, int i) { K[i] = k; lo = k < lo ? k : lo; hi = k > hi ? k : hi; });
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) { const KeyT a = __shfl_xor(lo, d), b = __shfl_xor(hi, d); lo = a < lo ? a : lo; hi = b > hi ? b : hi; }
-        if (lane == 0) { atomicMin(&s_min, lo); atomicMax(&s_max, hi); }
+        wg_key_range(lo, hi, s_kr, lane);
         __syncthreads();
         // about four keys per bucket
         int lg = 6;
         while (lg < SRT_LG_MAX && (4 << lg) < n) ++lg;
         const int B = 1 << lg;
-        const KeyT range = (KeyT)(s_max - s_min);
-        const int bits = range ? (int)(sizeof(KeyT) * 8) - (sizeof(KeyT) == 8 ? __clzll((long long)range) : __clz((int)range)) : 0;
+        const int bits = key_range_bits((KeyT)(s_kr[1] - s_kr[0]));
         BigRunFn<KeyT> f;
-        f.kmin = s_min;
+        f.kmin = s_kr[0];
         f.shift = bits > lg ? bits - lg : 0;
         if (tid == 0) big_fn[(size_t)gene * n_cand + cd] = f;
         for (int b = tid; b < B; b += NTK) cnt[b] = 0u;
@@ -774,21 +822,12 @@ __global__ __launch_bounds__(NT_) void k_bucket_big_runs(void *Xs, long long gen
             u32 loc[(1 << SRT_LG_MAX) / NTK], sum = 0;
 #pragma unroll
             for (int e = 0; e < (1 << SRT_LG_MAX) / NTK; ++e) { const int b = tid * per + e; loc[e] = (e < per && b < B) ? cnt[b] : 0u; sum += loc[e]; }
-            const u32 inc = (u32)wave_incl_scan_add((int)sum);
-            if (lane == 63) s_part[wave] = inc;
-            __syncthreads();
-            u32 base = inc - sum;
-            for (int w = 0; w < wave; ++w) base += s_part[w];
+            u32 base = wg_excl_scan(sum, s_part, lane, wave);
 #pragma unroll
             for (int e = 0; e < (1 << SRT_LG_MAX) / NTK; ++e) { const int b = tid * per + e; if (e < per && b < B) { cnt[b] = base; base += loc[e]; } }
         }
         __syncthreads();
-        if (run_cuts && n > OCR_COOP_MIN && tid >= 1 && tid <= OCR_CUTS) { // (as k_bucket_big_runs_global: the starts are still untouched)
-            const u32 t = (u32)((long long)n * tid / (OCR_CUTS + 1));
-            int lo_b = 0, hi_b = B;
-            while (lo_b < hi_b) { const int mid = (lo_b + hi_b) >> 1; if (cnt[mid] >= t) hi_b = mid; else lo_b = mid + 1; }
-            run_cuts[((size_t)gene * n_cand + cd) * OCR_CUTS + (tid - 1)] = lo_b < B ? cnt[lo_b] : (u32)n;
-        }
+        if (run_cuts && n > OCR_COOP_MIN) write_run_cuts(run_cuts + ((size_t)gene * n_cand + cd) * OCR_CUTS, cnt, B, n, tid);
         __syncthreads();
         // (dealt into a second LDS buffer first and written back in whole lines: no faster on dense input -- 11.05 vs 11.06 ms, 10 groups of
         //  30 000 cells -- and the LDS it takes halves the workgroups per CU: 1.43 -> 2.59 ms on CSC input with 50 groups)
@@ -844,27 +883,14 @@ __global__ __launch_bounds__(1024) void k_ref_cuts(OvoCompactParams P, PartCuts<
     const KeyT *Xg = (const KeyT *)P.Xs + (long long)gene * P.gene_stride;
     const KeyT *src = P.ref_by_gofs ? Xg + P.gofs[(size_t)gene * G + P.ref] : Xg + P.ref_out;
     const u16 *seg_nnz = P.seg_nnz + (size_t)gene * P.nseg;
-    auto for_ref = [&](auto f) {
-        for (int sg = wave; sg < P.nseg; sg += NW) {
-            const int c = (int)seg_nnz[sg];
-            const KeyT *sp = src + (size_t)sg * GCMP_SEG_ROWS;
-            for (int i = lane; i < c; i += 64) f(sp[i]);
-        }
-    };
     for (int i = tid; i < NC; i += NT) cells[i] = 0u;
     if (tid == 0) { s_kr[0] = MAXK; s_kr[1] = (KeyT)0; s_n = 0u; }
     __syncthreads();
     for (int sg = tid; sg < P.nseg; sg += NT) atomicAdd(&s_n, (u32)seg_nnz[sg]);
     {
         KeyT tmin = MAXK, tmax = (KeyT)0;
-        for_ref([&](KeyT k) { tmin = k < tmin ? k : tmin; tmax = k > tmax ? k : tmax; });
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            const KeyT o1 = __shfl_xor(tmin, d), o2 = __shfl_xor(tmax, d);
-            tmin = o1 < tmin ? o1 : tmin;
-            tmax = o2 > tmax ? o2 : tmax;
-        }
-        if (lane == 0) { atomicMin(&s_kr[0], tmin); atomicMax(&s_kr[1], tmax); }
+        ocr_ref_for_keys<NW>(src, seg_nnz, P.nseg, wave, lane, [&](KeyT k) { tmin = k < tmin ? k : tmin; tmax = k > tmax ? k : tmax; });
+        wg_key_range(tmin, tmax, s_kr, lane);
     }
     __syncthreads();
     const u32 n_all = s_n, cap_s = (u32)P.ref_cap - (u32)P.ref_cap / 8u;
@@ -874,19 +900,15 @@ __global__ __launch_bounds__(1024) void k_ref_cuts(OvoCompactParams P, PartCuts<
         if (tid == 0) { C.n_parts = 0u; P.route[gene] = P.ref_by_gofs ? 1u : (1u | (1u << 8)); }
         return;
     }
-    const KeyT kmin = s_kr[0], range = (KeyT)(s_kr[1] - s_kr[0]);
-    const int bits = range ? (int)(sizeof(KeyT) * 8) - (sizeof(KeyT) == 8 ? __clzll((long long)range) : __clz((int)range)) : 0;
+    const KeyT kmin = s_kr[0];
+    const int bits = key_range_bits((KeyT)(s_kr[1] - s_kr[0]));
     const int cs0 = bits > OCR_CELL_LG ? bits - OCR_CELL_LG : 0;
-    for_ref([&](KeyT k) { atomicAdd(&cells[(u32)((KeyT)(k - kmin) >> cs0)], 1u); });
+    ocr_ref_for_keys<NW>(src, seg_nnz, P.nseg, wave, lane, [&](KeyT k) { atomicAdd(&cells[(u32)((KeyT)(k - kmin) >> cs0)], 1u); });
     __syncthreads();
     u32 c4[CPT], sum = 0;
 #pragma unroll
     for (int e = 0; e < CPT; ++e) { c4[e] = cells[tid * CPT + e]; sum += c4[e]; }
-    const u32 inc = (u32)wave_incl_scan_add((int)sum);
-    if (lane == 63) s_scan[wave] = inc;
-    __syncthreads();
-    u32 ex = inc - sum;
-    for (int w = 0; w < wave; ++w) ex += s_scan[w];
+    u32 ex = wg_excl_scan(sum, s_scan, lane, wave);
     if (tid == 0) { C.n_parts = (u32)n_parts; C.n_all = n_all; C.kmin = kmin; C.kmax = s_kr[1]; C.lo[0] = (KeyT)0; C.n_low[0] = 0u; C.n_low[n_parts] = n_all; }
     // the cut in front of part j: the cell in which the running count passes j / P of the keys (the cell itself goes to part j)
 #pragma unroll
@@ -976,162 +998,133 @@ __global__ __launch_bounds__(DEAL_NT) void k_deal_runs(OvoCompactParams P, const
 // the zeros.  (Replaces, for references of any size, what rank_sum_and_ties_from_sorted does by merging: utils/ranking.py:52-158.)
 // NT_ = 256: small references and few groups (a wide matrix: 120 000 genes x 20 000 cells): a gene is a few microseconds of work behind a
 // dozen barriers -- several small workgroups per CU overlap them (one of 1024 threads per CU: 11.4 ms at that shape).
-template <typename KeyT, bool EQ, bool PARTS = false, int NT_ = OCR_NT>
-__global__ __launch_bounds__(NT_) void k_ovo_rank_compact(OvoCompactParams P) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int NT = NT_, NW = NT / 64, KMAX = OCR_KMAX;
+//
+// The kernel is a sequence of steps, each a function below: setup -- build the reference's table or leave (ocr_build_ref: census, the
+// part's range and bucket function, coarse cells, counters, crowd test and hand-over, scan, scatter, T_A) -- the groups of at most 256
+// keys (ocr_few_groups or ocr_group_blocks) -- the longer runs (ocr_big_runs, then ocr_long_runs with every wavefront).  The look-up
+// rounds are chosen in ocr_lookup, a dealt run's stretch in ocr_part_stretch, a long run's descriptor in ocr_big_run, and the statistic
+// is formed and written in ocr_emit, nowhere else.
+
+// What the steps of one workgroup -- one (gene, part) -- share.
+template <typename KeyT> struct OcrWg {
+    int tid, lane, wave, gene, part, G, ref, n_ref;
+    int n_parts_gene;       // PARTS: the parts this gene's reference is taken in
+    u16 *nnz;               // [G] the gene's run lengths
+    KeyT *Xg, *src;         // its packed keys; the reference's segments among them ...
+    const u16 *seg_nnz;     // ... and their lengths
+    // known once ocr_build_ref is through:
+    u32 nA, n_low;          // the part's reference keys; the reference's non-zero keys below the part
+    u32 aZ, nneg;           // the reference's zeros; its keys below zero
+    KeyT p_lo, p_hi;        // the part's key range, both ends included (part 0 starts at 0, the last part ends at MAXK)
+    u64 T_A;                // ties among the part's reference keys: sum over keys of (run length^2 - 1)
+};
+
+// the reference's keys of this part to f
+template <bool PARTS, int NW, typename KeyT, typename F> __device__ __forceinline__ void ocr_part_for_keys(const OvoCompactParams &P, const OcrWg<KeyT> &W, F f) {
+    if constexpr (PARTS) ocr_ref_for_keys<NW>(W.src, W.seg_nnz, P.nseg, W.wave, W.lane, [&](KeyT k) { if (k >= W.p_lo && k <= W.p_hi) f(k); });
+    else ocr_ref_for_keys<NW>(W.src, W.seg_nnz, P.nseg, W.wave, W.lane, f);
+}
+// Clears the tables; counts the reference's non-zero keys and decides whose gene this is (false: not this launch's, or not this part's);
+// then the keys' range and negatives, the longest ranked run and the reference's value sum.  A barrier must follow.
+template <typename KeyT, bool EQ, bool PARTS, int NT> __device__ __forceinline__ bool ocr_ref_census(const OvoCompactParams &P, const OcrSmem<KeyT> &S, OcrWg<KeyT> &W) {
+    constexpr int NW = NT / 64;
     constexpr KeyT ZEROK = KeyInfo<KeyT>::ZEROK, MAXK = KeyInfo<KeyT>::MAXK;
-    const int NWD = (1 << P.nbk_lg) >> 4; // table words
-    KeyT *A = (KeyT *)smem;
-    size_t off = (((size_t)P.ref_cap + 4) * sizeof(KeyT) + 15) & ~(size_t)15;
-    u32 *tab = (u32 *)(smem + off);
-    off += ((size_t)NWD + 2) * 8;
-    u32 *bloom_all = (u32 *)(smem + off);
-    off += (size_t)NW * OCR_BLOOM_WORDS * 4;
-    u32 *ctab = (u32 *)(smem + off); // [256] coarse cells (EQ)
-    u32 *ccnt = ctab + 256;          // [256] their key counts
-    off += 2048;
-    u64 *s_red = (u64 *)(smem + off); // [NW]
-    KeyT *s_kr = (KeyT *)(s_red + NW); // [2] min, max
-    u32 *s_cnt = (u32 *)(s_kr + 2);    // [0] negatives  [1] non-zero keys  [2] fullest overfull word  [3] largest group  [4] keys in overfull words
-    u32 *s_scan = s_cnt + 8;           // [NW]
-    u32 *s_b = s_scan + NW;            // PARTS: [0] first cell of the part  [1] reference keys below it  [2] one past its last cell  [3] keys below that
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // (part-major: the workgroups of part 0 first.  Gene-major would put the parts a gene does NOT need -- workgroups that return at once --
-    //  on every n_parts-th workgroup slot, i.e. on fixed XCDs: with two parts, half of the chip idle whenever the genes need one.)
-    const int gene = PARTS ? (int)blockIdx.x % P.n_genes : (int)blockIdx.x;
-    const int part = PARTS ? (int)blockIdx.x / P.n_genes : 0;
-    if (P.gene_flags && P.gene_flags[gene] == 0u) return; // (uniform)
-    if (P.big_sorted && (P.route[gene] & 255u) == 2u) return; // (uniform) k_bucket_big_runs met a run beyond its slots: the general route's gene
-    const int G = P.G, ref = P.ref;
-    const int n_ref = P.counts[ref];
-    u16 *nnz = P.nnz + (size_t)gene * G;
-    KeyT *Xg = (KeyT *)P.Xs + (long long)gene * P.gene_stride;
-    KeyT *src = P.ref_by_gofs ? Xg + P.gofs[(size_t)gene * G + ref] : Xg + P.ref_out;
-    const u16 *seg_nnz = P.seg_nnz + (size_t)gene * P.nseg;
-    // the reference's non-zero keys lie in nseg packed segments: wavefront w walks segments w, w + NW, ...
-    auto for_ref = [&](auto f) {
-        for (int sg = wave; sg < P.nseg; sg += NW) {
-            const int c = (int)seg_nnz[sg];
-            const KeyT *sp = src + (size_t)sg * GCMP_SEG_ROWS;
-            for (int i = lane; i < c; i += 64) f(sp[i]);
-        }
-    };
-
-    // ---- the reference's non-zero keys -> value buckets ----
-    for (int i = tid; i < NW * OCR_BLOOM_WORDS; i += NT) bloom_all[i] = 0u;
+    const int tid = W.tid, lane = W.lane, NWD = (1 << P.nbk_lg) >> 4; // table words
+    for (int i = tid; i < NW * OCR_BLOOM_WORDS; i += NT) S.bloom[i] = 0u;
     {
-        uint4 *t4 = (uint4 *)tab; // (the table starts on a 16-byte boundary and holds an even number of 64-bit words)
+        uint4 *t4 = (uint4 *)S.tab; // (the table starts on a 16-byte boundary and holds an even number of 64-bit words)
         for (int i = tid; i < (NWD + 2) / 2; i += NT) t4[i] = make_uint4(0u, 0u, 0u, 0u);
     }
-    if (EQ && tid < 256) ccnt[tid] = 0u;
-    if (tid == 0) { s_kr[0] = MAXK; s_kr[1] = (KeyT)0; s_cnt[0] = 0u; s_cnt[1] = 0u; s_cnt[2] = 0u; s_cnt[3] = 0u; s_cnt[4] = 0u; s_red[0] = 0ull; }
+    if (EQ && tid < 256) S.ccnt[tid] = 0u;
+    if (tid == 0) { S.s_kr[0] = MAXK; S.s_kr[1] = (KeyT)0; S.s_cnt[0] = 0u; S.s_cnt[1] = 0u; S.s_cnt[2] = 0u; S.s_cnt[3] = 0u; S.s_cnt[4] = 0u; S.s_red[0] = 0ull; }
     __syncthreads();
-    for (int sg = tid; sg < P.nseg; sg += NT) atomicAdd(&s_cnt[1], (u32)seg_nnz[sg]); // (a reference of any size: nseg = n_ref / 512)
-    int n_parts_gene = 1;
+    for (int sg = tid; sg < P.nseg; sg += NT) atomicAdd(&S.s_cnt[OCR_N_KEYS], (u32)W.seg_nnz[sg]); // (a reference of any size: nseg = n_ref / 512)
+    W.n_parts_gene = 1;
     if constexpr (!PARTS) {
         if (P.needs_parts) { // (uniform) a PARTS launch follows: the genes beyond the slots are its own
             __syncthreads();
-            if (s_cnt[1] > (u32)P.ref_cap) { if (tid == 0) P.needs_parts[gene] = 1u; return; }
+            if (S.s_cnt[OCR_N_KEYS] > (u32)P.ref_cap) { if (tid == 0) P.needs_parts[W.gene] = 1u; return false; }
         }
     }
     if constexpr (PARTS) { // how many parts this gene's reference needs (an eighth of the slots is slack: the cuts fall on cell boundaries)
-        if (P.needs_parts[gene] == 0u) return; // (uniform) the plain kernel's gene
-        n_parts_gene = (int)((const PartCuts<KeyT> *)P.cuts)[gene].n_parts; // (0: more parts than the launch has -- k_ref_cuts flagged the gene)
-        if (part >= n_parts_gene) return;       // (uniform)
+        if (P.needs_parts[W.gene] == 0u) return false; // (uniform) the plain kernel's gene
+        W.n_parts_gene = (int)((const PartCuts<KeyT> *)P.cuts)[W.gene].n_parts; // (0: more parts than the launch has -- k_ref_cuts flagged the gene)
+        if (W.part >= W.n_parts_gene) return false;       // (uniform)
     }
-    {
-        KeyT tmin = MAXK, tmax = (KeyT)0;
-        u32 ng = 0;
-        for_ref([&](KeyT k) {
-            tmin = k < tmin ? k : tmin;
-            tmax = k > tmax ? k : tmax;
-            ng += k < ZEROK ? 1u : 0u;
-        });
-        ng = (u32)wave_sum((int)ng);
+    KeyT tmin = MAXK, tmax = (KeyT)0;
+    u32 ng = 0;
+    ocr_ref_for_keys<NW>(W.src, W.seg_nnz, P.nseg, W.wave, lane, [&](KeyT k) { tmin = k < tmin ? k : tmin; tmax = k > tmax ? k : tmax; ng += k < ZEROK ? 1u : 0u; });
+    ng = (u32)wave_sum((int)ng);
+    wg_key_range(tmin, tmax, S.s_kr, lane);
+    if (lane == 0 && ng) atomicAdd(&S.s_cnt[OCR_N_NEG], ng);
+    u32 gmax = 0;
+    for (int gq = tid; gq < W.G; gq += NT) gmax = max(gmax, gq == W.ref ? 0u : (u32)W.nnz[gq]);
+    gmax = (u32)wave_incl_scan_max((int)gmax);
+    if (lane == 63 && gmax) atomicMax(&S.s_cnt[OCR_G_MAX], gmax);
+    if (tid == NT - 1 && P.seg_sum && W.part == 0) { // the reference's value sum: its segments' sums in order
+        double t = 0.0;
+        for (int sg = 0; sg < P.nseg; ++sg) t += P.seg_sum[(size_t)W.gene * P.nseg + sg];
+        P.out_sum[(size_t)W.gene * W.G + W.ref] = t;
+    }
+    return true;
+}
+// The part's key range and reference keys (PARTS: k_ref_cuts has them; else everything), the empty key slots, the bucket function.
+template <typename KeyT, bool EQ, bool PARTS, int NT> __device__ __forceinline__ void ocr_part_range(const OvoCompactParams &P, const OcrSmem<KeyT> &S, OcrWg<KeyT> &W, OcrRef<KeyT, EQ> &R) {
+    constexpr KeyT MAXK = KeyInfo<KeyT>::MAXK;
+    const u32 nA_all = S.s_cnt[OCR_N_KEYS];
+    W.aZ = (u32)W.n_ref - nA_all;
+    W.nA = nA_all; W.n_low = 0; W.p_lo = (KeyT)0; W.p_hi = MAXK;
+    KeyT kmin_p = S.s_kr[0], kmax_p = S.s_kr[1];  // the range the part's value buckets cover
+    if constexpr (PARTS) {
+        const PartCuts<KeyT> &C = ((const PartCuts<KeyT> *)P.cuts)[W.gene];
+        W.n_low = C.n_low[W.part];
+        W.nA = C.n_low[W.part + 1] - W.n_low;
+        if (W.part > 0) { W.p_lo = C.lo[W.part]; kmin_p = W.p_lo; }
+        if (W.part + 1 < W.n_parts_gene) { W.p_hi = (KeyT)(C.lo[W.part + 1] - (KeyT)1); kmax_p = W.p_hi; }
+    }
+    const u32 nA = W.nA;
+    for (u32 i = W.tid; i < min(nA, (u32)P.ref_cap) + 4u; i += NT) S.A[i] = MAXK; // empty slots (the scatter claims them by compare-and-swap) and the pad
+    R.A = S.A; R.tab = S.tab; R.ctab = S.ctab; R.last = (1u << P.nbk_lg) - 1u;
+    R.kmin = nA ? kmin_p : (KeyT)0;
+    const int bits = key_range_bits(nA ? (KeyT)(kmax_p - kmin_p) : (KeyT)0);
+    R.shift = bits > P.nbk_lg ? bits - P.nbk_lg : 0;
+    R.cshift = bits > 8 ? bits - 8 : 0;
+    R.cmask = (KeyT)(((KeyT)1 << R.cshift) - (KeyT)1);
+    R.nA = nA;
+}
+// EQ: key counts of the 256 coarse cells -> each cell's share of the fine buckets (ctab).  Barriers inside and at the end.
+template <typename KeyT, bool PARTS, int NT> __device__ __forceinline__ void ocr_coarse_cells(const OvoCompactParams &P, const OcrSmem<KeyT> &S, const OcrWg<KeyT> &W, const OcrRef<KeyT, true> &R) {
+    ocr_part_for_keys<PARTS, NT / 64>(P, W, [&](KeyT k) { atomicAdd(&S.ccnt[(u32)((KeyT)(k - R.kmin) >> R.cshift)], 1u); });
+    __syncthreads();
+    if (W.wave == 0) { // four cells per lane.  A cell of cnt keys asks for cnt (NB - 256) / (2 n) buckets, rounded up to a power of
+        // two (less than twice that) and at least one: the shares add up to at most NB
+        const int lane = W.lane;
+        const u64 nb_free = (u64)(1u << P.nbk_lg) - 256ull, den = 2ull * (u64)max(W.nA, 1u);
+        u32 e4[4], sz = 0;
 #pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            const KeyT o1 = __shfl_xor(tmin, d), o2 = __shfl_xor(tmax, d);
-            tmin = o1 < tmin ? o1 : tmin;
-            tmax = o2 > tmax ? o2 : tmax;
+        for (int j = 0; j < 4; ++j) {
+            const u64 want = (u64)S.ccnt[lane * 4 + j] * nb_free / den;
+            u32 e = want <= 1ull ? 0u : (u32)(64 - __clzll((long long)(want - 1ull)));
+            e = min(e, (u32)R.cshift);
+            e4[j] = e;
+            sz += 1u << e;
         }
-        if (lane == 0) {
-            atomicMin(&s_kr[0], tmin);
-            atomicMax(&s_kr[1], tmax);
-            if (ng) atomicAdd(&s_cnt[0], ng);
-        }
-        u32 gmax = 0;
-        for (int gq = tid; gq < G; gq += NT) gmax = max(gmax, gq == ref ? 0u : (u32)nnz[gq]);
-        gmax = (u32)wave_incl_scan_max((int)gmax);
-        if (lane == 63 && gmax) atomicMax(&s_cnt[3], gmax);
-        if (tid == NT - 1 && P.seg_sum && part == 0) { // the reference's value sum: its segments' sums in order
-            double t = 0.0;
-            for (int sg = 0; sg < P.nseg; ++sg) t += P.seg_sum[(size_t)gene * P.nseg + sg];
-            P.out_sum[(size_t)gene * G + ref] = t;
+        u32 base = (u32)wave_incl_scan_add((int)sz) - sz;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            S.ctab[lane * 4 + j] = base | (((u32)R.cshift - e4[j]) << 24);
+            base += 1u << e4[j];
         }
     }
     __syncthreads();
-    const u32 nA_all = s_cnt[1];
-    const u32 aZ = (u32)n_ref - nA_all;
-    u32 nA = nA_all, n_low = 0;               // the part's reference keys; the reference's non-zero keys below the part
-    KeyT p_lo = (KeyT)0, p_hi = MAXK;         // the part's key range, both ends included (part 0 starts at 0, the last part ends at MAXK)
-    KeyT kmin_p = s_kr[0], kmax_p = s_kr[1];  // the range its value buckets cover
-    if constexpr (PARTS) { // this part's key range, the reference's keys below it and inside it: k_ref_cuts has them
-        const PartCuts<KeyT> &C = ((const PartCuts<KeyT> *)P.cuts)[gene];
-        n_low = C.n_low[part];
-        nA = C.n_low[part + 1] - n_low;
-        if (part > 0) { p_lo = C.lo[part]; kmin_p = p_lo; }
-        if (part + 1 < n_parts_gene) { p_hi = (KeyT)(C.lo[part + 1] - (KeyT)1); kmax_p = p_hi; }
-    }
-    auto for_part = [&](auto f) { // the reference's keys of this part
-        if constexpr (PARTS) for_ref([&](KeyT k) { if (k >= p_lo && k <= p_hi) f(k); });
-        else for_ref(f);
-    };
-    for (u32 i = tid; i < min(nA, (u32)P.ref_cap) + 4u; i += NT) A[i] = MAXK; // empty slots (the scatter claims them by compare-and-swap) and the pad
-    OcrRef<KeyT, EQ> R;
-    R.A = A; R.tab = tab; R.last = (1u << P.nbk_lg) - 1u;
-    R.kmin = nA ? kmin_p : (KeyT)0;
-    R.ctab = ctab;
-    {
-        const KeyT range = nA ? (KeyT)(kmax_p - kmin_p) : (KeyT)0;
-        const int bits = range ? (int)(sizeof(KeyT) * 8) - (sizeof(KeyT) == 8 ? __clzll((long long)range) : __clz((int)range)) : 0;
-        R.shift = bits > P.nbk_lg ? bits - P.nbk_lg : 0;
-        R.cshift = bits > 8 ? bits - 8 : 0;
-        R.cmask = (KeyT)(((KeyT)1 << R.cshift) - (KeyT)1);
-    }
-    R.nA = nA;
-    if constexpr (EQ) { // key counts of the 256 coarse cells -> each cell's share of the fine buckets
-        for_part([&](KeyT k) { atomicAdd(&ccnt[(u32)((KeyT)(k - R.kmin) >> R.cshift)], 1u); });
-        __syncthreads();
-        if (wave == 0) { // four cells per lane.  A cell of cnt keys asks for cnt (NB - 256) / (2 n) buckets, rounded up to a power of
-            // two (less than twice that) and at least one: the shares add up to at most NB
-            const u64 nb_free = (u64)(1u << P.nbk_lg) - 256ull, den = 2ull * (u64)max(nA, 1u);
-            u32 e4[4], sz = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const u64 want = (u64)ccnt[lane * 4 + j] * nb_free / den;
-                u32 e = want <= 1ull ? 0u : (u32)(64 - __clzll((long long)(want - 1ull)));
-                e = min(e, (u32)R.cshift);
-                e4[j] = e;
-                sz += 1u << e;
-            }
-            u32 base = (u32)wave_incl_scan_add((int)sz) - sz;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ctab[lane * 4 + j] = base | (((u32)R.cshift - e4[j]) << 24);
-                base += 1u << e4[j];
-            }
-        }
-        __syncthreads();
-    }
-    const u32 nneg = s_cnt[0];
-    // counters: +1 on the bucket's two bits; a bucket already at 3 takes the increment back and marks its word overfull (the
-    // carry it sent into the next field in between is removed by the subtraction; whatever the fields of such a word end up
-    // holding is never used).  The word's key count is kept in the high half meanwhile.
-    for_part([&](KeyT k) {
+}
+// Counters: +1 on the bucket's two bits; a bucket already at 3 takes the increment back and marks its word overfull (the carry it sent
+// into the next field in between is removed by the subtraction; whatever the fields of such a word end up holding is never used).  The
+// word's key count is kept in the high half meanwhile.
+template <typename KeyT, bool EQ, bool PARTS, int NT> __device__ __forceinline__ void ocr_count_keys(const OvoCompactParams &P, const OcrSmem<KeyT> &S, const OcrWg<KeyT> &W, const OcrRef<KeyT, EQ> &R) {
+    ocr_part_for_keys<PARTS, NT / 64>(P, W, [&](KeyT k) {
         const u32 b = ocr_bucket(R, k), sh = (b & 15u) << 1;
-        u32 *pw = tab + 2 * (b >> 4);
+        u32 *pw = S.tab + 2 * (b >> 4);
         atomicAdd(&pw[1], 1u);
         const u32 old = atomicAdd(&pw[0], 1u << sh);
         if (((old >> sh) & 3u) == 3u) {
@@ -1139,210 +1132,223 @@ __global__ __launch_bounds__(NT_) void k_ovo_rank_compact(OvoCompactParams P) {
             atomicOr(&pw[1], 0x80000000u);
         }
     });
-    __syncthreads();
-    { // exclusive scan of the words' key counts.  Each wavefront owns a contiguous slice and walks it 64 words at a time.
-        const int per_wave = NWD / NW, iters = per_wave / 64; // NWD >= NW * 64
-        u32 *slice = tab + 2 * (wave * per_wave);
-        u32 tot = 0, fmax = 0, ftot = 0;
-        u64 fsq = 0;
-        for (int it = 0; it < iters; ++it) {
-            const u32 h = slice[2 * (it * 64 + lane) + 1], c = h & 0xFFFFu;
-            tot += c;
-            if (h >> 31) { fmax = max(fmax, c); ftot += c; fsq += (u64)c * c; }
-        }
-        tot = (u32)wave_sum((int)tot);
-        ftot = (u32)wave_sum((int)ftot);
-        fmax = (u32)wave_incl_scan_max((int)fmax);
-        if constexpr (PARTS) fsq = wave_sum<u64>(fsq);
-        if (lane == 0) { s_scan[wave] = tot; if (ftot) atomicAdd(&s_cnt[4], ftot); if (PARTS && fsq) atomicAdd((unsigned long long *)&s_red[0], (unsigned long long)fsq); }
-        if (lane == 63 && fmax) atomicMax(&s_cnt[2], fmax);
-        __syncthreads();
-        // Crowded tables.  What such a gene falls back to is k_ovo_rank (30 us a gene) without parts -- the thresholds are tuned for that --
-        // but the general route with them (a per-gene radix sort in HBM: 50 ms for a column of two million cells): there the gene stays
-        // unless the key-by-key walks would cost more than that -- a look-up that meets an overfull word of c keys walks c keys, and
-        // meets it with probability ~ c / nA: the expected walk is sum c^2 / nA keys per look-up; 32 is where the walks double the kernel.
-        const bool crowded = PARTS ? s_red[0] > 32ull * (u64)nA : (s_cnt[2] > OCR_MAX_WORD || s_cnt[4] * 2u > nA);
-        if (nA > (u32)P.ref_cap || crowded || (s_cnt[3] > 64u * OCR_KMAX && !P.big_sorted)) { // uniform: this gene goes to k_ovo_rank
-            if constexpr (PARTS) { // (the other parts of the gene are reading the segments: nothing is moved; the gene takes the general route)
-                // (dense layout: a reason in the high bits keeps k_ovo_rank away; regrouped sparse input: the reference is one run, that kernel can take it)
-                if (tid == 0) P.route[gene] = P.ref_by_gofs ? 1u : (1u | ((nA > (u32)P.ref_cap ? 2u : crowded ? 3u : 5u) << 8));
-#ifdef OCR_DEBUG_PRINT
-                if (tid == 0) printf("left: gene %d part %d/%d nA %u of %u, fullest word %u, in overfull words %u, kmin %llx kmax %llx, part range %llx .. %llx, n_low %u\n", gene, part,
-                                     n_parts_gene, nA, nA_all, s_cnt[2], s_cnt[4], (unsigned long long)s_kr[0], (unsigned long long)s_kr[1], (unsigned long long)kmin_p, (unsigned long long)kmax_p, n_low);
-#endif
-                return;
-            }
-            u32 dst = P.nseg ? (u32)seg_nnz[0] : 0u;
-            for (int sg = 1; sg < P.nseg; ++sg) { // move the reference's segments together (a segment holds at most GCMP_SEG_ROWS keys: NT keys a step)
-                const u32 c = (u32)seg_nnz[sg];
-                for (u32 o = 0; o < c; o += (u32)NT) { // (the destination ends below the source's start: a step's reads come before its writes, steps in order)
-                    KeyT k = (KeyT)0;
-                    if (o + (u32)tid < c) k = src[(size_t)sg * GCMP_SEG_ROWS + o + tid];
-                    __syncthreads();
-                    if (o + (u32)tid < c) src[dst + o + tid] = k;
-                    __syncthreads();
-                }
-                dst += c;
-            }
-            if (tid == 0) { nnz[ref] = (u16)nA; if (!P.ref_by_gofs) P.gofs[(size_t)gene * G + ref] = (u32)P.ref_out; P.route[gene] = 1u; }
-            return;
-        }
-        u32 base = 0;
-        for (int w = 0; w < wave; ++w) base += s_scan[w];
-        for (int it = 0; it < iters; ++it) {
-            const u32 h = slice[2 * (it * 64 + lane) + 1], c = h & 0xFFFFu;
-            const u32 inc = (u32)wave_incl_scan_add((int)c);
-            slice[2 * (it * 64 + lane) + 1] = (base + inc - c) | (h & 0x80000000u);
-            base += (u32)__builtin_amdgcn_readlane((int)inc, 63);
-        }
-        if (tid == 0) { tab[2 * NWD + 1] = nA; tab[2 * NWD + 3] = nA; } // sentinel words: where the last word's keys end
+}
+// Exclusive scan of the words' key counts -- each wavefront owns a contiguous slice and walks it 64 words at a time -- with, between
+// its two halves, the crowd test: false when this gene leaves the kernel (flagged in route; the plain kernel moves the reference's
+// segments together for k_ovo_rank first).  Barriers inside.
+template <typename KeyT, bool PARTS, int NT> __device__ __forceinline__ bool ocr_scan_or_leave(const OvoCompactParams &P, const OcrSmem<KeyT> &S, const OcrWg<KeyT> &W) {
+    constexpr int NW = NT / 64;
+    const int tid = W.tid, lane = W.lane, wave = W.wave, NWD = (1 << P.nbk_lg) >> 4;
+    const u32 nA = W.nA;
+    const int per_wave = NWD / NW, iters = per_wave / 64; // NWD >= NW * 64
+    u32 *slice = S.tab + 2 * (wave * per_wave);
+    u32 tot = 0, fmax = 0, ftot = 0;
+    u64 fsq = 0;
+    for (int it = 0; it < iters; ++it) {
+        const u32 h = slice[2 * (it * 64 + lane) + 1], c = h & 0xFFFFu;
+        tot += c;
+        if (h >> 31) { fmax = max(fmax, c); ftot += c; fsq += (u64)c * c; }
     }
+    tot = (u32)wave_sum((int)tot);
+    ftot = (u32)wave_sum((int)ftot);
+    fmax = (u32)wave_incl_scan_max((int)fmax);
+    if constexpr (PARTS) fsq = wave_sum<u64>(fsq);
+    if (lane == 0) { S.s_scan[wave] = tot; if (ftot) atomicAdd(&S.s_cnt[OCR_IN_FULL], ftot); if (PARTS && fsq) atomicAdd((unsigned long long *)&S.s_red[0], (unsigned long long)fsq); }
+    if (lane == 63 && fmax) atomicMax(&S.s_cnt[OCR_FULLEST], fmax);
     __syncthreads();
-    // scatter: a key's bucket owns the slots [lo, hi) (an overfull word: the word's slots); the first empty one is claimed
-    for_part([&](KeyT k) {
-        const u32 b = ocr_bucket(R, k), W = b >> 4, sh = (b & 15u) << 1;
-        const u32 w = tab[2 * W], h = tab[2 * W + 1];
+    // Crowded tables.  What such a gene falls back to is k_ovo_rank (30 us a gene) without parts -- the thresholds are tuned for that --
+    // but the general route with them (a per-gene radix sort in HBM: 50 ms for a column of two million cells): there the gene stays
+    // unless the key-by-key walks would cost more than that -- a look-up that meets an overfull word of c keys walks c keys, and
+    // meets it with probability ~ c / nA: the expected walk is sum c^2 / nA keys per look-up; 32 is where the walks double the kernel.
+    const bool crowded = PARTS ? S.s_red[0] > 32ull * (u64)nA : (S.s_cnt[OCR_FULLEST] > OCR_MAX_WORD || S.s_cnt[OCR_IN_FULL] * 2u > nA);
+    if (nA > (u32)P.ref_cap || crowded || (S.s_cnt[OCR_G_MAX] > 64u * OCR_KMAX && !P.big_sorted)) { // uniform: this gene goes to k_ovo_rank
+        if constexpr (PARTS) { // (the other parts of the gene are reading the segments: nothing is moved; the gene takes the general route)
+            // (dense layout: a reason in the high bits keeps k_ovo_rank away; regrouped sparse input: the reference is one run, that kernel can take it)
+            if (tid == 0) P.route[W.gene] = P.ref_by_gofs ? 1u : (1u | ((nA > (u32)P.ref_cap ? 2u : crowded ? 3u : 5u) << 8));
+            return false;
+        }
+        KeyT *src = W.src;
+        u32 dst = P.nseg ? (u32)W.seg_nnz[0] : 0u;
+        for (int sg = 1; sg < P.nseg; ++sg) { // move the reference's segments together (a segment holds at most GCMP_SEG_ROWS keys: NT keys a step)
+            const u32 c = (u32)W.seg_nnz[sg];
+            for (u32 o = 0; o < c; o += (u32)NT) { // (the destination ends below the source's start: a step's reads come before its writes, steps in order)
+                KeyT k = (KeyT)0;
+                if (o + (u32)tid < c) k = src[(size_t)sg * GCMP_SEG_ROWS + o + tid];
+                __syncthreads();
+                if (o + (u32)tid < c) src[dst + o + tid] = k;
+                __syncthreads();
+            }
+            dst += c;
+        }
+        if (tid == 0) { W.nnz[W.ref] = (u16)nA; if (!P.ref_by_gofs) P.gofs[(size_t)W.gene * W.G + W.ref] = (u32)P.ref_out; P.route[W.gene] = 1u; }
+        return false;
+    }
+    u32 base = 0;
+    for (int w = 0; w < wave; ++w) base += S.s_scan[w];
+    for (int it = 0; it < iters; ++it) {
+        const u32 h = slice[2 * (it * 64 + lane) + 1], c = h & 0xFFFFu;
+        const u32 inc = (u32)wave_incl_scan_add((int)c);
+        slice[2 * (it * 64 + lane) + 1] = (base + inc - c) | (h & 0x80000000u);
+        base += (u32)__builtin_amdgcn_readlane((int)inc, 63);
+    }
+    if (tid == 0) { S.tab[2 * NWD + 1] = nA; S.tab[2 * NWD + 3] = nA; } // sentinel words: where the last word's keys end
+    return true;
+}
+// Scatter: a key's bucket owns the slots [lo, hi) (an overfull word: the word's slots); the first empty one is claimed.
+template <typename KeyT, bool EQ, bool PARTS, int NT> __device__ __forceinline__ void ocr_scatter(const OvoCompactParams &P, const OcrSmem<KeyT> &S, const OcrWg<KeyT> &W, const OcrRef<KeyT, EQ> &R) {
+    constexpr KeyT MAXK = KeyInfo<KeyT>::MAXK;
+    ocr_part_for_keys<PARTS, NT / 64>(P, W, [&](KeyT k) {
+        const u32 b = ocr_bucket(R, k), Wd = b >> 4, sh = (b & 15u) << 1;
+        const u32 w = S.tab[2 * Wd], h = S.tab[2 * Wd + 1];
         u32 lo, hi;
-        if (h >> 31) { lo = h & 0xFFFFu; hi = tab[2 * W + 3] & 0xFFFFu; }
+        if (h >> 31) { lo = h & 0xFFFFu; hi = S.tab[2 * Wd + 3] & 0xFFFFu; }
         else { lo = h + ocr_below(w, sh); hi = lo + ((w >> sh) & 3u); }
         if (k != MAXK) // (a key equal to the empty marker is in place already)
             for (u32 t = lo; t < hi; ++t)
-                if (atomicCAS(&A[t], MAXK, k) == MAXK) break;
+                if (atomicCAS(&S.A[t], MAXK, k) == MAXK) break;
     });
+}
+// T_A: ties among the part's reference keys, sum over keys of (run length^2 - 1).  A barrier inside.
+template <typename KeyT, bool EQ, int NT> __device__ __forceinline__ u64 ocr_ref_ties(const OcrSmem<KeyT> &S, const OcrWg<KeyT> &W, const OcrRef<KeyT, EQ> &R) {
+    u64 ta = 0, T_A = 0;
+    for (u32 i = W.tid; i < W.nA; i += NT) {
+        u32 l, a;
+        ocr_find_exact(R, S.A[i], l, a);
+        ta += (u64)a * a - 1ull;
+    }
+    ta = wave_sum(ta);
+    if (W.lane == 0) S.s_red[W.wave] = ta;
     __syncthreads();
-    u64 T_A = 0; // ties among the reference's non-zero keys: sum over keys of (run length^2 - 1)
-    {
-        u64 ta = 0;
-        for (u32 i = tid; i < nA; i += NT) {
-            u32 l, a;
-            ocr_find_exact(R, A[i], l, a);
-            ta += (u64)a * a - 1ull;
-        }
-        ta = wave_sum(ta);
-        if (lane == 0) s_red[wave] = ta;
-        __syncthreads();
-        for (int w = 0; w < NW; ++w) T_A += s_red[w];
+    for (int w = 0; w < NT / 64; ++w) T_A += S.s_red[w];
+    return T_A;
+}
+// The reference's non-zero keys (of this part) -> value buckets in LDS, R the look-up's view of them; false: the gene is not this
+// workgroup's, or leaves the kernel.
+template <typename KeyT, bool EQ, bool PARTS, int NT> __device__ __forceinline__ bool ocr_build_ref(const OvoCompactParams &P, const OcrSmem<KeyT> &S, OcrWg<KeyT> &W, OcrRef<KeyT, EQ> &R) {
+    if (!ocr_ref_census<KeyT, EQ, PARTS, NT>(P, S, W)) return false;
+    __syncthreads();
+    ocr_part_range<KeyT, EQ, PARTS, NT>(P, S, W, R);
+    if constexpr (EQ) ocr_coarse_cells<KeyT, PARTS, NT>(P, S, W, R);
+    W.nneg = S.s_cnt[OCR_N_NEG];
+    ocr_count_keys<KeyT, EQ, PARTS, NT>(P, S, W, R);
+    __syncthreads();
+    if (!ocr_scan_or_leave<KeyT, PARTS, NT>(P, S, W)) return false;
+    __syncthreads();
+    ocr_scatter<KeyT, EQ, PARTS, NT>(P, S, W, R);
+    __syncthreads();
+    W.T_A = ocr_ref_ties<KeyT, EQ, NT>(S, W, R);
+    return true;
+}
+// One ranked group's statistics from its sums, by one lane: the only place that forms and writes them.  n_run: the group's non-zero keys
+// (of all parts); over the keys b that were looked up, s2_sum = sum of 2 #A<b + #A==b (against the table's keys), tt_sum = sum of
+// t (t + 1), negs = keys below zero.  The plain kernel looked all n_run keys up and stores.  PARTS: n_in keys of the run lie inside the
+// part, and the part ADDS its share -- its keys against the reference's keys below the part (n_low), inside it, and the reference's zeros;
+// part 0 alone adds the terms of the group's zeros (one run against the aZ reference zeros) and the constant term.
+template <bool PARTS, typename KeyT> __device__ __forceinline__ void ocr_emit(const OvoCompactParams &P, const OcrWg<KeyT> &W, int g, u32 n_run, u64 s2_sum, u64 tt_sum, u32 negs, u32 n_in) {
+    const size_t o = (size_t)W.gene * W.G + g;
+    const long long n_g = P.counts[g];
+    if constexpr (!PARTS) n_in = n_run;
+    u64 S2 = s2_sum + 2ull * W.aZ * (u64)(n_in - negs);
+    u64 tie = W.T_A + 3ull * tt_sum;
+    long long two_u = 0;
+    if constexpr (PARTS) S2 += 2ull * W.n_low * (u64)n_in;
+    if (!PARTS || W.part == 0) {
+        const u64 zc = (u64)(n_g - (long long)n_run), t0 = (u64)W.aZ + zc;
+        S2 += zc * (2ull * W.nneg + W.aZ);
+        tie += t0 * t0 * t0 - t0;
+        two_u = 2ll * (long long)W.n_ref * n_g;
     }
-
-    // ---- every other group: one wavefront each, 64 groups per output block ----
-    u32 *bloom = bloom_all + wave * OCR_BLOOM_WORDS;
-    const u64 lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    // Few groups (a cluster-level comparison, a small screen: fewer than 32 groups per wavefront): the blocks of 64 groups below would leave all
-    // but G / 64 wavefronts idle, each walking its 64 groups one after the other (20 000 cells x 120 000 genes x 100 groups: 31 ms, 66 us a gene,
-    // of which the two working wavefronts' 64 look-ups in a row are nearly all).  Here the groups are dealt round robin, one wavefront-sum each.
-    const bool few_groups = G < NW * 32;
-    if (few_groups) {
-        for (int g = wave; g < G; g += NW) {
-            const size_t o = (size_t)gene * G + g;
-            if (g == ref) { if (part == 0 && lane == 0) { P.out_2u[o] = -2; P.out_tie[o] = 0; } continue; }
-            const int n_run = (int)nnz[g];   // the group's non-zero keys (all parts)
-            if (n_run > 64 * KMAX) continue; // (big_sorted: walked piece by piece below)
-            const KeyT *seg = Xg + P.gofs[o];
-            int nB = n_run;
-            if constexpr (PARTS) { // a dealt run (k_deal_runs): this part's stretch of it
-                if (P.pofs && n_run) {
-                    const u16 *po = P.pofs + o * 4;
-                    if (po[0] == 1) {
-                        const int beg = part ? (int)po[part] : 0, end = part + 1 < n_parts_gene ? (int)po[part + 1] : n_run;
-                        seg += beg;
-                        nB = end - beg;
-                    }
-                }
-            }
-            KeyT cur[KMAX];
-            u32 nv = 0;
+    if constexpr (PARTS) { atomicAdd((unsigned long long *)&P.out_2u[o], (unsigned long long)(two_u - (long long)S2)); atomicAdd((unsigned long long *)&P.out_tie[o], (unsigned long long)tie); }
+    else { P.out_2u[o] = two_u - (long long)S2; P.out_tie[o] = tie; }
+}
+// PARTS: of a run of n_run keys (entry o of pofs) that k_deal_runs dealt by part -- 1 .. 256 keys, pofs[o][0] == 1 --, this part's
+// stretch; else the whole run (every key is looked up, the other parts' masked).
+__device__ __forceinline__ void ocr_part_stretch(const u16 *pofs, size_t o, int part, int n_parts_gene, u32 n_run, u32 *beg, u32 *len) {
+    *beg = 0u; *len = n_run;
+    if (pofs && n_run && n_run <= 64u * OCR_KMAX) {
+        const u16 *po = pofs + o * 4;
+        if (po[0] == 1) {
+            const u32 end = part + 1 < n_parts_gene ? (u32)po[part + 1] : n_run;
+            *beg = part ? (u32)po[part] : 0u;
+            *len = end - *beg;
+        }
+    }
+}
+// Few groups (a cluster-level comparison, a small screen: fewer than 32 groups per wavefront): the blocks of 64 groups of ocr_group_blocks would
+// leave all but G / 64 wavefronts idle, each walking its 64 groups one after the other (20 000 cells x 120 000 genes x 100 groups: 31 ms, 66 us
+// a gene, of which the two working wavefronts' 64 look-ups in a row are nearly all).  Here the groups are dealt round robin, one wavefront-sum each.
+template <typename KeyT, bool EQ, bool PARTS, int NW> __device__ __forceinline__ void ocr_few_groups(const OvoCompactParams &P, const OcrWg<KeyT> &W, const OcrRef<KeyT, EQ> &R, u32 *bloom, u64 lt_mask) {
+    constexpr int KMAX = OCR_KMAX;
+    constexpr KeyT ZEROK = KeyInfo<KeyT>::ZEROK;
+    const int lane = W.lane;
+    for (int g = W.wave; g < W.G; g += NW) {
+        const size_t o = (size_t)W.gene * W.G + g;
+        if (g == W.ref) { if (W.part == 0 && lane == 0) { P.out_2u[o] = -2; P.out_tie[o] = 0; } continue; }
+        const int n_run = (int)W.nnz[g]; // the group's non-zero keys (all parts)
+        if (n_run > 64 * KMAX) continue; // (big_sorted: walked piece by piece by ocr_big_runs)
+        u32 beg = 0, len = (u32)n_run;
+        if constexpr (PARTS) ocr_part_stretch(P.pofs, o, W.part, W.n_parts_gene, (u32)n_run, &beg, &len);
+        const KeyT *seg = W.Xg + P.gofs[o] + beg;
+        const int nB = (int)len;
+        KeyT cur[KMAX];
+        u32 nv = 0;
 #pragma unroll
-            for (int r = 0; r < KMAX; ++r) {
-                KeyT k = (r * 64 + lane < nB) ? seg[r * 64 + lane] : ZEROK;
-                if constexpr (PARTS) k = (k >= p_lo && k <= p_hi) ? k : ZEROK;
-                cur[r] = k;
-                if constexpr (PARTS) nv += (u32)__popcll(__ballot(k != ZEROK));
-            }
-            u32 less = 0, eqs = 0, negs = 0;
-            u64 TT = 0;
-            if (PARTS ? nv != 0u : nB != 0) {
-                if (nB <= 64) ocr_group<KeyT, 1, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
-                else if (nB <= 128) ocr_group<KeyT, 2, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
-                else if (nB <= 192) ocr_group<KeyT, 3, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
-                else ocr_group<KeyT, 4, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
-            }
-            const u64 s2_sum = wave_sum<u64>((u64)(2u * less + eqs));
-            const u64 tt_sum = __ballot(TT != 0ull) ? wave_sum<u64>(TT) : 0ull;
-            if (lane == 0) {
-                const long long n_g = P.counts[g];
-                const u64 zc = (u64)(n_g - (long long)n_run), t0 = (u64)aZ + zc;
-                if constexpr (PARTS) {
-                    u64 S2 = s2_sum + 2ull * n_low * (u64)nv + 2ull * aZ * (u64)(nv - negs);
-                    u64 tie = T_A + 3ull * tt_sum;
-                    long long two_u = 0;
-                    if (part == 0) { S2 += zc * (2ull * nneg + aZ); tie += t0 * t0 * t0 - t0; two_u = 2ll * (long long)n_ref * n_g; }
-                    atomicAdd((unsigned long long *)&P.out_2u[o], (unsigned long long)(two_u - (long long)S2));
-                    atomicAdd((unsigned long long *)&P.out_tie[o], (unsigned long long)tie);
-                } else {
-                    const u64 S2 = s2_sum + 2ull * aZ * (u64)((u32)n_run - negs) + zc * (2ull * nneg + aZ);
-                    P.out_2u[o] = 2ll * (long long)n_ref * n_g - (long long)S2;
-                    P.out_tie[o] = T_A + 3ull * tt_sum + (t0 * t0 * t0 - t0);
-                }
-            }
+        for (int r = 0; r < KMAX; ++r) {
+            KeyT k = (r * 64 + lane < nB) ? seg[r * 64 + lane] : ZEROK;
+            if constexpr (PARTS) k = (k >= W.p_lo && k <= W.p_hi) ? k : ZEROK;
+            cur[r] = k;
+            if constexpr (PARTS) nv += (u32)__popcll(__ballot(k != ZEROK));
         }
+        u32 less = 0, eqs = 0, negs = 0;
+        u64 TT = 0;
+        if (PARTS ? nv != 0u : nB != 0) ocr_lookup<KeyT, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
+        const u64 s2_sum = wave_sum<u64>((u64)(2u * less + eqs));
+        const u64 tt_sum = __ballot(TT != 0ull) ? wave_sum<u64>(TT) : 0ull;
+        if (lane == 0) ocr_emit<PARTS>(P, W, g, (u32)n_run, s2_sum, tt_sum, negs, nv);
     }
-    for (int g0 = wave * 64; g0 < G && !few_groups; g0 += NW * 64) {
+}
+// Many groups: one wavefront per block of 64 groups; lane j ends up with the totals of the block's group j and writes them.
+template <typename KeyT, bool EQ, bool PARTS, int NW> __device__ __forceinline__ void ocr_group_blocks(const OvoCompactParams &P, const OcrWg<KeyT> &W, const OcrRef<KeyT, EQ> &R, u32 *bloom, u64 lt_mask) {
+    constexpr int KMAX = OCR_KMAX;
+    constexpr KeyT ZEROK = KeyInfo<KeyT>::ZEROK;
+    const int lane = W.lane, G = W.G;
+    for (int g0 = W.wave * 64; g0 < G; g0 += NW * 64) {
         const int gl = g0 + lane;
-        const bool has = gl < G && gl != ref;
-        const u32 my_n = has ? (u32)nnz[gl] : 0u;
-        int my_pos = has ? (int)P.gofs[(size_t)gene * G + gl] : 0;
-        u32 my_len = my_n; // keys to look up: the whole run, or -- a dealt run (k_deal_runs) -- this part's stretch of it
-        if constexpr (PARTS) {
-            if (P.pofs && my_n && my_n <= 64u * KMAX) {
-                const u16 *po = P.pofs + ((size_t)gene * G + gl) * 4;
-                if (po[0] == 1) {
-                    const u32 beg = part ? (u32)po[part] : 0u, end = part + 1 < n_parts_gene ? (u32)po[part + 1] : my_n;
-                    my_pos += (int)beg;
-                    my_len = end - beg;
-                }
-            }
-        }
+        const bool has = gl < G && gl != W.ref;
+        const size_t o = (size_t)W.gene * G + gl;
+        const u32 my_n = has ? (u32)W.nnz[gl] : 0u;
+        u32 my_beg = 0, my_len = my_n; // keys to look up: the whole run, or -- a dealt run (k_deal_runs) -- this part's stretch of it
+        if constexpr (PARTS) ocr_part_stretch(P.pofs, o, W.part, W.n_parts_gene, my_n, &my_beg, &my_len);
+        const int my_pos = (has ? (int)P.gofs[o] : 0) + (int)my_beg;
         TrReduce<u32> rS2;
         u64 tt_out = 0;   // lane j: sum t (t + 1) over group g0 + j's keys (non-zero only where keys tie)
         u32 neg_out = 0;  // lane j: group g0 + j's keys below zero
         u32 nv_out = 0;   // PARTS, lane j: group g0 + j's keys inside the part
-        // OCR_PAIR groups' keys are requested ahead and looked up back to back
-        constexpr int PF = OCR_PAIR;
-        KeyT nxt[PF][KMAX];
-        int nB_n[PF];
-        auto fetch = [&](int j, int h) {
+        // One group's keys are requested ahead of the look-ups of the group before it.  (Two ahead measured the same at C2 / C5 shapes and
+        // 20 % slower in the 256-thread form: what the wavefronts wait on is the chain table word -> keys in LDS, not HBM.)
+        KeyT nxt[KMAX];
+        int nB_n;
+        auto fetch = [&](int j) {
             int nb = j < 64 ? (int)__builtin_amdgcn_readlane((int)my_len, j & 63) : 0;
-            if (nb > 64 * KMAX) nb = 0; // (big_sorted: such a group is walked piece by piece below)
-            nB_n[h] = nb;
-            const KeyT *seg = Xg + __builtin_amdgcn_readlane(my_pos, j & 63);
+            if (nb > 64 * KMAX) nb = 0; // (big_sorted: such a group is walked piece by piece by ocr_big_runs)
+            nB_n = nb;
+            const KeyT *seg = W.Xg + __builtin_amdgcn_readlane(my_pos, j & 63);
 #pragma unroll
             for (int r = 0; r < KMAX; ++r)
                 if (r * 64 < nb) {
                     KeyT k = (r * 64 + lane < nb) ? seg[r * 64 + lane] : ZEROK;
-                    if constexpr (PARTS) k = (k >= p_lo && k <= p_hi) ? k : ZEROK; // (keys of other parts: masked out)
-                    nxt[h][r] = k;
+                    if constexpr (PARTS) k = (k >= W.p_lo && k <= W.p_hi) ? k : ZEROK; // (keys of other parts: masked out)
+                    nxt[r] = k;
                 }
         };
+        fetch(0);
+        for (int j = 0; j < 64; ++j) { // always 64 pushes so that the transpose-reduce completes
+            KeyT cur[KMAX];
 #pragma unroll
-        for (int h = 0; h < PF; ++h) fetch(h, h);
-        for (int j0 = 0; j0 < 64; j0 += PF) { // always 64 pushes so that the transpose-reduce completes
-            KeyT cur2[PF][KMAX];
-            int nB2[PF];
-#pragma unroll
-            for (int h = 0; h < PF; ++h) {
-#pragma unroll
-                for (int r = 0; r < KMAX; ++r) cur2[h][r] = nxt[h][r];
-                nB2[h] = nB_n[h];
-            }
-#pragma unroll
-            for (int h = 0; h < PF; ++h) fetch(j0 + PF + h, h);
-#pragma unroll
-            for (int h = 0; h < PF; ++h) {
-            const int j = j0 + h;
-            const KeyT (&cur)[KMAX] = cur2[h];
-            const int nB = nB2[h];
-            u32 S2 = 0;
-            u32 nv = 0;
+            for (int r = 0; r < KMAX; ++r) cur[r] = nxt[r];
+            const int nB = nB_n;
+            fetch(j + 1);
+            u32 S2 = 0, nv = 0;
             if constexpr (PARTS) {
                 if (nB) {
 #pragma unroll
@@ -1354,10 +1360,7 @@ __global__ __launch_bounds__(NT_) void k_ovo_rank_compact(OvoCompactParams P) {
             if (PARTS ? nv != 0u : nB != 0) { // uniform
                 u32 less = 0, eqs = 0, negs = 0;
                 u64 TT = 0;
-                if (nB <= 64) ocr_group<KeyT, 1, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
-                else if (nB <= 128) ocr_group<KeyT, 2, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
-                else if (nB <= 192) ocr_group<KeyT, 3, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
-                else ocr_group<KeyT, 4, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
+                ocr_lookup<KeyT, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
                 S2 = 2u * less + eqs;
                 const u64 tm = __ballot(TT != 0ull);
                 if (tm) { // ties are few: mostly one lane holds the whole term
@@ -1375,173 +1378,169 @@ __global__ __launch_bounds__(NT_) void k_ovo_rank_compact(OvoCompactParams P) {
                 if (negs && lane == j) neg_out = negs;
             }
             rS2.push(S2, j, lane);
-            }
         }
         if (gl < G && my_n <= 64u * KMAX) { // lane j now holds the totals of group g0 + j
-            const size_t o = (size_t)gene * G + gl;
-            if (gl == ref) {
-                if (part == 0) { P.out_2u[o] = -2; P.out_tie[o] = 0; }
-            } else if constexpr (PARTS) { // this part's share, added: its keys against the reference's keys below the part, inside it, and the zeros
-                const long long n_g = P.counts[gl];
-                u64 S2 = (u64)rS2.result + 2ull * n_low * (u64)nv_out + 2ull * aZ * (u64)(nv_out - neg_out);
-                u64 tie = T_A + 3ull * tt_out;
-                long long two_u = 0;
-                if (part == 0) { // the group's zeros, the constant term
-                    const u64 zc = (u64)(n_g - (long long)my_n), t0 = (u64)aZ + zc;
-                    S2 += zc * (2ull * nneg + aZ);
-                    tie += t0 * t0 * t0 - t0;
-                    two_u = 2ll * (long long)n_ref * n_g;
-                }
-                atomicAdd((unsigned long long *)&P.out_2u[o], (unsigned long long)(two_u - (long long)S2));
-                atomicAdd((unsigned long long *)&P.out_tie[o], (unsigned long long)tie);
-            } else {
-                const long long n_g = P.counts[gl];
-                const u64 zc = (u64)(n_g - (long long)my_n);       // the group's zeros: one run against aZ reference zeros
-                const u64 S2 = (u64)rS2.result + 2ull * aZ * (u64)(my_n - neg_out) + zc * (2ull * nneg + aZ);
-                const u64 t0 = (u64)aZ + zc;
-                P.out_2u[o] = 2ll * (long long)n_ref * n_g - (long long)S2;
-                P.out_tie[o] = T_A + 3ull * tt_out + (t0 * t0 * t0 - t0);
-            }
+            if (gl == W.ref) { if (W.part == 0) { P.out_2u[o] = -2; P.out_tie[o] = 0; } }
+            else ocr_emit<PARTS>(P, W, gl, my_n, (u64)rS2.result, tt_out, neg_out, nv_out);
         }
     }
-    // ---- groups of more than 256 non-zero keys (dealt into value buckets by k_bucket_big_runs): one wavefront each, in pieces of at most
-    // 256 keys cut at bucket boundaries -- every piece is a group of its own to ocr_group, and S2, the tie term and the negatives add up ----
-    // A LONG run (a cluster of tens of thousands of cells: more than OCR_COOP_MIN keys) is walked by ALL the wavefronts together: the bucket
-    // kernels left NW - 1 cuts per such run (bucket boundaries at or behind w / NW of the run: run_cuts), wavefront w walks the pieces between
-    // cut w and cut w + 1, the stretches' sums meet in LDS.  (One wavefront per run left seven of sixteen idle on ten clusters, fifteen on a
-    // single cluster against the reference.)
-    if (P.big_sorted && s_cnt[3] > 64u * KMAX) {
-        u32 *lr_list = ccnt;                 // (the coarse cells' counters are done with) [0] long runs listed, [1 ..] their groups
-        u64 *lr_acc = (u64 *)(ccnt + 64);    // [0] S2 part  [1] tie part  [2] negatives  [3] keys inside the part  [4] a bucket above 256 keys
-        if (tid == 0) lr_list[0] = 0u;
-        __syncthreads();
-        // the pieces of seg[i_begin, i_end) (both bucket boundaries): sums into the accumulators; false: a bucket of more than 256 keys
-        auto walk = [&](const KeyT *seg, const BigRunFn<KeyT> &fn, int i_begin, int i_end, u64 &s2_acc, u64 &tt_acc, u32 &neg_acc, u32 &nv_acc) -> bool {
-            const int n = i_end;
-            bool bad = false;
-            for (int s0 = i_begin; s0 < n && !bad;) {
-                    const int win = min(64 * KMAX, n - s0);
-                    KeyT cur[KMAX];
+}
+// ---- groups of more than 256 non-zero keys (dealt into value buckets by k_bucket_big_runs): in pieces of at most 256 keys cut at bucket
+// boundaries -- every piece is a group of its own to ocr_group, and S2, the tie term and the negatives add up ----
+// A run as the bucket kernels left it: its exact length (run_n where the 16-bit count saturated), its bucket function, and where it lies --
+// in place or, dealt through HBM (BIG_RUN_IN_TMP), in the second key buffer.  ci: its place in the [n_genes][n_cand] arrays.
+template <typename KeyT> struct OcrBigRun { const KeyT *seg; BigRunFn<KeyT> fn; int n; size_t ci; };
+template <typename KeyT> __device__ __forceinline__ int ocr_run_length(const OvoCompactParams &P, const OcrWg<KeyT> &W, int gb) {
+    const int n = (int)W.nnz[gb];
+    return (n >= 65535 && P.run_n) ? (int)P.run_n[(size_t)W.gene * P.n_cand + P.cand_of[gb]] : n;
+}
+template <typename KeyT> __device__ __forceinline__ OcrBigRun<KeyT> ocr_big_run(const OvoCompactParams &P, const OcrWg<KeyT> &W, int gb) {
+    OcrBigRun<KeyT> r;
+    r.ci = (size_t)W.gene * P.n_cand + P.cand_of[gb];
+    r.n = ocr_run_length(P, W, gb);
+    r.fn = ((const BigRunFn<KeyT> *)P.big_fn)[r.ci];
+    r.seg = ((r.fn.shift & BIG_RUN_IN_TMP) ? (const KeyT *)P.big_tmp + (long long)W.gene * P.gene_stride : (const KeyT *)W.Xg) + P.gofs[(size_t)W.gene * W.G + gb];
+    r.fn.shift &= ~BIG_RUN_IN_TMP;
+    return r;
+}
+// (dense layout: the reference's segments lie where they were -- not k_ovo_rank's gene: a word above 255 sends it to the general route)
+__device__ __forceinline__ void ocr_leave_big(const OvoCompactParams &P, int gene) { P.route[gene] = P.ref_by_gofs ? 2u : (2u | (6u << 8)); }
+
+struct OcrSums { u64 s2, tt; u32 neg, nv; }; // a walk's sums: S2 and tie parts (per lane); keys below zero and -- PARTS -- keys inside the part (uniform)
+// the pieces of seg[i_begin, i_end) (both bucket boundaries): sums into acc; false: a bucket of more than 256 keys
+template <typename KeyT, bool EQ, bool PARTS> __device__ __forceinline__ bool ocr_walk_pieces(const KeyT *seg, const BigRunFn<KeyT> &fn, int i_begin, int i_end, const OcrWg<KeyT> &W, const OcrRef<KeyT, EQ> &R, u32 *bloom, u64 lt_mask, OcrSums &acc) {
+    constexpr int KMAX = OCR_KMAX;
+    constexpr KeyT ZEROK = KeyInfo<KeyT>::ZEROK;
+    const int n = i_end, lane = W.lane;
+    for (int s0 = i_begin; s0 < n;) {
+        const int win = min(64 * KMAX, n - s0);
+        KeyT cur[KMAX];
 #pragma unroll
-                    for (int r = 0; r < KMAX; ++r) cur[r] = (r * 64 + lane < win) ? seg[s0 + r * 64 + lane] : ZEROK;
-                    int nB = win;
-                    if (s0 + win < n) { // does the window's last bucket go on beyond it?  then the piece ends where that bucket starts
-                        const u32 bn = big_bucket(fn, seg[s0 + win]); // (uniform address)
-                        int same = 0;
+        for (int r = 0; r < KMAX; ++r) cur[r] = (r * 64 + lane < win) ? seg[s0 + r * 64 + lane] : ZEROK;
+        int nB = win;
+        if (s0 + win < n) { // does the window's last bucket go on beyond it?  then the piece ends where that bucket starts
+            const u32 bn = big_bucket(fn, seg[s0 + win]); // (uniform address)
+            int same = 0;
 #pragma unroll
-                        for (int r = 0; r < KMAX; ++r) same += (int)__popcll(__ballot(r * 64 + lane < win && big_bucket(fn, cur[r]) == bn));
-                        nB = win - same;
-                    }
-                    if (nB == 0) { bad = true; break; } // a bucket of more than 256 keys: a tie-heavy column, not for this kernel
-#pragma unroll
-                    for (int r = 0; r < KMAX; ++r) cur[r] = (r * 64 + lane < nB) ? cur[r] : ZEROK;
-                    if constexpr (PARTS) { // the run is in ascending bucket order: most pieces lie wholly inside or outside the part
-                        u32 nv = 0;
-#pragma unroll
-                        for (int r = 0; r < KMAX; ++r) {
-                            cur[r] = (cur[r] >= p_lo && cur[r] <= p_hi) ? cur[r] : ZEROK;
-                            nv += (u32)__popcll(__ballot(cur[r] != ZEROK));
-                        }
-                        nv_acc += nv;
-                        if (nv == 0u) { s0 += nB; continue; } // (uniform)
-                    }
-                    u32 less = 0, eqs = 0, negs = 0;
-                    u64 TT = 0;
-                    if (nB <= 64) ocr_group<KeyT, 1, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
-                    else if (nB <= 128) ocr_group<KeyT, 2, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
-                    else if (nB <= 192) ocr_group<KeyT, 3, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
-                    else ocr_group<KeyT, 4, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
-                    s2_acc += 2ull * less + eqs;
-                    tt_acc += TT;
-                    neg_acc += negs;
-                    s0 += nB;
-            }
-            return !bad;
-        };
-        // a big group's statistics from its run's sums (one lane)
-        auto emit_big = [&](int gb, int n, u64 s2_acc, u64 tt_acc, u32 neg_acc, u32 nv_acc) {
-            const size_t o = (size_t)gene * G + gb;
-            const long long n_g = P.counts[gb];
-            if constexpr (PARTS) {
-                u64 S2 = s2_acc + 2ull * n_low * (u64)nv_acc + 2ull * aZ * (u64)(nv_acc - neg_acc);
-                u64 tie = T_A + 3ull * tt_acc;
-                long long two_u = 0;
-                if (part == 0) {
-                    const u64 zc = (u64)(n_g - (long long)n), t0 = (u64)aZ + zc;
-                    S2 += zc * (2ull * nneg + aZ);
-                    tie += t0 * t0 * t0 - t0;
-                    two_u = 2ll * (long long)n_ref * n_g;
-                }
-                atomicAdd((unsigned long long *)&P.out_2u[o], (unsigned long long)(two_u - (long long)S2));
-                atomicAdd((unsigned long long *)&P.out_tie[o], (unsigned long long)tie);
-            } else {
-                const u64 zc = (u64)(n_g - (long long)n);
-                const u64 S2 = s2_acc + 2ull * aZ * (u64)((u32)n - neg_acc) + zc * (2ull * nneg + aZ);
-                const u64 t0 = (u64)aZ + zc;
-                P.out_2u[o] = 2ll * (long long)n_ref * n_g - (long long)S2;
-                P.out_tie[o] = T_A + 3ull * tt_acc + (t0 * t0 * t0 - t0);
-            }
-        };
-        for (int gb = wave; gb < G; gb += NW) { // (uniform per wavefront; few groups are big)
-            if (gb == ref) continue;
-            int n = (int)nnz[gb];
-            if (n <= 64 * KMAX) continue;
-            if (n >= 65535 && P.run_n) n = (int)P.run_n[(size_t)gene * P.n_cand + P.cand_of[gb]]; // (the 16-bit length saturated)
-            if (n > OCR_COOP_MIN && P.run_cuts) { // (at most 63 listed: the others are walked by their wavefront alone, below)
-                u32 slot = 0;
-                if (lane == 0) slot = atomicAdd(&lr_list[0], 1u);
-                slot = (u32)__builtin_amdgcn_readfirstlane((int)slot);
-                if (slot < 63u) { if (lane == 0) lr_list[1 + slot] = (u32)gb; continue; }
-            }
-            BigRunFn<KeyT> fn = ((const BigRunFn<KeyT> *)P.big_fn)[(size_t)gene * P.n_cand + P.cand_of[gb]];
-            const KeyT *seg = ((fn.shift & BIG_RUN_IN_TMP) ? (const KeyT *)P.big_tmp + (long long)gene * P.gene_stride : (const KeyT *)Xg) + P.gofs[(size_t)gene * G + gb];
-            fn.shift &= ~BIG_RUN_IN_TMP;
-            u64 s2_acc = 0, tt_acc = 0; // per-lane partial sums
-            u32 neg_acc = 0;            // (uniform)
-            u32 nv_acc = 0;             // (uniform) PARTS: keys inside the part
-            const bool bad = !walk(seg, fn, 0, n, s2_acc, tt_acc, neg_acc, nv_acc);
-            // (dense layout: the reference's segments lie where they were -- not k_ovo_rank's gene: a word above 255 sends it to the general route)
-            if (bad) { if (lane == 0) P.route[gene] = P.ref_by_gofs ? 2u : (2u | (6u << 8)); continue; }
-            s2_acc = wave_sum<u64>(s2_acc);
-            tt_acc = wave_sum<u64>(tt_acc);
-            if (lane == 0) emit_big(gb, n, s2_acc, tt_acc, neg_acc, nv_acc);
+            for (int r = 0; r < KMAX; ++r) same += (int)__popcll(__ballot(r * 64 + lane < win && big_bucket(fn, cur[r]) == bn));
+            nB = win - same;
         }
-        // ---- the long runs, every wavefront on each ----
-        __syncthreads();
-        const int n_long = (int)min(lr_list[0], 63u);
-        for (int li = 0; li < n_long; ++li) { // (uniform)
-            const int gb = (int)lr_list[1 + li];
-            if (tid < 5) lr_acc[tid] = 0ull;
-            __syncthreads();
-            int n = (int)nnz[gb];
-            if (n >= 65535 && P.run_n) n = (int)P.run_n[(size_t)gene * P.n_cand + P.cand_of[gb]];
-            const size_t ci = (size_t)gene * P.n_cand + P.cand_of[gb];
-            BigRunFn<KeyT> fn = ((const BigRunFn<KeyT> *)P.big_fn)[ci];
-            const KeyT *seg = ((fn.shift & BIG_RUN_IN_TMP) ? (const KeyT *)P.big_tmp + (long long)gene * P.gene_stride : (const KeyT *)Xg) + P.gofs[(size_t)gene * G + gb];
-            fn.shift &= ~BIG_RUN_IN_TMP;
-            const u32 *cuts = P.run_cuts + ci * OCR_CUTS; // cut w (w = 1 .. OCR_CUTS): the bucket boundary at or behind w / (OCR_CUTS + 1) of the run
-            // NW wavefronts over OCR_CUTS + 1 = 16 stretches: wavefront w takes stretches w * 16 / NW ... (NW = 16: one each; NW = 4: four each)
-            const int st0 = wave * (OCR_CUTS + 1) / NW, st1 = (wave + 1) * (OCR_CUTS + 1) / NW;
-            const int i0 = st0 == 0 ? 0 : min((int)cuts[st0 - 1], n), i1 = st1 > OCR_CUTS ? n : min((int)cuts[st1 - 1], n);
-            u64 s2_acc = 0, tt_acc = 0;
-            u32 neg_acc = 0, nv_acc = 0;
-            bool ok = true;
-            if (i0 < i1) ok = walk(seg, fn, i0, i1, s2_acc, tt_acc, neg_acc, nv_acc);
-            s2_acc = wave_sum<u64>(s2_acc);
-            tt_acc = wave_sum<u64>(tt_acc);
-            if (lane == 0) {
-                if (s2_acc) atomicAdd((unsigned long long *)&lr_acc[0], (unsigned long long)s2_acc);
-                if (tt_acc) atomicAdd((unsigned long long *)&lr_acc[1], (unsigned long long)tt_acc);
-                if (neg_acc) atomicAdd((unsigned long long *)&lr_acc[2], (unsigned long long)neg_acc);
-                if (nv_acc) atomicAdd((unsigned long long *)&lr_acc[3], (unsigned long long)nv_acc);
-                if (!ok) lr_acc[4] = 1ull;
+        if (nB == 0) return false; // a bucket of more than 256 keys: a tie-heavy column, not for this kernel
+#pragma unroll
+        for (int r = 0; r < KMAX; ++r) cur[r] = (r * 64 + lane < nB) ? cur[r] : ZEROK;
+        if constexpr (PARTS) { // the run is in ascending bucket order: most pieces lie wholly inside or outside the part
+            u32 nv = 0;
+#pragma unroll
+            for (int r = 0; r < KMAX; ++r) {
+                cur[r] = (cur[r] >= W.p_lo && cur[r] <= W.p_hi) ? cur[r] : ZEROK;
+                nv += (u32)__popcll(__ballot(cur[r] != ZEROK));
             }
-            __syncthreads();
-            if (tid == 0) {
-                if (lr_acc[4]) P.route[gene] = P.ref_by_gofs ? 2u : (2u | (6u << 8));
-                else emit_big(gb, n, lr_acc[0], lr_acc[1], (u32)lr_acc[2], (u32)lr_acc[3]);
-            }
-            __syncthreads();
+            acc.nv += nv;
+            if (nv == 0u) { s0 += nB; continue; } // (uniform)
         }
+        u32 less = 0, eqs = 0, negs = 0;
+        u64 TT = 0;
+        ocr_lookup<KeyT, EQ, PARTS>(cur, nB, R, bloom, lane, lt_mask, less, eqs, TT, negs);
+        acc.s2 += 2ull * less + eqs;
+        acc.tt += TT;
+        acc.neg += negs;
+        s0 += nB;
+    }
+    return true;
+}
+// One wavefront per run above 256 keys.  A LONG run (a cluster of tens of thousands of cells: more than OCR_COOP_MIN keys, cuts at hand) is
+// listed instead for ocr_long_runs (at most 63: the others are walked here all the same).
+template <typename KeyT, bool EQ, bool PARTS, int NW> __device__ __forceinline__ void ocr_big_runs(const OvoCompactParams &P, const OcrSmem<KeyT> &S, const OcrWg<KeyT> &W, const OcrRef<KeyT, EQ> &R, u32 *bloom, u64 lt_mask) {
+    const int lane = W.lane;
+    if (W.tid == 0) S.lr_list[0] = 0u;
+    __syncthreads();
+    for (int gb = W.wave; gb < W.G; gb += NW) { // (uniform per wavefront; few groups are big)
+        if (gb == W.ref || (int)W.nnz[gb] <= 64 * OCR_KMAX) continue;
+        if (P.run_cuts && ocr_run_length(P, W, gb) > OCR_COOP_MIN) {
+            u32 slot = 0;
+            if (lane == 0) slot = atomicAdd(&S.lr_list[0], 1u);
+            slot = (u32)__builtin_amdgcn_readfirstlane((int)slot);
+            if (slot < OcrLds::LR_LIST_WORDS - 1) { if (lane == 0) S.lr_list[1 + slot] = (u32)gb; continue; }
+        }
+        const OcrBigRun<KeyT> run = ocr_big_run(P, W, gb);
+        OcrSums acc = {0ull, 0ull, 0u, 0u};
+        if (!ocr_walk_pieces<KeyT, EQ, PARTS>(run.seg, run.fn, 0, run.n, W, R, bloom, lt_mask, acc)) { if (lane == 0) ocr_leave_big(P, W.gene); continue; }
+        acc.s2 = wave_sum<u64>(acc.s2);
+        acc.tt = wave_sum<u64>(acc.tt);
+        if (lane == 0) ocr_emit<PARTS>(P, W, gb, (u32)run.n, acc.s2, acc.tt, acc.neg, acc.nv);
+    }
+}
+// The listed long runs, ALL the wavefronts on each: the bucket kernels left OCR_CUTS cuts per such run (run_cuts: cut w = the bucket
+// boundary at or behind w / (OCR_CUTS + 1) of the run), a wavefront walks the pieces between its cuts, the stretches' sums meet in LDS.
+// (One wavefront per run left seven of sixteen idle on ten clusters, fifteen on a single cluster against the reference.)
+template <typename KeyT, bool EQ, bool PARTS, int NW> __device__ __forceinline__ void ocr_long_runs(const OvoCompactParams &P, const OcrSmem<KeyT> &S, const OcrWg<KeyT> &W, const OcrRef<KeyT, EQ> &R, u32 *bloom, u64 lt_mask) {
+    const int tid = W.tid, lane = W.lane, wave = W.wave;
+    u64 *lr_acc = S.lr_acc;
+    __syncthreads();
+    const int n_long = (int)min(S.lr_list[0], (u32)(OcrLds::LR_LIST_WORDS - 1));
+    for (int li = 0; li < n_long; ++li) { // (uniform)
+        const int gb = (int)S.lr_list[1 + li];
+        if (tid < (int)OcrLds::LR_ACC_WORDS) lr_acc[tid] = 0ull;
+        __syncthreads();
+        const OcrBigRun<KeyT> run = ocr_big_run(P, W, gb);
+        const int n = run.n;
+        const u32 *cuts = P.run_cuts + run.ci * OCR_CUTS;
+        // NW wavefronts over OCR_CUTS + 1 = 16 stretches: wavefront w takes stretches w * 16 / NW ... (NW = 16: one each; NW = 4: four each)
+        const int st0 = wave * (OCR_CUTS + 1) / NW, st1 = (wave + 1) * (OCR_CUTS + 1) / NW;
+        const int i0 = st0 == 0 ? 0 : min((int)cuts[st0 - 1], n), i1 = st1 > OCR_CUTS ? n : min((int)cuts[st1 - 1], n);
+        OcrSums acc = {0ull, 0ull, 0u, 0u};
+        bool ok = true;
+        if (i0 < i1) ok = ocr_walk_pieces<KeyT, EQ, PARTS>(run.seg, run.fn, i0, i1, W, R, bloom, lt_mask, acc);
+        acc.s2 = wave_sum<u64>(acc.s2);
+        acc.tt = wave_sum<u64>(acc.tt);
+        if (lane == 0) {
+            if (acc.s2) atomicAdd((unsigned long long *)&lr_acc[0], (unsigned long long)acc.s2);
+            if (acc.tt) atomicAdd((unsigned long long *)&lr_acc[1], (unsigned long long)acc.tt);
+            if (acc.neg) atomicAdd((unsigned long long *)&lr_acc[2], (unsigned long long)acc.neg);
+            if (acc.nv) atomicAdd((unsigned long long *)&lr_acc[3], (unsigned long long)acc.nv);
+            if (!ok) lr_acc[4] = 1ull;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            if (lr_acc[4]) ocr_leave_big(P, W.gene);
+            else ocr_emit<PARTS>(P, W, gb, (u32)n, lr_acc[0], lr_acc[1], (u32)lr_acc[2], (u32)lr_acc[3]);
+        }
+        __syncthreads();
+    }
+}
+
+template <typename KeyT, bool EQ, bool PARTS = false, int NT_ = OCR_NT>
+__global__ __launch_bounds__(NT_) void k_ovo_rank_compact(OvoCompactParams P0) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    // The parameter block is read where it lies -- the kernel's only argument, at the start of the kernel-argument segment -- field by field
+    // where a step uses it.  Read through P0, every field the steps use is loaded into scalar registers at entry and kept for the whole
+    // kernel: two dozen registers that are spilled at once, fields of the last steps among them.
+    const OvoCompactParams &P = *(const OvoCompactParams *)__builtin_amdgcn_kernarg_segment_ptr();
+    constexpr int NT = NT_, NW = NT / 64;
+    const OcrSmem<KeyT> S(smem, OcrLds(P.ref_cap, P.nbk_lg, sizeof(KeyT), NT));
+    OcrWg<KeyT> W;
+    W.tid = threadIdx.x; W.lane = W.tid & 63; W.wave = W.tid >> 6;
+    // (part-major: the workgroups of part 0 first.  Gene-major would put the parts a gene does NOT need -- workgroups that return at once --
+    //  on every n_parts-th workgroup slot, i.e. on fixed XCDs: with two parts, half of the chip idle whenever the genes need one.)
+    W.gene = PARTS ? (int)blockIdx.x % P.n_genes : (int)blockIdx.x;
+    W.part = PARTS ? (int)blockIdx.x / P.n_genes : 0;
+    if (P.gene_flags && P.gene_flags[W.gene] == 0u) return; // (uniform)
+    if (P.big_sorted && (P.route[W.gene] & 255u) == 2u) return; // (uniform) k_bucket_big_runs met a run beyond its slots: the general route's gene
+    W.G = P.G; W.ref = P.ref; W.n_ref = P.counts[W.ref];
+    W.nnz = P.nnz + (size_t)W.gene * W.G;
+    W.Xg = (KeyT *)P.Xs + (long long)W.gene * P.gene_stride;
+    W.src = P.ref_by_gofs ? W.Xg + P.gofs[(size_t)W.gene * W.G + W.ref] : W.Xg + P.ref_out;
+    W.seg_nnz = P.seg_nnz + (size_t)W.gene * P.nseg;
+
+    OcrRef<KeyT, EQ> R;
+    if (!ocr_build_ref<KeyT, EQ, PARTS, NT>(P, S, W, R)) return;
+    // every other group: one wavefront each
+    u32 *bloom = S.bloom + W.wave * OCR_BLOOM_WORDS;
+    const u64 lt_mask = (W.lane == 0) ? 0ull : (~0ull >> (64 - W.lane));
+    if (W.G < NW * 32) ocr_few_groups<KeyT, EQ, PARTS, NW>(P, W, R, bloom, lt_mask);
+    else ocr_group_blocks<KeyT, EQ, PARTS, NW>(P, W, R, bloom, lt_mask);
+    if (P.big_sorted && S.s_cnt[OCR_G_MAX] > 64u * OCR_KMAX) {
+        ocr_big_runs<KeyT, EQ, PARTS, NW>(P, S, W, R, bloom, lt_mask);
+        ocr_long_runs<KeyT, EQ, PARTS, NW>(P, S, W, R, bloom, lt_mask);
     }
 }

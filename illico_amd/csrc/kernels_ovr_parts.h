@@ -122,7 +122,7 @@ __global__ __launch_bounds__(NT_) void k_ovr_rank_gene_parts(OvrRankGeneParams P
             }
             __syncthreads();
             const KeyT kmin = s_k[0], kmax = s_k[1] >= s_k[0] ? s_k[1] : s_k[0];
-            const int shift = max(0, key_bits((KeyT)(kmax - kmin)) - P.lg_buckets);
+            const int shift = max(0, key_range_bits((KeyT)(kmax - kmin)) - P.lg_buckets);
             // table entry of a key: 1 + its bucket (buckets 0 .. NBKT - 2).  Entry 0 stays 0, so that after the scan and the scattering
             // pass bucket b is [entry b, entry b + 1): two neighbouring 16-bit reads, no special case for the first bucket.
             const KeyT last_bucket = (KeyT)(NBKT - 2);

@@ -8,6 +8,9 @@ Both replace the reference's linear merge for sizes of any kind (illico/utils/ra
 The limits are lowered by options ("packed_ref_cap", "big_runs_cap") so that small matrices take the routes; every case is held to the
 oracle (U exact, p rtol 1e-12) and, bit for bit, to the statistics of the same engine with the routes switched off.
 """
+import functools
+import re
+
 import numpy as np
 import pytest
 from scipy import sparse
@@ -24,7 +27,8 @@ def engine():
     eng = get_engine()
     eng.set_option("no_fused_path", 1)
     yield eng
-    for k in ("no_fused_path", "packed_ref_cap", "big_runs_cap", "no_ovo_parts", "no_big_runs_global", "no_deal_runs", "profile"):
+    for k in ("no_fused_path", "packed_ref_cap", "big_runs_cap", "no_ovo_parts", "no_big_runs_global", "no_deal_runs", "profile",
+              "debug_routes", "no_coop_runs", "no_packed_small_wg"):
         eng.set_option(k, 0)
 
 
@@ -156,3 +160,141 @@ def test_sparse_input_with_cluster_sized_groups_parts_and_long_runs(engine, fmt)
     for a, b in zip(got, base):
         np.testing.assert_array_equal(a, b)
     assert "k_ovo_rank_compact" in prof, prof
+
+
+# ---- the PARTS form of the 64-group block loop and of the all-wavefront walk of long runs ----
+_LEFT = re.compile(r"\[illico\] packed OVO: \d+ genes, parts \d, left (\d+) to the general route")
+
+
+def _left_to_general_route(engine, capfd, run):
+    """The genes the packed OVO kernels handed back, as the driver reports them with "debug_routes" (dense_driver.h): every gene
+    that leaves is recomputed by the general route, so the planes alone would not show a kernel that left them all."""
+    engine.set_option("debug_routes", 1)
+    capfd.readouterr()
+    try:
+        planes = run()
+    finally:
+        engine.set_option("debug_routes", 0)
+    lines = _LEFT.findall(capfd.readouterr().err)
+    assert lines, "no route line on stderr"
+    return planes, sum(int(n) for n in lines)
+
+
+def _labels_of(rng, n_ref, sizes):
+    labels = np.array(["non-targeting"] * n_ref + [f"pert_{1 + k:05d}" for k, s in enumerate(sizes) for _ in range(s)])
+    rng.shuffle(labels)
+    return labels
+
+
+def _mixed_sign(rng, n):
+    """Either sign, no zeros, magnitudes spread evenly over 2^-60 .. 2^60 and three in four positive.  The bucket kernels cut a run's KEY
+    range evenly -- for values of either sign that range spans every exponent below the largest magnitude --, so values crowded around
+    one magnitude would share a bucket, and a bucket above 256 keys sends its gene to the general route (float64 keys, 2048 buckets for a run
+    of 9000 keys: two binades per bucket)."""
+    return np.where(rng.rand(n) < 0.75, 1.0, -1.0) * np.exp2(rng.uniform(-60.0, 60.0, size=n))
+
+
+def _with_want(X, labels, dtype):
+    X = np.ascontiguousarray(X.astype(dtype))
+    X.setflags(write=False)
+    _, g = oracle.encode_and_count_groups(labels, "non-targeting")
+    return X, g, oracle.run(X, g)
+
+
+BLOCK_LOOP_SIZES = tuple(1 + i % 9 for i in range(520)) + (70, 130, 200, 256, 300)
+
+
+@functools.lru_cache(maxsize=None)
+def _block_loop_case(dtype, zero_frac):
+    rng = np.random.RandomState(21)
+    labels = _labels_of(rng, 4600, BLOCK_LOOP_SIZES)
+    n, m = len(labels), 24
+    X = _continuous(rng, n, m, zero_frac)
+    X[:, 1] = _mixed_sign(rng, n)
+    X[:, 3] = np.round(X[:, 3] * 256) / 256                   # a grid: ties with the reference and inside groups (1/8 .. 1/64 crowd the reference's table)
+    X[:, 5] = 2.25                                            # constant: leaves the packed kernels
+    X[:, 7] = -np.abs(rng.randn(n)) - 0.5                     # all negative, no zeros
+    return _with_want(X, labels, dtype)
+
+
+# genes left to the general route, recorded on an MI355X on the parent of the commit that split the rank kernel into steps: in every
+# case the constant column, and nothing else
+BLOCK_LOOP_LEFT = 1
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("zero_frac", [0.0, 0.4])
+@pytest.mark.parametrize("cap", [1024, 2048])
+def test_parts_in_the_block_loop(engine, capfd, dtype, zero_frac, cap):
+    """PARTS x the 64-group block loop of k_ovo_rank_compact (G = 526 >= 16 wavefronts x 32): a reference of 4600 cells against 520
+    groups of 1 .. 9 cells and one each of 70, 130, 200, 256 and 300 (two, three and four look-up rounds; without zeros the last is a
+    run above 256 keys inside a block of small groups).  1024 slots: six parts, looked up masked; 2048: three, the runs dealt by
+    k_deal_runs (pofs).  The number of genes handed to the general route is a literal recorded on the parent commit on an MI355X."""
+    X, g, want = _block_loop_case(dtype, zero_frac)
+    m = X.shape[1]
+    engine.set_groups(g)
+    engine.set_option("packed_ref_cap", cap)
+    got, prof = _profiled(engine, lambda: engine.run_dense(X, 0, m))
+    assert_planes_match(got, want, ref_row=g.encoded_ref_group, what=f"parts x block loop {dtype.__name__} zeros {zero_frac} slots {cap}")
+    assert "k_ovo_rank_compact" in prof, prof
+    again, left = _left_to_general_route(engine, capfd, lambda: engine.run_dense(X, 0, m))
+    print("left", dtype.__name__, zero_frac, cap, left)
+    _same(got, again)
+    assert left == BLOCK_LOOP_LEFT
+    engine.set_option("no_deal_runs", 1)
+    try:
+        _same(got, engine.run_dense(X, 0, m))
+    finally:
+        engine.set_option("no_deal_runs", 0)
+    stats = engine.rank_statistics(X, 0, m)
+    engine.set_option("no_ovo_parts", 1)
+    _same(got, engine.run_dense(X, 0, m))
+    stats_old = engine.rank_statistics(X, 0, m)
+    np.testing.assert_array_equal(stats[0], stats_old[0])
+    np.testing.assert_array_equal(stats[1], stats_old[1])
+
+
+LONG_RUN_SIZES = (9000, 8300, 300, 100)
+
+
+@functools.lru_cache(maxsize=None)
+def _long_run_case(dtype):
+    rng = np.random.RandomState(22)
+    labels = _labels_of(rng, 2500, LONG_RUN_SIZES)
+    n, m = len(labels), 8
+    X = _continuous(rng, n, m, 0.0)
+    X[:, 1] = np.round(X[:, 1] * 256) / 256                   # a grid: ties everywhere, no value 256 times in a run (1/64 crowds the reference's table)
+    X[:, 2] = _mixed_sign(rng, n)
+    X[:, 3] = -np.abs(X[:, 3]) - 0.5                          # all negative
+    return _with_want(X, labels, dtype)
+
+
+LONG_RUN_LEFT = 0  # recorded likewise: in every case nothing leaves
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("big_runs_cap", [0, 512])
+def test_parts_in_the_cooperative_walk(engine, capfd, dtype, big_runs_cap):
+    """PARTS x the walk of runs above OCR_COOP_MIN = 8192 keys by all the wavefronts (lr_list / lr_acc): groups of 9000 and 8300 cells
+    without zeros (both listed), one of 300 (walked by one wavefront) and one of 100, against a reference of 2500 cells in three parts
+    (1024 slots).  Runs dealt in LDS (cap 0) or through the second key buffer, cuts by k_bucket_big_runs_global (512).  Nothing is
+    expected to leave the packed kernels: the literal was recorded on the parent commit on an MI355X."""
+    X, g, want = _long_run_case(dtype)
+    m = X.shape[1]
+    engine.set_groups(g)
+    engine.set_option("packed_ref_cap", 1024)
+    engine.set_option("big_runs_cap", big_runs_cap)
+    got, prof = _profiled(engine, lambda: engine.run_dense(X, 0, m))
+    assert_planes_match(got, want, ref_row=g.encoded_ref_group, what=f"parts x cooperative walk {dtype.__name__} cap {big_runs_cap}")
+    assert "k_ovo_rank_compact" in prof, prof
+    again, left = _left_to_general_route(engine, capfd, lambda: engine.run_dense(X, 0, m))
+    print("left", dtype.__name__, big_runs_cap, left)
+    _same(got, again)
+    assert left == LONG_RUN_LEFT
+    engine.set_option("no_coop_runs", 1)
+    try:
+        _same(got, engine.run_dense(X, 0, m))
+    finally:
+        engine.set_option("no_coop_runs", 0)
+    engine.set_option("no_ovo_parts", 1)
+    _same(got, engine.run_dense(X, 0, m))

@@ -70,6 +70,25 @@ def test_launches_and_scratch_go_through_engine_h():
     assert "hipLaunchKernelGGL" in engine and "hipFuncSetAttribute" in engine and "get_scratch(" in engine
 
 
+def test_packed_rank_kernel_states_each_thing_once():
+    """kernels_ovo_compact.h: the statistic's tie term and the choice of look-up rounds are written once (ocr_emit, ocr_lookup), the bits of
+    a key range once in all of csrc (common.h), the retired prefetch depth and debug print are gone, and neither the file nor the body of
+    k_ovo_rank_compact is longer than before the kernel was split into steps (1547 and 568 lines)."""
+    csrc = ROOT / "illico_amd" / "csrc"
+    text = (csrc / "kernels_ovo_compact.h").read_text()
+    assert text.count("t0 * t0 * t0") == 1
+    assert text.count("ocr_group<KeyT, 4,") == 1
+    assert sum(p.read_text().count("__clzll((long long)range)") for p in sorted(csrc.glob("*.h")) + sorted(csrc.glob("*.hip"))) <= 1
+    assert "OCR_PAIR" not in text and "OCR_DEBUG_PRINT" not in text
+    lines = text.splitlines()
+    assert len(lines) < 1547
+    start = next(i for i, l in enumerate(lines) if "void k_ovo_rank_compact(" in l)
+    body = next(i for i in range(start, len(lines)) if lines[i] == "}") - start + 1
+    assert body < 568, body
+    # one layout: OcrLds's constructor, its static_assert on the tail, the host's byte count (ocr_lds_bytes), the kernel's pointers
+    assert text.count("OcrLds(") == 4
+
+
 def test_every_option_is_documented():
     """The option table (options.h) and the options comment of include/illico_hip.h name the same switches."""
     from option_names import engine_option_names
