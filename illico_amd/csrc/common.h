@@ -255,6 +255,13 @@ template <typename KeyT> __device__ __forceinline__ KeyT wave_max_key(KeyT x) {
     for (int d = 32; d > 0; d >>= 1) { KeyT o = __shfl_xor(x, d); x = o > x ? o : x; }
     return x;
 }
+// The workgroup's smallest and largest key into kr[0] / kr[1] from every thread's own (set to MAXK / 0 and a barrier before; a barrier
+// before they are read).
+template <typename KeyT> __device__ __forceinline__ void wg_key_range(KeyT lo, KeyT hi, KeyT *kr, int lane) {
+    lo = wave_min_key(lo);
+    hi = wave_max_key(hi);
+    if (lane == 0) { atomicMin(&kr[0], lo); atomicMax(&kr[1], hi); }
+}
 // bits of a key range (largest key - smallest key): 0 for a range of one key
 __device__ __forceinline__ int key_range_bits(u32 range) { return range ? 32 - __clz((int)range) : 0; }
 __device__ __forceinline__ int key_range_bits(u64 range) { return range ? 64 - __clzll((long long)range) : 0; }

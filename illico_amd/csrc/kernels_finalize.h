@@ -39,6 +39,9 @@ __device__ __forceinline__ u64 tie_f64_sparse(u64 t_nonzero, long long n_zeros) 
     t += n0 * n0 * n0 - n0;
     return (u64)__double_as_longlong(t);
 }
+// Doubled rank sum of z implicit zeros of a column with nneg negative values and n0 zeros: they tie at rank nneg + (n0 + 1) / 2
+// (ovr/sparse_ovr.py:70-83).
+__device__ __forceinline__ u64 zeros_rank_sum2(long long z, long long nneg, long long n0) { return (u64)z * (u64)(2 * nneg + n0 + 1); }
 
 __device__ __forceinline__ double pval_device_pre(double nnn, double var0, double n12, double tie_sum, double U, double mu, double cc, int alternative) {
     double tie_corr = 1.0 - tie_sum / nnn;                                         // math.py:95

@@ -165,6 +165,13 @@ template <typename KeyT> __device__ __forceinline__ u32 refbk_bucket(const RefBk
     const KeyT d = q > bk.kmin ? (KeyT)((KeyT)(q - bk.kmin) >> bk.shift) : (KeyT)0;
     return (u32)(d < bk.last ? d : bk.last);
 }
+// The pad rule of a bucket walk that reads four keys at a time, into the MAXK pad behind the last bucket: `less` and `eq` count the keys
+// of bucket [lo, hi) below q and equal to it; a query equal to the largest key (INT_MAX, an all-ones NaN) also matched the pad slots --
+// there every key of the bucket that is not smaller is equal.
+template <typename KeyT> __device__ __forceinline__ u32 bucket_eq_padded(KeyT q, u32 lo, u32 hi, u32 less, u32 eq) {
+    if (q == KeyInfo<KeyT>::MAXK) eq = (hi - lo) - less;
+    return eq;
+}
 // lb = #A < q, a = #A == q
 // PAD: 4 slots of the largest key follow the table's keys (the walk may read past the last bucket); without it the walk
 // checks every slot against the bucket's end (the reference run sits inside a larger buffer: k_csc_gene).
@@ -187,9 +194,7 @@ __device__ __forceinline__ void ref_find(const KeyT *A, const u16 *runend, u32 n
                 eq += (a0 == q ? 1u : 0u) + ((j + 1 < nA && a1 == q) ? 1u : 0u) + ((j + 2 < nA && a2 == q) ? 1u : 0u) + ((j + 3 < nA && a3 == q) ? 1u : 0u);
             }
         }
-        // a query equal to the largest key (INT_MAX, an all-ones NaN) also matches the MAXK pad slots past the last bucket:
-        // there every key of the bucket that is not smaller is equal
-        if (PAD && q == KeyInfo<KeyT>::MAXK) eq = (hi - lo) - less;
+        if (PAD) eq = bucket_eq_padded(q, lo, hi, less, eq);
         lb = lo + less;
         a = q == KeyInfo<KeyT>::ZEROK ? bk.zeros : eq;
     } else {

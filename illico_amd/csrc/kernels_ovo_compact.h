@@ -10,7 +10,7 @@
 //                       256-byte stores out of an LDS staging piece; beside them, per (gene, group): the number of non-zeros
 //                       (16 bit), where they start, and the group's value sum (float64, fixed order: deterministic).  HBM:
 //                       X once in, the non-zeros once out.  PACK = false keeps every key (dense OVR's transposition with the
-//                       group sums folded in); dense OVR's partition (kernels_csc_ovr.h) walks either form.
+//                       group sums folded in); dense OVR's partition (kernels_ovr_partition.h) walks either form.
 //   k_ovo_rank_compact  one workgroup per gene: the reference's non-zero keys are dealt into value buckets in LDS -- 2^17
 //                       buckets at half a byte each: per 16 buckets one 64-bit word of 2-bit counters + 16-bit prefix --, then
 //                       one wavefront per group looks every non-zero key up (one table word, three keys, six compares):
@@ -630,13 +630,7 @@ template <typename KeyT, int NT, typename F> __device__ __forceinline__ void run
 }
 
 // ---- steps the bucket kernels, k_ref_cuts and the rank kernel share ------------------------------------------------------------------
-// The workgroup's smallest and largest key into kr[0] / kr[1] from every thread's own (set to MAXK / 0 and a barrier before; a barrier
-// before they are read).
-template <typename KeyT> __device__ __forceinline__ void wg_key_range(KeyT lo, KeyT hi, KeyT *kr, int lane) {
-    lo = wave_min_key(lo);
-    hi = wave_max_key(hi);
-    if (lane == 0) { atomicMin(&kr[0], lo); atomicMax(&kr[1], hi); }
-}
+// (the workgroup's smallest and largest key: wg_key_range, common.h)
 // Exclusive scan over LDS counters dealt to the threads in order: from the sum of a thread's own counters, the sum of the counters of
 // all threads before it.  part: [threads / 64] words; a barrier inside.
 __device__ __forceinline__ u32 wg_excl_scan(u32 sum, u32 *part, int lane, int wave) {

@@ -556,7 +556,7 @@ __global__ __launch_bounds__(NT) void k_ovr_gene(OvrParams P) {
             u64 r2 = ACCG ? atomicAdd(&R2[g], 0ull) : R2[g]; // HBM accumulators: read at L2, where the atomics landed
             if (ZS) {
                 long long z = n_g - (long long)(ACCG ? atomicAdd(&gcnt[g], 0u) : gcnt[g]);
-                r2 += (u64)z * (u64)(2 * nneg + n0 + 1);
+                r2 += zeros_rank_sum2(z, nneg, (long long)n0);
             }
             long long two_u = 2ll * (P.n_cells - n_g) * n_g + n_g * (n_g + 1) - (long long)r2;
             P.out_2u[(size_t)gene * G + g] = two_u;

@@ -12,7 +12,7 @@
 // all of them integers that fit 64 bits while n_g + n_r < 2^21.  The zeros are never records: with neg_k / pos_k the negative / positive
 // cells of k and z_k = n_k - neg_k - pos_k, at the end L[g][r] += pos_g z_r + z_g neg_r, T[k] += z_k^3 - z_k, X[g][r] += z_g z_r (z_g + z_r).
 //
-// k_pw_rank_pairs walks the value-range parts k_ovr_partition wrote (kernels_csc_ovr.h: (key, group code) records of the non-zeros, part
+// k_pw_rank_pairs walks the value-range parts k_ovr_partition wrote (kernels_ovr_partition.h: (key, group code) records of the non-zeros, part
 // after part in value order, a part at most `cap` records): one workgroup per gene, drawn from a queue, its parts one after the other.
 // A part's records of selected groups go to LDS as u64 (key << 32 | slot) and are sorted there (block_sort_hybrid).  The sixteen
 // wavefronts split the sorted part into stretches cut at key changes; a small histogram per stretch gives each wavefront the counts
@@ -25,7 +25,7 @@
 // same functions as the one-versus-reference routes and the histogram pair route.
 #pragma once
 #include "common.h"
-#include "kernels_csc_ovr.h"
+#include "kernels_ovr_partition.h"
 #include "kernels_finalize.h"
 
 #define PWR_NT 1024

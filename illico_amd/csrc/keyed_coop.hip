@@ -1,4 +1,4 @@
-// The COOP form of k_ovr_partition_packed (kernels_csc_ovr.h: long blocks dealt over all the wavefronts of a gene's workgroup) in a
+// The COOP form of k_ovr_partition_packed (kernels_ovr_partition.h: long blocks dealt over all the wavefronts of a gene's workgroup) in a
 // translation unit of its own: the plain form in keyed_u32.hip / keyed_u64.hip keeps the code it had.
 #include "keyed_driver.h"
 

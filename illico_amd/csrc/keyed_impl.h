@@ -60,8 +60,8 @@ int run_ovr_dense_batch(illico_ctx *c, KeyT *Xt, int64_t stride, int nb, int N, 
     return launch_gene_totals(c, ssum, (int)c->n_groups, nb, gtot);
 }
 
-// Dense OVR, any values, in value-range parts (kernels_csc_ovr.h): partition each gene's non-zero keys into parts that
-// fit the LDS key buffer, rank every part with the bucket / sorted forms of k_csc_ovr_gene, sum the parts up.  Genes whose
+// Dense OVR, any values, in value-range parts (kernels_ovr_partition.h, kernels_ovr_parts.h): partition each gene's non-zero keys into parts that
+// fit the LDS key buffer, rank every part with the bucket / sorted forms of ovr_rank_run (kernels_ovr_rank.h), sum the parts up.  Genes whose
 // values crowd into one coarse bucket (heavy ties) are recomputed by the general route over the gene range that covers
 // them (run by run).  *done = false: the route does not apply (nothing was launched).
 // packed = non-null: Xt holds the PACKED rows of k_group_compact (non-zero keys only; nnz / blk_cnt beside them): the partition walks
@@ -81,12 +81,12 @@ int run_ovr_dense_parts(illico_ctx *c, KeyT *Xt, int64_t stride, int nb, int N, 
     // workgroup of 1024 threads, as before round 5.
     // (columns too long for 128 half-size parts -- two million cells -- take whole-size parts, up to OVRP_PMAX = 255 of them: the general
     //  route instead was 151 ms at 2 000 000 x 1200 continuous, where the parts are 17)
-    const bool half = !c->ovr_rank_whole && csco_key_cap(G, 13, sizeof(KeyT), kMaxLds / 2, true) >= 8192 &&
-                      (int64_t)(csco_key_cap(G, 13, sizeof(KeyT), kMaxLds / 2, true) & ~1023) * 128 >= N;
+    const bool half = !c->ovr_rank_whole && csco_key_cap(G, 13, sizeof(KeyT), kMaxLds / 2) >= 8192 &&
+                      (int64_t)(csco_key_cap(G, 13, sizeof(KeyT), kMaxLds / 2) & ~1023) * 128 >= N;
     const size_t lds_budget = half ? kMaxLds / 2 : kMaxLds;
     int lg = half ? 13 : 14;
-    if (csco_key_cap(G, lg, sizeof(KeyT), lds_budget, true) < 12288 && !half) lg = 13;
-    const int key_cap = csco_key_cap(G, lg, sizeof(KeyT), lds_budget, true);
+    if (csco_key_cap(G, lg, sizeof(KeyT), lds_budget) < 12288 && !half) lg = 13;
+    const int key_cap = csco_key_cap(G, lg, sizeof(KeyT), lds_budget);
     int cap = key_cap & ~1023; // any part can also take the sorted form (1024-key chunks)
     if (cap < 4096) return ILLICO_OK;
     if (c->ovr_parts_cap > 0) cap = (int)std::min<int64_t>(cap, std::max<int64_t>(1024, c->ovr_parts_cap & ~1023ll)); // tests: many small parts
@@ -135,7 +135,7 @@ int run_ovr_dense_parts(illico_ctx *c, KeyT *Xt, int64_t stride, int nb, int N, 
         P.gflag = gflag; P.gene_counter = gene_ctr; P.nb = nb; P.G = G; P.counts = c->d_counts; P.n_cells = N;
         P.key_cap = key_cap; P.lg_buckets = lg; P.force_sorted = c->csc_ovr_sorted_form ? 1 : 0;
         P.out_2u = s2u; P.out_tie = stie;
-        const size_t lds = csco_fixed_lds_bytes(G, lg, true) + (size_t)(key_cap + 4) * sizeof(KeyT);
+        const size_t lds = csco_fixed_lds_bytes(G, lg) + (size_t)(key_cap + 4) * sizeof(KeyT);
         ProfScope ps(c, KID_OVR_RANK_PARTS);
         int n_cu = 256;
         hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);

@@ -448,14 +448,14 @@ static int run_csc_ovr_route(const SparseCall<InT, IdxT> &S, int64_t max_nnz, st
     int g_lds = G; // groups whose accumulators stay in LDS
     if (key_cap < max_nnz) {
         int lg2 = 14;
-        if (csco_key_cap(G, lg2, sizeof(KeyT), kMaxLds, false, true) < max_nnz) lg2 = 13;
-        const int cap2 = csco_key_cap(G, lg2, sizeof(KeyT), kMaxLds, false, true);
+        if (csco_key_cap(G, lg2, sizeof(KeyT), kMaxLds, true) < max_nnz) lg2 = 13;
+        const int cap2 = csco_key_cap(G, lg2, sizeof(KeyT), kMaxLds, true);
         if (cap2 > key_cap) {
             accg = true; lg = lg2;
             // what the largest gene's keys leave of LDS holds the accumulators of the first groups; the others' live in HBM
-            const size_t need = csco_fixed_lds_bytes(0, lg, false) + ((size_t)std::min<int64_t>(max_nnz, cap2) + 8) * sizeof(KeyT);
+            const size_t need = csco_fixed_lds_bytes(0, lg) + ((size_t)std::min<int64_t>(max_nnz, cap2) + 8) * sizeof(KeyT);
             g_lds = need < kMaxLds ? (int)std::min<size_t>((size_t)G, ((kMaxLds - need) / 8) & ~(size_t)1) : 0;
-            key_cap = (int)std::min<size_t>((kMaxLds - csco_fixed_lds_bytes(g_lds, lg, false)) / sizeof(KeyT) - 4, 65535 - 4);
+            key_cap = (int)std::min<size_t>((kMaxLds - csco_fixed_lds_bytes(g_lds, lg)) / sizeof(KeyT) - 4, 65535 - 4);
         }
     }
     if (key_cap <= 0) return ILLICO_OK;
@@ -470,7 +470,7 @@ static int run_csc_ovr_route(const SparseCall<InT, IdxT> &S, int64_t max_nnz, st
     int rc;
     const int *d_cols;
     if ((rc = upload_cols(c, cols, &d_cols))) return rc;
-    const size_t lds = csco_fixed_lds_bytes(g_lds, lg, false, accg) + (size_t)(key_cap + 4) * sizeof(KeyT);
+    const size_t lds = csco_fixed_lds_bytes(g_lds, lg) + (size_t)(key_cap + 4) * sizeof(KeyT);
     const int64_t n = (int64_t)cols.size(), nb_max = stats_batch_genes(n, G);
     StatsPlanes st;
     if ((rc = carve_stats(c, nb_max, G, true, &st))) return rc;

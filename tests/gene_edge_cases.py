@@ -30,7 +30,7 @@ MAX_SHARE = 0.15
 # The host sizing functions, restated (one function each).  kMaxLds: illico_amd/csrc/engine.h
 # ---------------------------------------------------------------------------------------------------------------------------------------
 MAX_LDS = 160 * 1024
-CSCO_CHUNK = 1024        # kernels_csc_ovr.h: 64 * CSCO_K, the sort chunk of the sorted form
+CSCO_CHUNK = 1024        # kernels_ovr_rank.h: 64 * CSCO_K, the sort chunk of the sorted form
 CSCO_MAX_BUCKET = 192
 CSCO_MAX_AVG = 64
 CSCG_SMALL, CSCG_MEDIUM = 32, 128   # kernels_csc_gene.h
@@ -38,12 +38,12 @@ RUNEND_MAX = 8192        # sparse_driver.h: run_csc_gene_route
 
 
 def csco_fixed_lds_bytes(G, lg_buckets):
-    """kernels_csc_ovr.h: csco_fixed_lds_bytes"""
+    """kernels_ovr_rank.h: csco_fixed_lds_bytes"""
     return ((G + 1) & ~1) * 8 + (2 << lg_buckets) + 256
 
 
 def csco_key_cap(G, lg_buckets, key_size, accg=False):
-    """kernels_csc_ovr.h: csco_key_cap (lds_max = kMaxLds)"""
+    """kernels_ovr_rank.h: csco_key_cap (lds_max = kMaxLds)"""
     fixed = csco_fixed_lds_bytes(0 if accg else G, lg_buckets)
     if fixed + 1024 * 4 + 64 > MAX_LDS:
         return 0
@@ -82,7 +82,7 @@ def csc_ovr_plan(G, key_size, max_nnz, small_lds=True):
 
 
 def csc_ovr_takes(plan, ns, sorted_form):
-    """kernels_csc_ovr.h: k_csc_ovr_gene keeps a gene of ns stored entries (ns_ll > P.key_cap; sorted form: ncap > P.key_cap)."""
+    """kernels_csc_ovr.h: k_csc_ovr_gene keeps a gene of ns stored entries (k1 - k0 > P.key_cap; sorted form, ovr_rank_sorted in kernels_ovr_rank.h: ncap > key_cap)."""
     if ns > plan.key_cap:
         return False
     return not sorted_form or -(-ns // CSCO_CHUNK) * CSCO_CHUNK <= plan.key_cap
@@ -135,7 +135,8 @@ def keys_of(values, key_size):
 
 
 def bucket_occupancy(values, key_size, lg_buckets):
-    """kernels_csc_ovr.h, k_csc_ovr_gene steps 0-1: the bucket counters of a column whose stored non-zeros are `values`, in stored order.
+    """kernels_ovr_rank.h, ovr_rank_run up to its count pass (ovr_sampled_range, OvrBuckets, ovr_count_keys): the bucket counters of a
+    column whose stored non-zeros are `values`, in stored order.
     The key range comes from every eighth row of 1024 entries when the column holds more than 8192; shift = key bits of the range minus
     lg_buckets; the last two buckets are one."""
     keys = keys_of(values, key_size)

@@ -50,7 +50,7 @@ def route(request, engine):
     # a host matrix goes up as float32 windows ("fused-host": the byte form forbidden) or as byte windows ("fused-host-narrow": forced,
     # whatever the values: genes with a cell the bytes cannot hold come back and go up again in their own type)
     engine.set_option("host_narrow", 1 if request.param.startswith("fused-host-narrow") else (-1 if request.param.startswith("fused-host+") else 0))
-    # ... and is itself the fallback of the value-range parts route (k_ovr_partition + k_csc_ovr_gene), which the fused
+    # ... and is itself the fallback of the value-range parts route (k_ovr_partition + k_ovr_rank_gene_parts), which the fused
     # params leave on
     engine.set_option("no_ovr_parts_path", 0 if request.param.startswith("fused") else 1)
     # the OVO sort route keeps the reference column in value buckets (no sort) unless its values crowd; "sort-only" sorts it
@@ -201,7 +201,7 @@ def test_ovr_ragged(engine):
 @pytest.mark.parametrize("sorted_form,parts_cap", [(0, 0), (1, 0), (0, 1024)])
 def test_ovr_dense_value_range_parts_route(engine, dtype, sorted_form, parts_cap):
     """Dense OVR, any values: each gene's non-zero keys are split by value into parts that fit LDS and ranked part by
-    part (k_ovr_partition + k_csc_ovr_gene<PARTS>; bucket form, and the sorted form when forced).  70 000 cells: fully
+    part (k_ovr_partition + k_ovr_rank_gene_parts; bucket form, and the sorted form when forced).  70 000 cells: fully
     dense columns need 3+ parts (5+ for float64 keys); half-empty and nearly empty columns, negatives, exact repeats
     among continuous values, a tie-heavy column and a constant column (crowded coarse buckets: parts of their own, counted per
     group when they hold one value; two values in one crowded bucket: that gene leaves the route and the general route recomputes

@@ -89,6 +89,31 @@ def test_packed_rank_kernel_states_each_thing_once():
     assert text.count("OcrLds(") == 4
 
 
+def test_ovr_value_range_kernels_state_each_thing_once():
+    """The OVR ranking of a run of keys in LDS has one body (kernels_ovr_rank.h) for its two callers, the value-range partition one plan
+    for its two key walks: over the headers of csrc the bucket walk's pad rule, the crowd test, the closing statistic and the ballot match
+    are each written once, the partition's LDS layout once as a struct and nowhere as a sum of constants, and the family is shorter than
+    the 1030 lines of its two forked files."""
+    csrc = ROOT / "illico_amd" / "csrc"
+    headers = {p.name: p.read_text() for p in sorted(csrc.glob("*.h"))}
+    every = "".join(headers.values())
+    for once in ("eq = (hi - lo) - less", "CSCO_MAX_AVG * (u64)n", "2 * nneg + n0 + 1", "m &= on ? bl : ~bl"):
+        assert every.count(once) == 1, once
+    assert every.count("struct OvrpLds {") == 1 and "return OvrpLds::total;" in headers["kernels_ovr_partition.h"]
+    assert "(2 * OVRP_PMAX + 4) * 4" not in every and every.count("OVRP_PMAX * 4") == 1 and every.count("hist + NB") == 1
+    # the callers hold no step of their own: no bucket table, no sort, no look-up outside the body
+    for caller in ("kernels_csc_ovr.h", "kernels_ovr_parts.h"):
+        text = headers[caller]
+        assert text.count("ovr_rank_run<NT>(") == 1 and text.count("ovr_close_gene<NT>(") == 1, caller
+        code = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith("//"))
+        assert not any(w in code for w in ("tab16", "block_sort_hybrid", "bound_pow2", "block_excl_scan", "wave_min_key")), caller
+    # dead parameters are gone: one layout in front of the keys, whoever asks
+    assert "csco_fixed_lds_bytes(int G, int lg_buckets)" in every and "(void)parts" not in every
+    assert "csco_key_cap(int G, int lg_buckets, size_t key_size, size_t lds_max, bool accg = false)" in every
+    family = ("kernels_ovr_rank.h", "kernels_csc_ovr.h", "kernels_ovr_parts.h", "kernels_ovr_partition.h")
+    assert sum(len(headers[f].splitlines()) for f in family) < 1030
+
+
 def test_every_option_is_documented():
     """The option table (options.h) and the options comment of include/illico_hip.h name the same switches."""
     from option_names import engine_option_names

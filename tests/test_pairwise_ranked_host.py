@@ -378,7 +378,7 @@ def float_keys(x):
 
 
 def coarse_buckets(keys):
-    """the partition's bucket of each non-zero key when its key range is that of all of them (kernels_csc_ovr.h, OVRP_LG = 13; the
+    """the partition's bucket of each non-zero key when its key range is that of all of them (kernels_ovr_partition.h, OVRP_LG = 13; the
     device samples the range from an eighth of the rows: a narrower range only makes the buckets finer)"""
     kmin, kmax = int(keys.min()), int(keys.max())
     shift = max(0, (kmax - kmin).bit_length() - 13)
