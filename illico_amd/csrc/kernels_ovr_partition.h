@@ -149,6 +149,9 @@ template <int NT, typename KeyT> __device__ __forceinline__ OvrpPlan ovrp_plan(c
             const u32 p = S.hist[b] / quota;
             S.part_of[b] = (unsigned char)min(p, (u32)OVRP_PMAX - 1); // (empty buckets past the last key may overshoot)
             if (p < pl.n_parts && (b == 0 || S.hist[b - 1] / quota != p)) S.pstart[p] = S.hist[b];
+            // the last bucket may reach into a part that no bucket starts (key n - 1 lies one part beyond the bucket's first key, and no
+            // bucket follows): that part is empty -- its keys are placed with the bucket's, in part p
+            if (b == NB - 1 && p + 1 < pl.n_parts) S.pstart[p + 1] = pl.n;
         }
         if (tid == 0) S.pstart[pl.n_parts] = pl.n;
     }
