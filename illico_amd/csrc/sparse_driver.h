@@ -13,7 +13,7 @@ static size_t seg_lds_bytes(int G) { return (size_t)((G + 3) & ~3) * 4 + SEG_NT 
 // per CU), else equal windows of about 2000 groups (16-bit cells: about 1100), one launch per window over the same entries.
 static int cscc_group_window(int G, bool w16) {
     // (16-bit cells: windows rather than a 32-value table -- genes with a value of 32 .. 63 would leave the route)
-    const bool one = w16 ? cscc_lds_bytes16(G, 64) + 8192 <= kMaxLds : cscc_lds_bytes(G, 32) + 8192 <= kMaxLds;
+    const bool one = w16 ? cscc_lds_bytes(G, CSCC_16BIT, 64) + 8192 <= kMaxLds : cscc_lds_bytes(G, CSCC_8BIT, 32) + 8192 <= kMaxLds;
     if (one) return G;
     const int per = w16 ? 1100 : 2000;
     const int k = (G + per - 1) / per;
@@ -31,8 +31,9 @@ struct CscCountsLayout {
     int rt8 = 32;                    // table size of the 8-bit (or 16-bit) form
     bool mixed = false;              // first the mixed 8- / 4-bit cells
     bool pack16 = false;             // 16-byte statistics while every ranked group has at most 255 cells
+    int cells(bool mixed_pass) const { return w16 ? CSCC_16BIT : mixed_pass ? CSCC_MIXED : CSCC_8BIT; } // the kernel's layout parameter
     int rt(bool mixed_pass) const { return mixed_pass ? 64 : rt8; }
-    size_t lds(bool mixed_pass) const { return w16 ? cscc_lds_bytes16(Gw, rt(mixed_pass)) : cscc_lds_bytes(Gw, mixed_pass ? 0 : rt(mixed_pass)); }
+    size_t lds(bool mixed_pass) const { return cscc_lds_bytes(Gw, cells(mixed_pass), rt(mixed_pass)); }
 };
 static CscCountsLayout csc_counts_layout(const illico_ctx *c) {
     CscCountsLayout L;
@@ -52,10 +53,10 @@ static CscCountsLayout csc_counts_layout(const illico_ctx *c) {
     // the 16-bit code table's limit; 30 000 groups of ten cells at C3 shape: 52.7 ms through the per-gene sort routes when eight was the limit)
     L.Gw = cscc_group_window(G, L.w16);
     L.n_windows = (G + L.Gw - 1) / std::max(1, L.Gw);
-    L.rt8 = L.w16 ? (cscc_lds_bytes16(L.Gw, 64) + 8192 <= kMaxLds ? 64 : 32) : (cscc_lds_bytes(L.Gw, 64) + 8192 <= kMaxLds ? 64 : 32);
+    L.rt8 = cscc_lds_bytes(L.Gw, L.cells(false), 64) + 8192 <= kMaxLds ? 64 : 32;
     // the mixed layout pays when two workgroups fit a CU
     // (... or when 64 bytes per group do not fit at all: the mixed table still holds all 63 values where the 8-bit form would drop to 31)
-    L.mixed = !L.w16 && !c->no_csc_counts_mixed && (2 * (cscc_lds_bytes(L.Gw, 0) + 4096) <= kMaxLds || (L.rt8 == 32 && cscc_lds_bytes(L.Gw, 0) + 8192 <= kMaxLds));
+    L.mixed = !L.w16 && !c->no_csc_counts_mixed && (2 * (cscc_lds_bytes(L.Gw, CSCC_MIXED, 64) + 4096) <= kMaxLds || (L.rt8 == 32 && cscc_lds_bytes(L.Gw, CSCC_MIXED, 64) + 8192 <= kMaxLds));
     L.pack16 = L.n_big == 0 && !L.w16;
     return L;
 }
@@ -227,23 +228,21 @@ static int upload_cols(illico_ctx *c, const std::vector<int64_t> &cols, const in
     return ILLICO_OK;
 }
 
-// the launch of k_csc_counts for one window of the groups (kernels_csc_counts.h)
-template <typename InT, typename IdxT, bool MIXED>
-static int launch_csc_counts(illico_ctx *c, const CscCountsParams &P, int rt, bool has_big, bool ovr, size_t lds, bool w16 = false) {
+// the launch of k_csc_counts for one window of the groups (kernels_csc_counts.h; its template parameters: DESIGN.md section 25)
+template <typename InT, typename IdxT>
+static int launch_csc_counts(illico_ctx *c, const CscCountsParams &P, int cells, int rt, bool has_big, bool ovr, size_t lds) {
     ProfScope ps(c, KID_CSC_COUNTS);
     const bool win = P.G != P.G_total; // a window of the groups (instantiated for 16-bit group codes only: the host's case)
     if (win && !P.codes16) return fail(c, ILLICO_ERR_UNSUPPORTED, "group windows need the 16-bit code table");
-    // (C16F, WINF) takes three values: a window implies the 16-bit codes.  16-bit cells for every group (w16: more than CSCC_MAX_BIG
-    // groups above 255 cells) fix BIG and MIXED.
+    // (C16F, WINF) takes three values: a window implies the 16-bit codes.  16-bit cells hold every group: no side table.
     return dispatch_flags([&](auto ovr_c, auto big_c, auto c16_c, auto win_c) {
-        constexpr bool OVRF = decltype(ovr_c)::value, BIG = decltype(big_c)::value, C16F = decltype(c16_c)::value, WINF = decltype(win_c)::value;
-        return dispatch_int<64, 32>(rt, [&](auto rt_c) -> int {
-            constexpr int RTV = decltype(rt_c)::value;
-            if constexpr (WINF && !C16F) return ILLICO_OK; // (never called: checked above)
-            else if (w16)
-                return launch_kernel(c, k_csc_counts<InT, IdxT, OVRF, RTV, false, false, C16F, CSCC_WT, 0, CSCC_NT, CSCC_LEAN, false, true, WINF>, dim3(P.nb), dim3(CSCC_NT), lds, P);
-            else
-                return launch_kernel(c, k_csc_counts<InT, IdxT, OVRF, RTV, BIG, MIXED && RTV == 64, C16F, CSCC_WT, 0, CSCC_NT, CSCC_LEAN, CSCC_PUTB(OVRF), false, WINF>, dim3(P.nb), dim3(CSCC_NT), lds, P);
+        return dispatch_int<CSCC_MIXED, CSCC_8BIT, CSCC_16BIT>(cells, [&](auto cells_c) {
+            return dispatch_int<64, 32>(rt, [&](auto rt_c) -> int {
+                constexpr int CELLS = decltype(cells_c)::value, RTV = decltype(rt_c)::value;
+                constexpr bool C16F = decltype(c16_c)::value, WINF = decltype(win_c)::value, BIG = decltype(big_c)::value && CELLS != CSCC_16BIT;
+                if constexpr ((WINF && !C16F) || (CELLS == CSCC_MIXED && RTV != 64)) return ILLICO_OK; // (never called: checked above; CscCountsLayout::rt)
+                else return launch_kernel(c, k_csc_counts<InT, IdxT, decltype(ovr_c)::value, RTV, BIG, CELLS, C16F, WINF>, dim3(P.nb), dim3(CSCC_NT), lds, P);
+            });
         });
     }, ovr, has_big, win || P.codes16 != nullptr, win);
 }
@@ -290,8 +289,7 @@ static int launch_csc_counts_windows(const SparseCall<InT, IdxT> &S, CscCountsPa
     int rc;
     for (int g_lo = 0; g_lo < S.G; g_lo += L.Gw) {
         P.g_lo = g_lo; P.G = std::min(L.Gw, S.G - g_lo);
-        if (mixed) { if ((rc = launch_csc_counts<InT, IdxT, true>(S.c, P, L.rt(true), L.n_big > 0, S.ovr, L.lds(true)))) return rc; }
-        else if ((rc = launch_csc_counts<InT, IdxT, false>(S.c, P, L.rt(false), L.n_big > 0, S.ovr, L.lds(false), L.w16))) return rc;
+        if ((rc = launch_csc_counts<InT, IdxT>(S.c, P, L.cells(mixed), L.rt(mixed), L.n_big > 0, S.ovr, L.lds(mixed)))) return rc;
     }
     return ILLICO_OK;
 }

@@ -1,13 +1,14 @@
 // Microbenchmark harness for the count-valued CSC kernel (kernels_csc_counts.h) on a C3-shaped synthetic matrix built on the
 // device: 300k cells x 8k genes, ~10 % stored entries, Poisson-like small integers, 2000 groups (one of 10 000 cells).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I illico_amd/csrc -o tools/micro/cscc_bench tools/micro/cscc_bench.hip
-// Run:   tools/micro/cscc_bench [variant ...]
+// Run:   tools/micro/cscc_bench [launched | finalize]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 #include <algorithm>
+#include <type_traits>
 #include "common.h"
 #include "kernels_csc_counts.h"
 #include "kernels_finalize.h"
@@ -83,7 +84,7 @@ int main(int argc, char **argv) {
     CscCountsParams P;
     P.g_lo = 0; P.G_total = G; // (no group windows here)
     P.data = d_data; P.indices = d_indices; P.indptr = d_indptr; P.kshift = 0; P.col0 = 0; P.gene_cols = nullptr; P.nb = M; P.codes16 = d_codes16;
-    P.counts = d_counts; P.G = G; P.n_cells = N; P.big_slot = nullptr; P.fallback = fb; P.out_2u = s2u; P.out_tie = stie; P.out_sum = ssum; P.gene_total = nullptr; P.verdict = nullptr; P.pack16 = 0;
+    P.counts = d_counts; P.G = G; P.n_cells = N; P.big_slot = nullptr; P.fallback = fb; P.out_2u = s2u; P.out_tie = stie; P.out_sum = ssum; P.gene_total = nullptr; P.verdict = nullptr; P.pack16 = 0; P.tie_f64 = 0;
     hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
     auto time_it = [&](const char *name, auto launch) {
         launch(); CK(hipDeviceSynchronize());
@@ -117,41 +118,17 @@ int main(int argc, char **argv) {
             CK(hipMemcpy(d_counts, counts.data(), G * 4, hipMemcpyHostToDevice));
             CK(hipMemcpy(d_codes16, codes16.data(), N * 2, hipMemcpyHostToDevice));
         }
-        const size_t lds = cscc_lds_bytes(G, 0);
-#define VAR(NAME, OVRF, WTF, ABLF)                                                                                          \
-        if (want(NAME)) {                                                                                                       \
-            auto kern = k_csc_counts<float, int, OVRF, 64, false, true, true, WTF, ABLF>;                                        \
-            CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                   \
-            time_it(ovr ? NAME " ovr" : NAME " ovo", [&] { hipLaunchKernelGGL(kern, dim3(M), dim3(CSCC_NT), lds, 0, P); });       \
+        const size_t lds = cscc_lds_bytes(G, CSCC_MIXED, 64);
+        // the form the library launches at this shape: mixed cells, 64 values, no side table, 16-bit codes, no window
+        auto launched = [&](auto ovr_c) {
+            auto kern = k_csc_counts<float, int, decltype(ovr_c)::value, 64, false, CSCC_MIXED, true, false>;
+            CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            return kern;
+        };
+        if (want("launched")) {
+            if (ovr) { auto kern = launched(std::true_type{}); time_it("launched ovr", [&] { hipLaunchKernelGGL(kern, dim3(M), dim3(CSCC_NT), lds, 0, P); }); }
+            else { auto kern = launched(std::false_type{}); time_it("launched ovo", [&] { hipLaunchKernelGGL(kern, dim3(M), dim3(CSCC_NT), lds, 0, P); }); }
         }
-#define VARS(OVRF)                                                                                                          \
-        VAR("base", OVRF, false, 0) VAR("wt", OVRF, true, 0) VAR("base-nogather", OVRF, false, 1) VAR("base-noatomic", OVRF, false, 2)   \
-        VAR("base-nogather-noatomic", OVRF, false, 3) VAR("base-nosweep", OVRF, false, 4) VAR("base-nostore", OVRF, false, 8)              \
-        VAR("base-nosweep-nostore", OVRF, false, 12) VAR("base-noentries", OVRF, false, 16) VAR("base-entries-only", OVRF, false, 12 | 32)     \
-        VAR("wt-noentries", OVRF, true, 16) VAR("wt-nostore", OVRF, true, 8)
-        if (ovr) { VARS(true) } else { VARS(false) }
-#define VARN(NAME, OVRF, WTF)                                                                                               \
-        if (want(NAME)) {                                                                                                       \
-            auto kern = k_csc_counts<float, int, OVRF, 64, false, true, true, WTF, 0, 1024>;                              \
-            CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                   \
-            time_it(ovr ? NAME " ovr" : NAME " ovo", [&] { hipLaunchKernelGGL(kern, dim3(M), dim3(1024), lds, 0, P); });          \
-        }
-if (ovr) { VAR("stagger32-wt", true, true, 64) VAR("stagger96-wt", true, true, 128) } else { VAR("stagger32-wt", false, true, 64) VAR("stagger96-wt", false, true, 128) }
-#define VARL(NAME, OVRF, WTF, ABLF)                                                                                         \
-        if (want(NAME)) {                                                                                                       \
-            auto kern = k_csc_counts<float, int, OVRF, 64, false, true, true, WTF, ABLF, CSCC_NT, true>;                         \
-            CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                   \
-            time_it(ovr ? NAME " ovr" : NAME " ovo", [&] { hipLaunchKernelGGL(kern, dim3(M), dim3(CSCC_NT), lds, 0, P); });       \
-        }
-#define VARLB(NAME, OVRF, WTF)                                                                                              \
-        if (want(NAME)) {                                                                                                       \
-            auto kern = k_csc_counts<float, int, OVRF, 64, false, true, true, WTF, 0, CSCC_NT, true, false>;                     \
-            CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                   \
-            time_it(ovr ? NAME " ovr" : NAME " ovo", [&] { hipLaunchKernelGGL(kern, dim3(M), dim3(CSCC_NT), lds, 0, P); });       \
-        }
-        if (ovr) { VARLB("leanload-wt", true, true) VARLB("leanload-base", true, false) } else { VARLB("leanload-wt", false, true) VARLB("leanload-base", false, false) }
-        if (ovr) { VARL("lean-wt", true, true, 0) VARL("lean-base", true, false, 0) VARL("lean-wt-nogather", true, true, 1) } else { VARL("lean-wt", false, true, 0) VARL("lean-base", false, false, 0) VARL("lean-wt-entries-only", false, true, 12 | 32) VARL("lean-wt-nogather", false, true, 1) VARL("lean-wt-noatomic", false, true, 2) VARL("lean-wt-noentries", false, true, 16) }
-        if (ovr) { VARN("nt1024-wt", true, true) } else { VARN("nt1024-wt", false, true) VARN("nt1024-base", false, false) }
         if (!ovr && want("finalize")) { // k_finalize on the statistics, alone and under the next batch's k_csc_counts
             double *op, *ou, *ofc; int *d_cnt32 = d_counts;
             CK(hipMalloc(&op, (size_t)M * G * 8)); CK(hipMalloc(&ou, (size_t)M * G * 8)); CK(hipMalloc(&ofc, (size_t)M * G * 8));
@@ -159,8 +136,7 @@ if (ovr) { VAR("stagger32-wt", true, true, 64) VAR("stagger96-wt", true, true, 1
             F.in_2u = s2u; F.in_tie = stie; F.in_sum = ssum; F.gene_total = nullptr; F.counts = d_cnt32; F.G = G; F.ref = 0; F.nb = M; F.n_cells = N;
             F.use_continuity = 1; F.tie_correct = 1; F.alternative = 0; F.packed = 0; F.out_p = op; F.out_u = ou; F.out_fc = ofc; F.out_ld = M; F.col_map = nullptr;
             time_it("k_finalize alone", [&] { hipLaunchKernelGGL(k_finalize, dim3((M + 31) / 32, (G + 31) / 32), dim3(256), 0, 0, F); });
-            auto kern = k_csc_counts<float, int, false, 64, false, true, true, true, 0, CSCC_NT, true, false>;
-            CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            auto kern = launched(std::false_type{});
             time_it("counts+finalize serial", [&] {
                 hipLaunchKernelGGL(kern, dim3(M), dim3(CSCC_NT), lds, 0, P);
                 hipLaunchKernelGGL(k_finalize, dim3((M + 31) / 32, (G + 31) / 32), dim3(256), 0, 0, F);
