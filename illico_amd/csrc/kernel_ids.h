@@ -58,7 +58,9 @@
     X(KID_PW_PAIRS, "k_pw_pairs") /* illico_pairwise_from_hists */ \
     X(KID_OVO_FUSED_ST16, "k_ovo_fused_st16") /* k_ovo_fused's first pass in a 16-byte-store form ("fused_mem_policy" 8 / 12 where the planes allow it) */ \
     X(KID_PW_RANK_PAIRS, "k_pw_rank_pairs") /* illico_pairwise_ranked_* (kernels_pairwise_ranked.h) */ \
-    X(KID_PW_RANK_EMIT, "k_pw_rank_emit")
+    X(KID_PW_RANK_EMIT, "k_pw_rank_emit") \
+    X(KID_CSR_TILE_GATHER, "k_csr_tile_gather") /* pass 2 of the CSR -> CSC transposition (route_csr_transpose): the gather form ... */ \
+    X(KID_CSR_BLOCK_SCATTER, "k_csr_block_scatter") /* ... and the scatter form; the counting pass stays under k_sparse_seg */
 
 #define ILLICO_KERNEL_ID(id, name) id,
 #define ILLICO_KERNEL_NAME(id, name) name,

@@ -1021,7 +1021,7 @@ static int route_csr_transpose(SparseCall<InT, IdxT> &S, bool *done) {
         if ((rc = scratch(c, "tr_rows", (size_t)std::max<u32>(total, 1), &t_rows))) return rc;
         bool gathered = false;
         if (sorted) {
-            ProfScope ps(c, KID_SPARSE_SEG);
+            ProfScope ps(c, KID_CSR_TILE_GATHER);
             const size_t lds = (size_t)cap * (sizeof(InT) + 4 + 1);
             KERNELCHK(c, k_csr_tile_gather<InT, IdxT>, dim3(n_blocks, ny), dim3(TRG_NT), lds, d_data, d_indices, d_indptr, (int)n_rows, RB, (long long)w0, (int)wn,
                       (const u32 *)counts, (const u32 *)col_total, (const u32 *)col_ptr, cap, (const int *)c->d_codes, t_data, t_rows, d_over);
@@ -1035,7 +1035,7 @@ static int route_csr_transpose(SparseCall<InT, IdxT> &S, bool *done) {
             continue;
         }
         if (!gathered) {
-            ProfScope ps(c, KID_SPARSE_SEG);
+            ProfScope ps(c, KID_CSR_BLOCK_SCATTER);
             KERNELCHK(c, k_csr_block_scatter<InT, IdxT>, dim3(n_blocks), dim3(TR_NT), (size_t)wn * 4, d_data, d_indices, d_indptr, (int)n_rows, RB, (long long)w0,
                       (int)wn, (const u32 *)counts, (const u32 *)col_ptr, (const int *)c->d_codes, t_data, t_rows);
         }

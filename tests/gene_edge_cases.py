@@ -213,7 +213,7 @@ Case = namedtuple("Case", ["name", "edge", "width", "side", "test", "labels", "X
 #          plan, option whose result must equal the default's bit for bit)
 Edge = namedtuple("Edge", ["test", "appear", "pin", "bit_equal", "kind"], defaults=("gene",))
 LEAVES_OVR = {"csc": ("k_ovr_gene",), "csr": ("k_ovr_gene",)}
-# (CSR input: the device transposition is timed under k_sparse_seg on both sides)
+# (CSR input: the device transposition is timed on both sides -- its counting pass under k_sparse_seg, pass 2 under k_csr_tile_gather)
 LEAVES_OVO = {"csc": ("k_sparse_seg", "k_ovo_rank"), "csr": ("k_ovo_rank",)}
 PIN = {"no_csc_ovr_small_lds": 1}
 EDGES = {

@@ -300,8 +300,10 @@ def test_csr_counts_route(engine, test, dtype, idx):
 @pytest.mark.parametrize("dtype,idx", [(np.float32, np.int32), (np.float64, np.int64)])
 def test_csr_transposition_route(engine, test, dtype, idx):
     """CSR with continuous values: transposed to CSC on the device (count pass + tile gather), then the CSC routes.
-    A window wider than one transposition pass (32768 columns), a column window, rows longer than the register
-    window, empty rows, and rows with UNSORTED column indices (those take the scatter form of pass 2)."""
+    33 100 columns: with the rows in order that is ONE window of the counting pass (16-bit counters: up to 65 536 columns), and two
+    windows (32 768 + 332) only for the rows with UNSORTED column indices at the end, which take the scatter form of pass 2 (32-bit
+    cursors: up to 32 768 columns); a second window of the gather form is tests/test_gpu_csr_transpose_edges.py's 65 537-column case.
+    Also a column window, rows longer than the register window, and an empty row."""
     rng = np.random.RandomState(211)
     n, m = 150, 33100
     X = np.where(rng.rand(n, m) < 0.08, np.log1p(rng.poisson(3.0, size=(n, m)) * rng.uniform(0.5, 1.5, size=(n, m))), 0.0)

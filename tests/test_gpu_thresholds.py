@@ -56,7 +56,8 @@ SPARSE_INPUTS = ("csc-host", "csr-host", "csr-device")
 # the profile's names for the kernels of launch_csr_counts_route (sparse_driver.h): a CSR call whose profile holds nothing else took every
 # plane from that pass -- its verdict was good and no gene left it (a gene that leaves is redone by the sort routes, under their names)
 # That reading rests on the routes that redo a call or a gene launching at least one kernel outside this set (today k_ovo_fused,
-# k_ovr_fused, k_csc_gene, k_csc_ovr_gene, k_finalize): k_sparse_seg, k_fused_tables and k_ovr_gene are names they share with this pass.
+# k_ovr_fused, k_csc_gene, k_csc_ovr_gene, k_finalize; pass 2 of the CSR -> CSC transposition has names of its own, k_csr_tile_gather and
+# k_csr_block_scatter): k_sparse_seg, k_fused_tables and k_ovr_gene are names they share with this pass.
 # A new fall-back route made of those three names alone would pass unseen; give it a profile name of its own.
 CSR_COUNTS_ROUTE = {"k_sparse_seg", "k_fused_tables", "k_csr_counts", "k_ovr_gene"}
 # ... and for those of run_csc_counts_route (k_finalize: the statistics into planes; k_value_sums / k_gene_totals: the fold change)

@@ -37,7 +37,7 @@ KERNEL_NAMES = [  # id = position: "profile_only" selects by it, profiles/traffi
     "k_finalize_z", "k_top_validate", "k_top_sort", "k_top_merge", "k_top_scan",
     "k_gm_vmax", "k_gm_dense", "k_gm_csc", "k_gm_csr", "k_gm_totals", "k_gm_finalize", "k_ttest",
     "k_pw_hists_dense", "k_pw_hists_csc", "k_pw_hists_csr", "k_pw_hists_finish", "k_pw_pairs", "k_ovo_fused_st16",
-    "k_pw_rank_pairs", "k_pw_rank_emit"]
+    "k_pw_rank_pairs", "k_pw_rank_emit", "k_csr_tile_gather", "k_csr_block_scatter"]
 
 
 def test_kernel_ids_are_one_list():
