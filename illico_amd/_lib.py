@@ -101,6 +101,14 @@ RANKED_SIGNATURES = {
     "illico_pairwise_ranked_dense": (_DENSE + _RANKED, _ci),
     "illico_pairwise_ranked_csc": (_SPARSE + _RANKED, _ci),
 }
+#: the symbol include/illico_hip_markers.h declares (per-group marker statistics), exported by the same library:
+#: p, four effect planes; K, W, pitch; skip; method, rank_j, flags; p, rep, four selected effect planes; pitch
+MARKER_SIGNATURES = {
+    "illico_combine_pairs": ([_vp] * 6 + [_i64, _i64, _i64, _vp, _ci, _i64, _ci] + [_vp] * 6 + [_i64], _ci),
+}
+COMBINE_METHODS = {"all": 0, "any": 1, "some": 2}
+#: groups illico_combine_pairs takes at most (ILLICO_COMBINE_MAX_GROUPS), effect planes it selects at most
+COMBINE_MAX_GROUPS, COMBINE_MAX_EFFECTS = 256, 4
 
 _lib = None
 _lock = threading.Lock()
@@ -117,7 +125,7 @@ def load() -> ctypes.CDLL:
                 f"{_SO} is missing: the HIP engine has not been built. Run `python __graft_entry__.py` or "
                 "`python illico_amd/csrc/build.py`. There is no CPU fallback.")
         lib = ctypes.CDLL(str(_SO))
-        for name, (argtypes, restype) in {**SIGNATURES, **RANKED_SIGNATURES}.items():  # a symbol the library lacks fails here, not at first use
+        for name, (argtypes, restype) in {**SIGNATURES, **RANKED_SIGNATURES, **MARKER_SIGNATURES}.items():  # a symbol the library lacks fails here, not at first use
             f = getattr(lib, name)
             f.argtypes, f.restype = argtypes, restype
         _lib = lib
@@ -357,6 +365,36 @@ def _pair_planes(out, n, K, W, on_dev, device, with_left):
     ptrs = [_block(q, "an output plane", (np.float64,), (K, K, W), on_device=on_dev, writeable=True)[0] for q in planes]
     left_ptr = _block(left, "left", (np.int32, np.uint32) if on_dev else (np.uint32,), (W,), on_device=on_dev, writeable=True)[0] if with_left else None
     return planes, left, ptrs, left_ptr, on_dev
+
+
+def _pairs_as_rows(x, what):
+    """``(K, W, the [K * K, W] view)`` of a ``[K, K, W]`` numpy array or CUDA tensor whose ``[r, g]`` rows lie one pitch apart (a
+    contiguous block, or its first W columns): row ``r * K + g`` of the view is ``x[r, g]``, and ``_plane`` describes it."""
+    on_dev = _host_or_cuda(x, what)
+    if len(x.shape) != 3 or x.shape[0] != x.shape[1]:
+        raise ValueError(f"{what} must be a [K, K, W] plane, got shape {tuple(x.shape)}")
+    K, W = int(x.shape[0]), int(x.shape[2])
+    s0, s1, s2 = x.stride() if on_dev else x.strides
+    if K > 1 and s0 != K * s1:
+        raise ValueError(f"{what}: the [r, g] rows of a [K, K, W] plane must lie one row stride apart")
+    if on_dev:
+        return K, W, x.as_strided((K * K, W), (s1, s2))
+    return K, W, np.lib.stride_tricks.as_strided(x, (K * K, W), (s1, s2), writeable=False)
+
+
+def combine_rank(n: int, method: str, rank, min_prop) -> int:
+    """The rank j* handed to illico_combine_pairs: ``rank`` if given, else ``max(1, ceil(n * min_prop))`` with ``min_prop`` in (0, 1];
+    1 for the methods that do not read it.  ``ValueError`` for an unknown method, a bad ``min_prop`` or a ``rank`` that is no integer."""
+    import math
+    if not isinstance(method, str) or method not in COMBINE_METHODS:
+        raise ValueError(f"Unknown combination method {method!r}: one of {sorted(COMBINE_METHODS)}")
+    if isinstance(min_prop, bool) or not isinstance(min_prop, (int, float, np.integer, np.floating)) or not 0 < min_prop <= 1:
+        raise ValueError(f"min_prop must be a number in (0, 1], got {min_prop!r}")
+    if rank is not None and (isinstance(rank, bool) or not isinstance(rank, (int, np.integer))):
+        raise ValueError(f"rank must be an integer, got {rank!r}")
+    if method != "some":
+        return 1
+    return int(rank) if rank is not None else max(1, math.ceil(n * float(min_prop)))
 
 
 class Engine:
@@ -874,6 +912,56 @@ class Engine:
         self._bind_torch_stream(d.keep, i.keep, p.keep, keepalive[1], left, *planes)
         self._check(self.lib.illico_pairwise_ranked_csc(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols, col_lb, col_ub, *args))
         return (*planes, left)
+
+    # ---- per-group marker statistics (include/illico_hip_markers.h: illico_combine_pairs) ----
+    def combine_pairs(self, p, effects=(), *, method, rank=None, min_prop=0.5, skip=None, out=None):
+        """The K - 1 tests of each group against every other group combined into one p-value per (group, column)
+        (illico_combine_pairs; include/illico_hip_markers.h states the formulas).
+
+        ``p``: the float64 ``[K, K, W]`` p-value plane of a pair call, indexed ``[r, g, j]`` (numpy, or a CUDA tensor; a view of the
+        first W columns of a wider block is fine); its diagonal is never read.  ``effects``: up to four planes of the same layout
+        (U, fold change, z ...).  ``method``: ``"all"`` (the largest p), ``"any"`` (Simes) or ``"some"`` (Holm's adjusted p of rank
+        ``rank``; default ``max(1, ceil((K - 1) * min_prop))``).  ``skip``: ``[W]`` words (uint32 numpy / 32-bit integer CUDA tensor),
+        non-zero for a column that is neither validated nor written.  Everything lives on one side.  Returns
+        ``(p_comb float64 [K, W], rep int32 [K, W], *selected effects)``: ``rep[g, j]`` the representative reference, an index into
+        the K groups, and for each effect plane its value against it; allocated on the side of ``p`` unless ``out`` (a tuple of as
+        many ``[K, W]`` planes sharing one row stride) receives them.  ``ValueError``: an off-diagonal p of a live column that is NaN
+        or outside [0, 1] (device input: nothing is written), K < 2, a ``rank`` outside [1, K - 1]; ``NotImplementedError``: K > 256."""
+        effects = tuple(effects)
+        if len(effects) > COMBINE_MAX_EFFECTS:
+            raise ValueError(f"at most {COMBINE_MAX_EFFECTS} effect planes, got {len(effects)}")
+        K, W, p2 = _pairs_as_rows(p, "p")
+        rank_j = combine_rank(K - 1, method, rank, min_prop)
+        ins = [_plane(p2, "p")]
+        for k, e in enumerate(effects):
+            Ke, We, e2 = _pairs_as_rows(e, f"effect plane {k}")
+            if (Ke, We) != (K, W):
+                raise ValueError(f"effect plane {k} has shape {tuple(e.shape)}, p has {tuple(p.shape)}")
+            ins.append(_plane(e2, f"effect plane {k}"))
+        in_ptrs, _, in_ld = _plane_set(ins, "p and the effect planes")
+        on_dev = ins[0].on_device
+        device = p.device if on_dev else None
+        skip_keep = skip_ptr = None
+        if skip is not None:
+            if not on_dev and not _is_torch_tensor(skip):
+                skip = np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint32)
+            skip_ptr = _block(skip, "skip", (np.int32, np.uint32) if on_dev else (np.uint32,), (W,), on_device=on_dev)[0]
+            skip_keep = skip
+        if out is None:
+            out = [_empty((K, W), np.float64, device), _empty((K, W), np.int32, device)] + [_empty((K, W), np.float64, device) for _ in effects]
+        out = tuple(out)
+        if len(out) != 2 + len(effects):
+            raise ValueError(f"out must hold {2 + len(effects)} planes: p, rep and one per effect plane")
+        outs = [_plane(q, f"out[{k}]", dtype=np.int32 if k == 1 else np.float64, shape=(K, W), writeable=True) for k, q in enumerate(out)]
+        out_ptrs, oflag, out_ld = _plane_set(outs, "the output planes")
+        if bool(oflag) != on_dev:
+            raise ValueError("the output planes must live on the side of p (host or device)")
+        flags = (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0
+        pad = [None] * (COMBINE_MAX_EFFECTS - len(effects))
+        self._bind_torch_stream(p, *effects, skip_keep, *out)
+        self._check(self.lib.illico_combine_pairs(self.h, *in_ptrs, *pad, K, W, max(in_ld, W, 1), skip_ptr, COMBINE_METHODS[method], rank_j, flags,
+                                                  *out_ptrs, *pad, max(out_ld, W, 1)))
+        return out
 
     def csr_indices_sorted(self, indices, indptr, n_rows) -> bool:
         i, p = _Buf(indices), _Buf(indptr)

@@ -10,6 +10,9 @@ every ordered pair follows from them (illico_pairwise_from_hists).  Genes with o
 gathered once; float32 / int32 values and up to 64 groups take one sorted walk per gene that gives every pair
 (illico_pairwise_ranked_*): a log-normalised float32 matrix takes that path whole.  What it cannot take -- other value types, more
 groups, a gene with a NaN -- is completed by one one-versus-reference engine call per reference.
+
+``pairwise_markers`` is the marker workflow on top of it (scran's ``combineMarkers``): each group's K - 1 tests are combined on the
+device, block of columns by block (illico_combine_pairs), into one row per (group, gene); the K x K planes never reach the host.
 """
 from __future__ import annotations
 
@@ -18,9 +21,11 @@ import pandas as pd
 
 from illico_amd.utils.groups import encode_and_count_groups
 
-__all__ = ["pairwise_wilcoxon"]
+__all__ = ["pairwise_wilcoxon", "pairwise_markers"]
 
 ALTERNATIVES = ("two-sided", "less", "greater")
+#: scran's ``pval.type``: how ``pairwise_markers`` combines a group's tests against the other groups
+PVAL_TYPES = ("any", "some", "all")
 #: device bytes one gene window of the pair route may take (histograms in both layouts and the result planes); a window the engine's
 #: scratch budget refuses is halved
 PAIR_WINDOW_BYTES = 2 << 30
@@ -113,11 +118,13 @@ def _ranked_route_takes(eng, Xf, K: int) -> bool:
     return K <= eng.RANKED_MAX_GROUPS and str(dt).replace("torch.", "") in ("float32", "int32")
 
 
-def _ranked_pairs(eng, Xf, sel: np.ndarray, planes: np.ndarray, cols: np.ndarray, opts: dict) -> np.ndarray:
+def _ranked_pairs(eng, Xf, sel: np.ndarray, planes, cols: np.ndarray, opts: dict, sink=None) -> np.ndarray:
     """The gathered genes ``Xf`` (gene j is column ``cols[j]`` of ``planes``) through ``Engine.pairwise_ranked``, window by window,
-    under the engine's current groups.  Returns the genes (indices into ``Xf``'s columns) the route left: their columns are not written."""
+    under the engine's current groups.  Returns the genes (indices into ``Xf``'s columns) the route left: their columns are not written.
+    With a ``sink`` (``planes`` is then None) each window's planes are written on the device and handed over with its ``left`` words."""
     import torch
-    K, n_planes, nf = int(sel.size), int(planes.shape[0]), int(Xf.shape[1])
+    K, n_planes, nf = int(sel.size), 4 if opts["scores"] else 3, int(Xf.shape[1])
+    dev = torch.device("cuda", eng.device)
     sparse_f = hasattr(Xf, "indptr")
     if sparse_f:
         Xf.sort_indices()
@@ -125,14 +132,21 @@ def _ranked_pairs(eng, Xf, sel: np.ndarray, planes: np.ndarray, cols: np.ndarray
     left_genes = []
     for a, b in _windows(0, nf, width):
         try:
+            out = None
+            if sink is not None:
+                out = [torch.empty((K, K, b - a), dtype=torch.float64, device=dev) for _ in range(n_planes)] + [torch.empty((b - a,), dtype=torch.int32, device=dev)]
             if sparse_f:
                 sums = eng.group_stats_sparse("csc", Xf.data, Xf.indices, Xf.indptr, Xf.shape, a, b, is_log1p=opts["is_log1p"])[1]
-                got = eng.pairwise_ranked_sparse("csc", Xf.data, Xf.indices, Xf.indptr, Xf.shape, a, b, sums=sums, sel=sel, **opts)
+                got = eng.pairwise_ranked_sparse("csc", Xf.data, Xf.indices, Xf.indptr, Xf.shape, a, b, sums=sums, sel=sel, out=out, **opts)
             else:
                 sums = eng.group_stats(Xf, a, b, is_log1p=opts["is_log1p"])[1]
-                got = eng.pairwise_ranked(Xf, a, b, sums=sums, sel=sel, **opts)
+                got = eng.pairwise_ranked(Xf, a, b, sums=sums, sel=sel, out=out, **opts)
         except (MemoryError, torch.cuda.OutOfMemoryError):
             left_genes.append(np.arange(a, b))
+            continue
+        if sink is not None:
+            sink(cols[a:b], tuple(got[:n_planes]), got[-1])
+            left_genes.append(a + np.flatnonzero(got[-1].cpu().numpy() != 0))
             continue
         got = [q.cpu().numpy() if hasattr(q, "cpu") else q for q in got]
         done = np.flatnonzero(got[-1] == 0)
@@ -142,10 +156,38 @@ def _ranked_pairs(eng, Xf, sel: np.ndarray, planes: np.ndarray, cols: np.ndarray
     return np.concatenate(left_genes) if left_genes else np.empty(0, dtype=np.int64)
 
 
+def _fallback_blocks(eng, Xr, group_container, sel: np.ndarray, cols: np.ndarray, opts: dict, sink) -> None:
+    """The genes ``Xr`` (gene j is column ``cols[j]``) by one one-versus-reference call per reference, for a ``sink``: the K slabs of a
+    window of genes are gathered into one device block ``[K, K, w]`` per plane, the window sized by ``PAIR_WINDOW_BYTES``."""
+    import torch
+    dev = torch.device("cuda", eng.device)
+    K, G, n_planes, n = int(sel.size), int(np.asarray(group_container.counts).size), 4 if opts["scores"] else 3, int(Xr.shape[1])
+    sparse_f = hasattr(Xr, "indptr")
+    rows = torch.as_tensor(sel, device=dev)
+    containers = [group_container._replace(encoded_ref_group=int(r)) for r in sel]
+    width = max(64, (PAIR_WINDOW_BYTES // (n_planes * (K * K + G) * 8)) // 64 * 64)
+    for a, b in _windows(0, n, width):
+        block = tuple(torch.empty((K, K, b - a), dtype=torch.float64, device=dev) for _ in range(n_planes))
+        for ri, grp in enumerate(containers):
+            eng.set_groups(grp)
+            if sparse_f:
+                got = eng.run_sparse("csc", Xr.data, Xr.indices, Xr.indptr, Xr.shape, a, b, device_out=True, **opts)
+            else:
+                got = eng.run_dense(Xr, a, b, device_out=True, **opts)
+            for k in range(n_planes):
+                block[k][ri] = got[k][rows]
+        sink(cols[a:b], block, None)
+
+
 def pairwise_planes(X, handler, group_container, sel: np.ndarray, is_log1p: bool, alternative: str, use_continuity: bool, tie_correct: bool,
-                    scores: bool):
+                    scores: bool, sink=None):
     """(planes float64 [3 or 4, K, K, n_genes] indexed [plane, r, g, gene], number of flagged genes, number of them completed by the
-    per-reference fallback) for the groups ``sel``."""
+    per-reference fallback) for the groups ``sel``.
+
+    ``sink``: a callable ``sink(cols, planes, skip)``.  No host planes are then allocated (the first entry of the result is None):
+    every finished block of columns is handed over as it stands on the device -- ``cols`` the int64 gene numbers of its w columns,
+    ``planes`` the 3 or 4 float64 CUDA tensors ``[K, K, w]``, ``skip`` an int32 CUDA tensor ``[w]``, non-zero for a column the block
+    does not hold (it comes in a later block), or None.  Over all blocks every gene is held exactly once."""
     import torch
     from illico_amd import _lib
     from illico_amd.group_stats import _chunks
@@ -159,7 +201,7 @@ def pairwise_planes(X, handler, group_container, sel: np.ndarray, is_log1p: bool
     n_planes = 4 if scores else 3
     ovr_groups = group_container._replace(encoded_ref_group=-1)  # the histogram pass uses codes, counts and order only
     eng.set_groups(ovr_groups)
-    planes = np.empty((n_planes, K, K, M), dtype=np.float64)
+    planes = np.empty((n_planes, K, K, M), dtype=np.float64) if sink is None else None
     per_gene = 2 * G * 1024 + K * 1024 + n_planes * K * K * 8 + (G * 8 if is_log1p else 0) + 4
     width = max(64, (PAIR_WINDOW_BYTES // per_gene) // 64 * 64)
     flagged_cols, flagged_parts = [], []
@@ -194,8 +236,11 @@ def pairwise_planes(X, handler, group_container, sel: np.ndarray, is_log1p: bool
                 todo = _windows(o0, o1, half) + todo
                 H = fl = sums = None
                 continue
-            for k in range(n_planes):
-                planes[k][:, :, lb + o0:lb + o1] = got[k].cpu().numpy()
+            if sink is not None:
+                sink(np.arange(lb + o0, lb + o1, dtype=np.int64), tuple(got), fl)
+            else:
+                for k in range(n_planes):
+                    planes[k][:, :, lb + o0:lb + o1] = got[k].cpu().numpy()
             chunk_flagged.append(o0 + np.flatnonzero(fl.cpu().numpy()))
         chunk_flagged = np.concatenate(chunk_flagged) if chunk_flagged else np.empty(0, dtype=np.int64)
         if chunk_flagged.size:
@@ -210,12 +255,15 @@ def pairwise_planes(X, handler, group_container, sel: np.ndarray, is_log1p: bool
         Xf = _hstack(flagged_parts)
         opts = dict(is_log1p=is_log1p, use_continuity=use_continuity, tie_correct=tie_correct, alternative=alternative, scores=scores)
         # any float32 / int32 values, up to 64 groups: every pair from one sorted walk per gene (illico_pairwise_ranked_*) ...
-        rest = _ranked_pairs(eng, Xf, sel, planes, cols, opts) if _ranked_route_takes(eng, Xf, K) else np.arange(n_flagged)
+        rest = _ranked_pairs(eng, Xf, sel, planes, cols, opts, sink) if _ranked_route_takes(eng, Xf, K) else np.arange(n_flagged)
         n_fallback = int(rest.size)
         if n_fallback:
             # ... and for what it leaves, what a user does by hand: one one-versus-reference call per reference
             Xr = Xf if n_fallback == n_flagged else _gather_columns(Xf, rest)
             sparse_f = hasattr(Xr, "indptr")
+            if sink is not None:
+                _fallback_blocks(eng, Xr, group_container, sel, cols[rest], opts, sink)
+                return None, n_flagged, n_fallback
             for ri, r in enumerate(sel):
                 eng.set_groups(group_container._replace(encoded_ref_group=int(r)))
                 if sparse_f:
@@ -278,6 +326,96 @@ def pairwise_wilcoxon(adata, is_log1p: bool, group_keys: str, *, groups=None, al
     labels = np.asarray(unique_raw_groups)[sel]
     index = _pair_index(labels, np.asarray(adata.var_names), r_idx[rows], g_idx[rows])
     df = pd.DataFrame(cols, index=index, copy=False)
+    df.attrs["n_flagged_genes"] = n_flagged
+    df.attrs["n_ranked_genes"] = n_flagged - n_fallback
+    df.attrs["n_fallback_genes"] = n_fallback
+    return df
+
+
+class _MarkerSink:
+    """The sink of ``pairwise_planes`` that combines every block on the device (``Engine.combine_pairs``) and keeps ``[K, M]`` host
+    planes: the combined p, the representative reference, and U, fold change and z against it."""
+
+    def __init__(self, eng, K: int, M: int, method: str, rank: int):
+        self.eng, self.method, self.rank = eng, method, rank
+        self.p = np.empty((K, M), dtype=np.float64)
+        self.rep = np.empty((K, M), dtype=np.int32)
+        self.effects = [np.empty((K, M), dtype=np.float64) for _ in range(3)]
+
+    def __call__(self, cols, planes, skip):
+        got = self.eng.combine_pairs(planes[0], planes[1:], method=self.method, rank=self.rank, skip=skip)
+        live = slice(None) if skip is None else np.flatnonzero(skip.cpu().numpy() == 0)
+        for dst, q in zip([self.p, self.rep, *self.effects], got):
+            dst[:, cols[live]] = q.cpu().numpy()[:, live]
+
+
+def _check_marker_arguments(pval_type, min_prop, n_genes):
+    if not isinstance(pval_type, str) or pval_type not in PVAL_TYPES:
+        raise ValueError(f"pval_type must be one of {PVAL_TYPES}, got {pval_type!r}")
+    if isinstance(min_prop, bool) or not isinstance(min_prop, (int, float, np.integer, np.floating)) or not 0 < min_prop <= 1:
+        raise ValueError(f"min_prop must be a number in (0, 1], got {min_prop!r}")
+    if n_genes is not None and (isinstance(n_genes, bool) or not isinstance(n_genes, (int, np.integer)) or n_genes < 1):
+        raise ValueError(f"n_genes must be a positive integer or None, got {n_genes!r}")
+
+
+def pairwise_markers(adata, is_log1p: bool, group_keys: str, *, groups=None, pval_type: str = "any", min_prop: float = 0.5,
+                     alternative: str = "two-sided", use_continuity: bool = True, tie_correct: bool = True, layer: str | None = None,
+                     corr_method: str | None = "benjamini-hochberg", n_genes: int | None = None) -> pd.DataFrame:
+    """Marker genes of every group from the all-pairs Wilcoxon tests: scran's ``pairwiseWilcox`` followed by ``combineMarkers``, on
+    one MI355X, without the K (K - 1) tables per gene ever reaching the host.
+
+    The tests are those of ``pairwise_wilcoxon`` (same arguments, same routes).  For each group and gene its K - 1 p-values against
+    the other selected groups are combined on the device (include/illico_hip_markers.h: illico_combine_pairs): ``pval_type="all"``
+    -- the gene separates the group from every other group: the largest p --, ``"any"`` -- from any of them: Simes' combination --
+    or ``"some"`` -- from at least ``min_prop`` of them: Holm's adjusted p of rank ``max(1, ceil((K - 1) * min_prop))``.
+
+    Returns a DataFrame with MultiIndex ``(pert, feature)``, K x genes rows, groups in ``asymptotic_wilcoxon``'s order: ``p_value`` the
+    combined p; ``p_value_adj`` (unless ``corr_method`` is None) each group's combined p adjusted across the genes; ``reference`` the
+    label of the representative comparison (categorical) -- the one of largest p for ``"all"``, of smallest p for ``"any"``, of that
+    rank for ``"some"``, ties by group order --; ``statistic``, ``fold_change`` and ``z_score`` against that reference; ``auc`` =
+    ``statistic / (n_group x n_reference)``.  ``n_genes`` keeps each group's rows of smallest combined p (ties by gene order), in that
+    order.  ``df.attrs["n_flagged_genes"]`` / ``["n_ranked_genes"]`` / ``["n_fallback_genes"]`` as in ``pairwise_wilcoxon``.
+
+    ``ValueError``, before any device work: a bad ``pval_type``, ``min_prop`` outside (0, 1], a bad ``n_genes``, and what
+    ``pairwise_wilcoxon`` refuses (there is no ``max_result_bytes``: the result is K x genes).  ``NotImplementedError``: more than
+    256 selected groups."""
+    _check_marker_arguments(pval_type, min_prop, n_genes)
+    code = _check_arguments(is_log1p, alternative, use_continuity, tie_correct, True, corr_method, 0)
+    from illico_amd import _lib
+    from illico_amd.group_stats import _input
+    X = _input(adata, layer)
+    unique_raw_groups, group_container = encode_and_count_groups(groups=adata.obs[group_keys], ref_group=None)
+    sel = _select(np.asarray(unique_raw_groups), groups)
+    K, M = int(sel.size), int(X.shape[1])
+    if K > _lib.COMBINE_MAX_GROUPS:
+        raise NotImplementedError(f"{K} groups selected: pairwise_markers takes up to {_lib.COMBINE_MAX_GROUPS}")
+    rank = _lib.combine_rank(K - 1, pval_type, None, min_prop)
+    from illico_amd.utils.registry import data_handler_registry
+    handler = data_handler_registry.get(X)
+    eng = _lib.get_engine()
+    sink = _MarkerSink(eng, K, M, pval_type, rank)
+    _, n_flagged, n_fallback = pairwise_planes(X, handler, group_container, sel, bool(is_log1p), alternative, bool(use_continuity),
+                                               bool(tie_correct), True, sink=sink)
+    labels = np.asarray(unique_raw_groups)[sel]
+    n_cells = np.asarray(group_container.counts, dtype=np.float64)[sel]
+    cols = {"p_value": sink.p.reshape(-1)}
+    n_top = min(int(n_genes), M) if n_genes is not None else 0
+    top = None
+    if M and (code is not None or n_top):
+        res = eng.adjust_pvalues(sink.p, code or "bh", n_top=n_top)
+        adj, top = res if n_top else (res, None)
+        if code is not None:
+            cols["p_value_adj"] = np.asarray(adj).reshape(-1)
+    elif code is not None:
+        cols["p_value_adj"] = np.empty(0, dtype=np.float64)
+    cols["reference"] = pd.Categorical.from_codes(sink.rep.reshape(-1), categories=pd.Index(pd.Series(labels, dtype=str)))
+    cols["statistic"], cols["fold_change"], cols["z_score"] = (e.reshape(-1) for e in sink.effects)
+    cols["auc"] = (sink.effects[0] / (n_cells[:, None] * n_cells[sink.rep])).reshape(-1)
+    from illico_amd.asymptotic_wilcoxon import _product_index
+    index = _product_index(pd.Series(labels, dtype=str), pd.Series(np.asarray(adata.var_names), dtype=str))
+    df = pd.DataFrame(cols, index=index, copy=False)
+    if top is not None:
+        df = df.iloc[(np.arange(K, dtype=np.int64)[:, None] * M + np.asarray(top)[:, :n_top]).reshape(-1)]
     df.attrs["n_flagged_genes"] = n_flagged
     df.attrs["n_ranked_genes"] = n_flagged - n_fallback
     df.attrs["n_fallback_genes"] = n_fallback
