@@ -107,6 +107,13 @@ MARKER_SIGNATURES = {
     "illico_combine_pairs": ([_vp] * 6 + [_i64, _i64, _i64, _vp, _ci, _i64, _ci] + [_vp] * 6 + [_i64], _ci),
 }
 COMBINE_METHODS = {"all": 0, "any": 1, "some": 2}
+#: the symbols include/illico_hip_blocked.h declares (blocked Wilcoxon tests), exported by the same library:
+#: from_hists: H, flags, counts; G, B, W, ref; sums, pitch; flags, alternative; p, statistic, fold change, z; pitch
+#: from_planes: z, U, pitch; row map, counts; G, B, W, ref; sums, pitch; flags, alternative; p, statistic, fold change, z; pitch
+BLOCKED_SIGNATURES = {
+    "illico_blocked_from_hists": ([_vp] * 4 + [_i64] * 4 + [_vp, _i64, _ci, _ci] + [_vp] * 4 + [_i64], _ci),
+    "illico_blocked_from_planes": ([_vp] * 3 + [_i64, _vp, _vp] + [_i64] * 4 + [_vp, _i64, _ci, _ci] + [_vp] * 4 + [_i64], _ci),
+}
 #: groups illico_combine_pairs takes at most (ILLICO_COMBINE_MAX_GROUPS), effect planes it selects at most
 COMBINE_MAX_GROUPS, COMBINE_MAX_EFFECTS = 256, 4
 
@@ -125,7 +132,7 @@ def load() -> ctypes.CDLL:
                 f"{_SO} is missing: the HIP engine has not been built. Run `python __graft_entry__.py` or "
                 "`python illico_amd/csrc/build.py`. There is no CPU fallback.")
         lib = ctypes.CDLL(str(_SO))
-        for name, (argtypes, restype) in {**SIGNATURES, **RANKED_SIGNATURES, **MARKER_SIGNATURES}.items():  # a symbol the library lacks fails here, not at first use
+        for name, (argtypes, restype) in {**SIGNATURES, **RANKED_SIGNATURES, **MARKER_SIGNATURES, **BLOCKED_SIGNATURES}.items():  # a symbol the library lacks fails here, not at first use
             f = getattr(lib, name)
             f.argtypes, f.restype = argtypes, restype
         _lib = lib
@@ -380,6 +387,19 @@ def _pairs_as_rows(x, what):
     if on_dev:
         return K, W, x.as_strided((K * K, W), (s1, s2))
     return K, W, np.lib.stride_tricks.as_strided(x, (K * K, W), (s1, s2), writeable=False)
+
+
+def _pairs_as_rows_3d(x):
+    """The ``[B * G, W]`` view of a ``[B, G, W]`` array or tensor whose ``[b, row]`` rows lie one pitch apart (the first W columns of
+    a contiguous block); ``ValueError`` otherwise."""
+    B, G, W = (int(v) for v in x.shape)
+    on_dev = _is_torch_tensor(x)
+    s0, s1, s2 = x.stride() if on_dev else x.strides
+    if B > 1 and s0 != G * s1:
+        raise ValueError("the [b, row] rows of a [B, G, W] plane must lie one row stride apart")
+    if on_dev:
+        return x.as_strided((B * G, W), (s1, s2))
+    return np.lib.stride_tricks.as_strided(x, (B * G, W), (s1, s2), writeable=False)
 
 
 def combine_rank(n: int, method: str, rank, min_prop) -> int:
@@ -962,6 +982,110 @@ class Engine:
         self._check(self.lib.illico_combine_pairs(self.h, *in_ptrs, *pad, K, W, max(in_ld, W, 1), skip_ptr, COMBINE_METHODS[method], rank_j, flags,
                                                   *out_ptrs, *pad, max(out_ld, W, 1)))
         return out
+
+    # ---- blocked Wilcoxon tests (include/illico_hip_blocked.h: illico_blocked_from_hists, illico_blocked_from_planes) ----
+    @staticmethod
+    def _blocked_sizes(counts, GB, n_blocks, ref):
+        """``(counts int64 [G, B], G, B, ref code, n_blocks int64 [G])`` of a blocked call over ``GB`` compound groups ``g * B + b``:
+        ``n_blocks[g]`` the blocks that hold both a cell of g and a reference cell (those of ``ref``, or of the rest of the block)."""
+        if isinstance(n_blocks, bool) or not isinstance(n_blocks, (int, np.integer)) or n_blocks < 1:
+            raise ValueError(f"n_blocks must be a positive integer, got {n_blocks!r}")
+        B = int(n_blocks)
+        counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+        if counts.size != GB or GB % B:
+            raise ValueError(f"{GB} compound groups but counts has {counts.size} entries for {B} blocks")
+        G = GB // B
+        counts = counts.reshape(G, B)
+        ref = -1 if ref is None else int(ref)
+        if ref < -1 or ref >= G:
+            raise ValueError(f"reference {ref} is no group id (0 .. {G - 1})")
+        n_r = counts[ref][None, :] if ref >= 0 else counts.sum(axis=0)[None, :] - counts
+        return counts, G, B, ref, ((counts > 0) & (n_r > 0)).sum(axis=1).astype(np.int64)
+
+    def _blocked_io(self, G, B, W, sums, out, on_dev, device, with_fc=True):
+        """The optional ``sums`` plane ``[G * B, W]`` and the four ``[G, W]`` result planes (p, statistic, fold change, z; the third
+        None without ``with_fc``) of a blocked call whose input lives on the side ``on_dev``: (sums plane or None, planes, pointers,
+        output flag, pitch)."""
+        if sums is not None:
+            sums = _plane(sums, "sums", shape=(G * B, W), copy_ok=True)
+            if sums.on_device != on_dev:
+                raise ValueError("sums must live on the side of the input (host or device)")
+        if out is None:
+            out = [_empty((G, W), np.float64, device if on_dev else None) if (k != 2 or with_fc) else None for k in range(4)]
+        out = tuple(out)
+        if len(out) != 4 or (out[2] is not None) != with_fc or any(q is None for k, q in enumerate(out) if k != 2):
+            raise ValueError("out must hold 4 planes (p, statistic, fold change, z); the fold change is None exactly when there are no sums")
+        if W == 0:
+            return sums, out, [None] * 4, 0, 1
+        ptrs, oflag, ld = _plane_set([None if q is None else _plane(q, f"output plane {k}", shape=(G, W), writeable=True) for k, q in enumerate(out)],
+                                     "output planes")
+        return sums, out, ptrs, oflag, ld
+
+    def blocked_from_hists(self, H, flags, *, counts, n_blocks, ref=None, sums=None, tie_correct=True, alternative="two-sided", out=None):
+        """Blocked Wilcoxon rank-sum tests from the histograms of ``group_value_hists`` under the compound group coding ``g * B + b``
+        (illico_blocked_from_hists; include/illico_hip_blocked.h states the definition).
+
+        ``H`` ``[G * B, W, 256]`` and ``flags`` ``[W]`` as ``group_value_hists`` returns them (numpy, or CUDA tensors); ``counts``: the
+        ``G * B`` compound sizes; ``n_blocks``: B; ``ref``: the reference group id, None for the rest of each block.  ``sums``: an
+        optional float64 ``[G * B, W]`` plane of compound value sums for the fold change, on the side of ``H`` (under log1p the ``expm1``
+        sums of ``group_stats(..., is_log1p=True)``).  Returns ``(p, statistic, fold_change, z)``, float64 ``[G, W]`` on the side of
+        ``H``: each group's per-block tests combined by Stouffer's z weighted with ``n_g n_r``.  NaN in every plane where no block
+        holds both samples.  The columns of flagged genes are left as they are in ``out`` (four planes with one row stride)."""
+        alt = self._alt(alternative)
+        on_dev = _is_torch_tensor(H)
+        if on_dev != _is_torch_tensor(flags):
+            raise ValueError("H and flags must live on the same side (host or device)")
+        if on_dev:
+            if not (H.is_cuda and flags.is_cuda and H.is_contiguous() and flags.is_contiguous()) or H.dim() != 3 or H.element_size() != 4 \
+                    or flags.element_size() != 4 or H.dtype.is_floating_point or flags.dtype.is_floating_point:
+                raise ValueError("H and flags must be contiguous 32-bit integer CUDA tensors [G * B, W, 256] and [W]")
+        else:
+            H, flags = np.ascontiguousarray(H, dtype=np.uint32), np.ascontiguousarray(flags, dtype=np.uint32)
+            if H.ndim != 3:
+                raise ValueError("H must be [G * B, W, 256]")
+        GB, W, R = (int(x) for x in H.shape)
+        if R != self.HIST_VALUES or tuple(flags.shape) != (W,):
+            raise ValueError(f"H must be [G * B, W, {self.HIST_VALUES}] and flags [W], got {tuple(H.shape)} and {tuple(flags.shape)}")
+        counts, G, B, ref, _ = self._blocked_sizes(counts, GB, n_blocks, ref)
+        sums, planes, ptrs, oflag, out_ld = self._blocked_io(G, B, W, sums, out, on_dev, H.device if on_dev else None)
+        if W and bool(oflag) != on_dev:
+            raise ValueError("the output planes must live on the side of H (host or device)")
+        fl = (FLAG_TIE_CORRECT if tie_correct else 0) | ((FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0)
+        sums_array, sums_ptr, sums_ld = (None, None, 0) if sums is None else (sums.array, sums.ptr, sums.pitch)
+        self._bind_torch_stream(H, flags, sums_array, *planes)
+        self._check(self.lib.illico_blocked_from_hists(self.h, _ptr(H), _ptr(flags), counts.ctypes.data, G, B, W, ref, sums_ptr, sums_ld, fl, alt,
+                                                       *ptrs, max(out_ld, W, 1)))
+        return planes
+
+    def blocked_from_planes(self, z, U, row_map, *, counts, ref=None, sums=None, alternative="two-sided", out=None):
+        """Blocked Wilcoxon rank-sum tests from the z and U planes of B per-block engine calls made with ``scores=True,
+        use_continuity=False`` (illico_blocked_from_planes).
+
+        ``z``, ``U``: float64 ``[B, G, W]`` (numpy, or CUDA tensors; the ``[b, row]`` rows one pitch apart); ``row_map``: int32
+        ``[B, G]``, the row of group g in block b's plane set, -1 where g has no cells in b; ``counts``: the ``G * B`` compound
+        sizes, ``g * B + b``; ``ref``: the reference group id, None for the rest of each block.  ``sums``: float64 ``[G * B, W]``
+        compound value sums; without it there is no fold change (the third plane is None).  Returns ``(p, statistic, fold_change, z)``
+        as ``blocked_from_hists`` does."""
+        alt = self._alt(alternative)
+        on_dev = _is_torch_tensor(z)
+        if on_dev != _is_torch_tensor(U) or tuple(z.shape) != tuple(U.shape) or len(z.shape) != 3:
+            raise ValueError("z and U must be [B, G, W] planes of one shape on one side (host or device)")
+        B, G, W = (int(x) for x in z.shape)
+        ins = [_plane(_pairs_as_rows_3d(z), "z"), _plane(_pairs_as_rows_3d(U), "U")]
+        in_ptrs, _, in_ld = _plane_set(ins, "z and U")
+        row_map = np.ascontiguousarray(row_map, dtype=np.int32)
+        if row_map.shape != (B, G):
+            raise ValueError(f"row_map must be [B, G] = {(B, G)}, got {row_map.shape}")
+        counts, G2, B2, ref, _ = self._blocked_sizes(counts, G * B, B, ref)
+        sums, planes, ptrs, oflag, out_ld = self._blocked_io(G, B, W, sums, out, on_dev, z.device if on_dev else None, with_fc=sums is not None)
+        if W and bool(oflag) != on_dev:
+            raise ValueError("the output planes must live on the side of z (host or device)")
+        fl = (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0
+        sums_array, sums_ptr, sums_ld = (None, None, 0) if sums is None else (sums.array, sums.ptr, sums.pitch)
+        self._bind_torch_stream(z, U, sums_array, *planes)
+        self._check(self.lib.illico_blocked_from_planes(self.h, *in_ptrs, max(in_ld or 0, W, 1), row_map.ctypes.data, counts.ctypes.data, G, B, W, ref,
+                                                        sums_ptr, sums_ld, fl, alt, *ptrs, max(out_ld, W, 1)))
+        return planes
 
     def csr_indices_sorted(self, indices, indptr, n_rows) -> bool:
         i, p = _Buf(indices), _Buf(indptr)
