@@ -116,6 +116,15 @@ BLOCKED_SIGNATURES = {
 }
 #: groups illico_combine_pairs takes at most (ILLICO_COMBINE_MAX_GROUPS), effect planes it selects at most
 COMBINE_MAX_GROUPS, COMBINE_MAX_EFFECTS = 256, 4
+#: the symbol include/illico_hip_pair_ttest.h declares (all-pairs Welch t-tests from moment planes), exported by the same library:
+#: sum, sumsq, fsum; n_cols, pitch; sel, K; variant, alternative, flags; p, t, df, fold change, Cohen's d; pitch
+PAIR_TTEST_SIGNATURES = {
+    "illico_pair_ttest_from_moments": ([_vp] * 4 + [_i64, _i64, _vp, _i64, _ci, _ci, _ci] + [_vp] * 5 + [_i64], _ci),
+}
+#: the planes illico_pair_ttest_from_moments can write, in the order of its output arguments
+PAIR_TT_OUTPUTS = ("p", "t", "df", "fold_change", "cohen_d")
+#: the kernel's tiles (kernels_pair_ttest.h: PT_TILE genes, PT_GT groups) and the groups one launch takes at most
+PAIR_TT_GENE_TILE, PAIR_TT_GROUP_TILE, PAIR_TT_MAX_GROUPS = 64, 8, 2880
 
 _lib = None
 _lock = threading.Lock()
@@ -132,7 +141,8 @@ def load() -> ctypes.CDLL:
                 f"{_SO} is missing: the HIP engine has not been built. Run `python __graft_entry__.py` or "
                 "`python illico_amd/csrc/build.py`. There is no CPU fallback.")
         lib = ctypes.CDLL(str(_SO))
-        for name, (argtypes, restype) in {**SIGNATURES, **RANKED_SIGNATURES, **MARKER_SIGNATURES, **BLOCKED_SIGNATURES}.items():  # a symbol the library lacks fails here, not at first use
+        for name, (argtypes, restype) in {**SIGNATURES, **RANKED_SIGNATURES, **MARKER_SIGNATURES, **BLOCKED_SIGNATURES,
+                                          **PAIR_TTEST_SIGNATURES}.items():  # a symbol the library lacks fails here, not at first use
             f = getattr(lib, name)
             f.argtypes, f.restype = argtypes, restype
         _lib = lib
@@ -755,6 +765,73 @@ class Engine:
             self._bind_torch_stream(*[q.array for q in ins if q is not None], *planes)
             self._check(self.lib.illico_ttest_from_moments(self.h, *in_ptrs, M, max(ld, 1), var, alt, (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0,
                                                            *out_ptrs, out_ld))
+        return planes
+
+    def pair_ttest_from_moments(self, sum, sumsq, *, sel=None, fsum=None, variant="welch", alternative="two-sided", want=("p", "t"), out=None):
+        """Welch's t-test of every ordered pair of groups from moment planes (include/illico_hip_pair_ttest.h:
+        illico_pair_ttest_from_moments), for the sizes of the engine's current groups (their reference / one-versus-rest mode plays no part).
+
+        ``sum`` / ``sumsq``: float64 ``[G, W]`` numpy arrays or CUDA tensors as ``group_moments`` returns them; ``fsum``: the sums the
+        fold change is formed from (under log1p the ``expm1`` sums of ``group_stats(..., is_log1p=True)``; default ``sum``); all on one
+        side, unit column stride, one row stride.  ``sel``: the K >= 2 group ids to compare, strictly ascending (default: all G).
+        ``variant``: ``"welch"`` or ``"overestim_var"``.  ``want``: which of ``PAIR_TT_OUTPUTS`` (``"p"``, ``"t"``, ``"df"``,
+        ``"fold_change"``, ``"cohen_d"``) to compute.  Returns a tuple of float64 ``[K, K, W]`` planes in the order of ``want``, indexed
+        ``[r, g, j]`` -- group ``sel[g]`` against reference ``sel[r]``, the layout ``combine_pairs`` reads -- living where the moments
+        live; ``out``: a tuple of as many planes to write (contiguous, or the first W columns of contiguous blocks of one width).
+        ``plane[r]`` of ``p``, ``t``, ``df`` is, bit for bit, ``ttest_from_moments`` under the reference ``sel[r]``, rows ``sel``;
+        diagonal: (t, p) = (0, 1), ``cohen_d`` 0."""
+        try:
+            var = TT_VARIANTS[variant]
+        except (KeyError, TypeError):
+            raise ValueError(f"Unknown t-test variant {variant!r}: one of {sorted(TT_VARIANTS)}") from None
+        alt = self._alt(alternative)
+        want = tuple(want)
+        if not want or any(w not in PAIR_TT_OUTPUTS for w in want) or len(set(want)) != len(want):
+            raise ValueError(f"want must name distinct planes of {PAIR_TT_OUTPUTS}, got {want!r}")
+        ins = [None if x is None else _plane(x, name, copy_ok=True) for name, x in (("sum", sum), ("sumsq", sumsq), ("fsum", fsum))]
+        if ins[0] is None or ins[1] is None:
+            raise ValueError("sum and sumsq are required")
+        given = [q for q in ins if q is not None]
+        G, W, on_dev = given[0].rows, given[0].cols, given[0].on_device
+        if any((q.rows, q.cols) != (G, W) for q in given):
+            raise ValueError("the moment planes must share one shape")
+        if not any(q.on_device for q in given) and len({q.pitch for q in given}) > 1:  # host planes of several pitches: made contiguous
+            ins = [None if q is None else _plane(np.ascontiguousarray(q.array), "a moment plane") for q in ins]
+        in_ptrs, _, ld = _plane_set(ins, "the moment planes")
+        if G != getattr(self, "n_groups", None):
+            raise ValueError(f"the moment planes have {G} rows but the engine's groups number {getattr(self, 'n_groups', None)}")
+        sel = np.arange(G, dtype=np.int32) if sel is None else np.ascontiguousarray(sel).reshape(-1)
+        if sel.dtype.kind not in "iu":
+            raise ValueError(f"sel must hold integer group ids, got {sel.dtype}")
+        K = int(sel.size)
+        if K < 2:
+            raise ValueError(f"{K} groups selected: a pair needs two")
+        if sel.min() < 0 or sel.max() >= G or np.any(np.diff(sel.astype(np.int64)) <= 0):
+            raise ValueError(f"sel must name group ids 0 .. {G - 1} in strictly ascending order, got {sel.tolist()}")
+        if K > PAIR_TT_MAX_GROUPS:
+            raise NotImplementedError(f"{K} groups selected: pair_ttest_from_moments takes up to {PAIR_TT_MAX_GROUPS}")
+        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        if out is None:
+            planes = tuple(_empty((K, K, W), np.float64, given[0].array.device if on_dev else None) for _ in want)
+        else:
+            planes = tuple(out)
+            if len(planes) != len(want):
+                raise ValueError(f"out must hold {len(want)} planes, one per entry of want")
+        outs = dict.fromkeys(PAIR_TT_OUTPUTS)  # in the order of the library's output arguments
+        for w, pl in zip(want, planes):
+            Ko, Wo, rows = _pairs_as_rows(pl, f"out[{w}]")
+            if (Ko, Wo) != (K, W):
+                raise ValueError(f"out[{w}] must be a [K, K, W] = {(K, K, W)} plane, got shape {tuple(pl.shape)}")
+            if not on_dev and not pl.flags.writeable:
+                raise ValueError(f"out[{w}] must be writeable")
+            outs[w] = _plane(rows, f"out[{w}]", shape=(K * K, W))
+        out_ptrs, oflag, out_ld = _plane_set(list(outs.values()), "the output planes")
+        if bool(oflag) != on_dev:
+            raise ValueError("the output planes must live on the same side as the moments")
+        if W:
+            self._bind_torch_stream(*[q.array for q in ins if q is not None], *planes)
+            self._check(self.lib.illico_pair_ttest_from_moments(self.h, *in_ptrs, W, max(ld, 1), sel.ctypes.data, K, var, alt,
+                                                                (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0, *out_ptrs, max(out_ld, W, 1)))
         return planes
 
     def student_t_pvalues(self, t, df, alternative="two-sided"):

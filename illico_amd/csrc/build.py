@@ -1,9 +1,9 @@
 """Build libillico_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
 
-The library is twenty translation units -- the context / C-ABI (core.hip), the launchers that depend on the key type only
+The library is twenty-one translation units -- the context / C-ABI (core.hip), the launchers that depend on the key type only
 (keyed_u32 / keyed_u64), one unit per value type for the dense and for the sparse drivers, the p-value adjustment (adjust.hip) and
 the per-group expression statistics (group_stats.hip), the per-group moments with Welch's t-test
-(group_moments.hip) and the all-pairs Wilcoxon tests from value histograms (pairwise.hip) and from one sorted walk per gene
+(group_moments.hip) and for every pair of groups (pair_ttest.hip), and the all-pairs Wilcoxon tests from value histograms (pairwise.hip) and from one sorted walk per gene
 (pairwise_ranked.hip), their combination into per-group marker statistics (markers.hip), and the blocked Wilcoxon tests
 (blocked.hip) -- compiled in parallel into
 _build/*.o and linked.  A unit is recompiled when it, or a header its last compile read (the -MD dependency file), changed:
@@ -22,9 +22,9 @@ SO = HERE / "libillico_hip.so"
 OBJ = HERE / "_build"
 UNITS = ["core", "keyed_u32", "keyed_u64", "keyed_coop", "dense_f32", "dense_f64", "dense_i32", "dense_i64", "dense_u8",
          "sparse_f32", "sparse_f64", "sparse_i32", "sparse_i64", "adjust", "group_stats", "group_moments", "pairwise", "pairwise_ranked",
-         "markers", "blocked"]
+         "markers", "blocked", "pair_ttest"]
 DEV_UNITS = ["core", "keyed_u32", "keyed_coop", "dense_f32", "dense_u8", "sparse_f32", "adjust", "group_stats", "group_moments", "pairwise", "pairwise_ranked",
-             "markers", "blocked"]  # ILLICO_DEV_F32_ONLY=1: float32 values, int32 indices
+             "markers", "blocked", "pair_ttest"]  # ILLICO_DEV_F32_ONLY=1: float32 values, int32 indices
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value"]
 LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared", "-Wl,-z,defs", f"-Wl,--version-script={HERE / 'exports.map'}"]
 
@@ -97,7 +97,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int | None = None) -
     todo = [u for u in units if force or _unit_stale(u, tag)]
     jobs = jobs or int(os.environ.get("ILLICO_BUILD_JOBS", "0")) or min(len(todo) or 1, os.cpu_count() or 4)
     # the long units first: the pool then ends on the short ones
-    order = {"sparse": 0, "dense_": 1, "keyed": 2, "core": 3, "adjust": 4, "group_stats": 5, "group_moments": 5, "pairwise": 5, "markers": 5, "blocked": 5}
+    order = {"sparse": 0, "dense_": 1, "keyed": 2, "core": 3, "adjust": 4, "group_stats": 5, "group_moments": 5, "pairwise": 5, "markers": 5, "blocked": 5, "pair_ttest": 5}
     todo.sort(key=lambda u: next(v for k, v in order.items() if u.startswith(k)))
     with ThreadPoolExecutor(max_workers=jobs) as pool:
         results = list(pool.map(lambda u: _compile(u, hipcc, flags, verbose), todo))

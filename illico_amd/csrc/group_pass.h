@@ -1,5 +1,5 @@
 // Host scaffolding of the four units that read the matrix once per group family -- group_stats.hip, group_moments.hip, pairwise.hip,
-// pairwise_ranked.hip (the last two through pair_pass.h) -- and nothing else: the description of the input, the checks every entry point
+// pairwise_ranked.hip (the last two through pair_pass.h) -- and of pair_ttest.hip, which takes the plane copies only: the description of the input, the checks every entry point
 // makes, the upload of host-resident sparse arrays and dense windows, the copies of 8-byte planes, the dispatch on the index type, and the
 // groups' positions in chunks.  Everything is local to the including unit (the four are linked into one library).  The kernels, the
 // planes, the column windows, the outputs and the points at which the stream is synchronised are each family's own.

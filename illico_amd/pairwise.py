@@ -13,6 +13,7 @@ groups, a gene with a NaN -- is completed by one one-versus-reference engine cal
 
 ``pairwise_markers`` is the marker workflow on top of it (scran's ``combineMarkers``): each group's K - 1 tests are combined on the
 device, block of columns by block (illico_combine_pairs), into one row per (group, gene); the K x K planes never reach the host.
+With ``method="t-test"`` the blocks are those of the all-pairs Welch t-tests (pairwise_ttest.py: ``pair_ttest_blocks``).
 """
 from __future__ import annotations
 
@@ -334,19 +335,24 @@ def pairwise_wilcoxon(adata, is_log1p: bool, group_keys: str, *, groups=None, al
 
 class _MarkerSink:
     """The sink of ``pairwise_planes`` that combines every block on the device (``Engine.combine_pairs``) and keeps ``[K, M]`` host
-    planes: the combined p, the representative reference, and U, fold change and z against it."""
+    planes: the combined p, the representative reference, and the effects against it -- U, fold change and z; with a t-test method
+    (``n_effects=4``) t, fold change, df and Cohen's d."""
 
-    def __init__(self, eng, K: int, M: int, method: str, rank: int):
+    def __init__(self, eng, K: int, M: int, method: str, rank: int, n_effects: int = 3):
         self.eng, self.method, self.rank = eng, method, rank
         self.p = np.empty((K, M), dtype=np.float64)
         self.rep = np.empty((K, M), dtype=np.int32)
-        self.effects = [np.empty((K, M), dtype=np.float64) for _ in range(3)]
+        self.effects = [np.empty((K, M), dtype=np.float64) for _ in range(n_effects)]
 
     def __call__(self, cols, planes, skip):
         got = self.eng.combine_pairs(planes[0], planes[1:], method=self.method, rank=self.rank, skip=skip)
         live = slice(None) if skip is None else np.flatnonzero(skip.cpu().numpy() == 0)
         for dst, q in zip([self.p, self.rep, *self.effects], got):
             dst[:, cols[live]] = q.cpu().numpy()[:, live]
+
+
+#: ``pairwise_markers``' ``method`` -> the variant of ``pairwise_ttest`` (None: the Wilcoxon tests)
+MARKER_METHODS = {"wilcoxon": None, "t-test": "welch", "t-test_overestim_var": "overestim_var"}
 
 
 def _check_marker_arguments(pval_type, min_prop, n_genes):
@@ -360,9 +366,10 @@ def _check_marker_arguments(pval_type, min_prop, n_genes):
 
 def pairwise_markers(adata, is_log1p: bool, group_keys: str, *, groups=None, pval_type: str = "any", min_prop: float = 0.5,
                      alternative: str = "two-sided", use_continuity: bool = True, tie_correct: bool = True, layer: str | None = None,
-                     corr_method: str | None = "benjamini-hochberg", n_genes: int | None = None) -> pd.DataFrame:
+                     corr_method: str | None = "benjamini-hochberg", n_genes: int | None = None, method: str = "wilcoxon") -> pd.DataFrame:
     """Marker genes of every group from the all-pairs Wilcoxon tests: scran's ``pairwiseWilcox`` followed by ``combineMarkers``, on
-    one MI355X, without the K (K - 1) tables per gene ever reaching the host.
+    one MI355X, without the K (K - 1) tables per gene ever reaching the host.  ``method="t-test"`` / ``"t-test_overestim_var"``: from
+    the all-pairs Welch t-tests instead (``pairwiseTTests``; scran's ``findMarkers`` default), see below.
 
     The tests are those of ``pairwise_wilcoxon`` (same arguments, same routes).  For each group and gene its K - 1 p-values against
     the other selected groups are combined on the device (include/illico_hip_markers.h: illico_combine_pairs): ``pval_type="all"``
@@ -376,11 +383,26 @@ def pairwise_markers(adata, is_log1p: bool, group_keys: str, *, groups=None, pva
     ``statistic / (n_group x n_reference)``.  ``n_genes`` keeps each group's rows of smallest combined p (ties by gene order), in that
     order.  ``df.attrs["n_flagged_genes"]`` / ``["n_ranked_genes"]`` / ``["n_fallback_genes"]`` as in ``pairwise_wilcoxon``.
 
-    ``ValueError``, before any device work: a bad ``pval_type``, ``min_prop`` outside (0, 1], a bad ``n_genes``, and what
-    ``pairwise_wilcoxon`` refuses (there is no ``max_result_bytes``: the result is K x genes).  ``NotImplementedError``: more than
-    256 selected groups."""
+    With a t-test method the tests are those of ``pairwise_ttest`` (``variant="welch"`` for ``"t-test"``, ``"overestim_var"`` for
+    ``"t-test_overestim_var"``), combined in the same way; the frame then holds ``p_value``, ``p_value_adj``, ``reference``,
+    ``statistic`` (t against the representative), ``fold_change``, ``df`` (the Welch-Satterthwaite degrees of freedom) and ``cohen_d``
+    (the difference of the means over the root of the two variances' mean) -- no ``z_score`` or ``auc``, no ``attrs``.
+    ``use_continuity`` and ``tie_correct`` mean nothing to a t-test: a non-default value is a ``ValueError``.
+
+    ``ValueError``, before any device work: a bad ``pval_type``, ``min_prop`` outside (0, 1], a bad ``n_genes``, an unknown ``method``,
+    and what ``pairwise_wilcoxon`` refuses (there is no ``max_result_bytes``: the result is K x genes).  ``NotImplementedError``: more
+    than 256 selected groups."""
     _check_marker_arguments(pval_type, min_prop, n_genes)
-    code = _check_arguments(is_log1p, alternative, use_continuity, tie_correct, True, corr_method, 0)
+    if not isinstance(method, str) or method not in MARKER_METHODS:
+        raise ValueError(f"method must be one of {tuple(MARKER_METHODS)}, got {method!r}")
+    ttest = method != "wilcoxon"
+    if ttest:
+        from illico_amd.pairwise_ttest import MARKER_PLANES, _check_arguments as check_ttest_arguments, pair_ttest_blocks
+        if use_continuity is not True or tie_correct is not True:
+            raise ValueError("use_continuity and tie_correct belong to the Wilcoxon tests: leave them at their defaults with a t-test method")
+        code = check_ttest_arguments(is_log1p, MARKER_METHODS[method], alternative, corr_method, 0)
+    else:
+        code = _check_arguments(is_log1p, alternative, use_continuity, tie_correct, True, corr_method, 0)
     from illico_amd import _lib
     from illico_amd.group_stats import _input
     X = _input(adata, layer)
@@ -393,11 +415,16 @@ def pairwise_markers(adata, is_log1p: bool, group_keys: str, *, groups=None, pva
     from illico_amd.utils.registry import data_handler_registry
     handler = data_handler_registry.get(X)
     eng = _lib.get_engine()
-    sink = _MarkerSink(eng, K, M, pval_type, rank)
-    _, n_flagged, n_fallback = pairwise_planes(X, handler, group_container, sel, bool(is_log1p), alternative, bool(use_continuity),
-                                               bool(tie_correct), True, sink=sink)
+    if ttest:
+        effect_names = ("statistic", "fold_change", "df", "cohen_d")
+        sink = _MarkerSink(eng, K, M, pval_type, rank, n_effects=len(effect_names))
+        pair_ttest_blocks(X, handler, group_container, sel, bool(is_log1p), MARKER_METHODS[method], alternative, MARKER_PLANES, sink)
+    else:
+        effect_names = ("statistic", "fold_change", "z_score")
+        sink = _MarkerSink(eng, K, M, pval_type, rank)
+        _, n_flagged, n_fallback = pairwise_planes(X, handler, group_container, sel, bool(is_log1p), alternative, bool(use_continuity),
+                                                   bool(tie_correct), True, sink=sink)
     labels = np.asarray(unique_raw_groups)[sel]
-    n_cells = np.asarray(group_container.counts, dtype=np.float64)[sel]
     cols = {"p_value": sink.p.reshape(-1)}
     n_top = min(int(n_genes), M) if n_genes is not None else 0
     top = None
@@ -409,14 +436,18 @@ def pairwise_markers(adata, is_log1p: bool, group_keys: str, *, groups=None, pva
     elif code is not None:
         cols["p_value_adj"] = np.empty(0, dtype=np.float64)
     cols["reference"] = pd.Categorical.from_codes(sink.rep.reshape(-1), categories=pd.Index(pd.Series(labels, dtype=str)))
-    cols["statistic"], cols["fold_change"], cols["z_score"] = (e.reshape(-1) for e in sink.effects)
-    cols["auc"] = (sink.effects[0] / (n_cells[:, None] * n_cells[sink.rep])).reshape(-1)
+    for name, e in zip(effect_names, sink.effects):
+        cols[name] = e.reshape(-1)
+    if not ttest:
+        n_cells = np.asarray(group_container.counts, dtype=np.float64)[sel]
+        cols["auc"] = (sink.effects[0] / (n_cells[:, None] * n_cells[sink.rep])).reshape(-1)
     from illico_amd.asymptotic_wilcoxon import _product_index
     index = _product_index(pd.Series(labels, dtype=str), pd.Series(np.asarray(adata.var_names), dtype=str))
     df = pd.DataFrame(cols, index=index, copy=False)
     if top is not None:
         df = df.iloc[(np.arange(K, dtype=np.int64)[:, None] * M + np.asarray(top)[:, :n_top]).reshape(-1)]
-    df.attrs["n_flagged_genes"] = n_flagged
-    df.attrs["n_ranked_genes"] = n_flagged - n_fallback
-    df.attrs["n_fallback_genes"] = n_fallback
+    if not ttest:
+        df.attrs["n_flagged_genes"] = n_flagged
+        df.attrs["n_ranked_genes"] = n_flagged - n_fallback
+        df.attrs["n_fallback_genes"] = n_fallback
     return df
