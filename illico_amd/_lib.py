@@ -384,32 +384,134 @@ def _pair_planes(out, n, K, W, on_dev, device, with_left):
     return planes, left, ptrs, left_ptr, on_dev
 
 
+def _stacked_rows(x, what, layout="[a, b] rows of an [A, B, W]"):
+    """The ``[A * B, W]`` view (never a copy) of an ``[A, B, W]`` numpy array or tensor whose ``[a, b]`` rows lie one pitch apart (a
+    contiguous block, or its first W columns): row ``a * B + b`` of the view is ``x[a, b]``, and ``_plane`` describes it.
+    ``ValueError`` otherwise; ``layout``: what the message calls the rows."""
+    if len(x.shape) != 3:
+        raise ValueError(f"{what} must have three dimensions, got shape {tuple(x.shape)}")
+    A, B, W = x.shape
+    is_tensor = not isinstance(x, np.ndarray)
+    s0, s1, s2 = x.stride() if is_tensor else x.strides
+    if A > 1 and s0 != B * s1:
+        raise ValueError(f"{what}: the {layout} plane must lie one row stride apart")
+    if is_tensor:
+        return x.as_strided((A * B, W), (s1, s2))
+    return np.lib.stride_tricks.as_strided(x, (A * B, W), (s1, s2), writeable=False)
+
+
 def _pairs_as_rows(x, what):
-    """``(K, W, the [K * K, W] view)`` of a ``[K, K, W]`` numpy array or CUDA tensor whose ``[r, g]`` rows lie one pitch apart (a
-    contiguous block, or its first W columns): row ``r * K + g`` of the view is ``x[r, g]``, and ``_plane`` describes it."""
-    on_dev = _host_or_cuda(x, what)
+    """``(K, W, _stacked_rows(x))`` of a ``[K, K, W]`` numpy array or CUDA tensor: row ``r * K + g`` of the view is ``x[r, g]``."""
+    _host_or_cuda(x, what)
     if len(x.shape) != 3 or x.shape[0] != x.shape[1]:
         raise ValueError(f"{what} must be a [K, K, W] plane, got shape {tuple(x.shape)}")
-    K, W = int(x.shape[0]), int(x.shape[2])
-    s0, s1, s2 = x.stride() if on_dev else x.strides
-    if K > 1 and s0 != K * s1:
-        raise ValueError(f"{what}: the [r, g] rows of a [K, K, W] plane must lie one row stride apart")
-    if on_dev:
-        return K, W, x.as_strided((K * K, W), (s1, s2))
-    return K, W, np.lib.stride_tricks.as_strided(x, (K * K, W), (s1, s2), writeable=False)
+    return int(x.shape[0]), int(x.shape[2]), _stacked_rows(x, what, "[r, g] rows of a [K, K, W]")
 
 
-def _pairs_as_rows_3d(x):
-    """The ``[B * G, W]`` view of a ``[B, G, W]`` array or tensor whose ``[b, row]`` rows lie one pitch apart (the first W columns of
-    a contiguous block); ``ValueError`` otherwise."""
-    B, G, W = (int(v) for v in x.shape)
-    on_dev = _is_torch_tensor(x)
-    s0, s1, s2 = x.stride() if on_dev else x.strides
-    if B > 1 and s0 != G * s1:
-        raise ValueError("the [b, row] rows of a [B, G, W] plane must lie one row stride apart")
+def _io_flags(on_dev) -> int:
+    """The flags of a call whose inputs and outputs live on one side."""
+    return (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0
+
+
+def _tt_variant(variant) -> int:
+    try:
+        return TT_VARIANTS[variant]
+    except (KeyError, TypeError):
+        raise ValueError(f"Unknown t-test variant {variant!r}: one of {sorted(TT_VARIANTS)}") from None
+
+
+def _wanted(want, names):
+    """``want`` as a tuple of distinct entries of ``names``, at least one."""
+    want = tuple(want)
+    if not want or any(w not in names for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"want must name distinct planes of {names}, got {want!r}")
+    return want
+
+
+def _moment_planes(named_planes, required, n_groups):
+    """``(ins, G, W, on the device, pointers, row pitch)`` of the moment planes ``((name, plane or None), ...)`` of a t-test call:
+    float64 ``[G, W]`` planes of one shape on one side, those named in ``required`` given, ``G`` the ``n_groups`` of the engine.
+    ``ins``: their ``_Plane`` records (None where not given); host planes of several pitches are made contiguous."""
+    ins = [None if x is None else _plane(x, name, copy_ok=True) for name, x in named_planes]
+    if any(q is None for (name, _), q in zip(named_planes, ins) if name in required):
+        raise ValueError(f"{' and '.join(required)} are required")
+    given = [q for q in ins if q is not None]
+    G, W, on_dev = given[0].rows, given[0].cols, given[0].on_device
+    if any((q.rows, q.cols) != (G, W) for q in given):
+        raise ValueError("the moment planes must share one shape")
+    if not any(q.on_device for q in given) and len({q.pitch for q in given}) > 1:
+        ins = [None if q is None else _plane(np.ascontiguousarray(q.array), "a moment plane") for q in ins]
+    ptrs, _, ld = _plane_set(ins, "the moment planes")
+    if G != n_groups:
+        raise ValueError(f"the moment planes have {G} rows but the engine's groups number {n_groups}")
+    return ins, G, W, on_dev, ptrs, ld
+
+
+def _wanted_outputs(out, want, names, on_dev, alloc, describe):
+    """``(planes, pointers in the order of names, row pitch)`` of the output planes of a t-test call: ``out`` None (one ``alloc()``
+    per entry of ``want``) or as many planes, each described by ``describe(plane, what)`` and on the side ``on_dev`` of the moments."""
+    if out is None:
+        planes = tuple(alloc() for _ in want)
+    else:
+        planes = tuple(out)
+        if len(planes) != len(want):
+            raise ValueError(f"out must hold {len(want)} planes, one per entry of want")
+    outs = dict.fromkeys(names)  # in the order of the library's output arguments
+    for w, pl in zip(want, planes):
+        outs[w] = describe(pl, f"out[{w}]")
+    ptrs, oflag, ld = _plane_set(list(outs.values()), "the output planes")
+    if bool(oflag) != on_dev:
+        raise ValueError("the output planes must live on the same side as the moments")
+    return planes, ptrs, ld
+
+
+def _hists_input(H, flags, rows_name, sums=None, names="H and flags"):
+    """``(H, flags, rows, W, on the device)`` of the histograms ``[rows, W, 256]`` and gene flags ``[W]`` of ``group_value_hists``:
+    contiguous 32-bit integer CUDA tensors as they are, anything else as uint32 host arrays.  ``rows_name``: what the messages call
+    the rows ("G"); ``sums``, ``names``: a further array that must live on their side, and what the message then calls the three."""
+    on_dev = _is_torch_tensor(H)
+    if on_dev != _is_torch_tensor(flags) or (sums is not None and on_dev != _is_torch_tensor(sums)):
+        raise ValueError(f"{names} must live on the same side (host or device)")
     if on_dev:
-        return x.as_strided((B * G, W), (s1, s2))
-    return np.lib.stride_tricks.as_strided(x, (B * G, W), (s1, s2), writeable=False)
+        if not (H.is_cuda and flags.is_cuda and H.is_contiguous() and flags.is_contiguous()) or H.dim() != 3 or H.element_size() != 4 \
+                or flags.element_size() != 4 or H.dtype.is_floating_point or flags.dtype.is_floating_point:
+            raise ValueError(f"H and flags must be contiguous 32-bit integer CUDA tensors [{rows_name}, W, 256] and [W]")
+    else:
+        H, flags = np.ascontiguousarray(H, dtype=np.uint32), np.ascontiguousarray(flags, dtype=np.uint32)
+        if H.ndim != 3:
+            raise ValueError(f"H must be [{rows_name}, W, 256]")
+    rows, W, R = (int(x) for x in H.shape)
+    if R != Engine.HIST_VALUES or tuple(flags.shape) != (W,):
+        raise ValueError(f"H must be [{rows_name}, W, {Engine.HIST_VALUES}] and flags [W], got {tuple(H.shape)} and {tuple(flags.shape)}")
+    return H, flags, rows, W, on_dev
+
+
+def _sums_arg(sums, shape, on_dev, what):
+    """``(array, pointer, row pitch)`` of an optional float64 ``sums`` plane of ``shape`` that must live on the side ``on_dev`` of
+    ``what``; ``(None, None, 0)`` without one."""
+    if sums is None:
+        return None, None, 0
+    sums = _plane(sums, "sums", shape=shape, copy_ok=True)
+    if sums.on_device != on_dev:
+        raise ValueError(f"sums must live on the side of {what} (host or device)")
+    return sums.array, sums.ptr, sums.pitch
+
+
+#: a matrix as the entry points take it: the C arguments that name it, the arrays behind them, where they live, its columns and the
+#: symbol suffix of its kind ("dense", "csc", "csr", "bound")
+_Matrix = namedtuple("_Matrix", "args keep on_device n_cols suffix")
+
+
+def _dense_matrix(X):
+    ptr, on_dev, keep, n_rows, n_cols, ld, dt = _dense_input(X)
+    return _Matrix((ptr, dt, n_rows, n_cols, ld), (keep,), on_dev, n_cols, "dense")
+
+
+def _sparse_matrix(fmt, data, indices, indptr, shape, formats=("csc", "csr")):
+    if fmt not in formats:
+        raise ValueError(f"fmt must be {' or '.join(repr(f) for f in formats)}, got {fmt!r}")
+    d, i, p, idx, n_rows, n_cols = _sparse_input(data, indices, indptr, shape)
+    return _Matrix((d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols), (d.keep, i.keep, p.keep), d.on_device, n_cols, fmt)
 
 
 def combine_rank(n: int, method: str, rank, min_prop) -> int:
@@ -525,19 +627,18 @@ class Engine:
         ptrs, flag, ld = _plane_set([_plane(p, f"output plane {k}", shape=(G, W), writeable=True) for k, p in enumerate(planes)], "output planes")
         return planes, ptrs, flag, ld
 
-    def _rank_tests(self, fn, matrix, keep, on_dev, n_cols, col_lb, col_ub, is_log1p, use_continuity, tie_correct, alternative, out,
-                    device_out, defer, scores):
-        """What ``run_dense``, ``run_sparse`` and ``BoundMatrix.run`` share: ``fn``, one of illico_run_*_ex, on the columns
-        [col_lb, col_ub) of the matrix its arguments ``matrix`` name (``keep``: the arrays behind them, ``on_dev``: where), with the
-        keywords of those three.  Returns the planes of ``_outputs``; without a fourth one the library gets a null ``out_z``."""
+    def _rank_tests(self, m, col_lb, col_ub, is_log1p, use_continuity, tie_correct, alternative, out, device_out, defer, scores):
+        """What ``run_dense``, ``run_sparse`` and ``BoundMatrix.run`` share: illico_run_<kind>_ex on the columns [col_lb, col_ub) of the
+        ``_Matrix`` ``m``, with the keywords of those three.  Returns the planes of ``_outputs``; without a fourth one the library
+        gets a null ``out_z``."""
         alt = self._alt(alternative)
-        _check_chunk_bounds(col_lb, col_ub, n_cols)
+        _check_chunk_bounds(col_lb, col_ub, m.n_cols)
         planes, ptrs, oflag, out_ld = self._outputs(out, self.n_groups, col_ub - col_lb, device_out, scores)
         if ptrs is None:
             return planes
-        flags = self._flags(is_log1p, use_continuity, tie_correct) | (FLAG_INPUT_DEVICE if on_dev else 0) | oflag | (FLAG_DEFER if defer else 0)
-        self._bind_torch_stream(*keep, *planes)
-        self._check(fn(self.h, *matrix, col_lb, col_ub, flags, alt, *ptrs, *[None] * (4 - len(ptrs)), out_ld))
+        flags = self._flags(is_log1p, use_continuity, tie_correct) | (FLAG_INPUT_DEVICE if m.on_device else 0) | oflag | (FLAG_DEFER if defer else 0)
+        self._bind_torch_stream(*m.keep, *planes)
+        self._check(getattr(self.lib, f"illico_run_{m.suffix}_ex")(self.h, *m.args, col_lb, col_ub, flags, alt, *ptrs, *[None] * (4 - len(ptrs)), out_ld))
         return planes
 
     def run_dense(self, X, col_lb, col_ub, *, is_log1p=False, use_continuity=True, tie_correct=True, alternative="two-sided",
@@ -546,19 +647,15 @@ class Engine:
         ``defer=True`` (device input and device planes only): return once the pass is enqueued; the planes are complete
         after ``synchronize()`` or the next call on this engine (ILLICO_FLAG_DEFER, include/illico_hip.h).  ``scores=True``
         (or a 4-tuple ``out``): a fourth plane, the z-score of every test (include/illico_hip.h: illico_run_dense_ex)."""
-        ptr, on_dev, keep, n_rows, n_cols, ld, dt = _dense_input(X)
-        return self._rank_tests(self.lib.illico_run_dense_ex, (ptr, dt, n_rows, n_cols, ld), (keep,), on_dev, n_cols, col_lb, col_ub,
-                                is_log1p, use_continuity, tie_correct, alternative, out, device_out, defer, scores)
+        return self._rank_tests(_dense_matrix(X), col_lb, col_ub, is_log1p, use_continuity, tie_correct, alternative, out, device_out, defer, scores)
 
     def run_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, *, is_log1p=False, use_continuity=True, tie_correct=True,
                    alternative="two-sided", out=None, device_out=False, defer=False, scores=False):
         """``run_dense`` of a CSC (``fmt="csc"``) or CSR matrix given as its three arrays.  ``defer=True`` (device-resident CSC arrays
         and device planes only; ignored elsewhere): return once the count-valued pass is enqueued; the planes are complete after
         ``synchronize()`` or the next call on this engine."""
-        d, i, p, idx, n_rows, n_cols = _sparse_input(data, indices, indptr, shape)
-        fn = self.lib.illico_run_csc_ex if fmt == "csc" else self.lib.illico_run_csr_ex
-        return self._rank_tests(fn, (d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols), (d.keep, i.keep, p.keep), d.on_device,
-                                n_cols, col_lb, col_ub, is_log1p, use_continuity, tie_correct, alternative, out, device_out, defer, scores)
+        return self._rank_tests(_sparse_matrix("csc" if fmt == "csc" else "csr", data, indices, indptr, shape), col_lb, col_ub,
+                                is_log1p, use_continuity, tie_correct, alternative, out, device_out, defer, scores)
 
     def bind_sparse(self, fmt, data, indices, indptr, shape):
         """Upload a host CSR / CSC matrix once (or adopt device tensors) -- illico_csr_bind / illico_csc_bind; returns a
@@ -626,7 +723,7 @@ class Engine:
         top = _empty((G, n_top), np.int64, device) if n_top else None
         if G and M:
             self._bind_torch_stream(p.array, adj.array, top)
-            self._check(self.lib.illico_adjust_pvalues(self.h, p.ptr, G, M, p.pitch, code, (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if p.on_device else 0,
+            self._check(self.lib.illico_adjust_pvalues(self.h, p.ptr, G, M, p.pitch, code, _io_flags(p.on_device),
                                                        adj.ptr, adj.pitch, n_top, _ptr(top), max(n_top, 1)))
         return (adj.array, top) if n_top else adj.array
 
@@ -640,7 +737,7 @@ class Engine:
         top = _empty((G, n_top), np.int64, x.array.device if x.on_device else None) if out is None else out
         if G and M and n_top:
             self._bind_torch_stream(x.array, top)
-            self._check(self.lib.illico_top_by_score(self.h, x.ptr, G, M, x.pitch, (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if x.on_device else 0,
+            self._check(self.lib.illico_top_by_score(self.h, x.ptr, G, M, x.pitch, _io_flags(x.on_device),
                                                      n_top, _ptr(top), n_top))
         return top
 
@@ -663,32 +760,17 @@ class Engine:
                                      for k, p in enumerate(planes)], "output planes")
         return planes, ptrs + [None] * (4 - len(ptrs)), flag, max(ld, 1)
 
-    def _group_planes_dense(self, family, X, col_lb, col_ub, flags, rest, out, *planes_spec):
-        """illico_<family>_dense on X; ``planes_spec``: the ``kinds`` and ``names`` of ``_gs_outputs`` where they are not its defaults."""
-        ptr, on_dev, keep, n_rows, n_cols, ld, dt = _dense_input(X)
-        _check_chunk_bounds(col_lb, col_ub, n_cols)
+    def _group_planes(self, family, m, col_lb, col_ub, flags, rest, out, want_device, *planes_spec):
+        """illico_<family>_<kind> on the ``_Matrix`` ``m``; planes allocated here live on the device with ``want_device``;
+        ``planes_spec``: the ``kinds`` and ``names`` of ``_gs_outputs`` where they are not its defaults."""
+        _check_chunk_bounds(col_lb, col_ub, m.n_cols)
         G, W = self.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, on_dev, *planes_spec)
+        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, want_device, *planes_spec)
         if W == 0:
             return planes
-        self._bind_torch_stream(keep, *[p for p in planes if p is not None])
-        self._check(getattr(self.lib, f"illico_{family}_dense")(self.h, ptr, dt, n_rows, n_cols, ld, col_lb, col_ub,
-                                                                 flags | (FLAG_INPUT_DEVICE if on_dev else 0) | oflag, *ptrs, out_ld))
-        return planes
-
-    def _group_planes_sparse(self, family, fmt, data, indices, indptr, shape, col_lb, col_ub, flags, rest, out, *planes_spec):
-        """illico_<family>_csc / _csr on the three arrays; ``planes_spec`` as in ``_group_planes_dense``."""
-        if fmt not in ("csc", "csr"):
-            raise ValueError(f"fmt must be 'csc' or 'csr', got {fmt!r}")
-        d, i, p, idx, n_rows, n_cols = _sparse_input(data, indices, indptr, shape)
-        _check_chunk_bounds(col_lb, col_ub, n_cols)
-        G, W = self.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = self._gs_outputs(out, G, W, rest, d.on_device, *planes_spec)
-        if W == 0:
-            return planes
-        self._bind_torch_stream(d.keep, i.keep, p.keep, *[q for q in planes if q is not None])
-        self._check(getattr(self.lib, f"illico_{family}_{fmt}")(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols, col_lb, col_ub,
-                                                                flags | (FLAG_INPUT_DEVICE if d.on_device else 0) | oflag, *ptrs, out_ld))
+        self._bind_torch_stream(*m.keep, *[p for p in planes if p is not None])
+        self._check(getattr(self.lib, f"illico_{family}_{m.suffix}")(self.h, *m.args, col_lb, col_ub,
+                                                                      flags | (FLAG_INPUT_DEVICE if m.on_device else 0) | oflag, *ptrs, out_ld))
         return planes
 
     def group_stats(self, X, col_lb, col_ub, *, is_log1p=False, rest=False, out=None):
@@ -696,12 +778,14 @@ class Engine:
 
         ``X``: a row-major numpy array or a CUDA tensor.  Returns ``(nnz, sum)`` -- int64 / float64 ``[G, W]`` -- or, with
         ``rest=True``, ``(nnz, sum, nnz_rest, sum_rest)``, living where ``X`` lives unless ``out`` (see ``_gs_outputs``) says otherwise."""
-        return self._group_planes_dense("group_stats", X, col_lb, col_ub, FLAG_LOG1P if is_log1p else 0, rest, out)
+        m = _dense_matrix(X)
+        return self._group_planes("group_stats", m, col_lb, col_ub, FLAG_LOG1P if is_log1p else 0, rest, out, m.on_device)
 
     def group_stats_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, *, is_log1p=False, rest=False, out=None):
         """``group_stats`` of a CSC (``fmt="csc"``) or CSR (``"csr"``) matrix given as its three arrays (numpy or CUDA tensors);
         CSR rows need not be sorted.  Duplicate entries count once per stored entry."""
-        return self._group_planes_sparse("group_stats", fmt, data, indices, indptr, shape, col_lb, col_ub, FLAG_LOG1P if is_log1p else 0, rest, out)
+        m = _sparse_matrix(fmt, data, indices, indptr, shape)
+        return self._group_planes("group_stats", m, col_lb, col_ub, FLAG_LOG1P if is_log1p else 0, rest, out, m.on_device)
 
     # ---- per-group moments and Welch's t-test (include/illico_hip.h: illico_group_moments_*, illico_ttest_from_moments) ----
     _GM_KINDS = (np.float64, np.float64, np.float64, np.float64)
@@ -713,12 +797,14 @@ class Engine:
         ``X``: a row-major numpy array or a CUDA tensor.  Returns ``(sum, sumsq)`` -- float64 ``[G, W]`` -- or, with ``rest=True``,
         ``(sum, sumsq, sum_rest, sumsq_rest)``, living where ``X`` lives unless ``out`` (2 or 4 planes in that order, each a host
         ndarray, a CUDA tensor or None) says otherwise.  The values are taken as given: there is no ``is_log1p``."""
-        return self._group_planes_dense("group_moments", X, col_lb, col_ub, 0, rest, out, self._GM_KINDS, self._GM_NAMES)
+        m = _dense_matrix(X)
+        return self._group_planes("group_moments", m, col_lb, col_ub, 0, rest, out, m.on_device, self._GM_KINDS, self._GM_NAMES)
 
     def group_moments_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, *, rest=False, out=None):
         """``group_moments`` of a CSC (``fmt="csc"``) or CSR (``"csr"``) matrix given as its three arrays (numpy or CUDA tensors);
         CSR rows need not be sorted.  Duplicate entries count as separate values."""
-        return self._group_planes_sparse("group_moments", fmt, data, indices, indptr, shape, col_lb, col_ub, 0, rest, out, self._GM_KINDS, self._GM_NAMES)
+        m = _sparse_matrix(fmt, data, indices, indptr, shape)
+        return self._group_planes("group_moments", m, col_lb, col_ub, 0, rest, out, m.on_device, self._GM_KINDS, self._GM_NAMES)
 
     def ttest_from_moments(self, sum, sumsq, sum_rest=None, sumsq_rest=None, *, variant="welch", alternative="two-sided",
                            want=("p", "t"), out=None):
@@ -728,43 +814,14 @@ class Engine:
         unit column stride and one row stride, all on one side.  ``variant``: ``"welch"`` or ``"overestim_var"``.  ``want``: which of
         ``TT_OUTPUTS`` (``"p"``, ``"t"``, ``"df"``, ``"mean"``, ``"var"``, ``"mean_ref"``, ``"var_ref"``) to compute.  Returns a tuple of
         float64 ``[G, M]`` planes in the order of ``want``, living where the inputs live; ``out``: a tuple of as many planes to write."""
-        try:
-            var = TT_VARIANTS[variant]
-        except (KeyError, TypeError):
-            raise ValueError(f"Unknown t-test variant {variant!r}: one of {sorted(TT_VARIANTS)}") from None
-        alt = self._alt(alternative)
-        want = tuple(want)
-        if not want or any(w not in TT_OUTPUTS for w in want) or len(set(want)) != len(want):
-            raise ValueError(f"want must name distinct planes of {TT_OUTPUTS}, got {want!r}")
-        ins = [None if x is None else _plane(x, name, copy_ok=True)
-               for name, x in (("sum", sum), ("sumsq", sumsq), ("sum_rest", sum_rest), ("sumsq_rest", sumsq_rest))]
-        if ins[0] is None or ins[1] is None:
-            raise ValueError("sum and sumsq are required")
-        given = [q for q in ins if q is not None]
-        G, M, on_dev = given[0].rows, given[0].cols, given[0].on_device
-        if any((q.rows, q.cols) != (G, M) for q in given):
-            raise ValueError("the moment planes must share one shape")
-        if not any(q.on_device for q in given) and len({q.pitch for q in given}) > 1:  # host planes of several pitches: made contiguous
-            ins = [None if q is None else _plane(np.ascontiguousarray(q.array), "a moment plane") for q in ins]
-        in_ptrs, _, ld = _plane_set(ins, "the moment planes")
-        if G != getattr(self, "n_groups", None):
-            raise ValueError(f"the moment planes have {G} rows but the engine's groups number {getattr(self, 'n_groups', None)}")
-        if out is None:
-            planes = tuple(_empty((G, M), np.float64, given[0].array.device if on_dev else None) for _ in want)
-        else:
-            planes = tuple(out)
-            if len(planes) != len(want):
-                raise ValueError(f"out must hold {len(want)} planes, one per entry of want")
-        outs = dict.fromkeys(TT_OUTPUTS)  # in the order of the library's output arguments
-        for w, pl in zip(want, planes):
-            outs[w] = _plane(pl, f"out[{w}]", shape=(G, M), writeable=True)
-        out_ptrs, oflag, out_ld = _plane_set(list(outs.values()), "the output planes")
-        if bool(oflag) != on_dev:
-            raise ValueError("the output planes must live on the same side as the moments")
+        var, alt, want = _tt_variant(variant), self._alt(alternative), _wanted(want, TT_OUTPUTS)
+        ins, G, M, on_dev, in_ptrs, ld = _moment_planes((("sum", sum), ("sumsq", sumsq), ("sum_rest", sum_rest), ("sumsq_rest", sumsq_rest)),
+                                                        ("sum", "sumsq"), getattr(self, "n_groups", None))
+        planes, out_ptrs, out_ld = _wanted_outputs(out, want, TT_OUTPUTS, on_dev, lambda: _empty((G, M), np.float64, ins[0].array.device if on_dev else None),
+                                                   lambda pl, what: _plane(pl, what, shape=(G, M), writeable=True))
         if G and M:
             self._bind_torch_stream(*[q.array for q in ins if q is not None], *planes)
-            self._check(self.lib.illico_ttest_from_moments(self.h, *in_ptrs, M, max(ld, 1), var, alt, (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0,
-                                                           *out_ptrs, out_ld))
+            self._check(self.lib.illico_ttest_from_moments(self.h, *in_ptrs, M, max(ld, 1), var, alt, _io_flags(on_dev), *out_ptrs, out_ld))
         return planes
 
     def pair_ttest_from_moments(self, sum, sumsq, *, sel=None, fsum=None, variant="welch", alternative="two-sided", want=("p", "t"), out=None):
@@ -780,26 +837,8 @@ class Engine:
         live; ``out``: a tuple of as many planes to write (contiguous, or the first W columns of contiguous blocks of one width).
         ``plane[r]`` of ``p``, ``t``, ``df`` is, bit for bit, ``ttest_from_moments`` under the reference ``sel[r]``, rows ``sel``;
         diagonal: (t, p) = (0, 1), ``cohen_d`` 0."""
-        try:
-            var = TT_VARIANTS[variant]
-        except (KeyError, TypeError):
-            raise ValueError(f"Unknown t-test variant {variant!r}: one of {sorted(TT_VARIANTS)}") from None
-        alt = self._alt(alternative)
-        want = tuple(want)
-        if not want or any(w not in PAIR_TT_OUTPUTS for w in want) or len(set(want)) != len(want):
-            raise ValueError(f"want must name distinct planes of {PAIR_TT_OUTPUTS}, got {want!r}")
-        ins = [None if x is None else _plane(x, name, copy_ok=True) for name, x in (("sum", sum), ("sumsq", sumsq), ("fsum", fsum))]
-        if ins[0] is None or ins[1] is None:
-            raise ValueError("sum and sumsq are required")
-        given = [q for q in ins if q is not None]
-        G, W, on_dev = given[0].rows, given[0].cols, given[0].on_device
-        if any((q.rows, q.cols) != (G, W) for q in given):
-            raise ValueError("the moment planes must share one shape")
-        if not any(q.on_device for q in given) and len({q.pitch for q in given}) > 1:  # host planes of several pitches: made contiguous
-            ins = [None if q is None else _plane(np.ascontiguousarray(q.array), "a moment plane") for q in ins]
-        in_ptrs, _, ld = _plane_set(ins, "the moment planes")
-        if G != getattr(self, "n_groups", None):
-            raise ValueError(f"the moment planes have {G} rows but the engine's groups number {getattr(self, 'n_groups', None)}")
+        var, alt, want = _tt_variant(variant), self._alt(alternative), _wanted(want, PAIR_TT_OUTPUTS)
+        ins, G, W, on_dev, in_ptrs, ld = _moment_planes((("sum", sum), ("sumsq", sumsq), ("fsum", fsum)), ("sum", "sumsq"), getattr(self, "n_groups", None))
         sel = np.arange(G, dtype=np.int32) if sel is None else np.ascontiguousarray(sel).reshape(-1)
         if sel.dtype.kind not in "iu":
             raise ValueError(f"sel must hold integer group ids, got {sel.dtype}")
@@ -811,27 +850,21 @@ class Engine:
         if K > PAIR_TT_MAX_GROUPS:
             raise NotImplementedError(f"{K} groups selected: pair_ttest_from_moments takes up to {PAIR_TT_MAX_GROUPS}")
         sel = np.ascontiguousarray(sel, dtype=np.int32)
-        if out is None:
-            planes = tuple(_empty((K, K, W), np.float64, given[0].array.device if on_dev else None) for _ in want)
-        else:
-            planes = tuple(out)
-            if len(planes) != len(want):
-                raise ValueError(f"out must hold {len(want)} planes, one per entry of want")
-        outs = dict.fromkeys(PAIR_TT_OUTPUTS)  # in the order of the library's output arguments
-        for w, pl in zip(want, planes):
-            Ko, Wo, rows = _pairs_as_rows(pl, f"out[{w}]")
+
+        def describe(pl, what):
+            Ko, Wo, rows = _pairs_as_rows(pl, what)
             if (Ko, Wo) != (K, W):
-                raise ValueError(f"out[{w}] must be a [K, K, W] = {(K, K, W)} plane, got shape {tuple(pl.shape)}")
+                raise ValueError(f"{what} must be a [K, K, W] = {(K, K, W)} plane, got shape {tuple(pl.shape)}")
             if not on_dev and not pl.flags.writeable:
-                raise ValueError(f"out[{w}] must be writeable")
-            outs[w] = _plane(rows, f"out[{w}]", shape=(K * K, W))
-        out_ptrs, oflag, out_ld = _plane_set(list(outs.values()), "the output planes")
-        if bool(oflag) != on_dev:
-            raise ValueError("the output planes must live on the same side as the moments")
+                raise ValueError(f"{what} must be writeable")
+            return _plane(rows, what, shape=(K * K, W))
+
+        planes, out_ptrs, out_ld = _wanted_outputs(out, want, PAIR_TT_OUTPUTS, on_dev,
+                                                   lambda: _empty((K, K, W), np.float64, ins[0].array.device if on_dev else None), describe)
         if W:
             self._bind_torch_stream(*[q.array for q in ins if q is not None], *planes)
-            self._check(self.lib.illico_pair_ttest_from_moments(self.h, *in_ptrs, W, max(ld, 1), sel.ctypes.data, K, var, alt,
-                                                                (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0, *out_ptrs, max(out_ld, W, 1)))
+            self._check(self.lib.illico_pair_ttest_from_moments(self.h, *in_ptrs, W, max(ld, 1), sel.ctypes.data, K, var, alt, _io_flags(on_dev),
+                                                                *out_ptrs, max(out_ld, W, 1)))
         return planes
 
     def student_t_pvalues(self, t, df, alternative="two-sided"):
@@ -845,7 +878,7 @@ class Engine:
             if not (t.is_cuda and df.is_cuda) or _dtype_name(t) != "float64" or _dtype_name(df) != "float64" or t.shape != df.shape:
                 raise ValueError("t and df must be float64 CUDA tensors of one shape")
             t, df = t.contiguous(), df.contiguous()
-            p, n, flags = _empty(t.shape, np.float64, t.device), t.numel(), FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE
+            p, n, flags = _empty(t.shape, np.float64, t.device), t.numel(), _io_flags(True)
         else:
             t, df = np.ascontiguousarray(t, dtype=np.float64), np.ascontiguousarray(df, dtype=np.float64)
             if t.shape != df.shape:
@@ -882,32 +915,23 @@ class Engine:
         column ``col_lb + j`` is c, ``flags[j]`` non-zero when the column holds a value that is no integer in [0, 255] (``H`` of such a
         column is unspecified).  uint32 numpy arrays for host input, int32 CUDA tensors for device input, unless ``out`` (a pair of
         either) says otherwise."""
-        ptr, on_dev, keep, n_rows, n_cols, ld, dt = _dense_input(X)
-        _check_chunk_bounds(col_lb, col_ub, n_cols)
-        G, W = self.n_groups, col_ub - col_lb
-        H, fl, ptrs, oflag = self._hist_outputs(out, G, W, on_dev)
-        if W == 0:
-            return H, fl
-        self._bind_torch_stream(keep, H, fl)
-        self._check(self.lib.illico_group_value_hists_dense(self.h, ptr, dt, n_rows, n_cols, ld, col_lb, col_ub,
-                                                            (FLAG_INPUT_DEVICE if on_dev else 0) | oflag, *ptrs))
-        return H, fl
+        return self._value_hists(_dense_matrix(X), col_lb, col_ub, out)
 
     def group_value_hists_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, out=None):
         """``group_value_hists`` of a CSC (``fmt="csc"``) or CSR (``"csr"``) matrix given as its three arrays (numpy or CUDA tensors):
         the dense answer -- a stored zero counts in bin 0, and so do the cells that are not stored.  CSR rows need not be sorted."""
-        if fmt not in ("csc", "csr"):
-            raise ValueError(f"fmt must be 'csc' or 'csr', got {fmt!r}")
-        d, i, p, idx, n_rows, n_cols = _sparse_input(data, indices, indptr, shape)
-        _check_chunk_bounds(col_lb, col_ub, n_cols)
+        return self._value_hists(_sparse_matrix(fmt, data, indices, indptr, shape), col_lb, col_ub, out)
+
+    def _value_hists(self, m, col_lb, col_ub, out):
+        """illico_group_value_hists_<kind> on the ``_Matrix`` ``m``."""
+        _check_chunk_bounds(col_lb, col_ub, m.n_cols)
         G, W = self.n_groups, col_ub - col_lb
-        H, fl, ptrs, oflag = self._hist_outputs(out, G, W, d.on_device)
+        H, fl, ptrs, oflag = self._hist_outputs(out, G, W, m.on_device)
         if W == 0:
             return H, fl
-        fn = self.lib.illico_group_value_hists_csc if fmt == "csc" else self.lib.illico_group_value_hists_csr
-        self._bind_torch_stream(d.keep, i.keep, p.keep, H, fl)
-        self._check(fn(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols,
-                       col_lb, col_ub, (FLAG_INPUT_DEVICE if d.on_device else 0) | oflag, *ptrs))
+        self._bind_torch_stream(*m.keep, H, fl)
+        self._check(getattr(self.lib, f"illico_group_value_hists_{m.suffix}")(self.h, *m.args, col_lb, col_ub,
+                                                                               (FLAG_INPUT_DEVICE if m.on_device else 0) | oflag, *ptrs))
         return H, fl
 
     def pairwise_from_hists(self, H, flags, *, counts=None, sel=None, sums=None, is_log1p=False, use_continuity=True, tie_correct=True,
@@ -925,20 +949,7 @@ class Engine:
         flagged genes are left as they are in ``out`` (a tuple of 3 or 4 contiguous planes on the side of ``H``; uninitialised when
         the planes are allocated here)."""
         alt, n = self._alt(alternative), _n_result_planes(scores)
-        on_dev = _is_torch_tensor(H)
-        if on_dev != _is_torch_tensor(flags) or (sums is not None and on_dev != _is_torch_tensor(sums)):
-            raise ValueError("H, flags and sums must live on the same side (host or device)")
-        if on_dev:
-            if not (H.is_cuda and flags.is_cuda and H.is_contiguous() and flags.is_contiguous()) or H.dim() != 3 or H.element_size() != 4 \
-                    or flags.element_size() != 4 or H.dtype.is_floating_point or flags.dtype.is_floating_point:
-                raise ValueError("H and flags must be contiguous 32-bit integer CUDA tensors [G, W, 256] and [W]")
-        else:
-            H, flags = np.ascontiguousarray(H, dtype=np.uint32), np.ascontiguousarray(flags, dtype=np.uint32)
-            if H.ndim != 3:
-                raise ValueError("H must be [G, W, 256]")
-        G, W, R = (int(x) for x in H.shape)
-        if R != self.HIST_VALUES or tuple(flags.shape) != (W,):
-            raise ValueError(f"H must be [G, W, {self.HIST_VALUES}] and flags [W], got {tuple(H.shape)} and {tuple(flags.shape)}")
+        H, flags, G, W, on_dev = _hists_input(H, flags, "G", sums, "H, flags and sums")
         if counts is None:
             if self._groups_keep is None:
                 raise ValueError("counts is needed: no groups have been set on this engine")
@@ -947,11 +958,9 @@ class Engine:
         if counts.shape != (G,):
             raise ValueError(f"H holds {G} groups but counts has shape {counts.shape}")
         K, sel_arr, sel_ptr = _pair_selection(sel, G)
-        if sums is not None:
-            sums = _plane(sums, "sums", shape=(G, W), copy_ok=True)
+        sums_array, sums_ptr, sums_ld = _sums_arg(sums, (G, W), on_dev, "H")
         planes, _, ptrs, _, _ = _pair_planes(out, n, K, W, on_dev, H.device if on_dev else None, False)
-        fl = self._flags(is_log1p, use_continuity, tie_correct) | ((FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0)
-        sums_array, sums_ptr, sums_ld = (None, None, 0) if sums is None else (sums.array, sums.ptr, sums.pitch)
+        fl = self._flags(is_log1p, use_continuity, tie_correct) | _io_flags(on_dev)
         self._bind_torch_stream(H, flags, sums_array, *planes)
         self._check(self.lib.illico_pairwise_from_hists(self.h, _ptr(H), _ptr(flags), counts.ctypes.data, G, W, sel_ptr, K, sums_ptr, sums_ld, fl, alt,
                                                         *ptrs, *[None] * (4 - n), max(W, 1)))
@@ -966,14 +975,12 @@ class Engine:
         alt, n = self._alt(alternative), _n_result_planes(scores)
         if sums is None:
             raise ValueError("sums is required: the per-group value sums of group_stats (under is_log1p its expm1 sums)")
-        sums = _plane(sums, "sums", shape=(self.n_groups, W), copy_ok=True)
-        if sums.on_device != on_dev:
-            raise ValueError("sums must live on the side of the matrix (host or device)")
+        sums_array, sums_ptr, sums_ld = _sums_arg(sums, (self.n_groups, W), on_dev, "the matrix")
         K, sel_arr, sel_ptr = _pair_selection(sel, self.n_groups)
         planes, left, ptrs, left_ptr, out_dev = _pair_planes(out, n, K, W, on_dev, f"cuda:{self.device}", True)
         fl = self._flags(is_log1p, use_continuity, tie_correct) | (FLAG_INPUT_DEVICE if on_dev else 0) | (FLAG_OUTPUT_DEVICE if out_dev else 0)
-        args = [sel_ptr, K, sums.ptr, sums.pitch, fl, alt, *ptrs, *[None] * (4 - n), max(W, 1), left_ptr]
-        return planes, left, args, (sel_arr, sums.array)
+        args = [sel_ptr, K, sums_ptr, sums_ld, fl, alt, *ptrs, *[None] * (4 - n), max(W, 1), left_ptr]
+        return planes, left, args, (sel_arr, sums_array)
 
     def pairwise_ranked(self, X, col_lb, col_ub, *, sums, sel=None, is_log1p=False, use_continuity=True, tie_correct=True,
                         alternative="two-sided", scores=False, out=None):
@@ -988,26 +995,21 @@ class Engine:
         different values than fit crowded into one sliver of the value range -- whose entries are left as they are in ``out`` (a
         tuple of the 3 or 4 planes and ``left``, all on one side; uninitialised when allocated here).  ``NotImplementedError``: other
         value types, more than 64 selected groups, two selected groups of 2097152 cells or more together."""
-        ptr, on_dev, keep, n_rows, n_cols, ld, dt = _dense_input(X)
-        _check_chunk_bounds(col_lb, col_ub, n_cols)
-        W = col_ub - col_lb
-        planes, left, args, keepalive = self._ranked_args(W, on_dev, sums, sel, is_log1p, use_continuity, tie_correct, alternative, scores, out)
-        self._bind_torch_stream(keep, keepalive[1], left, *planes)
-        self._check(self.lib.illico_pairwise_ranked_dense(self.h, ptr, dt, n_rows, n_cols, ld, col_lb, col_ub, *args))
-        return (*planes, left)
+        return self._ranked(_dense_matrix(X), col_lb, col_ub, sums, sel, is_log1p, use_continuity, tie_correct, alternative, scores, out)
 
     def pairwise_ranked_sparse(self, fmt, data, indices, indptr, shape, col_lb, col_ub, *, sums, sel=None, is_log1p=False, use_continuity=True,
                                tie_correct=True, alternative="two-sided", scores=False, out=None):
         """``pairwise_ranked`` of a CSC matrix (``fmt="csc"``) given as its three arrays (numpy or CUDA tensors): the dense answer --
         a stored zero is a zero.  The row indices of a column must ascend (scipy: ``sort_indices()``)."""
-        if fmt != "csc":
-            raise ValueError(f"fmt must be 'csc', got {fmt!r}")
-        d, i, p, idx, n_rows, n_cols = _sparse_input(data, indices, indptr, shape)
-        _check_chunk_bounds(col_lb, col_ub, n_cols)
-        W = col_ub - col_lb
-        planes, left, args, keepalive = self._ranked_args(W, d.on_device, sums, sel, is_log1p, use_continuity, tie_correct, alternative, scores, out)
-        self._bind_torch_stream(d.keep, i.keep, p.keep, keepalive[1], left, *planes)
-        self._check(self.lib.illico_pairwise_ranked_csc(self.h, d.ptr, dtype_code(d.np_dtype), i.ptr, p.ptr, idx, n_rows, n_cols, col_lb, col_ub, *args))
+        return self._ranked(_sparse_matrix(fmt, data, indices, indptr, shape, ("csc",)), col_lb, col_ub, sums, sel, is_log1p, use_continuity,
+                            tie_correct, alternative, scores, out)
+
+    def _ranked(self, m, col_lb, col_ub, *ranked_args):
+        """illico_pairwise_ranked_<kind> on the ``_Matrix`` ``m``; ``ranked_args``: what ``_ranked_args`` takes after the side."""
+        _check_chunk_bounds(col_lb, col_ub, m.n_cols)
+        planes, left, args, keepalive = self._ranked_args(col_ub - col_lb, m.on_device, *ranked_args)
+        self._bind_torch_stream(*m.keep, keepalive[1], left, *planes)
+        self._check(getattr(self.lib, f"illico_pairwise_ranked_{m.suffix}")(self.h, *m.args, col_lb, col_ub, *args))
         return (*planes, left)
 
     # ---- per-group marker statistics (include/illico_hip_markers.h: illico_combine_pairs) ----
@@ -1053,7 +1055,7 @@ class Engine:
         out_ptrs, oflag, out_ld = _plane_set(outs, "the output planes")
         if bool(oflag) != on_dev:
             raise ValueError("the output planes must live on the side of p (host or device)")
-        flags = (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0
+        flags = _io_flags(on_dev)
         pad = [None] * (COMBINE_MAX_EFFECTS - len(effects))
         self._bind_torch_stream(p, *effects, skip_keep, *out)
         self._check(self.lib.illico_combine_pairs(self.h, *in_ptrs, *pad, K, W, max(in_ld, W, 1), skip_ptr, COMBINE_METHODS[method], rank_j, flags,
@@ -1081,12 +1083,9 @@ class Engine:
 
     def _blocked_io(self, G, B, W, sums, out, on_dev, device, with_fc=True):
         """The optional ``sums`` plane ``[G * B, W]`` and the four ``[G, W]`` result planes (p, statistic, fold change, z; the third
-        None without ``with_fc``) of a blocked call whose input lives on the side ``on_dev``: (sums plane or None, planes, pointers,
-        output flag, pitch)."""
-        if sums is not None:
-            sums = _plane(sums, "sums", shape=(G * B, W), copy_ok=True)
-            if sums.on_device != on_dev:
-                raise ValueError("sums must live on the side of the input (host or device)")
+        None without ``with_fc``) of a blocked call whose input lives on the side ``on_dev``: (sums, planes, pointers,
+        output flag, pitch); the sums as ``_sums_arg`` gives them."""
+        sums = _sums_arg(sums, (G * B, W), on_dev, "the input")
         if out is None:
             out = [_empty((G, W), np.float64, device if on_dev else None) if (k != 2 or with_fc) else None for k in range(4)]
         out = tuple(out)
@@ -1109,26 +1108,12 @@ class Engine:
         ``H``: each group's per-block tests combined by Stouffer's z weighted with ``n_g n_r``.  NaN in every plane where no block
         holds both samples.  The columns of flagged genes are left as they are in ``out`` (four planes with one row stride)."""
         alt = self._alt(alternative)
-        on_dev = _is_torch_tensor(H)
-        if on_dev != _is_torch_tensor(flags):
-            raise ValueError("H and flags must live on the same side (host or device)")
-        if on_dev:
-            if not (H.is_cuda and flags.is_cuda and H.is_contiguous() and flags.is_contiguous()) or H.dim() != 3 or H.element_size() != 4 \
-                    or flags.element_size() != 4 or H.dtype.is_floating_point or flags.dtype.is_floating_point:
-                raise ValueError("H and flags must be contiguous 32-bit integer CUDA tensors [G * B, W, 256] and [W]")
-        else:
-            H, flags = np.ascontiguousarray(H, dtype=np.uint32), np.ascontiguousarray(flags, dtype=np.uint32)
-            if H.ndim != 3:
-                raise ValueError("H must be [G * B, W, 256]")
-        GB, W, R = (int(x) for x in H.shape)
-        if R != self.HIST_VALUES or tuple(flags.shape) != (W,):
-            raise ValueError(f"H must be [G * B, W, {self.HIST_VALUES}] and flags [W], got {tuple(H.shape)} and {tuple(flags.shape)}")
+        H, flags, GB, W, on_dev = _hists_input(H, flags, "G * B")
         counts, G, B, ref, _ = self._blocked_sizes(counts, GB, n_blocks, ref)
-        sums, planes, ptrs, oflag, out_ld = self._blocked_io(G, B, W, sums, out, on_dev, H.device if on_dev else None)
+        (sums_array, sums_ptr, sums_ld), planes, ptrs, oflag, out_ld = self._blocked_io(G, B, W, sums, out, on_dev, H.device if on_dev else None)
         if W and bool(oflag) != on_dev:
             raise ValueError("the output planes must live on the side of H (host or device)")
-        fl = (FLAG_TIE_CORRECT if tie_correct else 0) | ((FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0)
-        sums_array, sums_ptr, sums_ld = (None, None, 0) if sums is None else (sums.array, sums.ptr, sums.pitch)
+        fl = (FLAG_TIE_CORRECT if tie_correct else 0) | _io_flags(on_dev)
         self._bind_torch_stream(H, flags, sums_array, *planes)
         self._check(self.lib.illico_blocked_from_hists(self.h, _ptr(H), _ptr(flags), counts.ctypes.data, G, B, W, ref, sums_ptr, sums_ld, fl, alt,
                                                        *ptrs, max(out_ld, W, 1)))
@@ -1148,20 +1133,19 @@ class Engine:
         if on_dev != _is_torch_tensor(U) or tuple(z.shape) != tuple(U.shape) or len(z.shape) != 3:
             raise ValueError("z and U must be [B, G, W] planes of one shape on one side (host or device)")
         B, G, W = (int(x) for x in z.shape)
-        ins = [_plane(_pairs_as_rows_3d(z), "z"), _plane(_pairs_as_rows_3d(U), "U")]
+        ins = [_plane(_stacked_rows(q, what, "[b, row] rows of a [B, G, W]"), what) for q, what in ((z, "z"), (U, "U"))]
         in_ptrs, _, in_ld = _plane_set(ins, "z and U")
         row_map = np.ascontiguousarray(row_map, dtype=np.int32)
         if row_map.shape != (B, G):
             raise ValueError(f"row_map must be [B, G] = {(B, G)}, got {row_map.shape}")
         counts, G2, B2, ref, _ = self._blocked_sizes(counts, G * B, B, ref)
-        sums, planes, ptrs, oflag, out_ld = self._blocked_io(G, B, W, sums, out, on_dev, z.device if on_dev else None, with_fc=sums is not None)
+        (sums_array, sums_ptr, sums_ld), planes, ptrs, oflag, out_ld = self._blocked_io(G, B, W, sums, out, on_dev, z.device if on_dev else None,
+                                                                                        with_fc=sums is not None)
         if W and bool(oflag) != on_dev:
             raise ValueError("the output planes must live on the side of z (host or device)")
-        fl = (FLAG_INPUT_DEVICE | FLAG_OUTPUT_DEVICE) if on_dev else 0
-        sums_array, sums_ptr, sums_ld = (None, None, 0) if sums is None else (sums.array, sums.ptr, sums.pitch)
         self._bind_torch_stream(z, U, sums_array, *planes)
         self._check(self.lib.illico_blocked_from_planes(self.h, *in_ptrs, max(in_ld or 0, W, 1), row_map.ctypes.data, counts.ctypes.data, G, B, W, ref,
-                                                        sums_ptr, sums_ld, fl, alt, *ptrs, max(out_ld, W, 1)))
+                                                        sums_ptr, sums_ld, _io_flags(on_dev), alt, *ptrs, max(out_ld, W, 1)))
         return planes
 
     def csr_indices_sorted(self, indices, indptr, n_rows) -> bool:
@@ -1210,29 +1194,20 @@ class BoundMatrix:
             out=None, device_out=False, defer=False, scores=False):
         """``Engine.run_dense`` of the bound matrix, with its keywords.  A call with the z-score plane computes its chunk directly: the
         windows of the option "bound_ahead_genes" are neither used nor replaced by it (include/illico_hip.h: illico_run_bound_ex)."""
-        eng = self.engine
-        return eng._rank_tests(eng.lib.illico_run_bound_ex, (self.h,), (), False, self.shape[1], col_lb, col_ub,
-                               is_log1p, use_continuity, tie_correct, alternative, out, device_out, defer, scores)
+        return self.engine._rank_tests(self._matrix(), col_lb, col_ub, is_log1p, use_continuity, tie_correct, alternative, out, device_out, defer, scores)
 
-    def _group_planes(self, family, col_lb, col_ub, flags, rest, out, device_out, *planes_spec):
-        """illico_<family>_bound on this matrix; ``planes_spec`` as in ``Engine._group_planes_dense``."""
-        eng = self.engine
-        _check_chunk_bounds(col_lb, col_ub, self.shape[1])
-        G, W = eng.n_groups, col_ub - col_lb
-        planes, ptrs, oflag, out_ld = eng._gs_outputs(out, G, W, rest, device_out, *planes_spec)
-        if W == 0:
-            return planes
-        eng._bind_torch_stream(*[p for p in planes if p is not None])
-        eng._check(getattr(eng.lib, f"illico_{family}_bound")(eng.h, self.h, col_lb, col_ub, flags | oflag, *ptrs, out_ld))
-        return planes
+    def _matrix(self):
+        """The ``_Matrix`` of this handle: the library knows where its arrays live."""
+        return _Matrix((self.h,), (), False, self.shape[1], "bound")
 
     def group_stats(self, col_lb, col_ub, *, is_log1p=False, rest=False, out=None, device_out=False):
         """``Engine.group_stats`` of the bound matrix (illico_group_stats_bound); host planes unless ``device_out`` or ``out``."""
-        return self._group_planes("group_stats", col_lb, col_ub, FLAG_LOG1P if is_log1p else 0, rest, out, device_out)
+        return self.engine._group_planes("group_stats", self._matrix(), col_lb, col_ub, FLAG_LOG1P if is_log1p else 0, rest, out, device_out)
 
     def group_moments(self, col_lb, col_ub, *, rest=False, out=None, device_out=False):
         """``Engine.group_moments`` of the bound matrix (illico_group_moments_bound); host planes unless ``device_out`` or ``out``."""
-        return self._group_planes("group_moments", col_lb, col_ub, 0, rest, out, device_out, self.engine._GM_KINDS, self.engine._GM_NAMES)
+        return self.engine._group_planes("group_moments", self._matrix(), col_lb, col_ub, 0, rest, out, device_out, self.engine._GM_KINDS,
+                                         self.engine._GM_NAMES)
 
     def touch(self):
         """Adopted device arrays were rewritten in place: forget what the context remembers about them (include/illico_hip.h)."""

@@ -1,6 +1,6 @@
 // illico_blocked_from_hists / illico_blocked_from_planes: Wilcoxon rank-sum tests spread over B blocks, the per-block tests combined on
 // the device (kernels_blocked.h; include/illico_hip_blocked.h states the definition).  A translation unit of its
-// own, a sibling of pairwise.hip and markers.hip: it shares the plane copies of group_pass.h and the histogram layouts of
+// own, a sibling of pairwise.hip and markers.hip: it shares the plane staging of plane_stage.h (through group_pass.h) and the histogram layouts of
 // kernels_pairwise.h, and touches no other route.  Its kernels have no profiled kernel id: callers time the calls with stream events.
 #include "group_pass.h"
 #include "../../include/illico_hip_blocked.h"
@@ -67,14 +67,15 @@ struct Carver {
     }
 };
 
-// The device side of one call: sizes, row map, staged inputs and outputs.  blk_plan runs twice over the same requests.
+// The work arrays of one call, and the block a host caller's planes are staged in.  blk_plan runs twice over the same requests.
 struct BlkDevice {
     long long *n, *ntot;
     int *row_map;
-    u32 *T, *TOT, *H, *gene_flags;
-    double *stot, *sums, *z, *U, *out[4];
+    u32 *T, *TOT;
+    double *stot;
+    unsigned char *stage;
 };
-void blk_plan(Carver &cv, const BlkCall &a, bool hists, bool in_dev, bool out_dev, BlkDevice *d) {
+void blk_plan(Carver &cv, const BlkCall &a, bool hists, size_t staged, BlkDevice *d) {
     const size_t GB = (size_t)(a.G * a.B), W = (size_t)a.W, tiles = (W + 63) / 64;
     d->n = cv.take<long long>(GB);
     d->ntot = cv.take<long long>((size_t)a.B);
@@ -82,21 +83,21 @@ void blk_plan(Carver &cv, const BlkCall &a, bool hists, bool in_dev, bool out_de
     d->T = hists ? cv.take<u32>(GB * tiles * PW_TILE_WORDS) : nullptr;
     d->TOT = hists && a.ref < 0 ? cv.take<u32>((size_t)a.B * tiles * PW_TILE_WORDS) : nullptr;
     d->stot = a.sums && a.ref < 0 ? cv.take<double>((size_t)a.B * W) : nullptr;
-    d->H = hists && !in_dev ? cv.take<u32>(GB * W * PW_RT) : nullptr;
-    d->gene_flags = hists && !in_dev ? cv.take<u32>(W) : nullptr;
-    d->sums = a.sums && !in_dev ? cv.take<double>(GB * W) : nullptr;
-    d->z = !hists && !in_dev ? cv.take<double>(GB * W) : nullptr;
-    d->U = !hists && !in_dev ? cv.take<double>(GB * W) : nullptr;
-    for (int k = 0; k < 4; ++k) d->out[k] = a.out[k] && !out_dev ? cv.take<double>((size_t)a.G * W) : nullptr;
+    d->stage = staged ? cv.take<unsigned char>(staged) : nullptr;
 }
 
 int blk_run(illico_ctx *c, const BlkCall &a, const BlkSizes &S, const u32 *H, const u32 *gene_flags, const double *z, const double *U, int64_t in_ld) {
     const bool hists = H != nullptr, in_dev = a.flags & ILLICO_FLAG_INPUT_DEVICE, out_dev = a.flags & ILLICO_FLAG_OUTPUT_DEVICE;
     const int64_t G = a.G, B = a.B, W = a.W, GB = G * B;
     const int wn = (int)W, tiles = (wn + 63) / 64;
+    // one window; a host caller's planes are staged: the sums, the histograms and the gene flags or z and U, the outputs
+    const size_t GBW = (size_t)GB * W;
+    int n_out = 0;
+    for (double *p : a.out) n_out += p ? 1 : 0;
+    const size_t staged = (in_dev ? 0 : (a.sums ? GBW * 8 : 0) + (hists ? GBW * PW_RT * 4 + (size_t)W * 4 + 8 : GBW * 16)) + (out_dev ? 0 : (size_t)n_out * G * W * 8);
     BlkDevice d;
     Carver cv;
-    blk_plan(cv, a, hists, in_dev, out_dev, &d);
+    blk_plan(cv, a, hists, staged, &d);
     if (cv.used > (size_t)std::max<int64_t>(c->scratch_bytes, 1))
         return fail(c, ILLICO_ERR_OOM, "%s needs %zu bytes of device scratch, the budget (\"scratch_bytes\") is %lld: pass a narrower gene window",
                     hists ? "illico_blocked_from_hists" : "illico_blocked_from_planes", cv.used, (long long)c->scratch_bytes);
@@ -106,7 +107,7 @@ int blk_run(illico_ctx *c, const BlkCall &a, const BlkSizes &S, const u32 *H, co
     const size_t need = cv.used;
     cv = Carver{};
     if ((rc = scratch(c, "blk_work", need, &cv.base))) return rc;
-    blk_plan(cv, a, hists, in_dev, out_dev, &d);
+    blk_plan(cv, a, hists, staged, &d);
 
     HIPCHK(c, hipMemcpyAsync(d.n, S.n.data(), (size_t)GB * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d.ntot, S.ntot.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
@@ -115,31 +116,18 @@ int blk_run(illico_ctx *c, const BlkCall &a, const BlkSizes &S, const u32 *H, co
     P.n = d.n; P.ntot = d.ntot; P.row_map = d.row_map;
     P.G = (int)G; P.B = (int)B; P.W = wn; P.ref = (int)a.ref; P.alternative = a.alternative;
     P.tiles = tiles; P.tie_correct = (a.flags & ILLICO_FLAG_TIE_CORRECT) ? 1 : 0;
-    P.sums = a.sums; P.sums_ld = a.sums_ld;
-    P.gene_flags = gene_flags; P.z = z; P.U = U; P.in_ld = in_ld;
-    const u32 *d_H = H;
-    if (!in_dev) {
-        if (a.sums) {
-            if ((rc = planes_to_device(c, d.sums, a.sums, a.sums_ld, GB, W))) return rc;
-            P.sums = d.sums; P.sums_ld = W;
-        }
-        if (hists) {
-            HIPCHK(c, hipMemcpyAsync(d.H, H, (size_t)GB * W * PW_RT * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(d.gene_flags, gene_flags, (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
-            d_H = d.H; P.gene_flags = d.gene_flags;
-        } else {
-            if ((rc = planes_to_device(c, d.z, z, in_ld, GB, W))) return rc;
-            if ((rc = planes_to_device(c, d.U, U, in_ld, GB, W))) return rc;
-            P.z = d.z; P.U = d.U; P.in_ld = W;
-        }
-    }
-    double **po[4] = {&P.out_p, &P.out_u, &P.out_fc, &P.out_z};
-    P.out_ld = out_dev ? a.out_ld : W;
-    for (int k = 0; k < 4; ++k) {
-        *po[k] = out_dev ? a.out[k] : d.out[k];
-        // a host caller's planes go up first: the columns of flagged genes come back as they were
-        if (!out_dev && hists && a.out[k] && (rc = planes_to_device(c, d.out[k], a.out[k], a.out_ld, G, W))) return rc;
-    }
+    PlaneStage sh(c, d.stage, 0, (int64_t)GBW * PW_RT); // the histograms [GB][W][PW_RT] go up as one row
+    const u32 *d_H = sh.in(H, 0, 1, in_dev);
+    if (sh.rc) return sh.rc;
+    PlaneStage st(c, sh.rest(), 0, W);
+    P.sums = st.in(a.sums, a.sums_ld, GB, in_dev); P.sums_ld = st.pitch(a.sums_ld, in_dev);
+    P.gene_flags = st.in(gene_flags, W, 1, in_dev);
+    P.z = st.in(z, in_ld, GB, in_dev); P.U = st.in(U, in_ld, GB, in_dev); P.in_ld = st.pitch(in_ld, in_dev);
+    // from histograms a host caller's planes go up first: the columns of flagged genes come back as they were
+    P.out_p = st.out(a.out[0], a.out_ld, G, out_dev, hists); P.out_u = st.out(a.out[1], a.out_ld, G, out_dev, hists);
+    P.out_fc = st.out(a.out[2], a.out_ld, G, out_dev, hists); P.out_z = st.out(a.out[3], a.out_ld, G, out_dev, hists);
+    P.out_ld = st.pitch(a.out_ld, out_dev);
+    if (st.rc) return st.rc;
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the sizes and the staged arrays came from pageable host memory)
 
     if (d.stot) {
@@ -157,12 +145,7 @@ int blk_run(illico_ctx *c, const BlkCall &a, const BlkSizes &S, const u32 *H, co
     } else {
         KERNELCHK(c, k_blk_from_planes, dim3((unsigned)((wn + 255) / 256), (unsigned)G), dim3(256), 0, P);
     }
-    if (!out_dev) {
-        for (int k = 0; k < 4; ++k)
-            if (a.out[k] && (rc = planes_to_host(c, a.out[k], a.out_ld, d.out[k], G, W))) return rc;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return ILLICO_OK;
+    return st.finish();
 }
 
 } // namespace

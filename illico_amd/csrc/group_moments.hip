@@ -111,16 +111,18 @@ int gm_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
     P.vmaxq = P.vmax + WW;
     P.nonfin = (int *)(P.vmaxq + WW);
     GmTotal *part = (GmTotal *)(((uintptr_t)(P.nonfin + WW) + 255) & ~(uintptr_t)255);
-    unsigned char *stage = (unsigned char *)(part + (size_t)n_part * WW);
-    double *st[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (!out_dev)
-        for (int k = 0; k < 4; ++k)
-            if (outs[k]) { st[k] = (double *)stage; stage += GW * 8; }
-    void *xwin = stage; // host dense: the window's rows, [N][wn] in the matrix's own type
+    unsigned char *stage = (unsigned char *)(part + (size_t)n_part * WW); // the staged host outputs, then the window's rows of a host dense matrix
 
     for (int64_t w0 = col_lb; w0 < col_ub; w0 += WW) {
         const int wn = (int)std::min<int64_t>(WW, col_ub - w0);
         P.W = wn;
+        PlaneStage st(c, stage, w0 - col_lb, wn);
+        GmOut O;
+        O.sum = st.out(o.sum, o.ld, G, out_dev, false); O.sumsq = st.out(o.sumsq, o.ld, G, out_dev, false);
+        O.sum_rest = st.out(o.sum_rest, o.ld, G, out_dev, false); O.sumsq_rest = st.out(o.sumsq_rest, o.ld, G, out_dev, false);
+        O.ld = st.pitch(o.ld, out_dev);
+        if (st.rc) return st.rc;
+        void *xwin = st.rest(); // host dense: [N][wn] in the matrix's own type
         // the six planes, the two magnitude rows and the flags lie back to back: one clear (a narrower last window clears a little more than it uses)
         HIPCHK(c, hipMemsetAsync(P.L0, 0, GW * 48 + (size_t)WW * 20, c->stream));
         if (!in.sparse) {
@@ -143,28 +145,12 @@ int gm_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
             ProfScope ps(c, KID_GM_TOTALS);
             KERNELCHK(c, k_gm_totals, dim3(gx, n_part), dim3(GM_NT), 0, P, (int)G, wn, part);
         }
-        GmOut O;
-        const int64_t off = w0 - col_lb;
-        if (out_dev) {
-            O.sum = o.sum ? o.sum + off : nullptr;
-            O.sumsq = o.sumsq ? o.sumsq + off : nullptr;
-            O.sum_rest = o.sum_rest ? o.sum_rest + off : nullptr;
-            O.sumsq_rest = o.sumsq_rest ? o.sumsq_rest + off : nullptr;
-            O.ld = o.ld;
-        } else {
-            O.sum = st[0]; O.sumsq = st[1]; O.sum_rest = st[2]; O.sumsq_rest = st[3];
-            O.ld = wn;
-        }
         {
             ProfScope ps(c, KID_GM_FINALIZE);
             const int gy = (int)std::max<int64_t>(1, std::min<int64_t>(G, (8192 + gx - 1) / gx));
             KERNELCHK(c, k_gm_finalize, dim3(gx, gy), dim3(GM_NT), 0, P, (int)G, wn, part, n_part, O);
         }
-        if (!out_dev) {
-            for (int k = 0; k < 4; ++k)
-                if (outs[k] && (rc = planes_to_host(c, outs[k] + off, o.ld, st[k], G, wn))) return rc;
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
+        if ((rc = st.finish())) return rc;
     }
     return ILLICO_OK;
 }
@@ -233,46 +219,26 @@ extern "C" int illico_ttest_from_moments(illico_ctx *c, const double *sum, const
     const double *const ins[4] = {sum, sumsq, ovr ? sum_rest : nullptr, ovr ? sumsq_rest : nullptr};
     const int n_in = ovr ? 4 : 2;
     // column windows under the scratch cap (host planes are staged)
-    const size_t per_col = (in_dev ? 0 : (size_t)G * 8 * n_in) + (out_dev ? 0 : (size_t)G * 8 * n_out);
-    const int64_t WW = per_col ? std::max<int64_t>(1, std::min<int64_t>(W, (int64_t)((size_t)std::max<int64_t>(c->scratch_bytes, 1) / per_col))) : W;
-    unsigned char *stage = nullptr;
-    if (per_col && (rc = scratch(c, "tt_stage", (size_t)WW * per_col + 64, &stage))) return rc;
-    for (int64_t w0 = 0; w0 < W; w0 += WW) {
-        const int wn = (int)std::min<int64_t>(WW, W - w0);
+    StageWindows sw;
+    if ((rc = plan_stage_windows(c, W, (in_dev ? 0 : (size_t)G * 8 * n_in) + (out_dev ? 0 : (size_t)G * 8 * n_out), kNoWindowCap, "tt_stage", &sw))) return rc;
+    for (int64_t w0 = 0; w0 < W; w0 += sw.WW) {
+        const int wn = (int)std::min<int64_t>(sw.WW, W - w0);
+        PlaneStage st(c, sw.block, w0, wn);
         TtParams T;
         T.G = (int)G; T.W = wn; T.ref = (int)c->ref; T.n_cells = (long long)c->n_cells; T.counts = c->d_counts;
         T.variant = variant; T.alternative = alternative;
-        unsigned char *s = stage;
-        const double *din[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int k = 0; k < 4; ++k) {
-            if (!ins[k]) continue;
-            if (in_dev) din[k] = ins[k] + w0;
-            else {
-                if ((rc = planes_to_device(c, s, ins[k] + w0, in_ld, G, wn))) return rc;
-                din[k] = (const double *)s;
-                s += (size_t)G * wn * 8;
-            }
-        }
-        T.S = din[0]; T.Q = din[1]; T.SR = din[2]; T.QR = din[3];
-        T.in_ld = in_dev ? in_ld : wn;
-        double *st[TT_N_OUT];
-        for (int k = 0; k < TT_N_OUT; ++k) {
-            st[k] = nullptr;
-            if (!outs[k]) { T.out[k] = nullptr; continue; }
-            if (out_dev) T.out[k] = outs[k] + w0;
-            else { st[k] = (double *)s; T.out[k] = st[k]; s += (size_t)G * wn * 8; }
-        }
-        T.out_ld = out_dev ? out_ld : wn;
+        T.S = st.in(ins[0], in_ld, G, in_dev); T.Q = st.in(ins[1], in_ld, G, in_dev);
+        T.SR = st.in(ins[2], in_ld, G, in_dev); T.QR = st.in(ins[3], in_ld, G, in_dev);
+        T.in_ld = st.pitch(in_ld, in_dev);
+        for (int k = 0; k < TT_N_OUT; ++k) T.out[k] = st.out(outs[k], out_ld, G, out_dev, false);
+        T.out_ld = st.pitch(out_ld, out_dev);
+        if (st.rc) return st.rc;
         {
             ProfScope ps(c, KID_TTEST);
             const int gx = (wn + TT_NT - 1) / TT_NT;
             KERNELCHK(c, k_ttest_from_moments, dim3(gx, (unsigned)std::min<int64_t>(G, 65535)), dim3(TT_NT), 0, T);
         }
-        if (!out_dev) {
-            for (int k = 0; k < TT_N_OUT; ++k)
-                if (outs[k] && (rc = planes_to_host(c, outs[k] + w0, out_ld, st[k], G, wn))) return rc;
-        }
-        if (!in_dev || !out_dev) HIPCHK(c, hipStreamSynchronize(c->stream)); // (the staging area is reused by the next window; host planes complete on return)
+        if ((rc = st.finish())) return rc;
     }
     return ILLICO_OK;
 }
@@ -287,28 +253,19 @@ extern "C" int illico_student_t_pvalues(illico_ctx *c, const double *t, const do
     if ((rc = resolve_pending(c))) return rc;
     if (n == 0) return ILLICO_OK;
     const bool in_dev = flags & ILLICO_FLAG_INPUT_DEVICE, out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
-    const int64_t chunk = (int64_t)1 << 24;
-    double *dt_ = nullptr, *ddf = nullptr, *dp = nullptr;
-    if (!in_dev || !out_dev) {
-        if ((rc = scratch(c, "tt_stage", (size_t)std::min(n, chunk) * 3 + 8, &dt_))) return rc;
-        ddf = dt_ + std::min(n, chunk); dp = ddf + std::min(n, chunk);
-    }
-    for (int64_t i0 = 0; i0 < n; i0 += chunk) {
-        const int64_t m = std::min(chunk, n - i0);
-        const double *kt = t + i0, *kd = df + i0;
-        double *kp = out_p + i0;
-        if (!in_dev) {
-            HIPCHK(c, hipMemcpyAsync(dt_, t + i0, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(ddf, df + i0, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
-            kt = dt_; kd = ddf;
-        }
-        if (!out_dev) kp = dp;
+    StageWindows sw; // the one-row case: t and df in, p out
+    if ((rc = plan_stage_windows(c, n, (in_dev ? 0 : 16) + (out_dev ? 0 : 8), (int64_t)1 << 24, "tt_stage", &sw))) return rc;
+    for (int64_t i0 = 0; i0 < n; i0 += sw.WW) {
+        const int64_t m = std::min(sw.WW, n - i0);
+        PlaneStage st(c, sw.block, i0, m);
+        const double *kt = st.in(t, n, 1, in_dev), *kd = st.in(df, n, 1, in_dev);
+        double *kp = st.out(out_p, n, 1, out_dev, false);
+        if (st.rc) return st.rc;
         {
             ProfScope ps(c, KID_TTEST);
             KERNELCHK(c, k_student_t_pvalues, dim3((unsigned)((m + TT_NT - 1) / TT_NT)), dim3(TT_NT), 0, kt, kd, (long long)m, alternative, kp);
         }
-        if (!out_dev) HIPCHK(c, hipMemcpyAsync(out_p + i0, dp, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
-        if (!in_dev || !out_dev) HIPCHK(c, hipStreamSynchronize(c->stream));
+        if ((rc = st.finish())) return rc;
     }
     return ILLICO_OK;
 }

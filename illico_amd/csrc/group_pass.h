@@ -1,10 +1,12 @@
-// Host scaffolding of the four units that read the matrix once per group family -- group_stats.hip, group_moments.hip, pairwise.hip,
-// pairwise_ranked.hip (the last two through pair_pass.h) -- and of pair_ttest.hip, which takes the plane copies only: the description of the input, the checks every entry point
-// makes, the upload of host-resident sparse arrays and dense windows, the copies of 8-byte planes, the dispatch on the index type, and the
-// groups' positions in chunks.  Everything is local to the including unit (the four are linked into one library).  The kernels, the
-// planes, the column windows, the outputs and the points at which the stream is synchronised are each family's own.
+// Host scaffolding of the units that read the matrix once per group family -- group_stats.hip, group_moments.hip, and through
+// pair_pass.h pairwise.hip and pairwise_ranked.hip: the description of the input, the checks every entry point makes, the upload of
+// host-resident sparse arrays and dense windows, the dispatch on the index type, and the groups' positions in chunks.  It brings in
+// plane_stage.h, the staging of host planes, which is all that pair_ttest.hip and blocked.hip take from here (markers.hip includes
+// that header alone).  Everything is local to the including unit (all are linked into one library).  The kernels, the planes, the
+// column windows, the outputs and the points at which the stream is synchronised are each family's own.
 #pragma once
 #include "engine.h"
+#include "plane_stage.h"
 
 namespace {
 
@@ -98,16 +100,6 @@ inline int stage_dense_window(illico_ctx *c, const MatrixInput &in, int64_t col0
                                (size_t)in.n_rows, hipMemcpyHostToDevice, c->stream));
     c->h2d_input_bytes += (int64_t)((size_t)in.n_rows * wn * esz);
     *out = DenseWindow{xwin, pitch, 0};
-    return ILLICO_OK;
-}
-
-// [rows][w] planes of 8-byte elements between a host pitch and the packed device pitch w.  Enqueued, not awaited.
-inline int planes_to_device(illico_ctx *c, void *dev, const void *host, int64_t host_ld, int64_t rows, int64_t w) {
-    HIPCHK(c, hipMemcpy2DAsync(dev, (size_t)w * 8, host, (size_t)host_ld * 8, (size_t)w * 8, (size_t)rows, hipMemcpyHostToDevice, c->stream));
-    return ILLICO_OK;
-}
-inline int planes_to_host(illico_ctx *c, void *host, int64_t host_ld, const void *dev, int64_t rows, int64_t w) {
-    HIPCHK(c, hipMemcpy2DAsync(host, (size_t)host_ld * 8, dev, (size_t)w * 8, (size_t)w * 8, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
     return ILLICO_OK;
 }
 

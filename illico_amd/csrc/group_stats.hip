@@ -102,23 +102,18 @@ int gs_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
     P.vmax = P.cat + (size_t)G * WW;
     P.nonfin = (int *)(P.vmax + WW);
     GsTotal *part = (GsTotal *)(((uintptr_t)(P.nonfin + WW) + 255) & ~(uintptr_t)255);
-    unsigned char *stage = (unsigned char *)(part + (size_t)n_part * WW);
-    double *st_sum = nullptr, *st_sum_rest = nullptr;
-    long long *st_nnz = nullptr, *st_nnz_rest = nullptr;
-    if (!out_dev) {
-        unsigned char *s = stage;
-        auto take = [&](bool want) { unsigned char *r = want ? s : nullptr; if (want) s += (size_t)G * WW * 8; return r; };
-        st_nnz = (long long *)take(o.nnz != nullptr);
-        st_sum = (double *)take(o.sum != nullptr);
-        st_nnz_rest = (long long *)take(o.nnz_rest != nullptr);
-        st_sum_rest = (double *)take(o.sum_rest != nullptr);
-        stage = s;
-    }
-    void *xwin = stage; // host dense: the window's rows, [N][wn] in the matrix's own type
+    unsigned char *stage = (unsigned char *)(part + (size_t)n_part * WW); // the staged host outputs, then the window's rows of a host dense matrix
 
     for (int64_t w0 = col_lb; w0 < col_ub; w0 += WW) {
         const int wn = (int)std::min<int64_t>(WW, col_ub - w0);
         P.W = wn;
+        PlaneStage st(c, stage, w0 - col_lb, wn);
+        GsOut O;
+        O.nnz = (long long *)st.out(o.nnz, o.ld, G, out_dev, false); O.sum = st.out(o.sum, o.ld, G, out_dev, false);
+        O.nnz_rest = (long long *)st.out(o.nnz_rest, o.ld, G, out_dev, false); O.sum_rest = st.out(o.sum_rest, o.ld, G, out_dev, false);
+        O.ld = st.pitch(o.ld, out_dev);
+        if (st.rc) return st.rc;
+        void *xwin = st.rest(); // host dense: [N][wn] in the matrix's own type
         HIPCHK(c, hipMemsetAsync(P.L0, 0, (size_t)G * wn * 8, c->stream));
         HIPCHK(c, hipMemsetAsync(P.L1, 0, (size_t)G * wn * 8, c->stream));
         HIPCHK(c, hipMemsetAsync(P.cnt, 0, (size_t)G * wn * 8, c->stream));
@@ -145,29 +140,12 @@ int gs_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub,
             ProfScope ps(c, KID_GS_TOTALS);
             KERNELCHK(c, k_gs_totals, dim3(gx, n_part), dim3(GS_NT), 0, P, (int)G, wn, part);
         }
-        GsOut O;
-        const int64_t off = w0 - col_lb;
-        if (out_dev) {
-            O.nnz = o.nnz ? (long long *)o.nnz + off : nullptr;
-            O.sum = o.sum ? o.sum + off : nullptr;
-            O.nnz_rest = o.nnz_rest ? (long long *)o.nnz_rest + off : nullptr;
-            O.sum_rest = o.sum_rest ? o.sum_rest + off : nullptr;
-            O.ld = o.ld;
-        } else {
-            O.nnz = st_nnz; O.sum = st_sum; O.nnz_rest = st_nnz_rest; O.sum_rest = st_sum_rest;
-            O.ld = wn;
-        }
         {
             ProfScope ps(c, KID_GS_FINALIZE);
             const int gy = (int)std::max<int64_t>(1, std::min<int64_t>(G, (8192 + gx - 1) / gx));
             KERNELCHK(c, k_gs_finalize, dim3(gx, gy), dim3(GS_NT), 0, P, (int)G, wn, part, n_part, O);
         }
-        if (!out_dev) {
-            auto down = [&](void *dst, const void *src) { return dst ? planes_to_host(c, (unsigned char *)dst + (size_t)off * 8, o.ld, src, G, wn) : ILLICO_OK; };
-            if ((rc = down(o.nnz, st_nnz)) || (rc = down(o.sum, st_sum)) || (rc = down(o.nnz_rest, st_nnz_rest)) || (rc = down(o.sum_rest, st_sum_rest)))
-                return rc;
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
+        if ((rc = st.finish())) return rc;
     }
     return ILLICO_OK;
 }

@@ -2,7 +2,7 @@
 // the effects against it per (group, gene) (kernels_markers.h; include/illico_hip_markers.h).  A translation unit
 // of its own: the kernels depend on nothing the Wilcoxon routes use.  They have no profiled kernel id: callers time the call with
 // stream events.
-#include "engine.h"
+#include "plane_stage.h"
 #include "../../include/illico_hip_markers.h"
 #include "kernels_markers.h"
 
@@ -57,81 +57,35 @@ int mk_run(illico_ctx *c, const CombineArgs &a) {
     // device bytes per column of a batch: the staged planes of host input, the staged outputs of host planes
     const size_t b_in = in_dev ? 0 : (size_t)(1 + ne) * KK * 8, b_skip = (in_dev || !a.skip) ? 0 : 4;
     const size_t b_out = out_dev ? 0 : (size_t)(1 + ne) * K * 8, b_rep = out_dev ? 0 : (size_t)K * 4;
-    const size_t per_col = b_in + b_out + b_rep + b_skip;
-    int64_t batch = W;
-    if (per_col) batch = std::max<int64_t>(1, std::min<int64_t>(W, (int64_t)((size_t)std::max<int64_t>(c->scratch_bytes, 1) / per_col)));
     int rc;
     u64 *d_err;
     if ((rc = scratch(c, "mk_err", 2, &d_err))) return rc;
-    unsigned char *work = nullptr;
-    if (per_col && (rc = scratch(c, "mk_work", per_col * (size_t)batch, &work))) return rc;
-    double *s_in = (double *)work;                               // [1 + ne][K][K][batch]
-    double *s_out = (double *)(work + b_in * batch);             // [1 + ne][K][batch]
-    int *s_rep = (int *)(work + (b_in + b_out) * batch);         // [K][batch]
-    u32 *s_skip = (u32 *)(work + (b_in + b_out + b_rep) * batch); // [batch]
+    StageWindows sw;
+    if ((rc = plan_stage_windows(c, W, b_in + b_out + b_rep + b_skip, kNoWindowCap, "mk_work", &sw))) return rc;
 
     // device input is looked at whole before anything is written; host input batch by batch, as it arrives
     if (in_dev && (rc = mk_validate(c, a, a.p, a.in_ld, W, a.skip, 0, false, d_err))) return rc;
-    for (int64_t b0 = 0; b0 < W; b0 += batch) {
-        const int64_t wb = std::min<int64_t>(batch, W - b0);
+    const bool preload = a.skip != nullptr; // with skipped columns the caller's planes go up first: those columns come back as they were
+    for (int64_t b0 = 0; b0 < W; b0 += sw.WW) {
+        const int64_t wb = std::min<int64_t>(sw.WW, W - b0);
+        PlaneStage st(c, sw.block, b0, wb);
         MkParams P{};
         P.K = (int)K;
         P.W = wb;
         P.rank_j = (int)a.rank_j;
-        if (in_dev) {
-            P.p = a.p + b0;
-            for (int k = 0; k < kMaxEffects; ++k) P.e[k] = a.e[k] ? a.e[k] + b0 : nullptr;
-            P.in_ld = a.in_ld;
-            P.skip = a.skip ? a.skip + b0 : nullptr;
-        } else {
-            double *dst = s_in;
-            HIPCHK(c, hipMemcpy2DAsync(dst, (size_t)batch * 8, a.p + b0, (size_t)a.in_ld * 8, (size_t)wb * 8, (size_t)KK, hipMemcpyHostToDevice, c->stream));
-            P.p = dst;
-            for (int k = 0; k < kMaxEffects; ++k) {
-                if (!a.e[k]) continue;
-                dst += (size_t)KK * batch;
-                HIPCHK(c, hipMemcpy2DAsync(dst, (size_t)batch * 8, a.e[k] + b0, (size_t)a.in_ld * 8, (size_t)wb * 8, (size_t)KK, hipMemcpyHostToDevice, c->stream));
-                P.e[k] = dst;
-            }
-            P.in_ld = batch;
-            if (a.skip) {
-                HIPCHK(c, hipMemcpyAsync(s_skip, a.skip + b0, (size_t)wb * 4, hipMemcpyHostToDevice, c->stream));
-                P.skip = s_skip;
-            }
-            if ((rc = mk_validate(c, a, P.p, P.in_ld, wb, P.skip, b0, true, d_err))) return rc;
-        }
-        if (out_dev) {
-            P.out_p = a.out_p + b0;
-            P.out_rep = a.out_rep + b0;
-            for (int k = 0; k < kMaxEffects; ++k) P.o[k] = a.e[k] ? a.o[k] + b0 : nullptr;
-            P.out_ld = a.out_ld;
-        } else {
-            // with skipped columns the caller's planes go up first: those columns come back as they were
-            double *dst = s_out;
-            P.out_p = dst;
-            P.out_rep = s_rep;
-            P.out_ld = batch;
-            if (a.skip) {
-                HIPCHK(c, hipMemcpy2DAsync(dst, (size_t)batch * 8, a.out_p + b0, (size_t)a.out_ld * 8, (size_t)wb * 8, (size_t)K, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipMemcpy2DAsync(s_rep, (size_t)batch * 4, a.out_rep + b0, (size_t)a.out_ld * 4, (size_t)wb * 4, (size_t)K, hipMemcpyHostToDevice, c->stream));
-            }
-            for (int k = 0; k < kMaxEffects; ++k) {
-                if (!a.e[k]) continue;
-                dst += (size_t)K * batch;
-                P.o[k] = dst;
-                if (a.skip)
-                    HIPCHK(c, hipMemcpy2DAsync(dst, (size_t)batch * 8, a.o[k] + b0, (size_t)a.out_ld * 8, (size_t)wb * 8, (size_t)K, hipMemcpyHostToDevice, c->stream));
-            }
-        }
+        P.p = st.in(a.p, a.in_ld, KK, in_dev);
+        for (int k = 0; k < kMaxEffects; ++k) P.e[k] = st.in(a.e[k], a.in_ld, KK, in_dev);
+        P.in_ld = st.pitch(a.in_ld, in_dev);
+        P.skip = st.in(a.skip, W, 1, in_dev);
+        if (st.rc) return st.rc;
+        if (!in_dev && (rc = mk_validate(c, a, P.p, P.in_ld, wb, P.skip, b0, true, d_err))) return rc;
+        P.out_p = st.out(a.out_p, a.out_ld, K, out_dev, preload);
+        for (int k = 0; k < kMaxEffects; ++k) P.o[k] = st.out(a.e[k] ? a.o[k] : nullptr, a.out_ld, K, out_dev, preload);
+        P.out_rep = st.out(a.out_rep, a.out_ld, K, out_dev, preload);
+        P.out_ld = st.pitch(a.out_ld, out_dev);
+        if (st.rc) return st.rc;
         if ((rc = mk_launch(c, P, a.method))) return rc;
-        if (!out_dev) {
-            HIPCHK(c, hipMemcpy2DAsync(a.out_p + b0, (size_t)a.out_ld * 8, P.out_p, (size_t)batch * 8, (size_t)wb * 8, (size_t)K, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpy2DAsync(a.out_rep + b0, (size_t)a.out_ld * 4, P.out_rep, (size_t)batch * 4, (size_t)wb * 4, (size_t)K, hipMemcpyDeviceToHost, c->stream));
-            for (int k = 0; k < kMaxEffects; ++k)
-                if (a.e[k])
-                    HIPCHK(c, hipMemcpy2DAsync(a.o[k] + b0, (size_t)a.out_ld * 8, P.o[k], (size_t)batch * 8, (size_t)wb * 8, (size_t)K, hipMemcpyDeviceToHost, c->stream));
-        }
-        if (!in_dev || !out_dev) HIPCHK(c, hipStreamSynchronize(c->stream)); // (the staging buffers are reused by the next batch)
+        if ((rc = st.finish())) return rc;
     }
     return ILLICO_OK;
 }

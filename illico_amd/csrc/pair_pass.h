@@ -1,6 +1,6 @@
 // Host scaffolding of the all-pairs families -- pairwise.hip, pairwise_ranked.hip, and nothing else -- on top of group_pass.h: the
-// selection of the K groups to compare with its checks and its upload, and the staging of a host caller's `sums` plane and of its
-// three or four [K*K][W] result planes.  The limits on K, the scratch buffers (names, sizes, budget), the kernels and the points at
+// selection of the K groups to compare with its checks and its upload, and the staging of a host caller's `sums` plane (its three
+// or four [K*K][W] result planes go through a PlaneStage, preloaded).  The limits on K, the scratch buffers (names, sizes, budget), the kernels and the points at
 // which the stream is synchronised are each family's own.
 #pragma once
 #include "group_pass.h"
@@ -42,34 +42,7 @@ inline int upload_pair_selection(illico_ctx *c, const PairSelection &S, long lon
 inline int stage_pair_sums(illico_ctx *c, const double *sums, int64_t sums_ld, int64_t G, int64_t W, void *scratch, const double **d_sums, int64_t *d_sums_ld) {
     *d_sums = (const double *)scratch;
     *d_sums_ld = W;
-    return planes_to_device(c, scratch, sums, sums_ld, G, W);
+    return copy_plane(c, scratch, W, sums, sums_ld, G, W, 8, hipMemcpyHostToDevice);
 }
-
-// The result planes (out[3] may be null) as the kernels write them: a device caller's own; a host caller's packed one after the other
-// in `scratch`, n_out * KK * W doubles the caller obtained.  Those go up first, so that the columns of the genes a route leaves come
-// back as they were, and down() brings them back (enqueued; the caller synchronises).
-struct PairOutputs {
-    double *host[4], *d_out[4];
-    int64_t host_ld, d_out_ld, KK, W;
-    int n_out;
-    bool out_dev;
-    int up(illico_ctx *c, double *const out[4], int64_t out_ld, int64_t KK_, int64_t W_, bool out_dev_, void *scratch) {
-        host_ld = d_out_ld = out_ld; KK = KK_; W = W_; out_dev = out_dev_;
-        n_out = out[3] ? 4 : 3;
-        for (int k = 0; k < 4; ++k) host[k] = d_out[k] = out[k];
-        if (out_dev) return ILLICO_OK;
-        d_out_ld = W;
-        for (int k = 0; k < n_out; ++k) {
-            d_out[k] = (double *)scratch + (size_t)k * KK * W;
-            if (int rc = planes_to_device(c, d_out[k], host[k], host_ld, KK, W)) return rc;
-        }
-        return ILLICO_OK;
-    }
-    int down(illico_ctx *c) const {
-        for (int k = 0; k < (out_dev ? 0 : n_out); ++k)
-            if (int rc = planes_to_host(c, host[k], host_ld, d_out[k], KK, W)) return rc;
-        return ILLICO_OK;
-    }
-};
 
 } // namespace

@@ -47,7 +47,6 @@ extern "C" int illico_pair_ttest_from_moments(illico_ctx *c, const double *sum, 
     if ((rc = resolve_pending(c))) return rc; // a plane written under ILLICO_FLAG_DEFER is complete only after its leftover genes
     if (W == 0) return ILLICO_OK;
     const bool in_dev = flags & ILLICO_FLAG_INPUT_DEVICE, out_dev = flags & ILLICO_FLAG_OUTPUT_DEVICE;
-    const double *const ins[3] = {sum, sumsq, fsum};
     const int n_in = fsum ? 3 : 2;
     const int64_t KK = K * K;
 
@@ -55,46 +54,23 @@ extern "C" int illico_pair_ttest_from_moments(illico_ctx *c, const double *sum, 
     if ((rc = scratch(c, "pt_sel", (size_t)K, &d_sel))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_sel, sel, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
     // column windows under the scratch cap (host planes are staged)
-    const size_t per_col = (in_dev ? 0 : (size_t)G * 8 * n_in) + (out_dev ? 0 : (size_t)KK * 8 * n_out);
-    const int64_t cap = (int64_t)1 << 24;
-    const int64_t WW = per_col ? std::max<int64_t>(1, std::min<int64_t>({W, cap, (int64_t)((size_t)std::max<int64_t>(c->scratch_bytes, 1) / per_col)}))
-                               : std::min<int64_t>(W, cap);
-    unsigned char *stage = nullptr;
-    if (per_col && (rc = scratch(c, "pt_stage", (size_t)WW * per_col + 64, &stage))) return rc;
+    StageWindows sw;
+    if ((rc = plan_stage_windows(c, W, (in_dev ? 0 : (size_t)G * 8 * n_in) + (out_dev ? 0 : (size_t)KK * 8 * n_out), (int64_t)1 << 24, "pt_stage", &sw))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the selection came from pageable host memory)
-    for (int64_t w0 = 0; w0 < W; w0 += WW) {
-        const int wn = (int)std::min<int64_t>(WW, W - w0);
+    for (int64_t w0 = 0; w0 < W; w0 += sw.WW) {
+        const int wn = (int)std::min<int64_t>(sw.WW, W - w0);
+        PlaneStage st(c, sw.block, w0, wn);
         PtParams T;
         T.K = (int)K; T.W = wn; T.n_tiles = (int)n_tiles; T.variant = variant; T.alternative = alternative;
         T.counts = c->d_counts; T.sel = d_sel;
-        unsigned char *s = stage;
-        const double *din[3] = {nullptr, nullptr, nullptr};
-        for (int k = 0; k < 3; ++k) {
-            if (!ins[k]) continue;
-            if (in_dev) din[k] = ins[k] + w0;
-            else {
-                if ((rc = planes_to_device(c, s, ins[k] + w0, in_ld, G, wn))) return rc;
-                din[k] = (const double *)s;
-                s += (size_t)G * wn * 8;
-            }
-        }
-        T.S = din[0]; T.Q = din[1]; T.F = din[2];
-        T.in_ld = in_dev ? in_ld : wn;
-        double *st[PT_N_OUT];
-        for (int k = 0; k < PT_N_OUT; ++k) {
-            st[k] = nullptr;
-            if (!outs[k]) { T.out[k] = nullptr; continue; }
-            if (out_dev) T.out[k] = outs[k] + w0;
-            else { st[k] = (double *)s; T.out[k] = st[k]; s += (size_t)KK * wn * 8; }
-        }
-        T.out_ld = out_dev ? out_ld : wn;
+        T.S = st.in(sum, in_ld, G, in_dev); T.Q = st.in(sumsq, in_ld, G, in_dev); T.F = st.in(fsum, in_ld, G, in_dev);
+        T.in_ld = st.pitch(in_ld, in_dev);
+        for (int k = 0; k < PT_N_OUT; ++k) T.out[k] = st.out(outs[k], out_ld, KK, out_dev, false);
+        T.out_ld = st.pitch(out_ld, out_dev);
+        if (st.rc) return st.rc;
         const int64_t gx = (wn + PT_TILE - 1) / PT_TILE;
         KERNELCHK(c, k_pair_ttest, dim3((unsigned)gx, (unsigned)tile_pairs, (unsigned)pt_split(c, gx, tile_pairs)), dim3(PT_NT), 0, T);
-        if (!out_dev) {
-            for (int k = 0; k < PT_N_OUT; ++k)
-                if (outs[k] && (rc = planes_to_host(c, outs[k] + w0, out_ld, st[k], KK, wn))) return rc;
-        }
-        if (!in_dev || !out_dev) HIPCHK(c, hipStreamSynchronize(c->stream)); // (the staging area is reused by the next window; host planes complete on return)
+        if ((rc = st.finish())) return rc;
     }
     return ILLICO_OK;
 }

@@ -188,10 +188,11 @@ extern "C" int illico_pairwise_from_hists(illico_ctx *c, const uint32_t *H, cons
         d_H = (const u32 *)u; d_flags = (const u32 *)(u + h_bytes);
     }
     double *const outs[4] = {out_p, out_u, out_fc, out_z};
-    PairOutputs O; // the caller's planes go up first: the columns of flagged genes come back as they were
-    double *stage_out = nullptr;
+    double *stage_out = nullptr, *d_out[4];
     if (!out_dev && (rc = scratch(c, "pw_stage_out", plane / 8 * n_out + 8, &stage_out))) return rc;
-    if ((rc = O.up(c, outs, out_ld, K * K, W, out_dev, stage_out))) return rc;
+    PlaneStage st(c, stage_out, 0, W);
+    for (int k = 0; k < 4; ++k) d_out[k] = st.out(outs[k], out_ld, K * K, out_dev, true); // preloaded: the columns of flagged genes come back as they were
+    if (st.rc) return st.rc;
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the selection and the staged arrays came from pageable host memory)
     PwParams P;
     P.T = T; P.gene_flags = d_flags; P.n = d_n; P.sel = d_sel; P.sums = d_sums; P.sums_ld = d_sums_ld;
@@ -199,7 +200,7 @@ extern "C" int illico_pairwise_from_hists(illico_ctx *c, const uint32_t *H, cons
     P.use_continuity = (flags & ILLICO_FLAG_CONTINUITY) ? 1 : 0;
     P.tie_correct = (flags & ILLICO_FLAG_TIE_CORRECT) ? 1 : 0;
     P.alternative = alternative;
-    P.out_p = O.d_out[0]; P.out_u = O.d_out[1]; P.out_fc = O.d_out[2]; P.out_z = O.d_out[3]; P.out_ld = O.d_out_ld;
+    P.out_p = d_out[0]; P.out_u = d_out[1]; P.out_fc = d_out[2]; P.out_z = d_out[3]; P.out_ld = st.pitch(out_ld, out_dev);
     {
         ProfScope ps(c, KID_PW_PAIRS);
         KERNELCHK(c, k_pw_transpose<false>, dim3(tiles, (unsigned)K), dim3(PW_NT), 0, const_cast<u32 *>(d_H), T, (const int *)d_sel, wn, tiles);
@@ -207,7 +208,5 @@ extern "C" int illico_pairwise_from_hists(illico_ctx *c, const uint32_t *H, cons
         if (out_z) KERNELCHK(c, k_pw_pairs<true>, grid, dim3(PW_NT), 0, P);
         else KERNELCHK(c, k_pw_pairs<false>, grid, dim3(PW_NT), 0, P);
     }
-    if ((rc = O.down(c))) return rc;
-    if (!out_dev) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ILLICO_OK;
+    return st.finish();
 }

@@ -84,14 +84,13 @@ int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub
         if ((rc = scratch(c, "pwr_sums", s_bytes / 8, &sums_stage))) return rc;
         if ((rc = stage_pair_sums(c, a.sums, a.sums_ld, G, W, sums_stage, &d_sums, &d_sums_ld))) return rc;
     }
-    PairOutputs O; // the caller's planes go up first: the columns of genes that leave come back as they were
-    u32 *d_left = a.out_left;
     unsigned char *stage_out = nullptr;
-    if (!out_dev) {
-        if ((rc = scratch(c, "pwr_stage_out", plane * n_out + (size_t)W * 4, &stage_out))) return rc;
-        d_left = (u32 *)((double *)stage_out + (size_t)n_out * KK * W);
-    }
-    if ((rc = O.up(c, a.out, a.out_ld, KK, W, out_dev, stage_out))) return rc;
+    if (!out_dev && (rc = scratch(c, "pwr_stage_out", plane * n_out + (size_t)W * 4, &stage_out))) return rc;
+    PlaneStage st(c, stage_out, 0, W);
+    double *d_out[4];
+    for (int k = 0; k < 4; ++k) d_out[k] = st.out(a.out[k], a.out_ld, KK, out_dev, true); // preloaded: the columns of genes that leave come back as they were
+    u32 *d_left = st.out(a.out_left, W, 1, out_dev, false);
+    if (st.rc) return st.rc;
     SparseOnDevice sp{};
     int64_t sp_c0 = 0; // column col_lb in sp.indptr
     if (in.sparse) {
@@ -151,16 +150,15 @@ int pwr_run(illico_ctx *c, const MatrixInput &in, int64_t col_lb, int64_t col_ub
             E.s2 = s2; E.tie = tie; E.left = d_left + b0; E.n = d_n; E.sel = d_sel; E.sums = d_sums; E.sums_ld = d_sums_ld; E.K = (int)K; E.nb = nb;
             E.col_off = b0; E.use_continuity = (a.flags & ILLICO_FLAG_CONTINUITY) ? 1 : 0; E.tie_correct = (a.flags & ILLICO_FLAG_TIE_CORRECT) ? 1 : 0;
             E.alternative = a.alternative;
-            E.out_p = O.d_out[0]; E.out_u = O.d_out[1]; E.out_fc = O.d_out[2]; E.out_z = O.d_out[3]; E.out_ld = O.d_out_ld;
+            E.out_p = d_out[0]; E.out_u = d_out[1]; E.out_fc = d_out[2]; E.out_z = d_out[3]; E.out_ld = st.pitch(a.out_ld, out_dev);
             const dim3 grid((unsigned)((nb + 63) / 64), (unsigned)((KK + PWE_PAIRS - 1) / PWE_PAIRS));
             ProfScope ps(c, KID_PW_RANK_EMIT);
-            if (O.d_out[3]) KERNELCHK(c, k_pw_rank_emit<true>, grid, dim3(PWE_NT), 0, E);
+            if (d_out[3]) KERNELCHK(c, k_pw_rank_emit<true>, grid, dim3(PWE_NT), 0, E);
             else KERNELCHK(c, k_pw_rank_emit<false>, grid, dim3(PWE_NT), 0, E);
         }
     }
-    if ((rc = O.down(c))) return rc;
-    if (!out_dev) HIPCHK(c, hipMemcpyAsync(a.out_left, d_left, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
-    if (!out_dev || !in_dev) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = st.finish())) return rc;
+    if (out_dev && !in_dev) HIPCHK(c, hipStreamSynchronize(c->stream));
     return ILLICO_OK;
 }
 

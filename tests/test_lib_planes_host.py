@@ -1,5 +1,5 @@
-"""The plane helpers of illico_amd._lib (_plane, _plane_set, _pair_selection, _pair_planes, Engine._outputs) and its signature table, on numpy arrays and CPU
-tensors: they need neither the library nor a device."""
+"""The plane helpers of illico_amd._lib (_plane, _plane_set, _pair_selection, _pair_planes, Engine._outputs; _stacked_rows, _hists_input,
+_moment_planes, _sums_arg) and its signature table, on numpy arrays and CPU tensors: they need neither the library nor a device."""
 import ctypes
 import re
 
@@ -221,3 +221,103 @@ def test_ex_signature_is_the_plain_one_with_one_more_plane(plain):
     args, restype = _lib.SIGNATURES[plain]
     assert _lib.SIGNATURES[plain + "_ex"] == (args[:-1] + [ctypes.c_void_p] + args[-1:], restype)
 
+
+
+# ---- the checks the plane-to-plane entry points share ----
+def test_stacked_rows_is_a_view_of_the_block_and_of_its_first_columns():
+    block = np.arange(2 * 3 * 8, dtype=np.float64).reshape(2, 3, 8)
+    for x, W in ((block, 8), (block[:, :, :5], 5)):
+        rows = _lib._stacked_rows(x, "x")
+        assert rows.shape == (6, W) and np.shares_memory(rows, block) and rows.ctypes.data == block.ctypes.data
+        assert np.array_equal(rows, x.reshape(6, W)) and _lib._plane(rows, "x").pitch == 8
+    t = torch.arange(2 * 3 * 8, dtype=torch.float64).reshape(2, 3, 8)
+    rows = _lib._stacked_rows(t[:, :, :5], "t")
+    assert tuple(rows.shape) == (6, 5) and rows.data_ptr() == t.data_ptr() and torch.equal(rows, t[:, :, :5].reshape(6, 5))
+    assert _lib._stacked_rows(block[:1, ::2], "x").shape == (2, 8)    # one stack: any row stride
+
+
+def test_stacked_rows_refusals():
+    block = np.zeros((4, 3, 8))
+    for bad in (block[::2], block[:, :2], block[:, ::2], block.transpose(1, 0, 2), torch.zeros(4, 3, 8)[:, :2]):
+        with pytest.raises(ValueError, match="one row stride apart"):
+            _lib._stacked_rows(bad, "x")
+    for bad in (np.zeros((3, 8)), np.zeros((2, 2, 2, 2))):
+        with pytest.raises(ValueError, match="three dimensions"):
+            _lib._stacked_rows(bad, "x")
+
+
+def test_pairs_as_rows_is_stacked_rows_of_a_square_stack():
+    x = np.arange(3 * 3 * 6, dtype=np.float64).reshape(3, 3, 6)[:, :, :4]
+    K, W, rows = _lib._pairs_as_rows(x, "p")
+    assert (K, W) == (3, 4) and np.array_equal(rows, x.reshape(9, 4)) and np.shares_memory(rows, x)
+    for bad in (np.zeros((2, 3, 4)), np.zeros((3, 4)), [[[0.0]]]):
+        with pytest.raises(ValueError):
+            _lib._pairs_as_rows(bad, "p")
+
+
+def test_hists_input_accepts_host_arrays_of_any_integer_type():
+    H, flags = np.arange(2 * 3 * 256, dtype=np.int64).reshape(2, 3, 256), [0, 1, 0]
+    H2, f2, rows, W, on_dev = _lib._hists_input(H, flags, "G")
+    assert (rows, W, on_dev) == (2, 3, False) and H2.dtype == f2.dtype == np.uint32 and H2.flags.c_contiguous
+    assert np.array_equal(H2, H) and f2.tolist() == flags
+    Hu = H.astype(np.uint32)
+    assert _lib._hists_input(Hu, np.zeros(3, np.uint32), "G")[0] is Hu    # as it is
+    assert _lib._hists_input(Hu, np.zeros(3, np.uint32), "G", np.zeros((2, 3)), "H, flags and sums")[2:] == (2, 3, False)
+
+
+def test_hists_input_refusals():
+    H, flags = np.zeros((2, 3, 256), np.uint32), np.zeros(3, np.uint32)
+    with pytest.raises(ValueError, match=r"H must be \[G \* B, W, 256\]$"):
+        _lib._hists_input(H[0], flags, "G * B")
+    for bad_H, bad_f in ((np.zeros((2, 3, 255), np.uint32), flags), (H, np.zeros(4, np.uint32)), (H, np.zeros((3, 1), np.uint32))):
+        with pytest.raises(ValueError, match=r"H must be \[G, W, 256\] and flags \[W\], got"):
+            _lib._hists_input(bad_H, bad_f, "G")
+    with pytest.raises(ValueError, match="^H and flags must live on the same side"):
+        _lib._hists_input(torch.zeros(2, 3, 256, dtype=torch.int32), flags, "G")
+    with pytest.raises(ValueError, match="^H, flags and sums must live on the same side"):
+        _lib._hists_input(H, flags, "G", torch.zeros(2, 3, dtype=torch.float64), "H, flags and sums")
+    with pytest.raises(ValueError, match="contiguous 32-bit integer CUDA tensors"):   # tensors, but not on a device
+        _lib._hists_input(torch.zeros(2, 3, 256, dtype=torch.int32), torch.zeros(3, dtype=torch.int32), "G")
+
+
+def test_moment_planes_accepted_forms():
+    S, Q = np.arange(12, dtype=np.float64).reshape(3, 4), np.ones((3, 4))
+    ins, G, W, on_dev, ptrs, ld = _lib._moment_planes((("sum", S), ("sumsq", Q), ("fsum", None)), ("sum", "sumsq"), 3)
+    assert (G, W, on_dev, ld) == (3, 4, False, 4) and ptrs == [S.ctypes.data, Q.ctypes.data, None]
+    assert ins[0].array is S and ins[1].array is Q and ins[2] is None
+    wide = np.zeros((3, 2, 9))
+    ins, G, W, _, ptrs, ld = _lib._moment_planes((("sum", wide[:, 0, 2:6]), ("sumsq", wide[:, 1, 2:6])), ("sum", "sumsq"), 3)   # one pitch: as they are
+    assert ld == 18 and ptrs == [wide.ctypes.data + 16, wide.ctypes.data + 16 + 72]
+    ins, G, W, _, ptrs, ld = _lib._moment_planes((("sum", S), ("sumsq", wide[:, 1, 2:6])), ("sum", "sumsq"), 3)   # two pitches: made contiguous
+    assert ld == 4 and all(q.array.flags.c_contiguous for q in ins) and np.array_equal(ins[0].array, S)
+    ins, _, _, _, _, ld = _lib._moment_planes((("sum", S[:, ::2]), ("sumsq", Q[:, ::2])), ("sum", "sumsq"), 3)   # a column stride: copied
+    assert ld == 2 and np.array_equal(ins[0].array, S[:, ::2])
+
+
+def test_moment_planes_refusals():
+    S, Q = np.zeros((3, 4)), np.zeros((3, 4))
+    for planes, n_groups, message in (((("sum", S), ("sumsq", None)), 3, "sum and sumsq are required"),
+                                      ((("sum", None), ("sumsq", Q)), 3, "sum and sumsq are required"),
+                                      ((("sum", S), ("sumsq", np.zeros((3, 5)))), 3, "share one shape"),
+                                      ((("sum", S), ("sumsq", Q), ("fsum", np.zeros((4, 4)))), 3, "share one shape"),
+                                      ((("sum", S), ("sumsq", Q)), 4, "have 3 rows but the engine's groups number 4"),
+                                      ((("sum", S), ("sumsq", Q)), None, "groups number None"),
+                                      ((("sum", S), ("sumsq", Q.astype(np.float32))), 3, "float64"),
+                                      ((("sum", S), ("sumsq", torch.zeros(3, 4, dtype=torch.float64))), 3, "CPU tensor"),
+                                      ((("sum", S), ("sumsq", np.zeros(12))), 3, "2-D")):
+        with pytest.raises(ValueError, match=message):
+            _lib._moment_planes(planes, ("sum", "sumsq"), n_groups)
+
+
+def test_sums_arg():
+    assert _lib._sums_arg(None, (3, 4), False, "H") == (None, None, 0)
+    assert _lib._sums_arg(None, (3, 4), True, "H") == (None, None, 0)
+    wide = np.zeros((3, 9))
+    array, ptr, ld = _lib._sums_arg(wide[:, 2:6], (3, 4), False, "H")
+    assert array.base is wide and (ptr, ld) == (wide.ctypes.data + 16, 9)
+    array, ptr, ld = _lib._sums_arg(wide[:, ::2][:, :4], (3, 4), False, "H")   # a column stride: copied
+    assert array.flags.c_contiguous and (ptr, ld) == (array.ctypes.data, 4)
+    for bad, on_dev, message in ((np.zeros((3, 5)), False, "shape"), (np.zeros((3, 4), np.float32), False, "float64"),
+                                 (torch.zeros(3, 4, dtype=torch.float64), False, "CPU tensor"), (wide[:, :4], True, "sums must live on the side of the matrix")):
+        with pytest.raises(ValueError, match=message):
+            _lib._sums_arg(bad, (3, 4), on_dev, "the matrix")
