@@ -1,5 +1,6 @@
 """A float64 numpy restatement of the blocked Wilcoxon definition (include/illico_hip_blocked.h), and the case
-builders of tests/test_blocked_host.py and tests/test_gpu_blocked.py.
+builders of tests/test_blocked_host.py, tests/test_gpu_blocked.py and their edge-case siblings (tests/test_blocked_edges_host.py,
+tests/test_gpu_blocked_edges.py).
 
 Per block the reference's U and the tie sum come from ``np.unique`` counts; z_b restates ``zscore_device_pre``; the combination is the
 weighted Stouffer sum over the used blocks in ascending block order, finished with ``scipy.special.erfc``.
@@ -56,6 +57,41 @@ def block_stats(X, g_codes, b_codes, G, B, ref=None, is_log1p=False) -> BlockSta
                 tie[g, b, j] = float(int((t * t * t - t).sum()))
                 S_g[g, b, j] = Sb[g, j]
                 S_r[g, b, j] = Sb[ref, j] if ref is not None else Sb[:, j].sum() - Sb[g, j]
+    return BlockStats(used, n_g, n_r, U, tie, S_g, S_r)
+
+
+def stats_from_hists(H, counts, ref=None) -> BlockStats:
+    """The statistics of every test from the value histograms ``H`` ``[G * B, W, 256]`` (compound ``g * B + b``) and the compound sizes
+    ``counts`` ``[G, B]`` alone, in Python integers: S2 (twice the cells of the reference below each cell of g, plus the ties), the tie
+    sum and the value sums are exact at any size; then ``U = 0.5 * float(2 n_r n_g - S2)`` and ``tie = float(TT)``, each rounded once."""
+    counts = np.asarray(counts, dtype=np.int64)
+    G, B = counts.shape
+    H = np.asarray(H)
+    W = H.shape[1]
+    used = np.zeros((G, B), dtype=bool)
+    n_g, n_r = counts.copy(), np.zeros((G, B), dtype=np.int64)
+    U, tie, S_g, S_r = (np.zeros((G, B, W)) for _ in range(4))
+    for b in range(B):
+        for g in range(G):
+            n_r[g, b] = counts[ref, b] if ref is not None else counts[:, b].sum() - counts[g, b]
+            used[g, b] = n_g[g, b] > 0 and n_r[g, b] > 0
+        for j in range(W):
+            h = [[int(x) for x in H[g * B + b, j]] for g in range(G)]
+            tot = [sum(col) for col in zip(*h)]
+            for g in range(G):
+                if not used[g, b]:
+                    continue
+                hg = h[g]
+                hr = h[ref] if ref is not None else [t - a for t, a in zip(tot, hg)]
+                below = S2 = TT = 0
+                for a, r in zip(hg, hr):
+                    S2 += a * (2 * below + r)
+                    below += r
+                    TT += (a + r) ** 3 - (a + r)
+                U[g, b, j] = 0.5 * float(2 * int(n_r[g, b]) * int(n_g[g, b]) - S2)
+                tie[g, b, j] = float(TT)
+                S_g[g, b, j] = float(sum(c * a for c, a in enumerate(hg)))
+                S_r[g, b, j] = float(sum(c * r for c, r in enumerate(hr)))
     return BlockStats(used, n_g, n_r, U, tie, S_g, S_r)
 
 
@@ -157,9 +193,14 @@ def combine_planes(zs, us, row_map, counts, ref=None, alternative="two-sided"):
 Case = namedtuple("Case", "X g_codes b_codes G B")
 
 
-def make_case(G: int, B: int, W: int, seed: int = 0, base: int = 7) -> Case:
+def make_case(G: int, B: int, W: int, seed: int = 0, base: int = 7, values: str = "small") -> Case:
     """Counts 0 .. 5 (float32) for G groups in B blocks of unequal sizes: compound (g, b) holds ``base + 3 b + (g + 2 b) % 4`` cells,
-    in shuffled row order.  Gene ``W // 2`` holds the values 0 and 255 only."""
+    in shuffled row order.  Gene ``W // 2`` holds the values 0 and 255 only.
+
+    ``values="full-range"``: counts 0 .. 255 instead, so that every part of the 256-value walk carries cells; gene 0 holds 248 .. 255
+    only (the last unroll group), gene 1 multiples of 8 (one value in every unroll group), gene ``W // 2`` 0 and 255 as before."""
+    if values not in ("small", "full-range"):
+        raise ValueError(values)
     rng = np.random.RandomState(1000 * G + 100 * B + W + seed)
     g_codes, b_codes = [], []
     for g in range(G):
@@ -171,8 +212,14 @@ def make_case(G: int, B: int, W: int, seed: int = 0, base: int = 7) -> Case:
     perm = rng.permutation(g_codes.size)
     g_codes, b_codes = g_codes[perm], b_codes[perm]
     N = g_codes.size
-    # a shift per (group, gene) keeps the tests from being all alike; values stay within 0 .. 5
-    X = rng.randint(0, 4, size=(N, W)) + (rng.rand(G, W) < 0.3)[g_codes] * rng.randint(0, 3, size=(N, W))
+    if values == "full-range":
+        X = rng.randint(0, 256, size=(N, W))
+        X[:, 0] = rng.randint(248, 256, size=N)
+        if W > 1:
+            X[:, 1] = 8 * rng.randint(0, 32, size=N)
+    else:
+        # a shift per (group, gene) keeps the tests from being all alike; values stay within 0 .. 5
+        X = rng.randint(0, 4, size=(N, W)) + (rng.rand(G, W) < 0.3)[g_codes] * rng.randint(0, 3, size=(N, W))
     X[:, W // 2] = 255 * (rng.rand(N) < 0.5)
     return Case(X.astype(np.float32), g_codes, b_codes, G, B)
 
@@ -182,12 +229,16 @@ def labels_of(codes, prefix: str) -> np.ndarray:
     return np.array([f"{prefix}{int(c):03d}" for c in codes])
 
 
-def edge_case(kind: str, W: int = 5) -> Case:
-    """The blocks that do not count (tests/test_gpu_blocked.py, case 4).  Group 0 is the reference of the reference-mode tests.
+def edge_case(kind: str, W: int = 5, ref: int = 0) -> Case:
+    """The blocks that do not count (tests/test_gpu_blocked.py, case 4).  Group ``ref`` is the reference of the reference-mode tests:
+    the cases are stated below for ``ref = 0``, and another ``ref`` rotates the roles of the groups, ``g -> (g + ref) % G``, over the
+    same rows and values.
 
     ``group-absent``: group 2 has no cells in block 1.  ``reference-absent``: group 0 has none in block 2.  ``no-shared-block``: group 3
     lives in block 3 alone, where group 0 has no cells.  ``one-against-one``: block 1 holds one cell of group 1 and one of group 0 (and
-    nothing else).  ``constant-block``: gene 1 is constant in block 0.  ``constant-gene``: gene 2 is constant everywhere."""
+    nothing else).  ``constant-block``: gene 1 is constant in block 0.  ``constant-gene``: gene 2 is constant everywhere.
+    ``below-reference-absent``: group 3 -- after the rotation group ``ref - 1``, the one just below the reference -- has no cells in
+    block 1, where the reference has: in that block the reference's row among the groups present is not ``ref``."""
     rng = np.random.RandomState(sum(map(ord, kind)))
     G, B = 4, 4
     sizes = np.array([[6 + (g + 2 * b) % 5 for b in range(B)] for g in range(G)])
@@ -201,8 +252,12 @@ def edge_case(kind: str, W: int = 5) -> Case:
     elif kind == "one-against-one":
         sizes[:, 1] = 0
         sizes[0, 1] = sizes[1, 1] = 1
+    elif kind == "below-reference-absent":
+        sizes[3, 1] = 0
     elif kind not in ("constant-block", "constant-gene"):
         raise ValueError(kind)
+    if not 0 <= ref < G:
+        raise ValueError(ref)
     g_codes = np.repeat(np.repeat(np.arange(G), B), sizes.reshape(-1))
     b_codes = np.repeat(np.tile(np.arange(B), G), sizes.reshape(-1))
     perm = rng.permutation(g_codes.size)
@@ -212,4 +267,41 @@ def edge_case(kind: str, W: int = 5) -> Case:
         X[b_codes == 0, 1] = 3
     if kind == "constant-gene":
         X[:, 2] = 2
-    return Case(X.astype(np.float32), g_codes, b_codes, G, B)
+    return Case(X.astype(np.float32), (g_codes + ref) % G, b_codes, G, B)
+
+
+LIMIT_CELLS = 2097151  # the largest test illico_blocked_from_hists accepts (n_g + n_r of one block)
+
+
+def limit_case(mode: str):
+    """``(H uint32 [6, 4, 256], flags uint32 [4], counts int64 [3, 2], ref)``: synthetic histograms of G = 3 groups in B = 2 blocks whose
+    largest test holds ``LIMIT_CELLS`` cells, for the C entry points -- no matrix of that size is needed.
+
+    ``"reference"``: ref = 1 and the test of group 0 in block 0 has 1048576 + 1048575 cells.  ``"rest"``: ref = None and block 0 holds
+    1048576 + 1048570 + 5 cells.  Every compound's histogram row sums to its count.  In block 0 gene 0 has all cells in bin 255 (the
+    largest tie sum there is, n^3 - n < 2^63, and z_b = 0); gene 1 bins 0 and 255 only, group 0 with n / 2 + 3000 cells in bin 255 and
+    every other group split evenly (the odd cell in bin 0): z_b of about 4; gene 2 a multinomial draw over the 256 bins per compound.
+    Block 1 holds 7, 9 and 11 cells: gene 0 constant (bin 0), genes 1 and 2 drawn over the whole range.  Gene 3 is flagged and its
+    words are 0xFFFFFFFF: nothing may read them."""
+    if mode == "reference":
+        counts, ref = np.array([[1048576, 7], [1048575, 9], [5, 11]], dtype=np.int64), 1
+    elif mode == "rest":
+        counts, ref = np.array([[1048576, 7], [1048570, 9], [5, 11]], dtype=np.int64), None
+    else:
+        raise ValueError(mode)
+    G, B, W = 3, 2, 4
+    rng = np.random.RandomState(0)
+    H = np.zeros((G * B, W, 256), dtype=np.uint32)
+    for g in range(G):
+        for b in range(B):
+            n, row = int(counts[g, b]), H[g * B + b]
+            if b == 0:
+                row[0, 255] = n
+                row[1, 255] = n // 2 + (3000 if g == 0 else 0)
+                row[1, 0] = n - int(row[1, 255])
+            else:
+                row[0, 0] = n
+                row[1] = rng.multinomial(n, [1.0 / 256] * 256)
+            row[2] = rng.multinomial(n, [1.0 / 256] * 256)
+            row[3] = 0xFFFFFFFF
+    return H, np.array([0, 0, 0, 1], dtype=np.uint32), counts, ref
