@@ -11,6 +11,7 @@ import numpy as np
 import pandas as pd
 
 from illico_amd import _lib
+from illico_amd._passes import METHODS, _method, adjust_and_cut, check_bool, check_corr_method, check_n_genes, cut_rows  # noqa: F401
 from illico_amd.asymptotic_wilcoxon import _planes_frame, _wilcoxon_planes
 
 __all__ = ["adjust_pvalues", "differential_expression", "top_by_score"]
@@ -21,17 +22,6 @@ RANK_BY = ("p_value", "z_score")
 RANK_BY_TTEST = ("p_value", "statistic")
 #: the tests ``differential_expression`` runs (scanpy's names) -> the variant of ``welch_ttest``, None for the Wilcoxon engine
 DE_METHODS = {"wilcoxon": None, "t-test": "welch", "t-test_overestim_var": "overestim_var"}
-
-#: method names -> the engine's codes (include/illico_hip.h: ILLICO_ADJ_*)
-METHODS = {"bh": "bh", "benjamini-hochberg": "bh", "by": "by", "benjamini-yekutieli": "by", "bonferroni": "bonferroni"}
-
-
-def _method(name) -> str:
-    try:
-        return METHODS[name.lower()]
-    except (KeyError, AttributeError):
-        raise ValueError(f"Unknown p-value correction method {name!r}: one of {sorted(METHODS)}") from None
-
 
 def adjust_pvalues(p, method: str = "benjamini-hochberg", *, n_top: int = 0):
     """Adjust each row of a p-value plane for multiple testing.
@@ -98,90 +88,43 @@ def differential_expression(adata, is_log1p: bool, group_keys: str, reference: s
     ``ValueError``; ``use_continuity`` / ``tie_correct`` mean nothing to a t-test and raise ``TypeError``; ``n_threads``,
     ``batch_size`` and ``precompile`` are accepted and ignored.
     """
-    code = _method(corr_method)
+    code = check_corr_method(corr_method)
     if not isinstance(method, str) or method not in DE_METHODS:
         raise ValueError(f"method must be one of {tuple(DE_METHODS)}, got {method!r}")
-    if DE_METHODS[method] is not None:
-        return _differential_expression_ttest(adata, is_log1p, group_keys, reference, code, n_genes, pts, scores, rank_by,
-                                              DE_METHODS[method], kw)
-    if not isinstance(pts, (bool, np.bool_)):
-        raise ValueError(f"pts must be a bool, got {pts!r}")
-    if not isinstance(scores, (bool, np.bool_)):
-        raise ValueError(f"scores must be a bool, got {scores!r}")
-    if not isinstance(rank_by, str) or rank_by not in RANK_BY:
-        raise ValueError(f"rank_by must be one of {RANK_BY}, got {rank_by!r}")
-    by_z = rank_by == "z_score"
-    scores = bool(scores) or by_z
-    if n_genes is not None and (isinstance(n_genes, bool) or not isinstance(n_genes, (int, np.integer)) or n_genes < 1):
-        raise ValueError(f"n_genes must be a positive integer or None, got {n_genes!r}")
-    unknown = set(kw) - {"n_threads", "batch_size", "alternative", "use_continuity", "tie_correct", "layer", "precompile"}
-    if unknown:
-        raise TypeError(f"differential_expression() got unexpected keyword arguments {sorted(unknown)}")
-    args = dict(n_threads=1, batch_size="auto", alternative="two-sided", use_continuity=True, tie_correct=True, layer=None)
-    args.update({k: v for k, v in kw.items() if k != "precompile"})
-    inputs: list = []
-    planes, index = _wilcoxon_planes(adata, is_log1p, group_keys, reference, **args, inputs=inputs, scores=scores)
-    G, M = planes.shape[1], planes.shape[2]
-    n_top = min(int(n_genes), M) if n_genes is not None else 0
-    if G and M:
-        eng = _lib.get_engine()
-        res = eng.adjust_pvalues(planes[0], code, n_top=0 if by_z else n_top)
-        adj, top = res if (n_top and not by_z) else (res, None)
-        if n_top and by_z:
-            top = eng.top_by_score(planes[3], n_top)
-    else:
-        adj, top = np.empty((G, M), dtype=np.float64), np.empty((G, 0), dtype=np.int64)
-    extra = {"z_score": planes[3]} if scores else {}
-    if pts:
-        from illico_amd.group_stats import stat_planes
-        X, handler, group_container = inputs[0]
-        extra.update(stat_planes(X, handler, group_container, bool(is_log1p)))
-    df = _planes_frame(planes[:3], index, p_value_adj=adj, **extra)
-    if n_genes is None:
-        return df
-    rows = (np.arange(G, dtype=np.int64)[:, None] * M + top[:, :n_top]).reshape(-1)
-    return df.iloc[rows]
-
-
-def _differential_expression_ttest(adata, is_log1p, group_keys, reference, code, n_genes, pts, scores, rank_by, variant, kw) -> pd.DataFrame:
-    """``differential_expression(method="t-test" / "t-test_overestim_var")``: ``welch_ttest``, then the same correction and cut."""
-    from illico_amd import ttest
-    if not isinstance(pts, (bool, np.bool_)):
-        raise ValueError(f"pts must be a bool, got {pts!r}")
-    if not isinstance(scores, (bool, np.bool_)):
-        raise ValueError(f"scores must be a bool, got {scores!r}")
-    if scores:
+    variant = DE_METHODS[method]
+    check_bool("pts", pts)
+    check_bool("scores", scores)
+    if variant is not None and scores:
         raise ValueError("scores=True belongs to method='wilcoxon': a t-test's statistic column is its score")
-    if not isinstance(rank_by, str) or rank_by not in RANK_BY_TTEST:
-        raise ValueError(f"rank_by must be one of {RANK_BY_TTEST} with a t-test method, got {rank_by!r}")
-    if n_genes is not None and (isinstance(n_genes, bool) or not isinstance(n_genes, (int, np.integer)) or n_genes < 1):
-        raise ValueError(f"n_genes must be a positive integer or None, got {n_genes!r}")
-    wilcoxon_only = set(kw) & {"use_continuity", "tie_correct"}
-    if wilcoxon_only:
-        raise TypeError(f"differential_expression(method='t-test...') got Wilcoxon-only keyword arguments {sorted(wilcoxon_only)}")
-    unknown = set(kw) - {"n_threads", "batch_size", "alternative", "layer", "precompile"}
+    ranks, where = (RANK_BY, "") if variant is None else (RANK_BY_TTEST, " with a t-test method")
+    if not isinstance(rank_by, str) or rank_by not in ranks:
+        raise ValueError(f"rank_by must be one of {ranks}{where}, got {rank_by!r}")
+    check_n_genes(n_genes)
+    wilcoxon_only = {"use_continuity", "tie_correct"}
+    if variant is not None and set(kw) & wilcoxon_only:
+        raise TypeError(f"differential_expression(method='t-test...') got Wilcoxon-only keyword arguments {sorted(set(kw) & wilcoxon_only)}")
+    unknown = set(kw) - {"n_threads", "batch_size", "alternative", "layer", "precompile"} - wilcoxon_only
     if unknown:
         raise TypeError(f"differential_expression() got unexpected keyword arguments {sorted(unknown)}")
-    alternative, layer = kw.get("alternative", "two-sided"), kw.get("layer")
-    ttest._check_arguments(is_log1p, variant, alternative)
-    planes, index, (X, handler, group_container) = ttest._ttest_frame_inputs(adata, is_log1p, group_keys, reference, variant, alternative, layer)
-    G, M = planes.shape[1], planes.shape[2]
-    n_top = min(int(n_genes), M) if n_genes is not None else 0
-    by_t = rank_by == "statistic"
-    if G and M:
-        eng = _lib.get_engine()
-        res = eng.adjust_pvalues(planes[0], code, n_top=0 if by_t else n_top)
-        adj, top = res if (n_top and not by_t) else (res, None)
-        if n_top and by_t:
-            top = eng.top_by_score(planes[1], n_top)
+    by_score = rank_by != "p_value"
+    if variant is None:
+        scores = bool(scores) or by_score
+        args = dict(n_threads=1, batch_size="auto", alternative="two-sided", use_continuity=True, tie_correct=True, layer=None)
+        args.update({k: v for k, v in kw.items() if k != "precompile"})
+        inputs: list = []
+        planes, index = _wilcoxon_planes(adata, is_log1p, group_keys, reference, **args, inputs=inputs, scores=scores)
+        score, extra = planes[3] if by_score else None, {"z_score": planes[3]} if scores else {}
+        planes, inputs = planes[:3], inputs[0] if pts else None
     else:
-        adj, top = np.empty((G, M), dtype=np.float64), np.empty((G, 0), dtype=np.int64)
-    extra = {}
+        from illico_amd import ttest
+        alternative, layer = kw.get("alternative", "two-sided"), kw.get("layer")
+        ttest._check_arguments(is_log1p, variant, alternative)
+        planes, index, inputs = ttest._ttest_frame_inputs(adata, is_log1p, group_keys, reference, variant, alternative, layer)
+        score, extra = planes[1] if by_score else None, {}
+    adj, top = adjust_and_cut(planes[0], code, n_genes, score)
     if pts:
         from illico_amd.group_stats import stat_planes
+        X, handler, group_container = inputs
         extra.update(stat_planes(X, handler, group_container, bool(is_log1p)))
     df = _planes_frame(planes, index, p_value_adj=adj, **extra)
-    if n_genes is None:
-        return df
-    rows = (np.arange(G, dtype=np.int64)[:, None] * M + top[:, :n_top]).reshape(-1)
-    return df.iloc[rows]
+    return df if top is None else cut_rows(df, top, planes.shape[2])

@@ -16,29 +16,26 @@ from __future__ import annotations
 import numpy as np
 import pandas as pd
 
+from illico_amd import _lib
+from illico_amd._passes import (FlaggedGenes, Matrix, _input, _product_index, _span, _windows, adjust_and_cut, check_alternative, check_bool,
+                                check_corr_method, check_n_genes, chunks, cut_rows, device_handler, walk_windows)
 from illico_amd.utils.groups import GroupContainer, encode_and_count_groups
 
 __all__ = ["blocked_wilcoxon"]
 
-ALTERNATIVES = ("two-sided", "less", "greater")
 #: device bytes one gene window may take (histograms in both layouts, block totals, sums and the result planes); a window the engine's
 #: scratch budget refuses is halved
 BLOCK_WINDOW_BYTES = 2 << 30
 
 
 def _check_arguments(adata, is_log1p, block_key, alternative, tie_correct, corr_method, n_genes):
-    if not isinstance(is_log1p, (bool, np.bool_)):
-        raise ValueError(f"is_log1p must be a bool, got {is_log1p!r}")
-    if not isinstance(alternative, str) or alternative not in ALTERNATIVES:
-        raise ValueError(f"Unsupported alternative hypothesis: {alternative}")
-    if not isinstance(tie_correct, (bool, np.bool_)):
-        raise ValueError(f"tie_correct must be a bool, got {tie_correct!r}")
-    if n_genes is not None and (isinstance(n_genes, bool) or not isinstance(n_genes, (int, np.integer)) or n_genes < 1):
-        raise ValueError(f"n_genes must be a positive integer or None, got {n_genes!r}")
+    check_bool("is_log1p", is_log1p)
+    check_alternative(alternative)
+    check_bool("tie_correct", tie_correct)
+    check_n_genes(n_genes)
     if not isinstance(block_key, str) or block_key not in adata.obs:
         raise ValueError(f"block_key {block_key!r} is no column of adata.obs")
-    from illico_amd.adjust import _method
-    return _method(corr_method)
+    return check_corr_method(corr_method)
 
 
 def compound_groups(g_codes: np.ndarray, b_codes: np.ndarray, G: int, B: int) -> GroupContainer:
@@ -67,8 +64,7 @@ def _plane_genes(eng, Xf, g_codes, b_codes, comp, G, B, ref, is_log1p, tie_corre
     ``Engine.blocked_from_planes``, window by window.  ``take_rows(Xf, rows)``: a block's rows of ``Xf``."""
     import torch
     dev = torch.device("cuda", eng.device)
-    nf = int(Xf.shape[1])
-    sparse_f = hasattr(Xf, "indptr")
+    genes, nf = Matrix(Xf), int(Xf.shape[1])
     counts = np.asarray(comp.counts, dtype=np.int64)
     row_map = np.full((B, G), -1, dtype=np.int32)
     blocks = []  # (b, the block's rows of Xf, its group container)
@@ -84,9 +80,9 @@ def _plane_genes(eng, Xf, g_codes, b_codes, comp, G, B, ref, is_log1p, tie_corre
         n_local = np.bincount(local, minlength=present.size).astype(np.int64)
         grp = GroupContainer(local.astype(np.int64), n_local, np.argsort(local, kind="stable").astype(np.int64),
                              np.concatenate([[0], np.cumsum(n_local)]).astype(np.int64), int(np.searchsorted(present, ref)) if ref >= 0 else -1)
-        blocks.append((b, take_rows(Xf, rows), grp))
+        blocks.append((b, Matrix(take_rows(Xf, rows)), grp))
     width = max(64, (BLOCK_WINDOW_BYTES // ((3 * G * B + 6 * G) * 8)) // 64 * 64)
-    for a, e in [(a, min(nf, a + width)) for a in range(0, nf, width)]:
+    for a, e in _windows(0, nf, width):
         w = e - a
         zs = torch.zeros((B, G, w), dtype=torch.float64, device=dev)
         us = torch.zeros((B, G, w), dtype=torch.float64, device=dev)
@@ -95,20 +91,13 @@ def _plane_genes(eng, Xf, g_codes, b_codes, comp, G, B, ref, is_log1p, tie_corre
             eng.set_groups(grp)
             k = int(grp.counts.size)
             out = (spare[0][:k], us[b, :k], spare[1][:k], zs[b, :k])
-            opts = dict(is_log1p=False, use_continuity=False, tie_correct=tie_correct, alternative=alternative, out=out, device_out=True, scores=True)
-            if sparse_f:
-                eng.run_sparse("csc", Xb.data, Xb.indices, Xb.indptr, Xb.shape, a, e, **opts)
-            else:
-                eng.run_dense(Xb, a, e, **opts)
+            Xb.run(eng, a, e, is_log1p=False, use_continuity=False, tie_correct=tie_correct, alternative=alternative, out=out, device_out=True,
+                   scores=True)
         eng.set_groups(comp)
         sums = torch.empty((G * B, w), dtype=torch.float64, device=dev)
-        if sparse_f:
-            eng.group_stats_sparse("csc", Xf.data, Xf.indices, Xf.indptr, Xf.shape, a, e, is_log1p=is_log1p, out=(None, sums))
-        else:
-            eng.group_stats(Xf, a, e, is_log1p=is_log1p, out=(None, sums))
+        genes.group_stats(eng, a, e, is_log1p=is_log1p, out=(None, sums))
         got = eng.blocked_from_planes(zs, us, row_map, counts=counts, ref=ref if ref >= 0 else None, sums=sums, alternative=alternative)
-        run = slice(int(cols[a]), int(cols[e - 1]) + 1)
-        where = run if run.stop - run.start == w else cols[a:e]  # (neighbouring genes -- a matrix flagged whole -- are written as a block)
+        where = _span(cols[a:e])  # (neighbouring genes -- a matrix flagged whole -- are written as a block)
         for k in range(4):
             planes[k][:, where] = got[k].cpu().numpy()
 
@@ -119,74 +108,42 @@ def blocked_planes(X, handler, g_codes, b_codes, G: int, B: int, ref: int, is_lo
     blocks; ``ref``: the reference group id, -1 for the rest of each block.  ``take_rows(Xf, rows)``: how a block's rows are taken from
     the gathered genes (a container of the caller's own, as tools/bench_blocked.py's device CSC arrays, brings its own)."""
     import torch
-    from illico_amd import _lib
-    from illico_amd.group_stats import _chunks
-    from illico_amd.pairwise import _gather_columns, _hstack, _windows
-    from illico_amd.ttest import device_handler
     eng = _lib.get_engine()
     dev = torch.device("cuda", eng.device)
-    src_handler = handler
+    flagged = FlaggedGenes(handler, whole=True)
     handler = device_handler(X, handler)  # an in-RAM CSR matrix goes up once
     comp = compound_groups(g_codes, b_codes, G, B)
     counts = np.asarray(comp.counts, dtype=np.int64)
     GB, M = G * B, int(X.shape[1])
     planes = np.empty((4, G, M), dtype=np.float64)
     per_gene = 2 * GB * 1024 + B * 1024 + 4 * G * 8 + (GB * 8 if is_log1p else 0) + 4
-    width = max(64, (BLOCK_WINDOW_BYTES // per_gene) // 64 * 64)
-    flagged_cols, flagged_parts = [], []
-    for lb, ub in _chunks(X, handler):
+
+    def hist_window(chunk, o0, o1):
+        w = o1 - o0
+        H = torch.empty((GB, w, eng.HIST_VALUES), dtype=torch.int32, device=dev)
+        fl = torch.empty((w,), dtype=torch.int32, device=dev)
+        chunk.group_value_hists(eng, o0, o1, out=(H, fl))
+        genes = np.flatnonzero(fl.cpu().numpy())
+        if genes.size < w:  # (a window without a count-valued gene -- every window of a log-normalised matrix -- has nothing to combine)
+            sums = None
+            if is_log1p:
+                sums = torch.empty((GB, w), dtype=torch.float64, device=dev)
+                chunk.group_stats(eng, o0, o1, is_log1p=True, out=(None, sums))
+            got = eng.blocked_from_hists(H, fl, counts=counts, n_blocks=B, ref=ref if ref >= 0 else None, sums=sums, tie_correct=tie_correct,
+                                         alternative=alternative)
+            for k in range(4):
+                planes[k][:, chunk.lb + o0:chunk.lb + o1] = got[k].cpu().numpy()
+        chunk_flagged.append(o0 + genes)
+
+    for chunk in chunks(X, handler):
         eng.set_groups(comp)
-        fetched, (a, b) = handler.fetch(lb, ub)
-        Xc = handler.to_nb(fetched)
-        sparse_in = hasattr(Xc, "indptr")
-        fmt = ("csr" if handler.fmt.name == "CSR" else "csc") if sparse_in else None
-        todo = _windows(0, ub - lb, width)
         chunk_flagged = []
-        while todo:
-            o0, o1 = todo.pop(0)
-            w = o1 - o0
-            try:
-                H = torch.empty((GB, w, eng.HIST_VALUES), dtype=torch.int32, device=dev)
-                fl = torch.empty((w,), dtype=torch.int32, device=dev)
-                if sparse_in:
-                    eng.group_value_hists_sparse(fmt, Xc.data, Xc.indices, Xc.indptr, Xc.shape, a + o0, a + o1, out=(H, fl))
-                else:
-                    eng.group_value_hists(Xc, a + o0, a + o1, out=(H, fl))
-                flagged = np.flatnonzero(fl.cpu().numpy())
-                got = sums = None
-                if flagged.size < w:  # (a window without a count-valued gene -- every window of a log-normalised matrix -- has nothing to combine)
-                    if is_log1p:
-                        sums = torch.empty((GB, w), dtype=torch.float64, device=dev)
-                        if sparse_in:
-                            eng.group_stats_sparse(fmt, Xc.data, Xc.indices, Xc.indptr, Xc.shape, a + o0, a + o1, is_log1p=True, out=(None, sums))
-                        else:
-                            eng.group_stats(Xc, a + o0, a + o1, is_log1p=True, out=(None, sums))
-                    got = eng.blocked_from_hists(H, fl, counts=counts, n_blocks=B, ref=ref if ref >= 0 else None, sums=sums, tie_correct=tie_correct,
-                                                 alternative=alternative)
-            except (MemoryError, torch.cuda.OutOfMemoryError):
-                if w <= 64:
-                    raise
-                half = max(64, (w // 2 + 63) // 64 * 64)
-                todo = _windows(o0, o1, half) + todo
-                H = fl = sums = None
-                continue
-            for k in range(4 if got is not None else 0):
-                planes[k][:, lb + o0:lb + o1] = got[k].cpu().numpy()
-            chunk_flagged.append(o0 + flagged)
-        chunk_flagged = np.concatenate(chunk_flagged) if chunk_flagged else np.empty(0, dtype=np.int64)
-        if chunk_flagged.size:
-            # gathered from the container as the caller gave it (the device copy of an in-RAM CSR matrix is not sliced by columns)
-            src, off = (fetched, a) if getattr(handler, "streams", False) else (src_handler.data, lb)
-            if chunk_flagged.size == M and fmt != "csr":
-                flagged_parts.append(src)  # every gene (a log-normalised matrix): the container itself, not a copy of it
-            else:
-                flagged_parts.append(_gather_columns(src, off + chunk_flagged))
-            flagged_cols.append(lb + chunk_flagged)
-    n_flagged = int(sum(c.size for c in flagged_cols))
-    if n_flagged:
-        _plane_genes(eng, _hstack(flagged_parts), g_codes, b_codes, comp, G, B, ref, is_log1p, tie_correct, alternative, planes,
-                     np.concatenate(flagged_cols), take_rows)
-    return planes, n_flagged
+        walk_windows(chunk, per_gene, BLOCK_WINDOW_BYTES, hist_window)
+        flagged.add(chunk, chunk_flagged)
+    Xf, cols = flagged.result()
+    if cols.size:
+        _plane_genes(eng, Xf, g_codes, b_codes, comp, G, B, ref, is_log1p, tie_correct, alternative, planes, cols, take_rows)
+    return planes, int(cols.size)
 
 
 def blocked_wilcoxon(adata, is_log1p: bool, group_keys: str, block_key: str, reference: str | None = None, *, alternative: str = "two-sided",
@@ -211,8 +168,6 @@ def blocked_wilcoxon(adata, is_log1p: bool, group_keys: str, block_key: str, ref
     ``ValueError``, before any device work: an unknown ``block_key``, a ``reference`` that is no group, a bad ``alternative``,
     ``corr_method`` or ``n_genes``, a non-bool ``is_log1p``."""
     code = _check_arguments(adata, is_log1p, block_key, alternative, tie_correct, corr_method, n_genes)
-    from illico_amd import _lib
-    from illico_amd.group_stats import _input
     X = _input(adata, layer)
     unique_groups, group_container = encode_and_count_groups(groups=adata.obs[group_keys], ref_group=reference)
     block_labels, block_container = encode_and_count_groups(groups=adata.obs[block_key], ref_group=None)
@@ -226,22 +181,22 @@ def blocked_wilcoxon(adata, is_log1p: bool, group_keys: str, block_key: str, ref
     n_r = counts[ref][None, :] if ref >= 0 else counts.sum(axis=0)[None, :] - counts
     weight = (counts * n_r * ((counts > 0) & (n_r > 0))).sum(axis=1).astype(np.float64)  # sum over the used blocks of n_g n_r
     live = np.flatnonzero(n_blocks > 0)
+    # a group without a used block keeps NaN rows and, under n_genes, its first genes in gene order
     adj = np.full((G, M), np.nan)
-    n_top = min(int(n_genes), M) if n_genes is not None else 0
-    top = np.tile(np.arange(n_top, dtype=np.int64), (G, 1))
+    top = np.tile(np.arange(min(int(n_genes), M) if n_genes is not None else 0, dtype=np.int64), (G, 1))
     if M and live.size:
-        res = eng.adjust_pvalues(np.ascontiguousarray(planes[0][live]), code, n_top=n_top)
-        adj[live], top[live] = res if n_top else (res, top[live])
+        adj[live], live_top = adjust_and_cut(np.ascontiguousarray(planes[0][live]), code, n_genes)
+        if live_top is not None:
+            top[live] = live_top
     with np.errstate(divide="ignore", invalid="ignore"):
         auc = planes[1] / weight[:, None]
     cols = {"p_value": planes[0].reshape(-1), "p_value_adj": adj.reshape(-1), "statistic": planes[1].reshape(-1),
             "fold_change": planes[2].reshape(-1), "z_score": planes[3].reshape(-1), "auc": auc.reshape(-1),
             "n_blocks": np.repeat(n_blocks, M)}
-    from illico_amd.asymptotic_wilcoxon import _product_index
     index = _product_index(pd.Series(np.asarray(unique_groups), dtype=str), pd.Series(np.asarray(adata.var_names), dtype=str))
     df = pd.DataFrame(cols, index=index, copy=False)
-    if n_top:
-        df = df.iloc[(np.arange(G, dtype=np.int64)[:, None] * M + top[:, :n_top]).reshape(-1)]
+    if top.shape[1]:
+        df = cut_rows(df, top, M)
     df.attrs["n_flagged_genes"] = n_flagged
     df.attrs["n_plane_genes"] = n_flagged
     df.attrs["blocks"] = [str(x) for x in block_labels]

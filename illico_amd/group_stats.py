@@ -12,6 +12,7 @@ import numpy as np
 import pandas as pd
 
 from illico_amd import _lib
+from illico_amd._passes import _input, _product_index, check_bool, chunks
 from illico_amd.utils.groups import encode_and_count_groups
 from illico_amd.utils.registry import data_handler_registry
 
@@ -19,25 +20,6 @@ __all__ = ["group_statistics"]
 
 #: the columns group_statistics adds, in order
 STAT_COLUMNS = ("pct_group", "pct_reference", "mean_group", "mean_reference")
-
-
-def _input(adata, layer):
-    X = adata.layers[layer] if layer is not None else adata.X
-    if len(getattr(X, "shape", ())) != 2:
-        raise ValueError(f"the expression matrix must be 2-D, got shape {getattr(X, 'shape', None)}")
-    return X
-
-
-def _chunks(X, handler) -> list[tuple[int, int]]:
-    """The gene ranges of one call: the whole range in RAM, chunks of about STREAM_CHUNK_BYTES for streamed containers."""
-    from illico_amd.asymptotic_wilcoxon import STREAM_CHUNK_BYTES
-    n_genes = int(X.shape[1])
-    if not getattr(handler, "streams", False) or n_genes == 0:
-        return [(0, n_genes)] if n_genes else []
-    per_gene = max(1, int(X.shape[0]) * getattr(getattr(X, "dtype", None), "itemsize", 4))
-    w = int(max(1, min(n_genes, STREAM_CHUNK_BYTES // per_gene)))
-    b = list(range(0, n_genes, w)) + [n_genes]
-    return list(zip(b[:-1], b[1:]))
 
 
 def stat_planes(X, handler, group_container, is_log1p: bool) -> dict[str, np.ndarray]:
@@ -50,15 +32,10 @@ def stat_planes(X, handler, group_container, is_log1p: bool) -> dict[str, np.nda
     ovr = ref < 0
     nnz = np.zeros((2 if ovr else 1, G, M), dtype=np.int64)
     sums = np.zeros((2 if ovr else 1, G, M), dtype=np.float64)
-    for lb, ub in _chunks(X, handler):
-        fetched, (a, b) = handler.fetch(lb, ub)
-        Xc = handler.to_nb(fetched)
+    for chunk in chunks(X, handler):
+        lb, ub = chunk.lb, chunk.lb + chunk.width
         out = (nnz[0][:, lb:ub], sums[0][:, lb:ub]) + ((nnz[1][:, lb:ub], sums[1][:, lb:ub]) if ovr else ())
-        if hasattr(Xc, "indptr"):
-            fmt = "csr" if handler.fmt.name == "CSR" else "csc"
-            eng.group_stats_sparse(fmt, Xc.data, Xc.indices, Xc.indptr, Xc.shape, a, b, is_log1p=is_log1p, rest=ovr, out=out)
-        else:
-            eng.group_stats(Xc, a, b, is_log1p=is_log1p, rest=ovr, out=out)
+        chunk.group_stats(eng, 0, chunk.width, is_log1p=is_log1p, rest=ovr, out=out)
     n_grp = counts.astype(np.float64)[:, None]
     n_ref = (N - n_grp) if ovr else np.full_like(n_grp, float(counts[ref]))
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -82,11 +59,9 @@ def group_statistics(adata, group_keys: str, reference: str | None = None, *, is
     ``asymptotic_wilcoxon`` accepts; streamed (backed) containers are read gene chunk by gene chunk.  Sparse input counts stored
     non-zero entries (a duplicate entry counts once per entry).
     """
-    if not isinstance(is_log1p, (bool, np.bool_)):
-        raise ValueError(f"is_log1p must be a bool, got {is_log1p!r}")
+    check_bool("is_log1p", is_log1p)
     X = _input(adata, layer)
     handler = data_handler_registry.get(X)
-    from illico_amd.asymptotic_wilcoxon import _product_index
     unique_raw_groups, group_container = encode_and_count_groups(groups=adata.obs[group_keys], ref_group=reference)
     planes = stat_planes(X, handler, group_container, bool(is_log1p))
     index = _product_index(pd.Series(unique_raw_groups, name="pert", dtype=str), pd.Series(np.asarray(adata.var_names), name="feature", dtype=str))

@@ -20,11 +20,14 @@ from __future__ import annotations
 import numpy as np
 import pandas as pd
 
+from illico_amd import _lib
+from illico_amd._passes import (FlaggedGenes, HostPlanes, Matrix, _gather_columns, _input, _product_index, _select, _windows, adjust_and_cut,
+                                check_alternative, check_bool, check_corr_method, check_max_result_bytes, check_n_genes, chunks, cut_rows,
+                                device_handler, pair_frame, walk_windows)
 from illico_amd.utils.groups import encode_and_count_groups
 
 __all__ = ["pairwise_wilcoxon", "pairwise_markers"]
 
-ALTERNATIVES = ("two-sided", "less", "greater")
 #: scran's ``pval.type``: how ``pairwise_markers`` combines a group's tests against the other groups
 PVAL_TYPES = ("any", "some", "all")
 #: device bytes one gene window of the pair route may take (histograms in both layouts and the result planes); a window the engine's
@@ -33,84 +36,12 @@ PAIR_WINDOW_BYTES = 2 << 30
 
 
 def _check_arguments(is_log1p, alternative, use_continuity, tie_correct, scores, corr_method, max_result_bytes):
-    if not isinstance(is_log1p, (bool, np.bool_)):
-        raise ValueError(f"is_log1p must be a bool, got {is_log1p!r}")
-    if not isinstance(alternative, str) or alternative not in ALTERNATIVES:
-        raise ValueError(f"Unsupported alternative hypothesis: {alternative}")
+    check_bool("is_log1p", is_log1p)
+    check_alternative(alternative)
     for name, v in (("use_continuity", use_continuity), ("tie_correct", tie_correct), ("scores", scores)):
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError(f"{name} must be a bool, got {v!r}")
-    if isinstance(max_result_bytes, bool) or not isinstance(max_result_bytes, (int, np.integer)) or max_result_bytes < 0:
-        raise ValueError(f"max_result_bytes must be a non-negative integer, got {max_result_bytes!r}")
-    if corr_method is None:
-        return None
-    from illico_amd.adjust import _method
-    return _method(corr_method)
-
-
-def _select(unique_groups: np.ndarray, groups) -> np.ndarray:
-    """The selected group ids, ascending: all of them, or those of the labels in ``groups``."""
-    G = int(len(unique_groups))
-    if groups is None:
-        sel = np.arange(G, dtype=np.int64)
-    else:
-        if isinstance(groups, (str, bytes)):
-            raise ValueError(f"groups must be a sequence of labels, got the single label {groups!r}")
-        labels = [str(x) for x in groups]
-        known = {str(x): k for k, x in enumerate(unique_groups)}
-        unknown = [x for x in labels if x not in known]
-        if unknown:
-            raise ValueError(f"groups names labels that are not present: {unknown}")
-        if len(set(labels)) != len(labels):
-            raise ValueError(f"groups names a label twice: {labels}")
-        sel = np.array(sorted(known[x] for x in labels), dtype=np.int64)
-    if sel.size < 2:
-        raise ValueError(f"pairwise tests need at least two groups, got {sel.size}")
-    return sel
-
-
-def _pair_index(labels: np.ndarray, features: np.ndarray, r_idx: np.ndarray, g_idx: np.ndarray) -> pd.MultiIndex:
-    """(pert, reference, feature) for the pairs (g_idx[k], r_idx[k]) in order, each over all features."""
-    names = ["pert", "reference", "feature"]
-    li, fi = pd.Index(pd.Series(labels, dtype=str)), pd.Index(pd.Series(features, dtype=str))
-    M, P = len(fi), len(r_idx)
-    if li.is_unique and fi.is_unique and not li.hasnans and not fi.hasnans and M:
-        ll, lf = li.sort_values(), fi.sort_values()
-        lcode, fcode = ll.get_indexer(li), lf.get_indexer(fi)
-        return pd.MultiIndex(levels=[ll, ll, lf], codes=[np.repeat(lcode[g_idx], M), np.repeat(lcode[r_idx], M), np.tile(fcode, P)],
-                             names=names, verify_integrity=False)
-    return pd.MultiIndex.from_arrays([np.repeat(np.asarray(li)[g_idx], M), np.repeat(np.asarray(li)[r_idx], M), np.tile(np.asarray(fi), P)],
-                                     names=names)
-
-
-def _gather_columns(src, cols: np.ndarray):
-    """The columns ``cols`` of one fetched container, in a form the one-versus-reference engine calls take: a dense matrix stays dense
-    (numpy, or a CUDA tensor), a sparse one becomes a scipy CSC matrix."""
-    from illico_amd._lib import _is_torch_tensor
-    if _is_torch_tensor(src):
-        import torch
-        return src[:, torch.as_tensor(cols, device=src.device)].contiguous()
-    if hasattr(src, "indptr"):
-        from scipy import sparse
-        return sparse.csc_matrix(src[:, cols])
-    return np.ascontiguousarray(np.asarray(src)[:, cols])
-
-
-def _hstack(parts):
-    from illico_amd._lib import _is_torch_tensor
-    if len(parts) == 1:
-        return parts[0]
-    if _is_torch_tensor(parts[0]):
-        import torch
-        return torch.cat(parts, dim=1)
-    if hasattr(parts[0], "indptr"):
-        from scipy import sparse
-        return sparse.hstack(parts, format="csc")
-    return np.ascontiguousarray(np.concatenate(parts, axis=1))
-
-
-def _windows(lb: int, ub: int, w: int):
-    return [(a, min(ub, a + w)) for a in range(lb, ub, w)]
+        check_bool(name, v)
+    check_max_result_bytes(max_result_bytes)
+    return check_corr_method(corr_method, optional=True)
 
 
 def _ranked_route_takes(eng, Xf, K: int) -> bool:
@@ -122,13 +53,14 @@ def _ranked_route_takes(eng, Xf, K: int) -> bool:
 def _ranked_pairs(eng, Xf, sel: np.ndarray, planes, cols: np.ndarray, opts: dict, sink=None) -> np.ndarray:
     """The gathered genes ``Xf`` (gene j is column ``cols[j]`` of ``planes``) through ``Engine.pairwise_ranked``, window by window,
     under the engine's current groups.  Returns the genes (indices into ``Xf``'s columns) the route left: their columns are not written.
-    With a ``sink`` (``planes`` is then None) each window's planes are written on the device and handed over with its ``left`` words."""
+    With a ``sink`` (``planes`` is then None) each window's planes are written on the device and handed over with its ``left`` words.
+    A window the engine refuses is not halved: its genes are left to the fallback."""
     import torch
     K, n_planes, nf = int(sel.size), 4 if opts["scores"] else 3, int(Xf.shape[1])
     dev = torch.device("cuda", eng.device)
-    sparse_f = hasattr(Xf, "indptr")
-    if sparse_f:
+    if hasattr(Xf, "indptr"):
         Xf.sort_indices()
+    genes = Matrix(Xf)
     width = max(64, (PAIR_WINDOW_BYTES // (n_planes * K * K * 8)) // 64 * 64)
     left_genes = []
     for a, b in _windows(0, nf, width):
@@ -136,24 +68,21 @@ def _ranked_pairs(eng, Xf, sel: np.ndarray, planes, cols: np.ndarray, opts: dict
             out = None
             if sink is not None:
                 out = [torch.empty((K, K, b - a), dtype=torch.float64, device=dev) for _ in range(n_planes)] + [torch.empty((b - a,), dtype=torch.int32, device=dev)]
-            if sparse_f:
-                sums = eng.group_stats_sparse("csc", Xf.data, Xf.indices, Xf.indptr, Xf.shape, a, b, is_log1p=opts["is_log1p"])[1]
-                got = eng.pairwise_ranked_sparse("csc", Xf.data, Xf.indices, Xf.indptr, Xf.shape, a, b, sums=sums, sel=sel, out=out, **opts)
-            else:
-                sums = eng.group_stats(Xf, a, b, is_log1p=opts["is_log1p"])[1]
-                got = eng.pairwise_ranked(Xf, a, b, sums=sums, sel=sel, out=out, **opts)
+            sums = genes.group_stats(eng, a, b, is_log1p=opts["is_log1p"])[1]
+            got = genes.pairwise_ranked(eng, a, b, sums=sums, sel=sel, out=out, **opts)
         except (MemoryError, torch.cuda.OutOfMemoryError):
             left_genes.append(np.arange(a, b))
             continue
         if sink is not None:
             sink(cols[a:b], tuple(got[:n_planes]), got[-1])
-            left_genes.append(a + np.flatnonzero(got[-1].cpu().numpy() != 0))
-            continue
-        got = [q.cpu().numpy() if hasattr(q, "cpu") else q for q in got]
-        done = np.flatnonzero(got[-1] == 0)
-        for k in range(n_planes):
-            planes[k][:, :, cols[a + done]] = got[k][:, :, done]
-        left_genes.append(a + np.flatnonzero(got[-1] != 0))
+            left = got[-1].cpu().numpy()
+        else:
+            got = [q.cpu().numpy() if hasattr(q, "cpu") else q for q in got]
+            left = got[-1]
+            done = np.flatnonzero(left == 0)
+            for k in range(n_planes):
+                planes[k][:, :, cols[a + done]] = got[k][:, :, done]
+        left_genes.append(a + np.flatnonzero(left != 0))
     return np.concatenate(left_genes) if left_genes else np.empty(0, dtype=np.int64)
 
 
@@ -163,7 +92,7 @@ def _fallback_blocks(eng, Xr, group_container, sel: np.ndarray, cols: np.ndarray
     import torch
     dev = torch.device("cuda", eng.device)
     K, G, n_planes, n = int(sel.size), int(np.asarray(group_container.counts).size), 4 if opts["scores"] else 3, int(Xr.shape[1])
-    sparse_f = hasattr(Xr, "indptr")
+    genes = Matrix(Xr)
     rows = torch.as_tensor(sel, device=dev)
     containers = [group_container._replace(encoded_ref_group=int(r)) for r in sel]
     width = max(64, (PAIR_WINDOW_BYTES // (n_planes * (K * K + G) * 8)) // 64 * 64)
@@ -171,13 +100,21 @@ def _fallback_blocks(eng, Xr, group_container, sel: np.ndarray, cols: np.ndarray
         block = tuple(torch.empty((K, K, b - a), dtype=torch.float64, device=dev) for _ in range(n_planes))
         for ri, grp in enumerate(containers):
             eng.set_groups(grp)
-            if sparse_f:
-                got = eng.run_sparse("csc", Xr.data, Xr.indices, Xr.indptr, Xr.shape, a, b, device_out=True, **opts)
-            else:
-                got = eng.run_dense(Xr, a, b, device_out=True, **opts)
+            got = genes.run(eng, a, b, device_out=True, **opts)
             for k in range(n_planes):
                 block[k][ri] = got[k][rows]
         sink(cols[a:b], block, None)
+
+
+def _fallback_planes(eng, Xr, group_container, sel: np.ndarray, cols: np.ndarray, opts: dict, planes) -> None:
+    """The same genes into host ``planes``: one call per reference over all of them, what a user does by hand."""
+    genes, n = Matrix(Xr), int(Xr.shape[1])
+    for ri, r in enumerate(sel):
+        eng.set_groups(group_container._replace(encoded_ref_group=int(r)))
+        got = genes.run(eng, 0, n, **opts)
+        for k in range(len(planes)):
+            q = got[k].cpu().numpy() if hasattr(got[k], "cpu") else got[k]
+            planes[k][ri][:, cols] = q[sel]
 
 
 def pairwise_planes(X, handler, group_container, sel: np.ndarray, is_log1p: bool, alternative: str, use_continuity: bool, tie_correct: bool,
@@ -188,92 +125,57 @@ def pairwise_planes(X, handler, group_container, sel: np.ndarray, is_log1p: bool
     ``sink``: a callable ``sink(cols, planes, skip)``.  No host planes are then allocated (the first entry of the result is None):
     every finished block of columns is handed over as it stands on the device -- ``cols`` the int64 gene numbers of its w columns,
     ``planes`` the 3 or 4 float64 CUDA tensors ``[K, K, w]``, ``skip`` an int32 CUDA tensor ``[w]``, non-zero for a column the block
-    does not hold (it comes in a later block), or None.  Over all blocks every gene is held exactly once."""
+    does not hold (it comes in a later block), or None.  Over all blocks every gene is held exactly once.  Without one, the histogram
+    route's blocks go to a sink that keeps host planes (``_passes.HostPlanes``)."""
     import torch
-    from illico_amd import _lib
-    from illico_amd.group_stats import _chunks
-    from illico_amd.ttest import device_handler
     eng = _lib.get_engine()
     dev = torch.device("cuda", eng.device)
-    src_handler = handler
+    flagged = FlaggedGenes(handler)
     handler = device_handler(X, handler)  # an in-RAM CSR matrix goes up once
     counts = np.asarray(group_container.counts, dtype=np.int64)
     G, M, K = int(counts.size), int(X.shape[1]), int(sel.size)
     n_planes = 4 if scores else 3
     ovr_groups = group_container._replace(encoded_ref_group=-1)  # the histogram pass uses codes, counts and order only
     eng.set_groups(ovr_groups)
-    planes = np.empty((n_planes, K, K, M), dtype=np.float64) if sink is None else None
+    planes = None
+    if sink is None:
+        hist_sink = HostPlanes(n_planes, K, M)
+        planes = hist_sink.planes
+    else:
+        hist_sink = sink
     per_gene = 2 * G * 1024 + K * 1024 + n_planes * K * K * 8 + (G * 8 if is_log1p else 0) + 4
-    width = max(64, (PAIR_WINDOW_BYTES // per_gene) // 64 * 64)
-    flagged_cols, flagged_parts = [], []
-    for lb, ub in _chunks(X, handler):
-        fetched, (a, b) = handler.fetch(lb, ub)
-        Xc = handler.to_nb(fetched)
-        sparse_in = hasattr(Xc, "indptr")
-        fmt = ("csr" if handler.fmt.name == "CSR" else "csc") if sparse_in else None
-        todo = _windows(0, ub - lb, width)
+
+    def hist_window(chunk, o0, o1):
+        w = o1 - o0
+        H = torch.empty((G, w, eng.HIST_VALUES), dtype=torch.int32, device=dev)
+        fl = torch.empty((w,), dtype=torch.int32, device=dev)
+        sums = torch.empty((G, w), dtype=torch.float64, device=dev) if is_log1p else None
+        chunk.group_value_hists(eng, o0, o1, out=(H, fl))
+        if is_log1p:
+            chunk.group_stats(eng, o0, o1, is_log1p=True, out=(None, sums))
+        got = eng.pairwise_from_hists(H, fl, counts=counts, sel=sel, sums=sums, is_log1p=is_log1p, use_continuity=use_continuity,
+                                      tie_correct=tie_correct, alternative=alternative, scores=scores)
+        hist_sink(np.arange(chunk.lb + o0, chunk.lb + o1, dtype=np.int64), tuple(got), fl)
+        chunk_flagged.append(o0 + np.flatnonzero(fl.cpu().numpy()))
+
+    for chunk in chunks(X, handler):
         chunk_flagged = []
-        while todo:
-            o0, o1 = todo.pop(0)
-            w = o1 - o0
-            try:
-                H = torch.empty((G, w, eng.HIST_VALUES), dtype=torch.int32, device=dev)
-                fl = torch.empty((w,), dtype=torch.int32, device=dev)
-                sums = torch.empty((G, w), dtype=torch.float64, device=dev) if is_log1p else None
-                if sparse_in:
-                    eng.group_value_hists_sparse(fmt, Xc.data, Xc.indices, Xc.indptr, Xc.shape, a + o0, a + o1, out=(H, fl))
-                    if is_log1p:
-                        eng.group_stats_sparse(fmt, Xc.data, Xc.indices, Xc.indptr, Xc.shape, a + o0, a + o1, is_log1p=True, out=(None, sums))
-                else:
-                    eng.group_value_hists(Xc, a + o0, a + o1, out=(H, fl))
-                    if is_log1p:
-                        eng.group_stats(Xc, a + o0, a + o1, is_log1p=True, out=(None, sums))
-                got = eng.pairwise_from_hists(H, fl, counts=counts, sel=sel, sums=sums, is_log1p=is_log1p, use_continuity=use_continuity,
-                                              tie_correct=tie_correct, alternative=alternative, scores=scores)
-            except (MemoryError, torch.cuda.OutOfMemoryError):
-                if w <= 64:
-                    raise
-                half = max(64, (w // 2 + 63) // 64 * 64)
-                todo = _windows(o0, o1, half) + todo
-                H = fl = sums = None
-                continue
-            if sink is not None:
-                sink(np.arange(lb + o0, lb + o1, dtype=np.int64), tuple(got), fl)
-            else:
-                for k in range(n_planes):
-                    planes[k][:, :, lb + o0:lb + o1] = got[k].cpu().numpy()
-            chunk_flagged.append(o0 + np.flatnonzero(fl.cpu().numpy()))
-        chunk_flagged = np.concatenate(chunk_flagged) if chunk_flagged else np.empty(0, dtype=np.int64)
-        if chunk_flagged.size:
-            # gathered from the container as the caller gave it (the device copy of an in-RAM CSR matrix is not sliced by columns)
-            src, off = (fetched, a) if getattr(handler, "streams", False) else (src_handler.data, lb)
-            flagged_parts.append(_gather_columns(src, off + chunk_flagged))
-            flagged_cols.append(lb + chunk_flagged)
-    n_flagged = int(sum(c.size for c in flagged_cols))
-    n_fallback = 0
+        walk_windows(chunk, per_gene, PAIR_WINDOW_BYTES, hist_window)
+        flagged.add(chunk, chunk_flagged)
+    Xf, cols = flagged.result()
+    n_flagged, n_fallback = int(cols.size), 0
     if n_flagged:
-        cols = np.concatenate(flagged_cols)
-        Xf = _hstack(flagged_parts)
         opts = dict(is_log1p=is_log1p, use_continuity=use_continuity, tie_correct=tie_correct, alternative=alternative, scores=scores)
         # any float32 / int32 values, up to 64 groups: every pair from one sorted walk per gene (illico_pairwise_ranked_*) ...
         rest = _ranked_pairs(eng, Xf, sel, planes, cols, opts, sink) if _ranked_route_takes(eng, Xf, K) else np.arange(n_flagged)
         n_fallback = int(rest.size)
         if n_fallback:
-            # ... and for what it leaves, what a user does by hand: one one-versus-reference call per reference
+            # ... and for what it leaves, one one-versus-reference call per reference
             Xr = Xf if n_fallback == n_flagged else _gather_columns(Xf, rest)
-            sparse_f = hasattr(Xr, "indptr")
             if sink is not None:
                 _fallback_blocks(eng, Xr, group_container, sel, cols[rest], opts, sink)
-                return None, n_flagged, n_fallback
-            for ri, r in enumerate(sel):
-                eng.set_groups(group_container._replace(encoded_ref_group=int(r)))
-                if sparse_f:
-                    got = eng.run_sparse("csc", Xr.data, Xr.indices, Xr.indptr, Xr.shape, 0, n_fallback, **opts)
-                else:
-                    got = eng.run_dense(Xr, 0, n_fallback, **opts)
-                for k in range(n_planes):
-                    q = got[k].cpu().numpy() if hasattr(got[k], "cpu") else got[k]
-                    planes[k][ri][:, cols[rest]] = q[sel]
+            else:
+                _fallback_planes(eng, Xr, group_container, sel, cols[rest], opts, planes)
     return planes, n_flagged, n_fallback
 
 
@@ -299,38 +201,18 @@ def pairwise_wilcoxon(adata, is_log1p: bool, group_keys: str, *, groups=None, al
     non-bool ``is_log1p``, and a result of more than ``max_result_bytes`` bytes (K (K - 1) x genes x 8 bytes x columns), raised before
     any device work.  ``NotImplementedError``: two selected groups of 2097152 cells or more together."""
     code = _check_arguments(is_log1p, alternative, use_continuity, tie_correct, scores, corr_method, max_result_bytes)
-    from illico_amd.group_stats import _input
     X = _input(adata, layer)
     unique_raw_groups, group_container = encode_and_count_groups(groups=adata.obs[group_keys], ref_group=None)
     sel = _select(np.asarray(unique_raw_groups), groups)
-    K, M = int(sel.size), int(X.shape[1])
-    n_cols = 3 + int(bool(scores)) + int(code is not None)
-    need = K * (K - 1) * M * 8 * n_cols
-    if need > max_result_bytes:
-        raise ValueError(f"the result of {K} x {K - 1} pairs over {M} genes with {n_cols} columns takes {need} bytes, more than "
-                         f"max_result_bytes = {int(max_result_bytes)}: restrict `groups`, or raise max_result_bytes")
-    from illico_amd.utils.registry import data_handler_registry
-    handler = data_handler_registry.get(X)
-    planes, n_flagged, n_fallback = pairwise_planes(X, handler, group_container, sel, bool(is_log1p), alternative, bool(use_continuity),
-                                                    bool(tie_correct), bool(scores))
-    r_idx, g_idx = np.divmod(np.arange(K * K), K)
-    off = r_idx != g_idx
-    rows = np.flatnonzero(off)
-    cols = {"p_value": planes[0].reshape(K * K, M)[rows].reshape(-1), "statistic": planes[1].reshape(K * K, M)[rows].reshape(-1),
-            "fold_change": planes[2].reshape(K * K, M)[rows].reshape(-1)}
-    if scores:
-        cols["z_score"] = planes[3].reshape(K * K, M)[rows].reshape(-1)
-    if code is not None:
-        from illico_amd import _lib
-        adj = _lib.get_engine().adjust_pvalues(np.ascontiguousarray(planes[0].reshape(K * K, M)[rows]), code)
-        cols["p_value_adj"] = np.asarray(adj).reshape(-1)
-    labels = np.asarray(unique_raw_groups)[sel]
-    index = _pair_index(labels, np.asarray(adata.var_names), r_idx[rows], g_idx[rows])
-    df = pd.DataFrame(cols, index=index, copy=False)
-    df.attrs["n_flagged_genes"] = n_flagged
-    df.attrs["n_ranked_genes"] = n_flagged - n_fallback
-    df.attrs["n_fallback_genes"] = n_fallback
-    return df
+
+    def compute():
+        from illico_amd.utils.registry import data_handler_registry
+        planes, n_flagged, n_fallback = pairwise_planes(X, data_handler_registry.get(X), group_container, sel, bool(is_log1p), alternative,
+                                                        bool(use_continuity), bool(tie_correct), bool(scores))
+        return planes, {"n_flagged_genes": n_flagged, "n_ranked_genes": n_flagged - n_fallback, "n_fallback_genes": n_fallback}
+
+    columns = ("p_value", "statistic", "fold_change") + (("z_score",) if scores else ())
+    return pair_frame(columns, np.asarray(unique_raw_groups)[sel], np.asarray(adata.var_names), code, max_result_bytes, compute)
 
 
 class _MarkerSink:
@@ -360,8 +242,7 @@ def _check_marker_arguments(pval_type, min_prop, n_genes):
         raise ValueError(f"pval_type must be one of {PVAL_TYPES}, got {pval_type!r}")
     if isinstance(min_prop, bool) or not isinstance(min_prop, (int, float, np.integer, np.floating)) or not 0 < min_prop <= 1:
         raise ValueError(f"min_prop must be a number in (0, 1], got {min_prop!r}")
-    if n_genes is not None and (isinstance(n_genes, bool) or not isinstance(n_genes, (int, np.integer)) or n_genes < 1):
-        raise ValueError(f"n_genes must be a positive integer or None, got {n_genes!r}")
+    check_n_genes(n_genes)
 
 
 def pairwise_markers(adata, is_log1p: bool, group_keys: str, *, groups=None, pval_type: str = "any", min_prop: float = 0.5,
@@ -397,14 +278,14 @@ def pairwise_markers(adata, is_log1p: bool, group_keys: str, *, groups=None, pva
         raise ValueError(f"method must be one of {tuple(MARKER_METHODS)}, got {method!r}")
     ttest = method != "wilcoxon"
     if ttest:
-        from illico_amd.pairwise_ttest import MARKER_PLANES, _check_arguments as check_ttest_arguments, pair_ttest_blocks
+        from illico_amd.pairwise_ttest import MARKER_PLANES, pair_ttest_blocks
         if use_continuity is not True or tie_correct is not True:
             raise ValueError("use_continuity and tie_correct belong to the Wilcoxon tests: leave them at their defaults with a t-test method")
-        code = check_ttest_arguments(is_log1p, MARKER_METHODS[method], alternative, corr_method, 0)
+        check_bool("is_log1p", is_log1p)
+        check_alternative(alternative)
+        code = check_corr_method(corr_method, optional=True)
     else:
         code = _check_arguments(is_log1p, alternative, use_continuity, tie_correct, True, corr_method, 0)
-    from illico_amd import _lib
-    from illico_amd.group_stats import _input
     X = _input(adata, layer)
     unique_raw_groups, group_container = encode_and_count_groups(groups=adata.obs[group_keys], ref_group=None)
     sel = _select(np.asarray(unique_raw_groups), groups)
@@ -426,11 +307,9 @@ def pairwise_markers(adata, is_log1p: bool, group_keys: str, *, groups=None, pva
                                                    bool(tie_correct), True, sink=sink)
     labels = np.asarray(unique_raw_groups)[sel]
     cols = {"p_value": sink.p.reshape(-1)}
-    n_top = min(int(n_genes), M) if n_genes is not None else 0
     top = None
-    if M and (code is not None or n_top):
-        res = eng.adjust_pvalues(sink.p, code or "bh", n_top=n_top)
-        adj, top = res if n_top else (res, None)
+    if M and (code is not None or n_genes is not None):  # (without a correction the ranking alone is wanted: any method gives it)
+        adj, top = adjust_and_cut(sink.p, code or "bh", n_genes)
         if code is not None:
             cols["p_value_adj"] = np.asarray(adj).reshape(-1)
     elif code is not None:
@@ -441,11 +320,10 @@ def pairwise_markers(adata, is_log1p: bool, group_keys: str, *, groups=None, pva
     if not ttest:
         n_cells = np.asarray(group_container.counts, dtype=np.float64)[sel]
         cols["auc"] = (sink.effects[0] / (n_cells[:, None] * n_cells[sink.rep])).reshape(-1)
-    from illico_amd.asymptotic_wilcoxon import _product_index
     index = _product_index(pd.Series(labels, dtype=str), pd.Series(np.asarray(adata.var_names), dtype=str))
     df = pd.DataFrame(cols, index=index, copy=False)
     if top is not None:
-        df = df.iloc[(np.arange(K, dtype=np.int64)[:, None] * M + np.asarray(top)[:, :n_top]).reshape(-1)]
+        df = cut_rows(df, top, M)
     if not ttest:
         df.attrs["n_flagged_genes"] = n_flagged
         df.attrs["n_ranked_genes"] = n_flagged - n_fallback

@@ -10,38 +10,19 @@ from __future__ import annotations
 
 import numpy as np
 import pandas as pd
-from scipy import sparse
 
 from illico_amd import _lib
+from illico_amd._passes import VARIANTS, _input, _product_index, check_alternative, check_bool, check_variant, chunks, device_handler
 from illico_amd.utils.groups import encode_and_count_groups
 from illico_amd.utils.registry import data_handler_registry
 
 __all__ = ["welch_ttest", "VARIANTS"]
 
-#: the variants of the test: Welch's, and scanpy's "overestim_var" (the reference's variance is divided by the GROUP's size)
-VARIANTS = ("welch", "overestim_var")
-ALTERNATIVES = ("two-sided", "less", "greater")
-
 
 def _check_arguments(is_log1p, variant, alternative):
-    if not isinstance(is_log1p, (bool, np.bool_)):
-        raise ValueError(f"is_log1p must be a bool, got {is_log1p!r}")
-    if not isinstance(variant, str) or variant not in VARIANTS:
-        raise ValueError(f"variant must be one of {VARIANTS}, got {variant!r}")
-    if not isinstance(alternative, str) or alternative not in ALTERNATIVES:
-        raise ValueError(f"Unsupported alternative hypothesis: {alternative}")
-
-
-def _is_ram_csr(X) -> bool:
-    return isinstance(X, sparse.csr_matrix) or (hasattr(sparse, "csr_array") and isinstance(X, sparse.csr_array))
-
-
-def device_handler(X, handler):
-    """The handler the passes of one call read: an in-RAM CSR matrix goes up once (every pass walks all of its rows)."""
-    if _is_ram_csr(X):
-        from illico_amd.asymptotic_wilcoxon import _csr_to_device
-        return _csr_to_device(X, handler, check=False)[1]
-    return handler
+    check_bool("is_log1p", is_log1p)
+    check_variant(variant)
+    check_alternative(alternative)
 
 
 def fold_change_planes(sum_g: np.ndarray, sum_ref: np.ndarray, counts: np.ndarray, n_cells: int, ref: int) -> np.ndarray:
@@ -59,7 +40,6 @@ def ttest_planes(X, handler, group_container, is_log1p: bool, variant: str, alte
     """float64 [3, G, n_genes]: p_value, t, fold_change for the groups of ``group_container`` (engine groups are set here).  The matrix
     is read by the moments pass alone, plus one ``group_stats`` pass for the expm1 sums of the fold change under ``is_log1p``."""
     import torch
-    from illico_amd.group_stats import _chunks
     eng = _lib.get_engine()
     eng.set_groups(group_container)
     counts = np.asarray(group_container.counts, dtype=np.int64)
@@ -68,22 +48,13 @@ def ttest_planes(X, handler, group_container, is_log1p: bool, variant: str, alte
     ovr = ref < 0
     planes = np.empty((3, G, M), dtype=np.float64)
     dev = torch.device("cuda", eng.device)
-    for lb, ub in _chunks(X, handler):
-        fetched, (a, b) = handler.fetch(lb, ub)
-        Xc = handler.to_nb(fetched)
-        w = ub - lb
+    for chunk in chunks(X, handler):
+        w, lb, ub = chunk.width, chunk.lb, chunk.lb + chunk.width
         mom = tuple(torch.empty((G, w), dtype=torch.float64, device=dev) for _ in range(4 if ovr else 2))
         fsum = tuple(np.empty((G, w), dtype=np.float64) for _ in range(2 if ovr else 1)) if is_log1p else None
-        if hasattr(Xc, "indptr"):
-            fmt = "csr" if handler.fmt.name == "CSR" else "csc"
-            eng.group_moments_sparse(fmt, Xc.data, Xc.indices, Xc.indptr, Xc.shape, a, b, rest=ovr, out=mom)
-            if is_log1p:
-                eng.group_stats_sparse(fmt, Xc.data, Xc.indices, Xc.indptr, Xc.shape, a, b, is_log1p=True, rest=ovr,
-                                       out=(None, fsum[0]) + ((None, fsum[1]) if ovr else ()))
-        else:
-            eng.group_moments(Xc, a, b, rest=ovr, out=mom)
-            if is_log1p:
-                eng.group_stats(Xc, a, b, is_log1p=True, rest=ovr, out=(None, fsum[0]) + ((None, fsum[1]) if ovr else ()))
+        chunk.group_moments(eng, 0, w, rest=ovr, out=mom)
+        if is_log1p:
+            chunk.group_stats(eng, 0, w, is_log1p=True, rest=ovr, out=(None, fsum[0]) + ((None, fsum[1]) if ovr else ()))
         p, t = eng.ttest_from_moments(*mom, variant=variant, alternative=alternative, want=("p", "t"))
         planes[0][:, lb:ub] = p.cpu().numpy()
         planes[1][:, lb:ub] = t.cpu().numpy()
@@ -98,8 +69,6 @@ def ttest_planes(X, handler, group_container, is_log1p: bool, variant: str, alte
 
 def _ttest_frame_inputs(adata, is_log1p, group_keys, reference, variant, alternative, layer):
     """(planes [3, G, M], index, (X, handler, GroupContainer)) of one t-test call."""
-    from illico_amd.asymptotic_wilcoxon import _product_index
-    from illico_amd.group_stats import _input
     X = _input(adata, layer)
     handler = device_handler(X, data_handler_registry.get(X))
     unique_raw_groups, group_container = encode_and_count_groups(groups=adata.obs[group_keys], ref_group=reference)
